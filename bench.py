@@ -5,11 +5,17 @@ configs[1] (batch 8 per GPU, 256x512 fp32; configs[2] = the same per-GPU work on
 
     python bench.py --gpus N --steps K --warmup W      (N > 1: starts one fresh process per GPU itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (the driver's form)
+    python bench.py --gpus 1 --steps K --warmup W --full               (everything beside the headline, see below)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   (+ the last timed step's outputs as .npy)
 
 A step = one forward pass of one batch already resident in HBM: encoder / decoder / flow estimator and
 the hot path (5 cost volumes + 4 warps) in the HIP kernels, the wide coarse-level pointwise GEMMs on
 rocBLAS, 6 per-level EPE reductions, and (N > 1) one RCCL all-gather of the 6-float EPE vector.
-Prints ONE JSON line (< 4 KB) on rank 0.  On one GPU the line also carries `extra_configs`: BASELINE
+Prints ONE JSON line (< 4 KB) on rank 0.
+
+A plain run only sets up, warms up, times the K steps (and writes --dump-outputs) for the headline.
+With --full it also measures and checks everything else: the CPU baseline and the parity gate against the
+oracle, live rooflines, the serving / bf16x3 / sustained-clock legs, and on one GPU `extra_configs`: BASELINE
 configs[3] (batch 16, 1024x2048 fp32) and configs[4] (batch 32, 256x512 fp16) measured the same way, each
 with its own `value`, `ms_per_step` and `roofline` -- reported beside the headline, never as `value`.
 Everything else that was measured (per-kernel times of the eager step, the other roofline blocks, method
@@ -68,7 +74,7 @@ def parse_args(argv=None):
                         "default and the only form reported as the headline); bf16x3 = three-way bf16 splits "
                         "(DESIGN.md 4.11) -- the run is then labelled so in config.matmul (profiling / A-B runs)")
     p.add_argument("--no-extra", action="store_true",
-                   help="skip the extra_configs legs (BASELINE configs[3] and configs[4]; N=1 default run only)")
+                   help="skip the extra_configs legs (BASELINE configs[3] and configs[4]; N=1 default run with --full only)")
     p.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                    help="f16 = BASELINE configs[4] (fp16 storage / convs, fp32 accumulate in the hot path)")
     p.add_argument("--data-format", default="channels_last", choices=["channels_last", "channels_first"],
@@ -76,8 +82,15 @@ def parse_args(argv=None):
                         "channels_first, app/optical_flow/test_infer.py:52)")
     p.add_argument("--dist-backend", default=None,
                    help="rehearsal only: 'gloo' runs N ranks on ONE GPU (EPE gathered through host memory)")
-    p.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                   help="file that receives everything measured beyond the one JSON line ('' = do not write)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beside the headline (CPU baseline + parity gate, "
+                        "rooflines, serving / bf16x3 / clock legs, extra_configs, bench_detail.json)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned (6 flows coarse to fine, per-level EPE) "
+                        "as DIR/<name>.npy in float32")
+    p.add_argument("--detail", default=None,
+                   help="file that receives everything measured beyond the one JSON line ('' = do not write; "
+                        "default: bench_detail.json beside this file with --full, nothing otherwise)")
     p.add_argument("--stub-forward", action="store_true",
                    help="TEST HOOK (tests/test_dist_cpu.py): no kernels, no GPU -- the launcher and the timed step "
                         "loop only, under gloo on CPU tensors; the line it prints is labelled as a rehearsal")
@@ -474,9 +487,11 @@ def rooflines(model, model_input, B, hw, dtype, tdtype, dev, args, copy_gbs):
     return out, hot
 
 
-def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_gbs, global_batch=0):
+def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_gbs, global_batch=0, dump=False):
     """One configuration end to end -> the fields of its JSON object.  global_batch > 0: B is this rank's shard of
-    that many pairs (strong scaling); otherwise every rank runs B pairs (weak scaling)."""
+    that many pairs (strong scaling); otherwise every rank runs B pairs (weak scaling).  The legs beside the timed
+    steps (serving, bf16x3, clock, rooflines) run only with args.full.  dump: also return the last timed step's
+    outputs as host arrays."""
     tdtype = torch.float32 if dtype == "f32" else torch.float16
     weights = synth.make_weights(42, hw)
     cl = args.data_format == "channels_last"
@@ -535,16 +550,19 @@ def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_
             graphs = None
             torch.cuda.synchronize()
 
+    last = {}   # the flows the latest step wrote (for --dump-outputs)
+
     def run_step(k):
         if graphs is not None and in_place:
             s = gather.next_slot()
             graphs[s].replay()
+            last["flows"] = graphs[s].outputs
             return s
         if graphs is not None:
             graphs[0].replay()
-            e = graphs[0].extra
+            last["flows"], e = graphs[0].outputs, graphs[0].extra
         else:
-            _, e = forward()
+            last["flows"], e = forward()
         return e.cpu() if gloo else e
 
     elapsed, results = qdist.timed_steps(run_step, gather, steps, warmup, dev)
@@ -553,6 +571,10 @@ def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_
     total_pairs = global_batch if global_batch else world * B
     if tuple(per_rank.shape) != (world, 6):
         raise RuntimeError("all-gather of the per-level EPE returned {} for {} ranks".format(tuple(per_rank.shape), world))
+    outputs = None
+    if dump:   # copied to the host now, before any later leg replays a graph
+        outputs = {"flow%d" % i: f.float().cpu().numpy() for i, f in enumerate(last["flows"])}
+        outputs["per_level_epe"] = epe_mean.float().cpu().numpy()
 
     res = {
         "metric": metric_name(hw, dtype),
@@ -592,7 +614,7 @@ def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_
     # ---- serving-style throughput, reported BESIDE the headline (never as `value`): two batches
     # in flight, each a hipGraph replay on its own stream, so that the launch-bound coarse levels of
     # one batch run under the encoder / finest level of the other.  Same K steps, same work per step.
-    if headline and graphs is not None and world == 1 and not args.no_inflight:
+    if args.full and headline and graphs is not None and world == 1 and not args.no_inflight:
         n_fly = max(2, args.inflight)
         lanes = [(torch.cuda.Stream(), graphs[0])]
         for k in range(1, n_fly):
@@ -624,7 +646,7 @@ def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_
     # ---- the same step with the fp32 matrix products as three-way bf16 splits on the bf16 matrix instructions
     # (QpwcNet.matmul = "bf16x3", csrc/split_bf16.h): reported BESIDE the headline, which stays on the fp32 matrix
     # instructions; same inputs, same K steps, flows compared with the headline's
-    if headline and graphs is not None and world == 1 and dtype == "f32" and not args.no_inflight and \
+    if args.full and headline and graphs is not None and world == 1 and dtype == "f32" and not args.no_inflight and \
             args.matmul == "f32":
         ref_flows = [f.clone() for f in graphs[0].outputs]
         model.matmul = "bf16x3"
@@ -655,7 +677,7 @@ def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_
         del ref_flows
 
     # ---- the shader clock the chip sustains under this step (reported, never used to scale anything)
-    if headline and graphs is not None and world == 1 and not args.no_inflight:
+    if args.full and headline and graphs is not None and world == 1 and not args.no_inflight:
         try:
             res["sustained_clock"] = sustained_clock(graphs[0].replay, dev, res["ms_per_step"])
         except (RuntimeError, ValueError, AttributeError) as e:
@@ -666,16 +688,17 @@ def measure(args, B, hw, dtype, steps, warmup, world, rank, dev, headline, copy_
             res["config1_kernels_B1"] = {"error": str(e).splitlines()[0][:160]}
 
     # ---- live rooflines (single stream, HIP events)
-    blocks, hot = rooflines(model, pairs, B, hw, dtype, tdtype, dev, args, copy_gbs)
-    # the dominant hot-path launch of THIS step: the fused WarpV2 + cost volume where UpFlow uses it at L4, the
-    # plain cost volume otherwise; the other one stays in rooflines_other (the standalone CostVolume layer and
-    # the coarse levels still launch the plain kernel)
-    fused_dom = blocks.get("warp_cost_volume_fused", {}).get("used_by_the_step_at_L4") is True
-    res["roofline"] = blocks.pop("warp_cost_volume_fused" if fused_dom else "cost_volume")
-    res["rooflines_other"] = blocks
-    res["hot_path"] = hot
+    if args.full:
+        blocks, hot = rooflines(model, pairs, B, hw, dtype, tdtype, dev, args, copy_gbs)
+        # the dominant hot-path launch of THIS step: the fused WarpV2 + cost volume where UpFlow uses it at L4, the
+        # plain cost volume otherwise; the other one stays in rooflines_other (the standalone CostVolume layer and
+        # the coarse levels still launch the plain kernel)
+        fused_dom = blocks.get("warp_cost_volume_fused", {}).get("used_by_the_step_at_L4") is True
+        res["roofline"] = blocks.pop("warp_cost_volume_fused" if fused_dom else "cost_volume")
+        res["rooflines_other"] = blocks
+        res["hot_path"] = hot
     res["whole_step"] = whole_step_block(res, B, hw, dtype, world)
-    return res, (weights, pairs_np, flows)
+    return res, (weights, pairs_np, flows, outputs)
 
 
 GFLOP_PER_PAIR_256x512 = 8.59   # encoder 3.68 + decoder 1.88 + OptFlow 2.71 + cost volume 0.32
@@ -688,6 +711,23 @@ def whole_step_block(res, B, hw, dtype, world):
     tf = gflop / res["ms_per_step"]   # GFLOP / ms = TFLOP/s
     peak = (F32_MFMA_PEAK_TFS if dtype == "f32" else F16_MFMA_PEAK_TFS) * world
     return {"gflop_per_step": round(gflop, 2), "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak}
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+
+
+def dump_outputs(directory, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write every host array as directory/<name>.npy in float32.  An array above its equal share of max_bytes is
+    written as a fixed sample of its flattened elements instead (sorted indices drawn by default_rng(0)), the same
+    elements in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    cap = (max_bytes - 4096 * len(arrays)) // (4 * len(arrays))   # elements per file, .npy headers left aside
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > cap:
+            a = a.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a.size, size=cap))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _r(x, sig=5):
@@ -723,7 +763,8 @@ def compact_line(full):
                                         "fused_upflow") if k in c}
     if c.get("matmul", "f32") != "f32":     # an explicitly requested arithmetic is named in the line
         line["config"]["matmul"] = c["matmul"]
-    line["roofline"] = compact_roofline(full["roofline"])
+    if "roofline" in full:   # measured with --full only
+        line["roofline"] = compact_roofline(full["roofline"])
     cb = full.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {k: _r(cb[k]) for k in ("value", "unit", "cores", "kind")}
@@ -842,7 +883,7 @@ def main():
     torch.backends.cudnn.benchmark = True  # MIOpen find mode (fp16 library convolutions): fastest solver once
 
     info = _hip.build_info()
-    copy_gbs = device_copy_ceiling(dev)
+    copy_gbs = device_copy_ceiling(dev) if args.full else None   # the rooflines' ceiling
     hw = (args.height, args.width)
     batch = args.batch
     if args.global_batch:
@@ -851,20 +892,24 @@ def main():
                 args.global_batch, world))
         lo, hi = qdist.shard_range(args.global_batch, rank, world)
         batch = hi - lo
-    result, (weights, pairs_np, flows) = measure(args, batch, hw, args.dtype, args.steps, args.warmup,
-                                                 world, rank, dev, True, copy_gbs, args.global_batch)
+    result, (weights, pairs_np, flows, outputs) = measure(
+        args, batch, hw, args.dtype, args.steps, args.warmup, world, rank, dev, True, copy_gbs, args.global_batch,
+        dump=bool(args.dump_outputs) and rank == 0)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+        del outputs
     result["library"] = info
     default_run = (world == 1 and batch == 8 and not args.global_batch and hw == (256, 512) and args.dtype == "f32" and
                    args.data_format == "channels_last" and not args.no_graph and args.matmul == "f32")
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base, epe_oracle = cpu_baseline(weights, pairs_np, args.cpu_pairs, args.cpu_reps, flows, hw)
             result["cpu_baseline"] = base
             result["per_level_epe_vs_oracle"] = epe_oracle
         else:
             result["cpu_baseline"] = None
     del flows
-    if default_run and not args.no_extra:
+    if default_run and args.full and not args.no_extra:
         # BASELINE configs[3] and configs[4] on the driver's clock too: same procedure, fewer steps
         # (config 3 is ~25 ms per step), their own roofline blocks; never the headline `value`
         extra = []
@@ -890,18 +935,22 @@ def main():
                 result["per_level_epe_vs_oracle"], PARITY_TOL_PX), file=sys.stderr)
             rc = 3
     elif rank == 0:
-        # said, not silent: this run did not compare its flows with the oracle (--no-cpu-baseline, N > 1 ranks, fp16 or bf16x3)
+        # said, not silent: this run did not compare its flows with the oracle (no --full, --no-cpu-baseline,
+        # N > 1 ranks, fp16 or bf16x3)
         result["parity_gate"] = {"tolerance_px": PARITY_TOL_PX, "pass": None,
-                                 "skipped": "no oracle comparison in this run (the default N=1 fp32 run makes it)"}
+                                 "skipped": "no oracle comparison in this run (the N=1 fp32 run with --full makes it)"}
     if rank == 0:
         result["detail_file"] = None
-        if args.detail:
+        detail = args.detail
+        if detail is None:
+            detail = os.path.join(ROOT, "bench_detail.json") if args.full else ""
+        if detail:
             try:
-                with open(args.detail, "w") as f:
+                with open(detail, "w") as f:
                     json.dump(result, f, indent=1)
-                result["detail_file"] = os.path.relpath(args.detail, ROOT)
+                result["detail_file"] = os.path.relpath(detail, ROOT)
             except OSError as e:
-                print("bench.py: could not write {} ({})".format(args.detail, e), file=sys.stderr)
+                print("bench.py: could not write {} ({})".format(detail, e), file=sys.stderr)
         print(json.dumps(compact_line(result), separators=(",", ":")))
     if world > 1:
         qdist.barrier()

@@ -370,6 +370,52 @@ def test_bench_line_fits_the_drivers_window():
     assert d["matmul_bf16x3"]["value"] == 6967.1 and d["value"] == 6624.861 and "note" not in d["matmul_bf16x3"]
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """A plain run leaves the side legs to --full and its line keeps the headline fields without a roofline;
+    --dump-outputs writes float32 .npy files within 64 MB, the same fixed sample of an array above its share
+    in every run."""
+    import json
+    import os
+    import numpy as np
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs, a.detail) == (7, 2, False, None, None)
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    res = {"metric": bench.metric_name((256, 512), "f32"), "value": 7000.0, "unit": "pairs/s", "n_gpus": 1,
+           "steps": 7, "warmup": 2, "ms_per_step": 1.14, "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "BASELINE configs[1]: ...", "global_batch": 8, "batch_per_gpu": 8,
+                      "parallelism": "dp1", "hipgraph": True, "fused_upflow": [False, True, True, True]},
+           "cpu_baseline": None, "library": {"build": "b", "version": 1, "product": True}, "detail_file": None,
+           "whole_step": bench.whole_step_block({"ms_per_step": 1.14}, 8, (256, 512), "f32", 1)}
+    d = json.loads(json.dumps(bench.compact_line(res)))
+    assert (d["metric"], d["value"], d["unit"], d["higher_is_better"], d["dtype"], d["ms_per_step"]) == \
+        ("image-pairs/sec at 256x512 fp32", 7000.0, "pairs/s", True, "f32", 1.14)
+    assert "roofline" not in d and d["cpu_baseline"] is None
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    rng = np.random.default_rng(3)
+    arrays = {"flow%d" % i: rng.standard_normal((2, 8 << i, 16 << i, 2)).astype(np.float16) for i in range(6)}
+    arrays["per_level_epe"] = np.arange(6, dtype=np.float64)
+    small, big = tmp_path / "small", tmp_path / "big"
+    bench.dump_outputs(str(small), arrays)     # 2.8 MB: every array whole
+    f5 = np.load(str(small / "flow5.npy"))
+    assert f5.dtype == np.float32 and np.array_equal(f5, arrays["flow5"].astype(np.float32))
+    assert np.array_equal(np.load(str(small / "per_level_epe.npy")), np.arange(6, dtype=np.float32))
+    budget = 1 << 20
+    for run in ("1", "2"):
+        bench.dump_outputs(str(big / run), arrays, max_bytes=budget)
+    files = sorted(os.listdir(str(big / "1")))
+    assert files == sorted(n + ".npy" for n in arrays)
+    assert sum(os.path.getsize(str(big / "1" / f)) for f in files) <= budget
+    for f in files:
+        x, y = np.load(str(big / "1" / f)), np.load(str(big / "2" / f))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    flat = arrays["flow5"].astype(np.float32).reshape(-1)
+    s = np.load(str(big / "1" / "flow5.npy"))
+    assert s.ndim == 1 and 0 < s.size < flat.size and np.isin(s, flat).all()
+
+
 def test_decoder_side_stream_mapping_must_not_return_to_an_earlier_stream():
     """Round 3: a two-stream forward whose decoder levels alternate between two side streams makes the runtime crash
     during hipGraph capture (the round-1 multi-stream crash, reproduced once in its own process by

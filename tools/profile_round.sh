@@ -5,7 +5,7 @@
 #   2. tools/kbench.py at the level shapes of BASELINE configs 2, 4 and 5 -> <tag>_kbench*.json
 #   3. bench.py under rocprofv3 --kernel-trace --stats -> <tag>_bench_under_rocprofv3.json, kernel stats, per-grid
 #      durations, steady-state stats, one forward's timeline
-#   4. bench.py (the line the driver will see; roofline.traffic now matches the kernel sources) -> <tag>_bench.json
+#   4. bench.py --full (the whole line; roofline.traffic now matches the kernel sources) -> <tag>_bench.json
 set -u
 tag=${1:-r03}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -21,7 +21,7 @@ python3 tools/kbench.py --batch 32 --dtype f16 --json profiles/${tag}_kbench_con
 prof=$root/gpurun_out/prof_$tag
 rm -rf "$prof"
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$prof" -- \
-    python3 "$root/bench.py" --no-extra --no-cpu-baseline --no-inflight --detail "" \
+    python3 "$root/bench.py" --full --no-extra --no-cpu-baseline --no-inflight --detail "" \
     > "$root/profiles/${tag}_bench_under_rocprofv3.json" 2> "$root/$out/rocprof_bench.err" ) || echo "rocprofv3 bench failed"
 trace=$(find "$prof" -name '*kernel_trace.csv' | head -1)
 stats=$(find "$prof" -name '*kernel_stats.csv' | head -1)
@@ -32,7 +32,7 @@ if [ -n "$trace" ]; then
   python3 tools/ktrace.py "$prof" "$out/timeline.csv" 4000 > /dev/null 2>&1
   python3 tools/fwd_timeline.py "$out/timeline.csv" profiles/${tag}_forward_timeline.txt > /dev/null 2>&1
 fi
-python3 bench.py > profiles/${tag}_bench.json 2> "$out/bench.err"
+python3 bench.py --full > profiles/${tag}_bench.json 2> "$out/bench.err"
 cp bench_detail.json profiles/${tag}_bench_detail.json 2>/dev/null
 cp profiles/${tag}_* profiles/traffic.json "$out/" 2>/dev/null
 tail -c 600 profiles/${tag}_bench.json

@@ -13,7 +13,7 @@ mkdir -p "$out"
 prof=$root/gpurun_out/prof_x3_$tag
 rm -rf "$prof"
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$prof" -- \
-    python3 "$root/bench.py" --matmul bf16x3 --no-extra --no-cpu-baseline --no-inflight --detail "" \
+    python3 "$root/bench.py" --full --matmul bf16x3 --no-extra --no-cpu-baseline --no-inflight --detail "" \
     > "$root/$out/${tag}_x3_bench_under_rocprofv3.json" 2> "$root/$out/rocprof_bench.err" ) || echo "rocprofv3 bench failed"
 trace=$(find "$prof" -name '*kernel_trace.csv' | head -1)
 if [ -n "$trace" ]; then
