@@ -129,6 +129,40 @@ int qpwc_warp_fwd(const void* img, const void* flo, void* out,
                   int B, int H, int W, int C, int flo_bcast_mask,
                   int layout, int dtype, int mode, void* stream);
 
+/* ---- Backward passes (training through the layers; the reference trains with them through TF autograd,
+ * qpwcnet/app/optical_flow/train.py, qpwcnet/train/loss.py).  NHWC, dense; fp32 or fp16 storage, fp32 accumulation. */
+
+/* CostVolume / CostVolumeV2 backward: the gradient of qpwc_cost_volume_fwd (layers.py:72-100, 128-132) with
+ * g' = grad_out * (out > 0 ? 1 : slope), out the saved forward output (for slope > 0 the sign of the pre-activation;
+ * slope at exactly 0, as tf.nn.leaky_relu's gradient, layers.py:99, 131):
+ *   grad_prv[b,y,x,c]   = (1/C) sum_ij g'[b,y,x,ij] nxt[b,y+i-r,x+j-r,c]
+ *   grad_nxt[b,y',x',c] = (1/C) sum_ij g'[b,y'-i+r,x'-j+r,ij] prv[b,y'-i+r,x'-j+r,c]  (source pixels inside the image)
+ * prv, nxt, grad_prv, grad_nxt: (B,H,W,C); out, grad_out: (B,H,W,d*d); all of `dtype`.  Either gradient may be NULL
+ * (not both).  lrelu_slope must be >= 0 (QPWC_E_RANGE otherwise: with a negative slope out > 0 is not the sign
+ * of the pre-activation).  Gathers only: the result is bitwise reproducible. */
+int qpwc_cost_volume_bwd(const void* prv, const void* nxt, const void* out, const void* grad_out,
+                         void* grad_prv, void* grad_nxt, int B, int H, int W, int C, int search_range,
+                         int dtype, float lrelu_slope, void* stream);
+
+/* Floats of device scratch qpwc_warp_bwd needs for grad_img: 0 for fp32, B*H*W*C for fp16 (the fp32 accumulation
+ * target, cast once); negative QPWC_E_* for bad arguments. */
+int64_t qpwc_warp_bwd_workspace_floats(int B, int H, int W, int C, int dtype);
+
+/* Warp / WarpV2 backward: the gradient of qpwc_warp_fwd (NHWC, flo dense (B,H,W,2) fp32).
+ *   mode CLAMP  (WarpV2, layers.py:177-186; tfa interpolate_bilinear, warp.py:157-185,207): floor = clamp(floor(q),
+ *               0, size-2) carries no gradient, alpha = clamp(q - floor, 0, 1) passes it on [0, 1] -- a coordinate
+ *               outside [0, size-1] gets zero flow gradient, an exact integer the one-sided (forward) difference.
+ *               H, W >= 2 as in the forward (QPWC_E_SHAPE otherwise).
+ *   mode TFWARP (Warp / tf_warp, warp.py:100-151): truncated, clipped corner indices carry no gradient; the raw
+ *               weights wa..wd (warp.py:139-142) carry it through the float x, y; coinciding clipped corners each
+ *               receive their weight.
+ * grad_flo: fp32 (B,H,W,2), a per-pixel reduction over C (deterministic).  grad_img: (B,H,W,C) of `dtype`, zeroed by
+ * this call on `stream`, then the weighted corner contributions are scattered with float atomics (fp16: into
+ * `workspace`, qpwc_warp_bwd_workspace_floats() floats, cast once).  Either gradient may be NULL (not both). */
+int qpwc_warp_bwd(const void* img, const void* flo, const void* grad_out,
+                  void* grad_img, void* grad_flo, void* workspace, int B, int H, int W, int C,
+                  int dtype, int mode, void* stream);
+
 /* UpFlow front end in one launch (non_layers.py:377-385):
  *   nxt_w = WarpV2(nxt, flo); cost = CostVolumeV2(prv, nxt_w)
  * without materialising nxt_w.  NHWC, mode CLAMP, flo dense (B,H,W,2) fp32,

@@ -30,6 +30,7 @@ SYMBOLS = (
     "qpwc_cost_volume_to_flow_fwd", "qpwc_sepconv3x3_fwd", "qpwc_sepconv3x3_f16_fwd", "qpwc_bias_mish_pad_fwd", "qpwc_split_frames_pad_fwd",
     "qpwc_invert_flow_fwd", "qpwc_occlusion_fwd", "qpwc_conv3x3_mish_fwd", "qpwc_conv3x3_mish_f16_fwd", "qpwc_conv3x3_mish_x3_fwd", "qpwc_split_bf16x3_fwd", "qpwc_sepconv3x3_x3_fwd", "qpwc_conv3x3s2_mish_x3_fwd", "qpwc_upconv4x4s2_mish_x3_fwd",
     "qpwc_first_conv_mish_fwd", "qpwc_first_conv_mish_f16_fwd", "qpwc_conv3x3s2_mish_fwd", "qpwc_conv3x3s2_mish_c_fwd", "qpwc_conv3x3s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_fwd", "qpwc_upconv4x4s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_cat_fwd", "qpwc_upconv4x4s2_mish_cat_f16_fwd",
+    "qpwc_cost_volume_bwd", "qpwc_warp_bwd_workspace_floats", "qpwc_warp_bwd",
 )
 
 _lib = None
@@ -166,6 +167,12 @@ def lib():
     L.qpwc_upconv4x4s2_mish_cat_fwd.restype = ci
     L.qpwc_upconv4x4s2_mish_cat_f16_fwd.argtypes = L.qpwc_upconv4x4s2_mish_cat_fwd.argtypes
     L.qpwc_upconv4x4s2_mish_cat_f16_fwd.restype = ci
+    L.qpwc_cost_volume_bwd.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]
+    L.qpwc_cost_volume_bwd.restype = ci
+    L.qpwc_warp_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci]
+    L.qpwc_warp_bwd_workspace_floats.restype = i64
+    L.qpwc_warp_bwd.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+    L.qpwc_warp_bwd.restype = ci
     _lib = L
     return L
 

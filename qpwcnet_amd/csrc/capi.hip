@@ -104,6 +104,10 @@ int first_conv_mish_launch(const void* x, const void* weight, const void* bias, 
 int conv3x3s2_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                           hipStream_t s);
 int bias_mish_launch(void* x, const void* bias, int64_t n_pixels, int C, int dtype, hipStream_t s);
+int cost_volume_bwd_launch(const void* prv, const void* nxt, const void* out, const void* gout, void* gprv,
+                           void* gnxt, int B, int H, int W, int C, int r, int dtype, float slope, hipStream_t s);
+int warp_bwd_launch(const void* img, const void* flo, const void* gout, void* gimg, void* gflo, void* ws, int B,
+                    int H, int W, int C, int dtype, int mode, hipStream_t s);
 
 // 16-byte-per-lane streaming copy: the box's achievable HBM ceiling (read + write) for bench.py's roofline
 // block.  tools/micro/copybench.hip on MI355X: one float4 per thread over a one-shot grid with non-temporal
@@ -333,6 +337,72 @@ int qpwc_warp_fwd(const void* img, const void* flo, void* out, int B, int H, int
         return fail(QPWC_E_ALIAS, "out overlaps an input");
     return warp_launch(img, flo, out, B, H, W, C, flo_bcast_mask, layout, dtype, mode,
                        (hipStream_t)stream);
+}
+
+int qpwc_cost_volume_bwd(const void* prv, const void* nxt, const void* out, const void* grad_out, void* grad_prv,
+                         void* grad_nxt, int B, int H, int W, int C, int search_range, int dtype, float lrelu_slope,
+                         void* stream) {
+    if (!prv || !nxt || !out || !grad_out || (!grad_prv && !grad_nxt)) return fail(QPWC_E_NULL, "null pointer argument");
+    int rc = check_common(B, H, W, C, QPWC_NHWC, dtype);
+    if (rc != QPWC_OK) return rc;
+    if (search_range < 0 || search_range > 16) return fail(QPWC_E_RANGE, "search_range %d outside [0,16]", search_range);
+    // the mask is read from the saved output as out > 0: the sign of the pre-activation only for slope >= 0
+    if (!(lrelu_slope >= 0.0f)) return fail(QPWC_E_RANGE, "lrelu_slope %g: the backward needs slope >= 0", (double)lrelu_slope);
+    const size_t es = esize(dtype);
+    if ((uintptr_t)prv % es || (uintptr_t)nxt % es || (uintptr_t)out % es || (uintptr_t)grad_out % es ||
+        (uintptr_t)grad_prv % es || (uintptr_t)grad_nxt % es)
+        return fail(QPWC_E_ALIGN, "pointer not aligned to its element size");
+    const int64_t DD = (int64_t)(2 * search_range + 1) * (2 * search_range + 1);
+    const size_t n_in = (size_t)B * H * W * C * es, n_cv = (size_t)B * H * W * DD * es;
+    const void* ins[4] = {prv, nxt, out, grad_out};
+    const size_t ns[4] = {n_in, n_in, n_cv, n_cv};
+    for (void* g : {grad_prv, grad_nxt}) {
+        if (!g) continue;
+        for (int i = 0; i < 4; ++i)
+            if (overlaps(g, n_in, ins[i], ns[i])) return fail(QPWC_E_ALIAS, "a gradient buffer overlaps an input");
+    }
+    if (grad_prv && grad_nxt && overlaps(grad_prv, n_in, grad_nxt, n_in))
+        return fail(QPWC_E_ALIAS, "grad_prv overlaps grad_nxt");
+    return cost_volume_bwd_launch(prv, nxt, out, grad_out, grad_prv, grad_nxt, B, H, W, C, search_range, dtype,
+                                  lrelu_slope, (hipStream_t)stream);
+}
+
+int64_t qpwc_warp_bwd_workspace_floats(int B, int H, int W, int C, int dtype) {
+    if (dtype != QPWC_F32 && dtype != QPWC_F16) return fail(QPWC_E_DTYPE, "unsupported dtype %d", dtype);
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0)
+        return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d C=%d", B, H, W, C);
+    return dtype == QPWC_F32 ? 0 : (int64_t)B * H * W * C;
+}
+
+int qpwc_warp_bwd(const void* img, const void* flo, const void* grad_out, void* grad_img, void* grad_flo,
+                  void* workspace, int B, int H, int W, int C, int dtype, int mode, void* stream) {
+    if (!img || !flo || !grad_out || (!grad_img && !grad_flo)) return fail(QPWC_E_NULL, "null pointer argument");
+    int rc = check_common(B, H, W, C, QPWC_NHWC, dtype);
+    if (rc != QPWC_OK) return rc;
+    if (mode != QPWC_WARP_CLAMP && mode != QPWC_WARP_TFWARP) return fail(QPWC_E_MODE, "unknown warp mode %d", mode);
+    if (mode == QPWC_WARP_CLAMP && (H < 2 || W < 2))
+        return fail(QPWC_E_SHAPE, "Grid must be at least 2x2 (got %dx%d)", H, W);
+    const bool need_ws = grad_img && dtype == QPWC_F16;
+    if (need_ws && !workspace) return fail(QPWC_E_NULL, "fp16 grad_img needs the fp32 workspace");
+    const size_t es = esize(dtype);
+    if ((uintptr_t)img % es || (uintptr_t)grad_out % es || (uintptr_t)grad_img % es || (uintptr_t)flo % 4 ||
+        (uintptr_t)grad_flo % 4 || (need_ws && (uintptr_t)workspace % 4))
+        return fail(QPWC_E_ALIGN, "pointer not aligned to its element size");
+    const size_t n = (size_t)B * H * W * C * es, nf = (size_t)B * H * W * 2 * 4, nw = (size_t)B * H * W * C * 4;
+    const void* ins[3] = {img, flo, grad_out};
+    const size_t ns[3] = {n, nf, n};
+    void* outs[3] = {grad_img, grad_flo, need_ws ? workspace : nullptr};
+    const size_t no[3] = {n, nf, nw};
+    for (int o = 0; o < 3; ++o) {
+        if (!outs[o]) continue;
+        for (int i = 0; i < 3; ++i)
+            if (overlaps(outs[o], no[o], ins[i], ns[i])) return fail(QPWC_E_ALIAS, "a gradient buffer overlaps an input");
+        for (int k = o + 1; k < 3; ++k)
+            if (outs[k] && overlaps(outs[o], no[o], outs[k], no[k]))
+                return fail(QPWC_E_ALIAS, "gradient / workspace buffers overlap each other");
+    }
+    return warp_bwd_launch(img, flo, grad_out, grad_img, grad_flo, need_ws ? workspace : nullptr, B, H, W, C, dtype,
+                           mode, (hipStream_t)stream);
 }
 
 int qpwc_epe_workspace_floats(void) { return epe_workspace_floats(); }

@@ -187,8 +187,89 @@ def _nchw_fast_path(C, search_range=4):
     return C % 4 == 0 and search_range == 4
 
 
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def _refuse_capture(what):
+    """The differentiable path is not capturable yet: a torch.cuda.graph holding this forward and its backward
+    crashed in the graph instantiation on MI355X / ROCm, with the cause not isolated.  Refuse with
+    a clear error, before anything of ours is enqueued, instead of taking the process down.  The no-grad path (the
+    network's inference graphs) is not affected."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(
+            "qpwcnet_amd: {} with autograd cannot be captured in a torch.cuda graph yet; capture the no-grad "
+            "forward (torch.no_grad()) or run the training step eagerly".format(what))
+
+
+def _to_nhwc(t, data_format):
+    """Dense (B,H,W,C) form of a layer operand or gradient for the channels-last backward kernels: a channels_first
+    tensor that is physically NHWC (torch channels_last memory) through its permuted view, else transposed."""
+    if data_format == CHANNELS_LAST:
+        return t.contiguous()
+    v = t.permute(0, 2, 3, 1)
+    return v if v.is_contiguous() else layout_transpose(t, CHANNELS_LAST)
+
+
+def _from_nhwc(t, data_format):
+    return t if data_format == CHANNELS_LAST else t.permute(0, 3, 1, 2)
+
+
+class _CostVolumeFn(torch.autograd.Function):
+    """cost_volume() with qpwc_cost_volume_bwd as its gradient: the forward is the no-grad forward itself."""
+
+    @staticmethod
+    def forward(ctx, prv, nxt, search_range, data_format, lrelu_slope):
+        out = cost_volume(prv, nxt, search_range, data_format, lrelu_slope)
+        ctx.save_for_backward(prv, nxt, out)
+        ctx.cfg = (int(search_range), data_format, float(lrelu_slope))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the cost-volume backward")
+        prv, nxt, out = ctx.saved_tensors
+        r, fmt, slope = ctx.cfg
+        need_p, need_n = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gp, gn = cost_volume_bwd(_to_nhwc(prv, fmt), _to_nhwc(nxt, fmt), _to_nhwc(out, fmt),
+                                 _to_nhwc(grad_out.to(out.dtype), fmt), r, slope, need_p, need_n)
+        return (_from_nhwc(gp, fmt) if need_p else None, _from_nhwc(gn, fmt) if need_n else None, None, None, None)
+
+
+def cost_volume_bwd(prv, nxt, out, grad_out, search_range=4, lrelu_slope=0.1, need_prv=True, need_nxt=True):
+    """(grad_prv, grad_nxt) of cost_volume() for dense NHWC operands (qpwc_cost_volume_bwd); out = the saved forward
+    output.  A gradient that is not asked for comes back as None."""
+    for name, t in (("prv", prv), ("nxt", nxt), ("out", out), ("grad_out", grad_out)):
+        _check_tensor(name, t)
+        if t.dtype != prv.dtype or not t.is_contiguous():
+            raise ValueError("cost_volume_bwd takes dense NHWC tensors of one dtype")
+    B, H, W, C = prv.shape
+    d = 2 * int(search_range) + 1
+    if nxt.shape != prv.shape or tuple(out.shape) != (B, H, W, d * d) or out.shape != grad_out.shape:
+        raise ValueError("cost_volume_bwd: shapes {} {} {} {}".format(
+            tuple(prv.shape), tuple(nxt.shape), tuple(out.shape), tuple(grad_out.shape)))
+    gp = torch.empty_like(prv) if need_prv else None
+    gn = torch.empty_like(nxt) if need_nxt else None
+    with torch.cuda.device(prv.device), _timed("cost_volume_bwd", (B, H, W, C)):
+        rc = _hip.lib().qpwc_cost_volume_bwd(
+            prv.data_ptr(), nxt.data_ptr(), out.data_ptr(), grad_out.data_ptr(),
+            gp.data_ptr() if need_prv else None, gn.data_ptr() if need_nxt else None, B, H, W, C, int(search_range),
+            _DTYPES[prv.dtype], float(lrelu_slope), _stream(prv))
+    _hip.check(rc)
+    return gp, gn
+
+
 def cost_volume(prv, nxt, search_range=4, data_format=CHANNELS_LAST, lrelu_slope=0.1):
-    """CostVolume / CostVolumeV2 forward (reference: qpwcnet/core/layers.py:72-100,128-132)."""
+    """CostVolume / CostVolumeV2 forward (reference: qpwcnet/core/layers.py:72-100,128-132).
+    Differentiable in prv and nxt: with grad enabled and an input requiring grad the same forward runs inside an
+    autograd Function whose backward is qpwc_cost_volume_bwd (lrelu_slope >= 0 there: the backward reads the
+    LeakyReLU mask from the saved output as out > 0)."""
+    if _wants_grad(prv, nxt):
+        if not float(lrelu_slope) >= 0.0:
+            raise ValueError("the cost-volume gradient needs lrelu_slope >= 0 (got {})".format(lrelu_slope))
+        _refuse_capture("the cost volume")
+        return _CostVolumeFn.apply(prv, nxt, search_range, data_format, lrelu_slope)
     _check_tensor("prv", prv)
     _check_tensor("nxt", nxt)
     if prv.shape != nxt.shape:
@@ -275,9 +356,89 @@ def _flow_physical(flo, dims, data_format, layout):
     return f.contiguous(), mask
 
 
+class _WarpFn(torch.autograd.Function):
+    """warp() with qpwc_warp_bwd as its gradient.  flo arrives fp32 and expanded to the image's (B,H,W) by torch ops
+    outside (autograd reduces and casts the flow gradient back); the forward is the no-grad forward itself."""
+
+    @staticmethod
+    def forward(ctx, img, flo, mode, data_format):
+        out = warp(img, flo, mode, data_format)
+        ctx.save_for_backward(img, flo)
+        ctx.cfg = (mode, data_format)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the warp backward")
+        img, flo = ctx.saved_tensors
+        mode, fmt = ctx.cfg
+        need_i, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gi, gf = warp_bwd(_to_nhwc(img, fmt), _to_nhwc(flo, fmt), _to_nhwc(grad_out.to(img.dtype), fmt), mode,
+                          need_i, need_f)
+        return (_from_nhwc(gi, fmt) if need_i else None, _from_nhwc(gf, fmt) if need_f else None, None, None)
+
+
+def warp_bwd(img, flo, grad_out, mode="clamp", need_img=True, need_flo=True):
+    """(grad_img, grad_flo) of warp() for a dense NHWC image / grad_out and a dense fp32 (B,H,W,2) flow
+    (qpwc_warp_bwd); grad_flo is fp32.  A gradient that is not asked for comes back as None."""
+    _check_tensor("img", img)
+    _check_tensor("grad_out", grad_out)
+    if grad_out.dtype != img.dtype or grad_out.shape != img.shape or not (img.is_contiguous() and grad_out.is_contiguous()):
+        raise ValueError("warp_bwd takes a dense NHWC image and grad_out of one shape and dtype")
+    B, H, W, C = img.shape
+    if tuple(flo.shape) != (B, H, W, 2) or flo.dtype != torch.float32 or not flo.is_contiguous() or flo.device != img.device:
+        raise ValueError("warp_bwd takes a dense fp32 (B,H,W,2) flow on the image's device")
+    if mode not in ("clamp", "tfwarp"):
+        raise ValueError("unknown warp mode '{}'".format(mode))
+    L = _hip.lib()
+    dt = _DTYPES[img.dtype]
+    gi = torch.empty_like(img) if need_img else None
+    gf = torch.empty((B, H, W, 2), dtype=torch.float32, device=img.device) if need_flo else None
+    nws = L.qpwc_warp_bwd_workspace_floats(B, H, W, C, dt) if need_img else 0
+    _hip.check(min(int(nws), 0))
+    ws = torch.empty(nws, dtype=torch.float32, device=img.device) if nws > 0 else None
+    with torch.cuda.device(img.device), _timed("warp_bwd_" + mode, (B, H, W, C)):
+        rc = L.qpwc_warp_bwd(img.data_ptr(), flo.data_ptr(), grad_out.data_ptr(), gi.data_ptr() if need_img else None,
+                             gf.data_ptr() if need_flo else None, ws.data_ptr() if ws is not None else None, B, H, W, C,
+                             dt, _hip.WARP_CLAMP if mode == "clamp" else _hip.WARP_TFWARP, _stream(img))
+    _hip.check(rc)
+    return gi, gf
+
+
+def _grad_flow(flo, img, data_format):
+    """The flow as _WarpFn takes it: fp32, expanded to the image's batch and pixels (torch ops, so that autograd
+    reduces a broadcast flow's gradient and casts an fp16 flow's back)."""
+    if not isinstance(flo, torch.Tensor) or flo.dim() != 4:
+        raise ValueError("flo must be a rank 4 tensor")
+    if data_format == CHANNELS_LAST:
+        B, H, W = img.shape[0], img.shape[1], img.shape[2]
+        full = (B, H, W, 2)
+    else:
+        B, H, W = img.shape[0], img.shape[2], img.shape[3]
+        full = (B, 2, H, W)
+    # An fp16 flow from flow_head_up() carries an fp32 side copy (_qpwc_f32) that the no-grad path reads; it holds
+    # exactly flo.float() (fp16 -> fp32 is exact), so this cast gives the same forward bits, and unlike the side
+    # copy it stays connected to flo in the autograd graph.
+    f = flo.to(torch.float32)
+    try:
+        return f.expand(full)
+    except RuntimeError:
+        raise ValueError("flo shape {} is not broadcastable to the image".format(tuple(flo.shape)))
+
+
 def warp(img, flo, mode="clamp", data_format=CHANNELS_LAST):
     """Warp (mode 'tfwarp', qpwcnet/core/warp.py:63-153) / WarpV2 (mode 'clamp',
-    qpwcnet/core/layers.py:177-186): sample img at (y + flo[...,1], x + flo[...,0])."""
+    qpwcnet/core/layers.py:177-186): sample img at (y + flo[...,1], x + flo[...,0]).
+    Differentiable in img and flo: with grad enabled and an input requiring grad the same forward runs inside an
+    autograd Function whose backward is qpwc_warp_bwd."""
+    if _wants_grad(img, flo):
+        _refuse_capture("the warp")
+        _check_tensor("img", img)
+        get_axis(data_format)
+        if mode not in ("clamp", "tfwarp"):
+            raise ValueError("unknown warp mode '{}'".format(mode))
+        return _WarpFn.apply(img, _grad_flow(flo, img, data_format), mode, data_format)
     _check_tensor("img", img)
     if not isinstance(flo, torch.Tensor) or not flo.is_cuda or flo.device != img.device:
         raise RuntimeError("flo must be a tensor on the same HIP device as img")
