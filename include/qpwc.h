@@ -163,6 +163,50 @@ int qpwc_warp_bwd(const void* img, const void* flo, const void* grad_out,
                   void* grad_img, void* grad_flo, void* workspace, int B, int H, int W, int C,
                   int dtype, int mode, void* stream);
 
+/* ---- Training losses (qpwcnet/train/loss.py; train.py:98-122 sums one per prediction level).  One full-resolution
+ * ground truth y_true (B,H,W,C) / (B,C,H,W) fp32 against n_levels (1..8) predictions y_pred[l] (B,h[l],w[l],C) /
+ * (B,C,h[l],w[l]) of the same layout, storage pred_dtype[l] (QPWC_F32 / QPWC_F16), all dense; fp32 arithmetic.
+ * The ground truth of level l is y_true resampled to (h[l], w[l]) and, for the flow losses, multiplied by h[l] / H on
+ * BOTH channels (the reference's flow scale, kept as it is even when H / h != W / w). */
+#define QPWC_LOSS_FLOW_MSE_V2 0    /* FlowMseLossV2 (loss.py:134-174): area mean over sh x sw blocks (sh = H/h,
+                                    * sw = W/w: H % h == W % w == 0), Keras Huber(delta = p0, the reference's 0.1) of
+                                    * s*gt - s*pred with s = 2/(w+h), quadratic at |e| <= delta; mean over elements */
+#define QPWC_LOSS_FLOW_MSE 1       /* FlowMseLoss (loss.py:25-82): bilinear (tf.image.resize, half-pixel centres, no
+                                    * antialias), ||gt - pred||_2 over the 2 channels, mean over pixels.  Gradient at
+                                    * a zero residual: 0 (TF gives NaN there; train.py:120 replaces NaN gradients by 0) */
+#define QPWC_LOSS_FLOW_FINETUNE 2  /* FlowMseLossFineTune (loss.py:85-131): bilinear, (||gt - pred||_1 + eps)^q with
+                                    * q = p0, eps = p1, mean over pixels; the L1 norm's gradient uses sign(0) = 0 */
+#define QPWC_LOSS_AUTORESIZE_MSE 3 /* AutoResizeMseLoss (loss.py:177-197): bilinear, no flow scale, any C, squared
+                                    * error, mean over elements */
+
+/* Floats of device scratch qpwc_loss_fwd needs (the per-level partial sums); negative QPWC_E_* for bad arguments. */
+int64_t qpwc_loss_workspace_floats(int kind, int B, int H, int W, int C, const int* h, const int* w, int n_levels);
+
+/* out_losses[l] = loss of level l (n_levels fp32), in two launches for all levels: one partial-sum kernel (the area
+ * loss reads y_true once for every level when the factors are nested powers of two: 32x32 tiles, H % 32 == W % 32 ==
+ * 0, sh*sw >= 4, y_true 16-byte aligned; otherwise one thread per predicted pixel) and one fixed-order fold.
+ * Bitwise reproducible: no atomics, fixed grids.
+ * dpred: NULL, or n_levels fp32 buffers shaped like y_pred[l]: written with d out_losses[l] / d y_pred[l].
+ * gt_out: NULL, or n_levels fp32 buffers (NULL entries skipped) shaped like y_pred[l] with y_true's C: written with
+ * level l's resampled, flow-scaled ground truth.  y_pred[l] may be NULL where gt_out[l] is not (the prediction is
+ * then taken as zero).  Outputs and workspace (qpwc_loss_workspace_floats()) must not overlap the inputs or each
+ * other.  Errors: QPWC_E_MODE kind, QPWC_E_LAYOUT layout, QPWC_E_DTYPE pred_dtype, QPWC_E_SHAPE n_levels outside
+ * 1..8 / extents / C != 2 for a flow loss / an area factor that does not divide, QPWC_E_RANGE delta < 0,
+ * QPWC_E_NULL, QPWC_E_ALIGN, QPWC_E_ALIAS. */
+int qpwc_loss_fwd(int kind, float p0, float p1, const void* y_true, int B, int H, int W, int C, int layout,
+                  const void* const* y_pred, const int* h, const int* w, const int* pred_dtype, int n_levels,
+                  void* out_losses, void* const* dpred, void* const* gt_out, void* workspace, void* stream);
+
+/* The kernel qpwc_loss_fwd launches for these arguments ("loss_area_tile_kernel" / "loss_pixel_kernel"), "" for
+ * arguments it refuses (host only). */
+const char* qpwc_loss_fwd_kernel(int kind, const void* y_true, int B, int H, int W, int C, const int* h, const int* w,
+                                 int n_levels);
+
+/* Backward of qpwc_loss_fwd in one launch: grad_pred[l][i] = grad_losses[l] * dpred[l][i] (n_elems[l] elements;
+ * grad_losses: n_levels fp32 on the device), stored in pred_dtype[l]. */
+int qpwc_loss_bwd(const void* const* dpred, const void* grad_losses, void* const* grad_pred, const int64_t* n_elems,
+                  const int* pred_dtype, int n_levels, void* stream);
+
 /* UpFlow front end in one launch (non_layers.py:377-385):
  *   nxt_w = WarpV2(nxt, flo); cost = CostVolumeV2(prv, nxt_w)
  * without materialising nxt_w.  NHWC, mode CLAMP, flo dense (B,H,W,2) fp32,

@@ -15,6 +15,7 @@ NHWC, NCHW = 0, 1
 F32, F16 = 0, 1
 WARP_CLAMP, WARP_TFWARP = 0, 1
 BCAST_B, BCAST_H, BCAST_W = 1, 2, 4
+LOSS_FLOW_MSE_V2, LOSS_FLOW_MSE, LOSS_FLOW_FINETUNE, LOSS_AUTORESIZE_MSE = 0, 1, 2, 3
 
 E_NULL, E_LAYOUT, E_DTYPE, E_SHAPE, E_RANGE, E_MODE, E_ALIAS, E_LAUNCH, E_ALIGN, E_STRIDE, \
     E_NODEVICE = range(-1, -12, -1)
@@ -31,6 +32,7 @@ SYMBOLS = (
     "qpwc_invert_flow_fwd", "qpwc_occlusion_fwd", "qpwc_conv3x3_mish_fwd", "qpwc_conv3x3_mish_f16_fwd", "qpwc_conv3x3_mish_x3_fwd", "qpwc_split_bf16x3_fwd", "qpwc_sepconv3x3_x3_fwd", "qpwc_conv3x3s2_mish_x3_fwd", "qpwc_upconv4x4s2_mish_x3_fwd",
     "qpwc_first_conv_mish_fwd", "qpwc_first_conv_mish_f16_fwd", "qpwc_conv3x3s2_mish_fwd", "qpwc_conv3x3s2_mish_c_fwd", "qpwc_conv3x3s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_fwd", "qpwc_upconv4x4s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_cat_fwd", "qpwc_upconv4x4s2_mish_cat_f16_fwd",
     "qpwc_cost_volume_bwd", "qpwc_warp_bwd_workspace_floats", "qpwc_warp_bwd",
+    "qpwc_loss_workspace_floats", "qpwc_loss_fwd", "qpwc_loss_fwd_kernel", "qpwc_loss_bwd",
 )
 
 _lib = None
@@ -173,6 +175,15 @@ def lib():
     L.qpwc_warp_bwd_workspace_floats.restype = i64
     L.qpwc_warp_bwd.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
     L.qpwc_warp_bwd.restype = ci
+    pi, pvp = ctypes.POINTER(ci), ctypes.POINTER(vp)
+    L.qpwc_loss_workspace_floats.argtypes = [ci, ci, ci, ci, ci, pi, pi, ci]
+    L.qpwc_loss_workspace_floats.restype = i64
+    L.qpwc_loss_fwd.argtypes = [ci, cf, cf, vp, ci, ci, ci, ci, ci, pvp, pi, pi, pi, ci, vp, pvp, pvp, vp, vp]
+    L.qpwc_loss_fwd.restype = ci
+    L.qpwc_loss_fwd_kernel.argtypes = [ci, vp, ci, ci, ci, ci, pi, pi, ci]
+    L.qpwc_loss_fwd_kernel.restype = ctypes.c_char_p
+    L.qpwc_loss_bwd.argtypes = [pvp, vp, pvp, ctypes.POINTER(i64), pi, ci, vp]
+    L.qpwc_loss_bwd.restype = ci
     _lib = L
     return L
 

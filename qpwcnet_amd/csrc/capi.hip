@@ -108,6 +108,13 @@ int cost_volume_bwd_launch(const void* prv, const void* nxt, const void* out, co
                            void* gnxt, int B, int H, int W, int C, int r, int dtype, float slope, hipStream_t s);
 int warp_bwd_launch(const void* img, const void* flo, const void* gout, void* gimg, void* gflo, void* ws, int B,
                     int H, int W, int C, int dtype, int mode, hipStream_t s);
+int64_t loss_workspace_floats(int n_levels);
+const char* loss_fwd_kernel(int kind, int H, int W, const int* h, const int* w, int n, const void* gt);
+int loss_fwd_launch(int kind, float p0, float p1, const float* gt, int B, int H, int W, int C, int layout,
+                    const void* const* pred, const int* h, const int* w, const int* pred_dtype, int n, float* out,
+                    void* const* dpred, void* const* gt_out, float* ws, hipStream_t s);
+int loss_bwd_launch(const void* const* dpred, const float* grad_losses, void* const* grad_pred, const int64_t* n_elems,
+                    const int* pred_dtype, int n, hipStream_t s);
 
 // 16-byte-per-lane streaming copy: the box's achievable HBM ceiling (read + write) for bench.py's roofline
 // block.  tools/micro/copybench.hip on MI355X: one float4 per thread over a one-shot grid with non-temporal
@@ -174,6 +181,23 @@ static int cost_volume_checked(const void* prv, const void* nxt, const void* flo
     const bool pad84 = strided && r == 4 && ops == 84 && off == 0;
     return cost_volume_launch(prv, nxt, flo, o, B, H, W, C, r, layout, dtype, ops, slope, fuse, pad84,
                               (hipStream_t)stream);
+}
+
+// the shape rules of the training losses, shared by qpwc_loss_workspace_floats / _fwd / _fwd_kernel
+static int loss_check_shapes(int kind, int B, int H, int W, int C, const int* h, const int* w, int n_levels) {
+    if (kind < QPWC_LOSS_FLOW_MSE_V2 || kind > QPWC_LOSS_AUTORESIZE_MSE) return fail(QPWC_E_MODE, "unknown loss kind %d", kind);
+    if (!h || !w) return fail(QPWC_E_NULL, "null pointer argument");
+    if (n_levels < 1 || n_levels > 8) return fail(QPWC_E_SHAPE, "n_levels %d outside [1,8]", n_levels);
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0)
+        return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d C=%d", B, H, W, C);
+    if (kind != QPWC_LOSS_AUTORESIZE_MSE && C != 2) return fail(QPWC_E_SHAPE, "flow losses take 2 channels, got %d", C);
+    for (int i = 0; i < n_levels; ++i) {
+        if (h[i] <= 0 || w[i] <= 0) return fail(QPWC_E_SHAPE, "level %d: non-positive extent %dx%d", i, h[i], w[i]);
+        // einops.reduce('(h sh) (w sw)') in the reference fails the same way
+        if (kind == QPWC_LOSS_FLOW_MSE_V2 && (H % h[i] || W % w[i]))
+            return fail(QPWC_E_SHAPE, "level %d: %dx%d is not a whole-block area reduction of %dx%d", i, h[i], w[i], H, W);
+    }
+    return QPWC_OK;
 }
 
 }  // namespace qpwc
@@ -403,6 +427,99 @@ int qpwc_warp_bwd(const void* img, const void* flo, const void* grad_out, void* 
     }
     return warp_bwd_launch(img, flo, grad_out, grad_img, grad_flo, need_ws ? workspace : nullptr, B, H, W, C, dtype,
                            mode, (hipStream_t)stream);
+}
+
+int64_t qpwc_loss_workspace_floats(int kind, int B, int H, int W, int C, const int* h, const int* w, int n_levels) {
+    const int rc = loss_check_shapes(kind, B, H, W, C, h, w, n_levels);
+    return rc != QPWC_OK ? rc : loss_workspace_floats(n_levels);
+}
+
+const char* qpwc_loss_fwd_kernel(int kind, const void* y_true, int B, int H, int W, int C, const int* h, const int* w,
+                                 int n_levels) {
+    if (loss_check_shapes(kind, B, H, W, C, h, w, n_levels) != QPWC_OK) return "";
+    return loss_fwd_kernel(kind, H, W, h, w, n_levels, y_true);
+}
+
+int qpwc_loss_fwd(int kind, float p0, float p1, const void* y_true, int B, int H, int W, int C, int layout,
+                  const void* const* y_pred, const int* h, const int* w, const int* pred_dtype, int n_levels,
+                  void* out_losses, void* const* dpred, void* const* gt_out, void* workspace, void* stream) {
+    if (!y_true || !y_pred || !pred_dtype || !out_losses || !workspace) return fail(QPWC_E_NULL, "null pointer argument");
+    int rc = loss_check_shapes(kind, B, H, W, C, h, w, n_levels);
+    if (rc != QPWC_OK) return rc;
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if (kind == QPWC_LOSS_FLOW_MSE_V2 && !(p0 >= 0.0f)) return fail(QPWC_E_RANGE, "Huber delta %g < 0", (double)p0);
+    if ((uintptr_t)y_true % 4 || (uintptr_t)out_losses % 4 || (uintptr_t)workspace % 4)
+        return fail(QPWC_E_ALIGN, "pointer not aligned to its element size");
+    // every input and output extent, for the alias checks
+    const void* ins[1 + 8];
+    size_t nin[1 + 8];
+    void* outs[2 + 16];
+    size_t nout[2 + 16];
+    int ni = 0, no = 0;
+    ins[ni] = y_true;
+    nin[ni++] = (size_t)B * H * W * C * 4;
+    outs[no] = out_losses;
+    nout[no++] = (size_t)n_levels * 4;
+    outs[no] = workspace;
+    nout[no++] = (size_t)loss_workspace_floats(n_levels) * 4;
+    for (int i = 0; i < n_levels; ++i) {
+        if (pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported prediction dtype %d", i, pred_dtype[i]);
+        const bool want_gt = gt_out && gt_out[i];
+        if (!y_pred[i] && !want_gt) return fail(QPWC_E_NULL, "null prediction at level %d", i);
+        if (dpred && !dpred[i]) return fail(QPWC_E_NULL, "null dpred buffer at level %d", i);
+        const size_t es = esize(pred_dtype[i]), ne = (size_t)B * h[i] * w[i] * C;
+        if ((uintptr_t)y_pred[i] % es || (dpred && (uintptr_t)dpred[i] % 4) || (want_gt && (uintptr_t)gt_out[i] % 4))
+            return fail(QPWC_E_ALIGN, "level %d: pointer not aligned to its element size", i);
+        if (y_pred[i]) {
+            ins[ni] = y_pred[i];
+            nin[ni++] = ne * es;
+        }
+        if (dpred) {
+            outs[no] = dpred[i];
+            nout[no++] = ne * 4;
+        }
+        if (want_gt) {
+            outs[no] = gt_out[i];
+            nout[no++] = ne * 4;
+        }
+    }
+    for (int o = 0; o < no; ++o) {
+        for (int i = 0; i < ni; ++i)
+            if (overlaps(outs[o], nout[o], ins[i], nin[i])) return fail(QPWC_E_ALIAS, "an output overlaps an input");
+        for (int k = o + 1; k < no; ++k)
+            if (overlaps(outs[o], nout[o], outs[k], nout[k])) return fail(QPWC_E_ALIAS, "two outputs overlap");
+    }
+    return loss_fwd_launch(kind, p0, p1, (const float*)y_true, B, H, W, C, layout, y_pred, h, w, pred_dtype, n_levels,
+                           (float*)out_losses, dpred, gt_out, (float*)workspace, (hipStream_t)stream);
+}
+
+int qpwc_loss_bwd(const void* const* dpred, const void* grad_losses, void* const* grad_pred, const int64_t* n_elems,
+                  const int* pred_dtype, int n_levels, void* stream) {
+    if (!dpred || !grad_losses || !grad_pred || !n_elems || !pred_dtype) return fail(QPWC_E_NULL, "null pointer argument");
+    if (n_levels < 1 || n_levels > 8) return fail(QPWC_E_SHAPE, "n_levels %d outside [1,8]", n_levels);
+    if ((uintptr_t)grad_losses % 4) return fail(QPWC_E_ALIGN, "grad_losses not 4-byte aligned");
+    for (int i = 0; i < n_levels; ++i) {
+        if (!dpred[i] || !grad_pred[i]) return fail(QPWC_E_NULL, "null buffer at level %d", i);
+        if (pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported prediction dtype %d", i, pred_dtype[i]);
+        if (n_elems[i] <= 0) return fail(QPWC_E_SHAPE, "level %d has no elements", i);
+        if ((uintptr_t)dpred[i] % 4 || (uintptr_t)grad_pred[i] % esize(pred_dtype[i]))
+            return fail(QPWC_E_ALIGN, "level %d: pointer not aligned to its element size", i);
+    }
+    for (int i = 0; i < n_levels; ++i) {
+        const size_t ng = (size_t)n_elems[i] * esize(pred_dtype[i]);
+        if (overlaps(grad_pred[i], ng, grad_losses, (size_t)n_levels * 4))
+            return fail(QPWC_E_ALIAS, "grad_pred overlaps grad_losses");
+        for (int k = 0; k < n_levels; ++k) {
+            if (overlaps(grad_pred[i], ng, dpred[k], (size_t)n_elems[k] * 4))
+                return fail(QPWC_E_ALIAS, "grad_pred overlaps a dpred buffer");
+            if (k > i && overlaps(grad_pred[i], ng, grad_pred[k], (size_t)n_elems[k] * esize(pred_dtype[k])))
+                return fail(QPWC_E_ALIAS, "two grad_pred buffers overlap");
+        }
+    }
+    return loss_bwd_launch(dpred, (const float*)grad_losses, grad_pred, n_elems, pred_dtype, n_levels,
+                           (hipStream_t)stream);
 }
 
 int qpwc_epe_workspace_floats(void) { return epe_workspace_floats(); }

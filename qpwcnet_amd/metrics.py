@@ -11,8 +11,15 @@ from . import ops
 from .backend import CHANNELS_LAST
 
 
-def multiscale_ground_truth(flow_gt, shapes, data_format=CHANNELS_LAST):
-    """flow_gt (B,H,W,2) -> list of (B,h,w,2), one per (h,w) in shapes."""
+def multiscale_ground_truth(flow_gt, shapes, data_format=CHANNELS_LAST, mode="bilinear"):
+    """flow_gt (B,H,W,2) -> list of (B,h,w,2), one per (h,w) in shapes.
+    mode 'bilinear': FlowMseLoss's ground truth (F.interpolate, align_corners=False); 'area': FlowMseLossV2's
+    (loss.py:160-173, the mean over (H/h) x (W/w) blocks, HIP: every level from one pass over flow_gt).  Both times
+    h / H on both channels."""
+    if mode == "area":
+        return [t.contiguous() for t in ops.area_ground_truth(flow_gt, shapes, data_format)]
+    if mode != "bilinear":
+        raise ValueError("unknown mode '{}' (bilinear, area)".format(mode))
     x = flow_gt.permute(0, 3, 1, 2) if data_format == CHANNELS_LAST else flow_gt
     H = x.shape[2]
     out = []

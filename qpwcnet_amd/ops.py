@@ -775,6 +775,142 @@ def epe_multi(flows_true, flows_pred, out=None, data_format=CHANNELS_LAST):
     return out
 
 
+def _loss_layout(y_true, preds, data_format):
+    """-> (y_true, preds, layout code, nhwc_view): 'channels_first' operands that are all physically NHWC (torch
+    channels_last memory) are read through their permuted views; everything else dense in its declared layout."""
+    get_axis(data_format)
+    ts = [y_true] + [p for p in preds if p is not None]
+    if data_format == CHANNELS_FIRST and all(
+            t.shape[1] > 1 and t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous() for t in ts):
+        return (y_true.permute(0, 2, 3, 1), [None if p is None else p.permute(0, 2, 3, 1) for p in preds], _hip.NHWC,
+                True)
+    return (y_true.contiguous(), [None if p is None else p.contiguous() for p in preds],
+            _hip.NHWC if data_format == CHANNELS_LAST else _hip.NCHW, False)
+
+
+def loss_fwd(kind, y_true, y_preds, data_format=CHANNELS_LAST, p0=0.0, p1=0.0, want_dpred=False, want_gt=False,
+             shapes=None):
+    """Per-level training loss of 1..8 predictions against one full-resolution ground truth (qpwc_loss_fwd; kind
+    _hip.LOSS_*; qpwcnet/train/loss.py) -> (losses: fp32 [L] on the device, dpred, gt).
+    dpred (want_dpred): fp32 d losses[l] / d y_preds[l], shaped like each prediction; gt (want_gt): each level's
+    resampled, flow-scaled ground truth.  y_preds=None with shapes=[(h, w), ...]: the ground truth only (want_gt).
+    Enqueues and returns: no host synchronisation."""
+    if not isinstance(y_true, torch.Tensor):
+        raise TypeError("y_true must be a torch.Tensor")
+    if _wants_grad(y_true):
+        raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
+                         "would be dropped (detach it)")
+    _check_tensor("y_true", y_true)
+    if y_true.dtype != torch.float32:
+        raise ValueError("y_true must be float32, got {}".format(y_true.dtype))
+    preds = [None] * len(shapes) if y_preds is None else list(y_preds)
+    n = len(preds)
+    if not 1 <= n <= 8:
+        raise ValueError("the losses take 1..8 prediction levels, got {}".format(n))
+    for i, p in enumerate(preds):
+        if p is not None:
+            _check_tensor("y_pred[%d]" % i, p)
+            if p.device != y_true.device:
+                raise ValueError("y_pred[{}] is on {}, y_true on {}".format(i, p.device, y_true.device))
+    gt, preds, layout, view = _loss_layout(y_true, preds, data_format)
+    nhwc = layout == _hip.NHWC
+    B, H, W, C = gt.shape if nhwc else (gt.shape[0], gt.shape[2], gt.shape[3], gt.shape[1])
+    hs, ws_ = [], []
+    for i, p in enumerate(preds):
+        if p is None:
+            pb, pc, (h, w) = B, C, shapes[i]
+        else:
+            pb, h, w, pc = p.shape if nhwc else (p.shape[0], p.shape[2], p.shape[3], p.shape[1])
+        if pb != B or pc != C:
+            raise ValueError("level {}: prediction of batch {} / {} channels against a ground truth of {} / {}".format(
+                i, pb, pc, B, C))
+        hs.append(int(h))
+        ws_.append(int(w))
+    L = _hip.lib()
+    ha, wa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws_)
+    nws = L.qpwc_loss_workspace_floats(int(kind), B, H, W, C, ha, wa, n)
+    _hip.check(min(int(nws), 0))
+    dev = gt.device
+    ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+
+    def buffers():
+        return [torch.empty((B, h, w, C) if nhwc else (B, C, h, w), dtype=torch.float32, device=dev)
+                for h, w in zip(hs, ws_)]
+
+    dbuf = buffers() if want_dpred else None
+    gbuf = buffers() if want_gt else None
+    ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+    pp = (ctypes.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in preds])
+    pdt = (ctypes.c_int * n)(*[_hip.F32 if p is None else _DTYPES[p.dtype] for p in preds])
+    with torch.cuda.device(dev), _timed("loss", (B, H, W, C)):
+        rc = L.qpwc_loss_fwd(int(kind), float(p0), float(p1), gt.data_ptr(), B, H, W, C, layout, pp, ha, wa, pdt, n,
+                             out.data_ptr(), ptrs(dbuf), ptrs(gbuf), ws.data_ptr(), _stream(gt))
+    _hip.check(rc)
+    back = (lambda ts: [t.permute(0, 3, 1, 2) for t in ts]) if view else (lambda ts: ts)
+    return out, (back(dbuf) if dbuf else None), (back(gbuf) if gbuf else None)
+
+
+def loss_bwd(dpreds, grad_losses, dtypes):
+    """grad_pred[l] = grad_losses[l] * dpreds[l] in dtypes[l], all levels in one launch (qpwc_loss_bwd); dpreds from
+    loss_fwd(want_dpred=True), grad_losses [L] on the device."""
+    n = len(dpreds)
+    g = grad_losses.to(torch.float32).contiguous()
+    if g.numel() != n or not g.is_cuda:
+        raise ValueError("grad_losses must be a device vector of {} elements".format(n))
+    grads = [torch.empty_like(d, dtype=dt) for d, dt in zip(dpreds, dtypes)]   # same strides: same memory order
+    with torch.cuda.device(g.device), _timed("loss_bwd", (n,)):
+        rc = _hip.lib().qpwc_loss_bwd((ctypes.c_void_p * n)(*[d.data_ptr() for d in dpreds]), g.data_ptr(),
+                                      (ctypes.c_void_p * n)(*[t.data_ptr() for t in grads]),
+                                      (ctypes.c_int64 * n)(*[d.numel() for d in dpreds]),
+                                      (ctypes.c_int * n)(*[_DTYPES[dt] for dt in dtypes]), n, _stream(g))
+    _hip.check(rc)
+    return grads
+
+
+class _LossFn(torch.autograd.Function):
+    """loss_fwd() with qpwc_loss_bwd as its gradient: the forward also stores d losses[l] / d y_pred[l] (fp32), the
+    backward scales it by the incoming per-level gradient (cheaper than recomputing it, which reads y_true again)."""
+
+    @staticmethod
+    def forward(ctx, cfg, y_true, *y_preds):
+        kind, data_format, p0, p1 = cfg
+        losses, dpred, _ = loss_fwd(kind, y_true, y_preds, data_format, p0, p1, want_dpred=True)
+        ctx.dpred = dpred
+        ctx.dtypes = [p.dtype for p in y_preds]
+        return losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_losses):
+        _refuse_capture("the loss backward")
+        grads = loss_bwd(ctx.dpred, grad_losses, ctx.dtypes)
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+def loss(kind, y_true, y_preds, data_format=CHANNELS_LAST, p0=0.0, p1=0.0):
+    """Per-level losses (fp32 [L]) of loss_fwd(); differentiable in y_preds when grad is enabled and one of them
+    requires it."""
+    if isinstance(y_true, torch.Tensor) and _wants_grad(y_true):
+        raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
+                         "would be dropped (detach it)")
+    if _wants_grad(*y_preds):
+        _refuse_capture("the loss")
+        return _LossFn.apply((int(kind), data_format, float(p0), float(p1)), y_true, *y_preds)
+    return loss_fwd(kind, y_true, y_preds, data_format, p0, p1)[0]
+
+
+def area_ground_truth(flow_gt, shapes, data_format=CHANNELS_LAST):
+    """FlowMseLossV2's per-level ground truth (qpwcnet/train/loss.py:160-173): the mean over sh x sw blocks times h / H
+    on both channels -> list of fp32 tensors in data_format; up to 8 levels per pass over flow_gt (qpwc_loss_fwd with
+    gt_out only)."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    out = []
+    for k in range(0, len(shapes), 8):
+        out += loss_fwd(_hip.LOSS_FLOW_MSE_V2, flow_gt, None, data_format, 0.1, want_gt=True, shapes=shapes[k:k + 8])[2]
+    return out
+
+
 def _dw_sources(sources):
     """-> (kept tensors, ctypes pointer/channel/stride arrays, B, H, W, C) for 1..3 sources."""
     import ctypes
