@@ -270,14 +270,19 @@ __global__ __launch_bounds__(kLossThreads) void loss_pixel_kernel(const float* _
         const int y = r / w, x = r - y * w;
         if (KIND == QPWC_LOSS_FLOW_MSE_V2) {
             const int sh = lv.sh[l], sw = lv.sw[l];
+            // each row's sum first, then the rows: one running sum over all sh * sw terms put a 32 x 32 mean ~1e-6 of
+            // the level's largest value off (the tile path's 2 x 2 steps: ~1e-7)
             float sx = 0.0f, sy = 0.0f;
             for (int yy = 0; yy < sh; ++yy) {
                 const int64_t o = pix_offset<LAYOUT>(b, y * sh + yy, x * sw, H, W, 2);
+                float rx = 0.0f, ry = 0.0f;
                 for (int xx = 0; xx < sw; ++xx) {
                     const int64_t oo = o + (LAYOUT == QPWC_NHWC ? 2 * xx : xx);
-                    sx += gt[oo];
-                    sy += gt[oo + gcs];
+                    rx += gt[oo];
+                    ry += gt[oo + gcs];
                 }
+                sx += rx;
+                sy += ry;
             }
             acc += flow_pixel<KIND, LAYOUT>(lv, l, b, y, x, (sx * lv.inv_area[l]) * lv.fscale[l],
                                             (sy * lv.inv_area[l]) * lv.fscale[l], p0, p1,
