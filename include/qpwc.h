@@ -59,9 +59,8 @@ extern "C" {
 int qpwc_version(void);
 const char* qpwc_last_error(void);
 const char* qpwc_strerror(int code);
-/* Static description of the build.  The product library selects kernels from the call's arguments
- * only (no environment variable changes what runs); the `make experimental` build of the same ABI
- * keeps A/B switches and reports "EXPERIMENTAL" here. */
+/* Static description of the build.  The library selects kernels from the call's arguments only (no
+ * environment variable changes what runs; the experimental build that did is removed after 784aa79, see git history). */
 const char* qpwc_build_info(void);
 
 /* Layout conversion at the boundary: out = in with the same logical (B,H,W,C) content in `to_layout`
@@ -213,11 +212,11 @@ int qpwc_loss_bwd(const void* const* dpred, const void* grad_losses, void* const
  * search_range 4, C % 4 == 0.  Output addressing as in
  * qpwc_cost_volume_fwd_strided (pass stride d*d, offset 0 for a dense result).
  * PERFORMANCE NOTE: this entry point always computes what it is asked.  Where the matrix-core
- * kernels do not apply (qpwc_warp_cost_volume_kernel() names the choice: anything but
+ * kernels do not apply (qpwc_cost_volume_kernel(..., fused=1) names the choice: anything but
  * "cost_volume_mfma_lds*" means fewer than 256 regions of 8x8 pixels, C % 32 != 0, or a generic
  * shape) it runs the LDS-tiled vector kernel, which is SLOWER than calling qpwc_warp_fwd +
  * qpwc_cost_volume_fwd (B=8, 16x32x256: 94 us against 5.6 + 7.8 us).  A caller that wants the
- * faster of the two asks qpwc_warp_cost_volume_kernel() first, as qpwcnet_amd/non_layers.py does. */
+ * faster of the two asks qpwc_cost_volume_kernel(..., fused=1) first, as qpwcnet_amd/non_layers.py does. */
 int qpwc_warp_cost_volume_fwd(const void* prv, const void* nxt, const void* flo, void* out,
                               int B, int H, int W, int C, int search_range,
                               int dtype, float lrelu_slope,

@@ -190,11 +190,11 @@ def lib():
 
 def build_info():
     """{'path', 'version', 'build', 'product'} of the loaded library: bench.py prints it, so that a number
-    from another build (QPWC_HIP_LIB -> `make experimental`) can never pass for the product's."""
+    from another build (QPWC_HIP_LIB -> e.g. `make ab`) can never pass for the product's."""
     L = lib()
     info = L.qpwc_build_info().decode()
     return {"path": LIB_PATH, "version": int(L.qpwc_version()), "build": info,
-            "product": "EXPERIMENTAL" not in info and not os.environ.get("QPWC_HIP_LIB")}
+            "product": not os.environ.get("QPWC_HIP_LIB")}
 
 
 def source_sha256(names=("cost_volume_mfma.hip", "cost_volume.hip", "warp.hip", "common.h")):

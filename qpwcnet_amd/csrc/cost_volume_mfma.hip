@@ -203,40 +203,17 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr unsigned kOob = 0x80000000u;  // >= any descriptor size we accept: the load returns 0
 
-// WarpV2's clamp-mode blend (common.h: blend<QPWC_WARP_CLAMP>) on two channels at a time: the same three lerps, every
-// subtract / multiply / add rounded separately (contraction off), as packed fp32 instructions (v_pk_add_f32 /
-// v_pk_mul_f32) -- bit-identical to the scalar form, half the vector-ALU issue slots of the gather.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 blend_clamp2(float ax, float ay, f32x2 tl, f32x2 tr, f32x2 bl, f32x2 br) {
-#pragma clang fp contract(off)
-    const f32x2 top = ax * (tr - tl) + tl;
-    const f32x2 bot = ax * (br - bl) + bl;
-    return ay * (bot - top) + top;
-}
-#ifndef QPWC_PK_BLEND
-#define QPWC_PK_BLEND 0   // 1 = packed fp32 blend: bit-identical, measured +-0 (B=8 L4 47.5 vs 47.5-47.9 us), so the scalar code of common.h stays
-#endif
+// WarpV2's clamp-mode blend (common.h: blend<QPWC_WARP_CLAMP>) of one 16-byte chunk.  (The same three lerps as packed fp32
+// instructions, v_pk_add_f32 / v_pk_mul_f32: bit-identical, measured +-0 -- B=8 L4 47.5 vs 47.5-47.9 us -- so the scalar code of common.h stays.)
 __device__ __forceinline__ u32x4 blend_clamp_chunk(float ax, float ay, u32x4 tl, u32x4 tr, u32x4 bl, u32x4 br) {
     u32x4 v;
-    if (!QPWC_PK_BLEND) {
-        Taps t;
-        t.ax = ax;
-        t.ay = ay;
+    Taps t;
+    t.ax = ax;
+    t.ay = ay;
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-            v[e] = __float_as_uint(blend<QPWC_WARP_CLAMP>(t, __uint_as_float(tl[e]), __uint_as_float(tr[e]),
-                                                          __uint_as_float(bl[e]), __uint_as_float(br[e])));
-        return v;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; e += 2) {
-        const f32x2 r = blend_clamp2(ax, ay, f32x2{__uint_as_float(tl[e]), __uint_as_float(tl[e + 1])},
-                                     f32x2{__uint_as_float(tr[e]), __uint_as_float(tr[e + 1])},
-                                     f32x2{__uint_as_float(bl[e]), __uint_as_float(bl[e + 1])},
-                                     f32x2{__uint_as_float(br[e]), __uint_as_float(br[e + 1])});
-        v[e] = __float_as_uint(r.x);
-        v[e + 1] = __float_as_uint(r.y);
-    }
+    for (int e = 0; e < 4; ++e)
+        v[e] = __float_as_uint(blend<QPWC_WARP_CLAMP>(t, __uint_as_float(tl[e]), __uint_as_float(tr[e]),
+                                                      __uint_as_float(bl[e]), __uint_as_float(br[e])));
     return v;
 }
 
@@ -990,12 +967,6 @@ __global__ __launch_bounds__(1024) void cost_volume_mfma_lds16_kernel(
 // each) and still stages every nxt pixel 3 x instead of 4 x (24 + 8 = 32 block loads per 8 tiles = 4 per tile).
 //   pieces : block B = it*4 + (wave >> 1), it = 0..7: blocks 0..23 = nxt (bi, bj) = (B / 6, B % 6) of the 16-row x
 //            24-column neighbourhood, 24..31 = prv tile B - 24; every lane stages 6 nxt + 2 prv pieces per step.
-#ifndef QPWC_R8_PRV_FIRST
-#define QPWC_R8_PRV_FIRST 0   // A/B (round 4): the two prv pieces requested before the first round of gathers -- 50.5-51.4 vs 49.1-49.5 us in one call: off
-#endif
-#ifndef QPWC_R8_PR
-#define QPWC_R8_PR 3   // A/B: 6 = every gather of the first step in one round: 48.0-48.8 vs 47.3-47.8 us, not better
-#endif
 constexpr int kR8NxtBlocks = 24, kR8Blocks = 32;
 constexpr int kR8StageBytes = kR8Blocks * 2048;              // 65536
 constexpr int kR8FrameBytes = 8 * kFrameFloats * 4;          // 75776: the 10 KB past the staging image hold the records
@@ -1062,7 +1033,8 @@ __global__ __launch_bounds__(512, 2) void cost_volume_mfma_lds8x16_warp_kernel(
     const int nsteps = C / 32;
     auto step = [&](int s, auto first) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first)::value;
-        constexpr int PR = FIRST ? QPWC_R8_PR : 2;   // pieces per round: no accumulator is live in the first step
+        constexpr int PR = FIRST ? 3 : 2;   // pieces per round: no accumulator is live in the first step (A/B: 6 = every gather
+                                            // of the first step in one round: 48.0-48.8 vs 47.3-47.8 us, not better)
         const int soff = s * 128;
         u32x4 c[PR][4];
         float ax[PR], ay[PR];
@@ -1079,22 +1051,11 @@ __global__ __launch_bounds__(512, 2) void cost_volume_mfma_lds8x16_warp_kernel(
         auto mix = [&](int q) __attribute__((always_inline)) {
             return blend_clamp_chunk(ax[q], ay[q], c[q][0], c[q][1], c[q][2], c[q][3]);
         };
-        // Round 4 (QPWC_R8_PRV_FIRST): in the first step -- no accumulator is live -- the two prv pieces, which depend on
-        // nothing, are requested BEFORE the first round of gathers instead of after the last one, where their round trip
-        // stood between the last blend and the barrier in front of the matrix phase.
-        constexpr bool PRV_FIRST = FIRST && QPWC_R8_PRV_FIRST;
-        u32x4 pp0, pp1;
-        if (PRV_FIRST) {
-            pp0 = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[0], soff, 0);
-            pp1 = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[1], soff, 0);
-        }
+        // (A/B, round 4: the two prv pieces requested before the first round of gathers of the first step instead of
+        // after the last one -- 50.5-51.4 vs 49.1-49.5 us in one call: not kept)
 #pragma unroll
         for (int q = 0; q < PR; ++q) issue(q, q);
         if (!FIRST) __syncthreads();  // previous step's operand reads are done
-        if (PRV_FIRST) {
-            *reinterpret_cast<u32x4*>(smem + lds_w + 6 * 8192) = pp0;
-            *reinterpret_cast<u32x4*>(smem + lds_w + 7 * 8192) = pp1;
-        }
 #pragma unroll
         for (int it = 0; it < 6; it += PR) {
             u32x4 v[PR];
@@ -1103,17 +1064,15 @@ __global__ __launch_bounds__(512, 2) void cost_volume_mfma_lds8x16_warp_kernel(
             if (it + PR < 6) {
 #pragma unroll
                 for (int q = 0; q < PR; ++q) issue(it + PR + q, q);
-            } else if (!PRV_FIRST) {   // last round: the two prv pieces ride in the freed registers
+            } else {   // last round: the two prv pieces ride in the freed registers
                 c[0][0] = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[0], soff, 0);
                 c[0][1] = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[1], soff, 0);
             }
 #pragma unroll
             for (int q = 0; q < PR; ++q) *reinterpret_cast<u32x4*>(smem + lds_w + (it + q) * 8192) = v[q];
         }
-        if (!PRV_FIRST) {
-            *reinterpret_cast<u32x4*>(smem + lds_w + 6 * 8192) = c[0][0];
-            *reinterpret_cast<u32x4*>(smem + lds_w + 7 * 8192) = c[0][1];
-        }
+        *reinterpret_cast<u32x4*>(smem + lds_w + 6 * 8192) = c[0][0];
+        *reinterpret_cast<u32x4*>(smem + lds_w + 7 * 8192) = c[0][1];
         if (FIRST) asm volatile("" : "+v"(tab.x), "+v"(tab.y), "+v"(tab.z), "+v"(tab.w));
         __syncthreads();
 #pragma unroll
@@ -1341,25 +1300,7 @@ static int launch_lds_f16(const __half* prv, const __half* nxt, const float* flo
     return check_launch("cost_volume_mfma_lds_f16_kernel");
 }
 
-
-#ifdef QPWC_EXPERIMENTAL
-#include "experimental/cost_volume_pipe.inc"
-#endif
-
-// The product build reads NO environment variable: every rank of a multi-GPU job runs the same kernels.
-// Only `make experimental` (libqpwc_exp.so, reported by qpwc_build_info()) keeps the A/B switch
-// QPWC_CV_LDS=0 = every shape on the per-wave split-K kernel.
-#ifdef QPWC_EXPERIMENTAL
-static int lds_mode() {
-    static const int v = [] {
-        const char* e = getenv("QPWC_CV_LDS");
-        return e ? atoi(e) : 1;
-    }();
-    return v;
-}
-#else
-static constexpr int lds_mode() { return 1; }
-#endif
+// This library reads NO environment variable: every rank of a multi-GPU job runs the same kernels.
 
 // Region size policy of the workgroup-shared fp32 kernels (measured, tools/kbench.py --regions):
 // 16 x 16 regions need one workgroup of 16 waves per CU to be worth it.
@@ -1370,17 +1311,9 @@ static constexpr int lds_mode() { return 1; }
 #define QPWC_R16_MIN_WARP 512    // 16 x 16 regions per launch from which the fused front end takes them (two rounds of
                                  // one-per-CU workgroups; see use_regions16)
 #endif
-#ifndef QPWC_R16_MIN_PLAIN
-#define QPWC_R16_MIN_PLAIN (1 << 30)   // the plain cost volume: never (B=8 L3 19.4 vs 17.6 us, config 4 L1-L3 +5 ... +14 %:
-                                       // its staging is 10 plain loads per lane, not the limiter -- DESIGN.md 4.5)
-#endif
-#ifndef QPWC_CV_R16
-#define QPWC_CV_R16 1   // 0 = never, 1 = by the rule below, 2 = wherever the kernel applies (A/B builds)
-#endif
 static bool use_regions16(int B, int H, int W, int C, bool warp) {
     const int64_t regs16 = (int64_t)((W + 15) / 16) * ((H + 15) / 16) * B;
-    if (QPWC_CV_R16 == 0 || (int64_t)(H + 24) * (W + 24) * C * 4 >= 0x7fffffff) return false;
-    if (QPWC_CV_R16 == 2) return true;
+    if ((int64_t)(H + 24) * (W + 24) * C * 4 >= 0x7fffffff) return false;
     // One workgroup per CU means nothing overlaps a region's staging, matrix and store phases: with a single
     // 32-channel step (C = 32, the finest level) the three phases are of comparable length and the 8 x 8 kernel's
     // three workgroups per CU win (B=8 L4: 48.7 vs 52.7 us); from two steps on the staging share grows and the
@@ -1389,7 +1322,9 @@ static bool use_regions16(int B, int H, int W, int C, bool warp) {
     // slower there (23.5 vs 22.4 us), but inside the two-queue forward the finest decoder level runs beside this launch
     // (QpwcNet.dec_chunks) and a 148 KB workgroup cannot share a CU with that kernel's 46 KB ones, a 75 KB one can:
     // 50.7 -> ~45 us in the step's kernel trace, step 1.2027 -> 1.1988 ms (three interleaved pairs of one call).
-    return C >= 64 && regs16 >= (warp ? QPWC_R16_MIN_WARP : QPWC_R16_MIN_PLAIN);
+    // The plain cost volume: never (B=8 L3 19.4 vs 17.6 us, config 4 L1-L3 +5 ... +14 %: its staging is 10 plain loads
+    // per lane, not the limiter -- DESIGN.md 4.5).
+    return warp && C >= 64 && regs16 >= QPWC_R16_MIN_WARP;
 }
 
 static int launch_lds16(const float* prv, const float* nxt, const float* flo, float* out, int B, int H, int W, int C,
@@ -1407,19 +1342,10 @@ static int launch_lds16(const float* prv, const float* nxt, const float* flo, fl
                            flo, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
         return check_launch("cost_volume_mfma_lds16_kernel<warp>");
     }
-#if QPWC_R16_MIN_PLAIN < (1 << 30)   // A/B builds only: the plain cost volume measured slower on 16 x 16 regions
-    hipLaunchKernelGGL(cost_volume_mfma_lds16_kernel<false>, dim3((unsigned)nblk), dim3(1024), 0, s, prv, nxt,
-                       (const float*)nullptr, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
-    return check_launch("cost_volume_mfma_lds16_kernel");
-#else
     set_error("cost volume on 16 x 16 regions: fused front end only in this build");
     return QPWC_E_SHAPE;
-#endif
 }
 
-#ifndef QPWC_R8X16_ANYC
-#define QPWC_R8X16_ANYC 1     // 8 x 16 regions for every channel count the 16 x 16 form does not take (0: C = 32 only)
-#endif
 #ifndef QPWC_R8X16_MIN
 #define QPWC_R8X16_MIN 512    // 8 x 16 regions per launch from which the single-step fused front end takes them (2 per CU)
 #endif
@@ -1438,7 +1364,8 @@ static int launch_lds(const float* prv, const float* nxt, const float* flo, floa
                       int64_t ops, float slope, int pad84, hipStream_t s) {
     if (use_regions16(B, H, W, C, flo != nullptr))
         return launch_lds16(prv, nxt, flo, out, B, H, W, C, ops, slope, pad84, s);
-    if (flo && (C == 32 || QPWC_R8X16_ANYC) && QPWC_R8X16_MIN > 0 && (int64_t)((W + 15) / 16) * ((H + 7) / 8) * B >= QPWC_R8X16_MIN &&
+    // 8 x 16 regions for every channel count the 16 x 16 form does not take
+    if (flo && QPWC_R8X16_MIN > 0 && (int64_t)((W + 15) / 16) * ((H + 7) / 8) * B >= QPWC_R8X16_MIN &&
         (int64_t)(H + 16) * (W + 24) * C * 4 < 0x7fffffff && (int64_t)H * W * ops <= INT32_MAX)
         return launch_lds8x16_warp(prv, nxt, flo, out, B, H, W, C, ops, slope, pad84, s);
     const int regs_x = (W + 7) / 8, regs_y = (H + 7) / 8;
@@ -1455,12 +1382,6 @@ static int launch_lds(const float* prv, const float* nxt, const float* flo, floa
                            flo, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
         return check_launch("cost_volume_mfma_lds_kernel<warp>");
     }
-#ifdef QPWC_EXPERIMENTAL
-    {
-        const int rc = launch_experimental(prv, nxt, out, H, W, C, regs_x, regs_y, nblk, ops, slope, inv_c, s);
-        if (rc <= 0) return rc;
-    }
-#endif
     if (dry_run("cost_volume_mfma_lds_kernel")) return QPWC_OK;
     hipLaunchKernelGGL(cost_volume_mfma_lds_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, s, prv, nxt,
                        (const float*)nullptr, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
@@ -1520,7 +1441,6 @@ int cost_volume_mfma_launch(const void* prv, const void* nxt, const void* flo, v
     const int64_t regions8 = (int64_t)((W + 7) / 8) * ((H + 7) / 8) * B;
     if (flo && (C % 32 != 0 || reinterpret_cast<uintptr_t>(flo) % 8 || H < 2 || W < 2 || regions8 < QPWC_FUSED_MIN_REGIONS))
         return 1;
-    if (flo && lds_mode() == 0) return 1;   // (experimental build, QPWC_CV_LDS=0: no fused form on the split-K kernel)
     // 32-bit byte offsets inside one image (buffer descriptors) and 32-bit element offsets
     // inside one output image: larger problems take the 64-bit vector kernel instead
     const int64_t es = dtype == QPWC_F16 ? 2 : 4;
@@ -1530,8 +1450,7 @@ int cost_volume_mfma_launch(const void* prv, const void* nxt, const void* flo, v
     if (dtype == QPWC_F32) {
         // >= one region per CU: share the staged neighbourhood across a workgroup (L2 of the 256x512
         // pyramid, 256 regions x 4 steps: 10.2 us vs 11.8 us on the per-wave split-K kernel)
-        if (C % 32 == 0 && regions8 >= (flo ? QPWC_FUSED_MIN_REGIONS : 256) && lds_mode() != 0)
-        {
+        if (C % 32 == 0 && regions8 >= (flo ? QPWC_FUSED_MIN_REGIONS : 256)) {
             // every tile dense: full 4x4 tiles, 16-byte aligned rows
             if (pads_written)
                 *pads_written = pad84 && W % 4 == 0 && H % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
@@ -1544,7 +1463,7 @@ int cost_volume_mfma_launch(const void* prv, const void* nxt, const void* flo, v
         return dispatch_mfma<float, 4>((const float*)prv, (const float*)nxt, (float*)out, B, H, W, C,
                                        ops, slope, pad84, s);
     }
-    if (C % 32 == 0 && (int64_t)((W + 7) / 8) * ((H + 7) / 8) * B >= 256 && lds_mode() != 0) {
+    if (C % 32 == 0 && (int64_t)((W + 7) / 8) * ((H + 7) / 8) * B >= 256) {
         if (pads_written)   // dense 8-byte rows of 4 px x 84 halves
             *pads_written = pad84 && W % 4 == 0 && H % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
         return launch_lds_f16((const __half*)prv, (const __half*)nxt, (const float*)flo, (__half*)out, B, H, W, C, ops,
@@ -1559,14 +1478,9 @@ int cost_volume_mfma_launch(const void* prv, const void* nxt, const void* flo, v
 
 }  // namespace qpwc
 
-// Which build this is: the product library has no run-time kernel switches; the experimental one does
-// and says so, so that a bench line can never silently come from it.
+// Which build this is: the library has no run-time kernel switches and says so (bench.py records the line).
 extern "C" const char* qpwc_build_info(void) {
-#ifdef QPWC_EXPERIMENTAL
-    return "libqpwc_hip gfx950 EXPERIMENTAL (env switches QPWC_CV_LDS / QPWC_CV_RING / QPWC_CV_PIPE active)";
-#else
     return "libqpwc_hip gfx950 product (no environment switches)";
-#endif
 }
 
 #ifdef QPWC_CV_STAMP
@@ -1576,6 +1490,3 @@ extern "C" int qpwc_debug_cv_stamps(long long* out, int n) {
 }
 #endif
 
-#if defined(QPWC_EXPERIMENTAL) && defined(QPWC_STAMP)
-#include "experimental/debug_exports.inc"
-#endif

@@ -29,11 +29,7 @@ __device__ __forceinline__ float enc_mishf(float x) {
     const float e = __builtin_amdgcn_exp2f(fminf(x, 20.0f) * 1.4426950408889634f);
     const float t = e * (e + 2.0f);
     const float m = x * (t * __builtin_amdgcn_rcpf(t + 2.0f));
-#if QPWC_MISH_SELECT
-    return x > 20.0f ? x : m;
-#else
     return m;   // x > 20: e is clamped, t / (t + 2) rounds to 1 +- 1 ulp, m = x to 2 ulp -- no compare + select per value
-#endif
 }
 
 typedef float f32x4e __attribute__((ext_vector_type(4)));
@@ -81,24 +77,10 @@ __device__ __forceinline__ int ec_slot(int q, int hp) {
 // runs): stride-1 layers C = 64 / 128 / 256: 33.3 / 30.4 / 33.2 -> 29.7 / 29.7 / 30.1 us (two steps ahead: 32.0 / 29.4 /
 // 30.2), step 1.2006 -> 1.1826 ms -- kept until the LDS-DMA ring kernel replaced that kernel.  The stride-2 layers do not move (17.4-20.6 us either
 // way, step 1.1816 vs 1.1809) and the decoder's transposed convolution gets 7 us SLOWER per step with it (1.1886 vs
-// 1.1816: on the second queue, beside the coarse flow levels, see QpwcNet.dec_chunks; on the finest decoder level only,
-// QPWC_UPCONV_PIPE = 2: 1.1758 vs 1.1780, inside the noise) -- both stay as the compiler schedules them.
-#ifndef QPWC_ENC16_PIPE
-#define QPWC_ENC16_PIPE 1   // the fp16 wide kernel: a tap's operand reads one tap ahead (0 = as the compiler places them)
-#endif
-// (the same one / two taps ahead in the fp16 transposed and stride-2 kernels: config 5's step 1.709 vs 1.706 ms -- off)
-#ifndef QPWC_UPCONV16_PIPE
-#define QPWC_UPCONV16_PIPE 0
-#endif
-#ifndef QPWC_S2_16_PIPE
-#define QPWC_S2_16_PIPE 0
-#endif
-#ifndef QPWC_S2_PIPE
-#define QPWC_S2_PIPE 0
-#endif
-#ifndef QPWC_UPCONV_PIPE
-#define QPWC_UPCONV_PIPE 0
-#endif
+// 1.1816: on the second queue, beside the coarse flow levels, see QpwcNet.dec_chunks; on the finest decoder level only:
+// 1.1758 vs 1.1780, inside the noise) -- both stay as the compiler schedules them.  The fp16 wide kernel keeps its
+// operand reads one tap ahead; the same one / two taps ahead in the fp16 transposed and stride-2 kernels: config 5's
+// step 1.709 vs 1.706 ms -- not kept.
 // Round 4: the next block's weights are requested UNCONDITIONALLY (the last trip re-reads its own block, an L1 hit).  With
 // `if (kb + 1 < NKB) load_w(...)` the compiler's s_waitcnt pass must be right for the trip that issued no request as well, so
 // it waited with vmcnt(7), (6), .. (0) through the trip's eight groups of matrix instructions -- i.e. for the requests that
@@ -113,11 +95,8 @@ __device__ __forceinline__ int ec_slot(int q, int hp) {
 #ifndef QPWC_UPCONV128_TH
 #define QPWC_UPCONV128_TH 4
 #endif
-#ifndef QPWC_UPCONV_LDS_TOTAL
-#define QPWC_UPCONV_LDS_TOTAL 0
-#endif
 #ifndef QPWC_UPCONV64_LDS_TOTAL
-#define QPWC_UPCONV64_LDS_TOTAL 82944   // the same for the finest decoder level only (it has ~120 us of slack before flow level 4
+#define QPWC_UPCONV64_LDS_TOTAL 82944   // LDS footprint padding (see upconv_launch_t) for the finest decoder level only (it has ~120 us of slack before flow level 4
                                         // needs it): ONE of its workgroups per CU leaves the flow chain's 79-80 KiB workgroups room beside
                                         // it -- config 2 step 1.1124 vs 1.1158 ms (five interleaved pairs); 0 = off
 #endif
@@ -131,9 +110,6 @@ __device__ __forceinline__ int ec_slot(int q, int hp) {
 #define QPWC_LOAD_W_NEXT(END) load_w(wn, kb + 1 < (END) ? kb + 1 : kb)
 #else
 #define QPWC_LOAD_W_NEXT(END) do { if (kb + 1 < (END)) load_w(wn, kb + 1); } while (0)
-#endif
-#ifndef QPWC_ENC_NARROW_EARLY
-#define QPWC_ENC_NARROW_EARLY 0   // A/B (round 4): narrow fp32 kernel, weights (C = 16) + bias requested with the tile's inputs: 32.4 vs 32.3, 30.2 vs 30.3 us, step +-0 -- off
 #endif
 #ifdef QPWC_ENC_STAMP
 // diagnostic build only (make ab ABSRC=encoder ABFLAGS=-DQPWC_ENC_STAMP; tools/enc_census.py): per workgroup of
@@ -199,27 +175,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_mish_kernel(const float* __res
     ENC_CENSUS(0);
     float4 st[NLD];
     stage_load(tid0, tx0, st);
-    // Round 4 (one tile per workgroup): the first output block's weights and every bias value are requested HERE, with the
-    // tile's inputs, and land under the same wait.  As the compiler placed them, each tap's weights were loaded a few matrix
-    // instructions ahead of their use behind counted vmcnt waits, and the bias right before the epilogue behind
-    // `s_waitcnt vmcnt(0)` -- L2-hit latencies exposed inside a 2.3 k-cycle matrix phase.
-    constexpr bool EARLYB = QPWC_ENC_NARROW_EARLY && NT == 1;   // every bias value
-    constexpr bool EARLY = EARLYB && C == 16;                   // ... and the weights (C = 32: 18 requests with 18 address pairs on top
-                                                                // of the staged tile spill 29-33 registers under the 128 of four waves per SIMD)
-    f32x4e wpre[EARLY ? 9 : 1][EARLY ? NKC : 1];
-    float4 bpre[EARLYB ? NFT : 1];
-    if (EARLYB) {
-        if (EARLY) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-#pragma unroll
-                for (int kc = 0; kc < NKC; ++kc)
-                    wpre[k][kc] = *reinterpret_cast<const f32x4e*>(weight + ((int64_t)k * C + n0) * C + 16 * kc + 4 * g0);
-        }
-#pragma unroll
-        for (int ft = 0; ft < NFT; ++ft) bpre[ft] = *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // also a compiler barrier: the loads above stay above
-    }
+    // (A/B, round 4: weights (C = 16) + bias requested HERE with the tile's inputs: 32.4 vs 32.3, 30.2 vs 30.3 us, step +-0 -- not kept)
 #ifdef QPWC_ENC_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -245,18 +201,12 @@ __global__ __launch_bounds__(256, 4) void conv3x3_mish_kernel(const float* __res
 #pragma unroll
         for (int ft = 0; ft < NFT; ++ft) {
             // weights of output block ft for this lane: row f = 16 ft + n, channels 16 kc + 4g .. + 3, 9 taps
-            f32x4e wld[EARLY ? 1 : 9][EARLY ? 1 : NKC];
-            if (!EARLY) {
+            f32x4e wld[9][NKC];
 #pragma unroll
-                for (int k = 0; k < 9; ++k)
+            for (int k = 0; k < 9; ++k)
 #pragma unroll
-                    for (int kc = 0; kc < NKC; ++kc)
-                        wld[k][kc] = *reinterpret_cast<const f32x4e*>(wt + ((int64_t)k * C + 16 * ft + n) * C + 16 * kc + 4 * g);
-            }
-            auto wv = [&](int k, int kc) __attribute__((always_inline)) -> f32x4e& {
-                if constexpr (EARLY) return wpre[k][kc];
-                else return wld[k][kc];
-            };
+                for (int kc = 0; kc < NKC; ++kc)
+                    wld[k][kc] = *reinterpret_cast<const f32x4e*>(wt + ((int64_t)k * C + 16 * ft + n) * C + 16 * kc + 4 * g);
             f32x4e acc[2];
             acc[0] = f32x4e{0.f, 0.f, 0.f, 0.f};
             acc[1] = f32x4e{0.f, 0.f, 0.f, 0.f};
@@ -280,19 +230,11 @@ __global__ __launch_bounds__(256, 4) void conv3x3_mish_kernel(const float* __res
                         for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
                             for (int m = 0; m < 2; ++m)
-                                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv(ky * 3 + kx, kc)[tt], bv[m][tt], acc[m], 0, 0, 0);
-                        // the next output block's weights of this (tap, chunk) are requested as soon as its registers are free:
-                        // a whole block of matrix work lies between the request and the first use
-                        if (EARLY && ft + 1 < NFT) {
-                            __builtin_amdgcn_sched_barrier(0);   // (unfenced, the scheduler hoists these requests: two register sets, 33 spilled)
-                            wpre[ky * 3 + kx][kc] = *reinterpret_cast<const f32x4e*>(
-                                wt + ((int64_t)(ky * 3 + kx) * C + 16 * (ft + 1) + n) * C + 16 * kc + 4 * g);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
+                                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wld[ky * 3 + kx][kc][tt], bv[m][tt], acc[m], 0, 0, 0);
                     }
             if (ft == NFT - 1) ENC_CENSUS(3);
             // ---- bias + Mish: lane = pixel n of tile row 2 wave + m, outputs 16 ft + 4g .. + 3 ----
-            const float4 bq = EARLYB ? bpre[ft] : *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
+            const float4 bq = *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const int gy = Y0 + 2 * wave + m, gx = X0 + n;
@@ -628,7 +570,6 @@ __global__ __launch_bounds__(256) void conv3x3_mish_f16_kernel(const __half* __r
         __syncthreads();
         // one 32-channel block with the weights in `wv`; the two register sets alternate (QPWC_W_NEXT_ALWAYS)
         auto block = [&](f16x8e (&wv)[9], int kb) __attribute__((always_inline)) {
-#if QPWC_ENC16_PIPE
             // one step = one tap: TH ds_read_b128 feed TH matrix instructions of 16 cycles each; the reads of tap
             // t + 1 go out before the matrix instructions of tap t (round 3: as the compiler placed them every matrix
             // instruction waited for its own read -- 33 us for a layer whose bytes and products are 4 us each)
@@ -650,18 +591,6 @@ __global__ __launch_bounds__(256) void conv3x3_mish_f16_kernel(const __half* __r
                     acw[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[tap], bb[tap & 1][r], acw[r], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#else
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-                for (int r = 0; r < TH; ++r) {
-                    const int hp = (r + ky) * kEcHW + n + kx;
-                    const f16x8e bv = *reinterpret_cast<const f16x8e*>(in_s + hp * CP + 8 * f16_slot<CP>(4 * kb + g, hp));
-                    acw[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[tap], bv, acw[r], 0, 0, 0);
-                }
-            }
-#endif
         };
 #if QPWC_W_NEXT_ALWAYS_F16
         {
@@ -1033,31 +962,8 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_kernel(const float* _
     // one 32-channel block of the reduction with the weights in `wv` (the two register sets alternate: no copy, and
     // every trip issues the same requests, so the compiler's vmcnt counts are exact -- see QPWC_W_NEXT_ALWAYS)
     auto block = [&](f32x4e (&wv)[4][2], int kb) __attribute__((always_inline)) {
-        // QPWC_UPCONV_PIPE: 1 = every level, 2 = the finest decoder level (C = 64) only
-        if constexpr (QPWC_UPCONV_PIPE == 1 || (QPWC_UPCONV_PIPE == 2 && C == 64)) {
-        // one step = (tap, 16-channel chunk); the operand reads of step i + 1 go out before the matrix instructions of
-        // step i (as the register-staged wide stride-1 kernel did)
-        f32x4e bb[2][TH];
-        auto read_b = [&](f32x4e (&bv)[TH], int i) __attribute__((always_inline)) {
-            const int t = i >> 1, kc = i & 1;
-#pragma unroll
-            for (int m = 0; m < TH; ++m) {
-                const int hp = (m + 1 + offy[t]) * kEcHW + n + 1 + offx[t];
-                bv[m] = *reinterpret_cast<const f32x4e*>(in_s + hp * C + 4 * ((8 * kb + 4 * kc + g) ^ (hp & 15)));
-            }
-        };
-        read_b(bb[0], 0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (i + 1 < 8) read_b(bb[(i + 1) & 1], i + 1);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int m = 0; m < TH; ++m)
-                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i >> 1][i & 1][j], bb[i & 1][m][j], acc[m], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        } else {
+        // (operand reads one (tap, chunk) step ahead of the matrix instructions: 7 us SLOWER per step, 1.1886 vs 1.1816 ms;
+        // on the finest decoder level only 1.1758 vs 1.1780, inside the noise -- as the compiler schedules them)
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -1074,7 +980,6 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_kernel(const float* _
                     for (int m = 0; m < TH; ++m)
                         acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[t][kc][j], bv[m][j], acc[m], 0, 0, 0);
             }
-        }
     };
     static_assert(NKB % 2 == 0, "two blocks per trip");
     if constexpr (QPWC_W_NEXT_ALWAYS && NKB > 2) {   // (C = 64, two blocks: +-0, and 5 spilled registers at TH = 8)
@@ -1136,12 +1041,11 @@ static int upconv_launch_t(const void* x, const void* weight, const void* bias, 
         set_error("upconv4x4s2_mish: too many tiles");
         return QPWC_E_SHAPE;
     }
-    // QPWC_UPCONV_LDS_TOTAL (A/B, round 4): pad the workgroup's LDS footprint to this many bytes with dynamic LDS the kernel never
+    // QPWC_UPCONV64_LDS_TOTAL (A/B, round 4): pad the workgroup's LDS footprint to this many bytes with dynamic LDS the kernel never
     // touches -- 81 KiB leaves ONE decoder workgroup per CU and room for a 79 KiB SeparableConv2D workgroup of the flow chain
     constexpr size_t kStatic = (size_t)(TH + 2) * kEcHW * C * sizeof(float);
     // (the finest decoder level of a SMALL step only: at config 4's 32 k workgroups one per CU costs +0.7 %)
-    const size_t want = (C == 64 && QPWC_UPCONV64_LDS_TOTAL && n_tiles * (F / 16) <= 2048) ? QPWC_UPCONV64_LDS_TOTAL
-                                                                                         : QPWC_UPCONV_LDS_TOTAL;
+    const size_t want = (C == 64 && QPWC_UPCONV64_LDS_TOTAL && n_tiles * (F / 16) <= 2048) ? QPWC_UPCONV64_LDS_TOTAL : 0;
     const size_t extra = want > kStatic ? want - kStatic : 0;
     hipLaunchKernelGGL((upconv4x4s2_mish_kernel<C, TH>), dim3((unsigned)(n_tiles * (F / 16))), dim3(256), extra, s,
                        (const float*)x, (const float*)weight, (const float*)bias, (float*)out, H, W, F,
@@ -1222,25 +1126,7 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
     __syncthreads();
     // one 32-channel block with the weights in `wv`; the two register sets alternate (QPWC_W_NEXT_ALWAYS)
     auto block = [&](f16x8e (&wv)[4], int kb) __attribute__((always_inline)) {
-#if QPWC_UPCONV16_PIPE
-        // a tap's TH operand reads go out one tap ahead of its matrix instructions (as in conv3x3_mish_f16_kernel)
-        f16x8e bb[2][TH];
-        auto read_b = [&](f16x8e (&bv)[TH], int t) __attribute__((always_inline)) {
-#pragma unroll
-            for (int m = 0; m < TH; ++m) {
-                const int hp = (m + 1 + offy[t]) * kEcHW + n + 1 + offx[t];
-                bv[m] = *reinterpret_cast<const f16x8e*>(in_s + hp * C + 8 * f16_slot<C>(4 * kb + g, hp));
-            }
-        };
-        read_b(bb[0], 0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (t + 1 < 4) read_b(bb[(t + 1) & 1], t + 1);
-#pragma unroll
-            for (int m = 0; m < TH; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[t], bb[t & 1][m], acc[m], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#else
+        // (operand reads one tap ahead, as in conv3x3_mish_f16_kernel: config 5's step 1.709 vs 1.706 ms -- as the compiler places them)
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -1249,7 +1135,6 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
                 const f16x8e bv = *reinterpret_cast<const f16x8e*>(in_s + hp * C + 8 * f16_slot<C>(4 * kb + g, hp));
                 acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[t], bv, acc[m], 0, 0, 0);
             }
-#endif
     };
 #pragma unroll 1
     for (int fb = 0; fb < nfb; ++fb) {
@@ -1617,30 +1502,7 @@ __global__ __launch_bounds__(256, (2 * (2 * TH + 1) * (kEcTW + 1) * CI * 4 > 80 
     __syncthreads();
     // one 32-channel block with the weights in `wv`; the two register sets alternate (QPWC_W_NEXT_ALWAYS)
     auto block = [&](f32x4e (&wv)[9][2], int kb) __attribute__((always_inline)) {
-#if QPWC_S2_PIPE
-        // one step = (tap, 16-channel chunk); the operand reads of step i + 1 go out before the matrix instructions of
-        // step i (as the register-staged wide stride-1 kernel did)
-        f32x4e bb[2][TH];
-        auto read_b = [&](f32x4e (&bv)[TH], int i) __attribute__((always_inline)) {
-            const int tap = i >> 1, kc = i & 1, ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-            for (int m = 0; m < TH; ++m) {
-                const int pix = ((kx & 1) * IH + 2 * m + ky) * PW + n + (kx >> 1);
-                bv[m] = *reinterpret_cast<const f32x4e*>(in_s + pix * CI + 4 * slot(8 * kb + 4 * kc + g, pix));
-            }
-        };
-        read_b(bb[0], 0);
-#pragma unroll
-        for (int i = 0; i < 18; ++i) {
-            if (i + 1 < 18) read_b(bb[(i + 1) & 1], i + 1);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int m = 0; m < TH; ++m)
-                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i >> 1][i & 1][t], bb[i & 1][m][t], acc[m], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#else
+        // (operand reads one (tap, chunk) step ahead of the matrix instructions: the stride-2 layers do not move, 17.4-20.6 us either way, step 1.1816 vs 1.1809 ms -- as the compiler schedules them)
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
@@ -1659,7 +1521,6 @@ __global__ __launch_bounds__(256, (2 * (2 * TH + 1) * (kEcTW + 1) * CI * 4 > 80 
                         for (int m = 0; m < TH; ++m)
                             acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ky * 3 + kx][kc][t], bv[m][t], acc[m], 0, 0, 0);
                 }
-#endif
     };
 #if QPWC_W_NEXT_ALWAYS
     {
@@ -1813,28 +1674,7 @@ __global__ __launch_bounds__(256) void conv3x3s2_mish_f16_kernel(const __half* _
     __syncthreads();
     // one 32-channel block with the weights in `wv`; the two register sets alternate (QPWC_W_NEXT_ALWAYS)
     auto block = [&](f16x8e (&wv)[9], int kb) __attribute__((always_inline)) {
-#if QPWC_S2_16_PIPE
-        // operand reads two taps ahead of their matrix instructions (RW of 16 cycles per tap: one tap would not cover
-        // the LDS latency)
-        f16x8e bb[3][RW];
-        auto read_b = [&](f16x8e (&bv)[RW], int tap) __attribute__((always_inline)) {
-            const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-            for (int r = 0; r < RW; ++r) {
-                const int hp = ((kx & 1) * IH + 2 * (r0 + r) + ky) * PW + n + (kx >> 1);
-                bv[r] = *reinterpret_cast<const f16x8e*>(in_s + hp * CP + 8 * f16_slot<CP>(4 * kb + g, hp));
-            }
-        };
-        read_b(bb[0], 0);
-        read_b(bb[1], 1);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            if (tap + 2 < 9) read_b(bb[(tap + 2) % 3], tap + 2);
-#pragma unroll
-            for (int r = 0; r < RW; ++r) acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[tap], bb[tap % 3][r], acc[r], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#else
+        // (operand reads two taps ahead of their matrix instructions: config 5's step 1.709 vs 1.706 ms -- as the compiler places them)
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap - 3 * ky;
@@ -1845,7 +1685,6 @@ __global__ __launch_bounds__(256) void conv3x3s2_mish_f16_kernel(const __half* _
                 acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[tap], bv, acc[r], 0, 0, 0);
             }
         }
-#endif
     };
 #if QPWC_W_NEXT_ALWAYS_F16
     {

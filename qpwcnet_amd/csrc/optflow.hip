@@ -305,35 +305,18 @@ __device__ long long g_sc_census[4096 * 6];   // per workgroup: start, staged0, 
 
 __device__ __attribute__((aligned(16))) const float kScZeros[4] = {0.f, 0.f, 0.f, 0.f};
 
-#ifndef QPWC_SC_W_AHEAD
-#define QPWC_SC_W_AHEAD 1   // A/B (round 4): pointwise A operands read one block of eight matrix instructions ahead (F = 128)
-#endif
 #ifndef QPWC_SC_AGPR
 #define QPWC_SC_AGPR 0   // A/B (round 4): accumulators pinned to AGPRs -- every matrix instruction then accumulates in place (no renamed
                          // result, 0 suspects in tools/mfma_war_lint.py) but the epilogue pays a v_accvgpr_read per value: 129-131 vs 123-126 us
 #endif
-#ifndef QPWC_SC_BUF_STORE
-#define QPWC_SC_BUF_STORE 1   // A/B (round 4): output stores through a buffer descriptor (no per-store address arithmetic / branch)
-#endif
 typedef unsigned u32x4sc __attribute__((ext_vector_type(4)));
-#ifndef QPWC_SC_BIAS_EARLY
-#define QPWC_SC_BIAS_EARLY 1   // A/B (round 4): the last step's bias values requested before its matrix instructions
-#endif
-#ifndef QPWC_SC_ASYM_PRIO
-#define QPWC_SC_ASYM_PRIO 0   // A/B: asymmetric wave priority inside the fused SeparableConv2D (see the kernel)
-#endif
 template <int F, bool ACT, bool VEC, bool ACT_OUT, bool RES = false>
 __global__ __launch_bounds__(256, 2) void sepconv3x3_fused_kernel(
     DwSrc src, const float* __restrict__ dw, const float* __restrict__ pw, const float* __restrict__ bias,
     float* __restrict__ out, int H, int W, int C, int cpad, int tiles_x, int tiles_y, int slices, int n_work) {
     QPWC_FLOW_CHAIN_PRIO();
-#if QPWC_SC_ASYM_PRIO
-    // Two waves share a SIMD (one of each resident workgroup).  When both are in their matrix phase each runs at half
-    // rate and they leave it together -- a stable lock step in which the matrix pipe idles while both do their
-    // staging / depthwise / store work.  The wave in the odd hardware slot asks for more issue priority: it finishes its
-    // matrix phase at full rate while the other waits, and from then on the two alternate.
-    if (__builtin_amdgcn_s_getreg((4) | (0 << 6) | (3 << 11)) & 1) __builtin_amdgcn_s_setprio(3);   // HW_ID.wave_id bit 0
-#endif
+    // (A/B, round 4: asymmetric wave priority -- the wave in the odd hardware slot of a SIMD asking for more issue priority, to break
+    // the lock step of the two resident workgroups' matrix phases: 132.4 vs 133.4 us, step +0.5 % -- not kept)
     // F = output channels of THIS workgroup.  slices > 1 (coarse levels: few tiles, many 32-channel steps): the
     // layer's slices * F outputs are split over `slices` workgroups per tile -- each repeats the (cheap)
     // depthwise convolution and takes 1 / slices of the matrix work, and the launch has slices x more
@@ -585,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void sepconv3x3_fused_kernel(
         }
     };
     auto pointwise = [&](const float* ys) {   // D[f][px] += W[f][k] * y[px][k] on the matrix cores
-        if (QPWC_SC_W_AHEAD && F >= 128) {   // (F = 64: 76.3 vs 73.3 us at L4 with it, F = 128: 124 vs 126)
+        if (F >= 128) {   // (F = 64: 76.3 vs 73.3 us at L4 with it, F = 128: 124 vs 126)
             // Round 4: a block's A operand is read while the block BEFORE it multiplies (both B operands up front).  As the
             // compiler placed them, every eight matrix instructions ended in `ds_read_b128; s_waitcnt lgkmcnt(0)` for the
             // next eight: ~90 cycles of an idle matrix pipe per 256 (ISA of round 3's build).
@@ -719,15 +702,11 @@ __global__ __launch_bounds__(256, 2) void sepconv3x3_fused_kernel(
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
                     yv[u][m] = *reinterpret_cast<const f32x4v*>(ys + (32 * wave + 16 * m + n) * kScKC + (((4 * u + g) ^ sw) << 2));
-            float* orow[2];
-            bool ook[2];
             int ooff[2];
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const int pix = 32 * wave + 16 * m + n;
-                const int gy = eY0 + pix / kScTW, gx = eX0 + pix % kScTW;
-                ook[m] = gy < H && gx < W;
-                orow[m] = out + ((int64_t)(eb * H + gy) * W + gx) * FT + 4 * g;
+                const int gx = eX0 + pix % kScTW;
                 // buffer form: offset inside the tile's band of rows; a column past the image is an out-of-range offset
                 // (a row past it is past the descriptor's end): the store is dropped, no branch, no 64-bit address
                 ooff[m] = gx < W ? (((pix / kScTW) * W + gx) * FT + 4 * g) * 4 : (int)0x80000000;
@@ -743,28 +722,23 @@ __global__ __launch_bounds__(256, 2) void sepconv3x3_fused_kernel(
             // Loaded inside epilogue(ft), each block's load sat right in front of its use behind an `s_waitcnt vmcnt(0)` --
             // and on gfx950 vmcnt counts STORES too, so every block also waited for the previous block's two output stores
             // to be acknowledged: the last step of a tile took 11.5-12 k cycles against 5 k for the others (stamps of the
-            // ping-pong lab kernel, which shares this epilogue).
-            float4 bvs[QPWC_SC_BIAS_EARLY ? NFT : 1];
-            if (QPWC_SC_BIAS_EARLY) {
+            // round-4 ping-pong lab kernel, which shared this epilogue).
+            float4 bvs[NFT];
 #pragma unroll
-                for (int ft = 0; ft < NFT; ++ft) bvs[ft] = *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
-            }
+            for (int ft = 0; ft < NFT; ++ft) bvs[ft] = *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
             auto epilogue = [&](int ft) __attribute__((always_inline)) {
-                const float4 bv = QPWC_SC_BIAS_EARLY ? bvs[QPWC_SC_BIAS_EARLY ? ft : 0]
-                                                     : *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
+                const float4 bv = bvs[ft];
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
                     float4 z = make_float4(acc[m][ft][0] + bv.x, acc[m][ft][1] + bv.y, acc[m][ft][2] + bv.z,
                                            acc[m][ft][3] + bv.w);
                     // the activation applied once per output element instead of once per (halo) load of the next layer
                     if (ACT_OUT) z = make_float4(mishf(z.x), mishf(z.y), mishf(z.z), mishf(z.w));
-                    if (QPWC_SC_BUF_STORE)
-                        // (the block's 64 * ft bytes go into the instruction's immediate offset, NOT the scalar offset: with a
-                        // REGISTER there hipcc assumes the store has read its data when the next instruction issues and lets
-                        // the Mish of the next values overwrite v[4:7] right behind `buffer_store_dwordx4 v[4:7], .., s4 offen`
-                        // -- on gfx950 it has not: channel 4g+1 of one block came out as garbage, run-to-run different)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4sc, z), ro, ooff[m] + 64 * ft, 0, 0);
-                    else if (ook[m]) *reinterpret_cast<float4*>(orow[m] + 16 * ft) = z;
+                    // (the block's 64 * ft bytes go into the instruction's immediate offset, NOT the scalar offset: with a
+                    // REGISTER there hipcc assumes the store has read its data when the next instruction issues and lets
+                    // the Mish of the next values overwrite v[4:7] right behind `buffer_store_dwordx4 v[4:7], .., s4 offen`
+                    // -- on gfx950 it has not: channel 4g+1 of one block came out as garbage, run-to-run different)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4sc, z), ro, ooff[m] + 64 * ft, 0, 0);
                 }
             };
 #pragma unroll
@@ -803,21 +777,6 @@ __global__ __launch_bounds__(256, 2) void sepconv3x3_fused_kernel(
     } while (RES && (v += (int)gridDim.x) < n_work);
 }
 
-#ifdef QPWC_SC_WS
-#include "experimental/sepconv_role_split.inc"
-#endif
-
-#ifdef QPWC_SC_PP     // lab note (round 4): eight-wave ping-pong, make ab ABSRC=optflow ABFLAGS=-DQPWC_SC_PP=1
-#include <type_traits>
-#include "experimental/sepconv_pp.inc"
-#endif
-#ifdef QPWC_SC_FLAT   // lab note (round 4): parity-correct only by luck of the register allocation, slower -- never in the product build
-#include "experimental/sepconv_flat.inc"
-#endif
-
-#ifndef QPWC_SC_SPLIT_ONE_ROUND
-#define QPWC_SC_SPLIT_ONE_ROUND 0   // 0 = off; else the smallest F it applies to
-#endif
 #ifndef QPWC_SC_SLICE_TARGET
 #define QPWC_SC_SLICE_TARGET 192   // split a layer's outputs over workgroups until the launch has this many
 #endif
@@ -871,7 +830,7 @@ int sepconv3x3_launch(const void* const* srcs, const int* chans, const int64_t* 
         set_error("sepconv3x3: too many tiles");
         return QPWC_E_SHAPE;
     }
-    if (QPWC_SC_BUF_STORE && (int64_t)kScTH * W * F * 4 >= 0x7fffffff) {   // the output descriptor spans a tile's band of rows
+    if ((int64_t)kScTH * W * F * 4 >= 0x7fffffff) {   // the output descriptor spans a tile's band of rows
         set_error("sepconv3x3: 8 rows of outputs must stay below 2 GiB");
         return QPWC_E_SHAPE;
     }
@@ -879,9 +838,7 @@ int sepconv3x3_launch(const void* const* srcs, const int* chans, const int64_t* 
     // outputs) until the launch has ~one workgroup per CU
     int slices = 1;
     while (nblk * slices < QPWC_SC_SLICE_TARGET && F / (slices * 2) >= 16) slices *= 2;
-    // A/B (round 4): a launch of 257..512 tiles is ONE round of two workgroups per CU -- every workgroup's prologue and
-    // epilogue exposed at the same time; with its outputs split over two workgroups per tile it is two rounds
-    if (QPWC_SC_SPLIT_ONE_ROUND && slices == 1 && nblk > 256 && nblk <= 512 && F >= QPWC_SC_SPLIT_ONE_ROUND) slices = 2;
+    // (A/B, round 4: a launch of 257..512 tiles -- ONE round of two workgroups per CU -- split over two workgroups per tile: not kept)
     const dim3 grid((unsigned)(nblk * slices));
     // 16-byte loads: every source but the last holds a multiple of 4 channels in 16-byte aligned
     // pixels; the last one either does too or is read element-wise (it must not straddle a quad
@@ -904,51 +861,6 @@ int sepconv3x3_launch(const void* const* srcs, const int* chans, const int64_t* 
         set_error("sepconv3x3: unsupported filter count %d (16/32/64/128)", F);
         return QPWC_E_SHAPE;
     }
-#ifdef QPWC_SC_WS
-    {
-        // role-split kernel: every source but the last in whole 16-byte chunks (the last may be a short tail),
-        // no activation on load, byte offsets inside one image below 2^31
-        bool ws = vec && slices == 1 && nblk >= QPWC_SC_WS && (act & 1) == 0;
-        for (int i = 0; i < n_src; ++i)
-            if (((int64_t)H * W * strides[i] + 4) * 4 >= 0x7fffffff) ws = false;
-        if (ws) {
-            const bool oa = (act & 2) != 0;
-#define QPWC_WS_LAUNCH(FF, AO)                                                                           \
-    hipLaunchKernelGGL((sepconv3x3_ws_kernel<FF, AO>), grid, dim3(512), 0, s, d, fdw, fpw, fb, (float*)out, \
-                       B, H, W, C, cpad, tiles_x, tiles_y)
-#define QPWC_WS_F(FF) do { if (oa) QPWC_WS_LAUNCH(FF, true); else QPWC_WS_LAUNCH(FF, false); } while (0)
-            switch (F) {
-                case 128: QPWC_WS_F(128); break;
-                case 64: QPWC_WS_F(64); break;
-                case 32: QPWC_WS_F(32); break;
-                default: QPWC_WS_F(16); break;
-            }
-#undef QPWC_WS_F
-#undef QPWC_WS_LAUNCH
-            return check_launch("sepconv3x3_ws_kernel");
-        }
-    }
-#endif
-#ifdef QPWC_SC_PP
-    if (QPWC_SC_PP && vec && slices == 1 && (F == 64 || F == 128) && nblk >= QPWC_SC_PP_MIN_TILES &&
-        (int64_t)H * W * F * 4 < 0x7fffffff) {
-        if (dry_run(F == 128 ? "sepconv3x3_pp_kernel<128>" : "sepconv3x3_pp_kernel<64>")) return QPWC_OK;
-        if (F == 128)
-            sepconv_pp_dispatch<128>(d, act, fdw, fpw, fb, (float*)out, H, W, C, cpad, tiles_x, tiles_y, (int)nblk, s);
-        else
-            sepconv_pp_dispatch<64>(d, act, fdw, fpw, fb, (float*)out, H, W, C, cpad, tiles_x, tiles_y, (int)nblk, s);
-        return check_launch("sepconv3x3_pp_kernel");
-    }
-#endif
-#ifdef QPWC_SC_FLAT
-    // round 4: the wide layers of the big levels as ONE flat software pipeline per resident workgroup (sepconv_flat.inc)
-    if (vec && slices == 1 && (F == 64 || F == 128) && nblk >= QPWC_SC_FLAT_MIN_TILES &&
-        (int64_t)H * W * F * 4 < 0x7fffffff) {
-        if (dry_run(F == 128 ? "sepconv3x3_flat_kernel<64> x 2 slices" : "sepconv3x3_flat_kernel<64>")) return QPWC_OK;
-        sepconv_flat_dispatch<64>(d, act, fdw, fpw, fb, (float*)out, H, W, C, cpad, tiles_x, tiles_y, (int)nblk, F / 64, s);
-        return check_launch("sepconv3x3_flat_kernel");
-    }
-#endif
     switch (F / slices) {   // outputs per workgroup
         case 128: sepconv_dispatch<128>(d, act, vec, fdw, fpw, fb, (float*)out, H, W, C, cpad, tiles_x, tiles_y, grid, slices, s); break;
         case 64: sepconv_dispatch<64>(d, act, vec, fdw, fpw, fb, (float*)out, H, W, C, cpad, tiles_x, tiles_y, grid, slices, s); break;
@@ -1253,15 +1165,12 @@ __global__ __launch_bounds__(256) void upsample2x_flow_pair_kernel(const T* __re
     }
 }
 
-#ifndef QPWC_UPSAMPLE_PAIRS
-#define QPWC_UPSAMPLE_PAIRS 1   // 0: every call on the one-pixel-per-thread kernel (A/B)
-#endif
 int upsample2x_flow_launch(const void* in, void* out, int B, int h, int w, float scale, int dtype,
                            int in_layout, int out_layout, hipStream_t s) {
     const int in_nchw = in_layout == QPWC_NCHW, out_nchw = out_layout == QPWC_NCHW;
     const int64_t n_pairs = (int64_t)B * 2 * h * w;
     const size_t es = dtype == QPWC_F32 ? 4 : 2;
-    if (QPWC_UPSAMPLE_PAIRS && !in_nchw && !out_nchw && n_pairs * 4 < INT32_MAX &&
+    if (!in_nchw && !out_nchw && n_pairs * 4 < INT32_MAX &&
         reinterpret_cast<uintptr_t>(in) % (2 * es) == 0 && reinterpret_cast<uintptr_t>(out) % (4 * es) == 0) {
         const int64_t wantp = (n_pairs + 255) / 256;
         const dim3 gridp((unsigned)(wantp < 16384 ? wantp : 16384));

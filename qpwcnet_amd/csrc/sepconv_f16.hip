@@ -23,15 +23,6 @@ constexpr int kDwHoistC = 128;      // widest layer (padded channels) whose taps
 #ifndef QPWC_SC16_HOIST_TAPS
 #define QPWC_SC16_HOIST_TAPS 0      // A/B (round 4): measured +-0 on the wide layers, -4 % on the first layer (L4 B=32: 259-264 vs 248 us): off
 #endif
-#ifndef QPWC_SC16_DEEP
-#define QPWC_SC16_DEEP 0            // A/B (round 4): two staged steps in flight in the one-shot form -- measured +-0 (L4 B=32: 258.3 vs 261.2, 171.4 vs 172.8 us): the kernel is not bound by its bytes in flight
-#endif
-#ifndef QPWC_SC16_BIAS_EARLY
-#define QPWC_SC16_BIAS_EARLY 1      // A/B (round 4): bias values requested before the last matrix step
-#endif
-#ifndef QPWC_SC16_WIDE_STORES
-#define QPWC_SC16_WIDE_STORES 0     // A/B (round 4): 16-byte output stores through v_permlane16_swap -- parity-green, +-0 (config 5 step 1.679 vs 1.656 ms with both switches on): off
-#endif
 
 template <int F, bool ACT, bool ACT_OUT, bool WIDE, bool RES = false>
 __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv3x3_fused_f16_kernel(   // resident narrow layers: 3 workgroups per CU (<= 168 registers)
@@ -88,17 +79,15 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
         }
     };
     set_goff();
-    // one step's staged inputs (+ its taps where they are not staged whole).  Round 4: the one-shot form keeps TWO sets
-    // in flight (DEEP): the kernel's HBM rate is (bytes in flight per CU) / (memory latency under load) -- two
-    // workgroups x one 11.5 KB request each per ~2.5 us round trip = the 2.0-2.3 TB/s it measured -- so step k + 3 is
-    // requested when step k + 1 is committed, into the register set that commit frees (12 more registers).
+    // one step's staged inputs (+ its taps where they are not staged whole).  (A/B, round 4: TWO sets in flight in the
+    // one-shot form, step k + 3 requested when step k + 1 is committed -- measured +-0, L4 B=32: 258.3 vs 261.2, 171.4 vs
+    // 172.8 us: the kernel is not bound by its bytes in flight; not kept.)
     struct Stage {
         uint4 st[WIDE ? NST : 1];
         uint2 st2[WIDE ? 1 : NST];
         float dreg[2];
     };
-    constexpr bool DEEP = QPWC_SC16_DEEP && !RES;
-    Stage sa, sb;
+    Stage sa;
     uint4 wreg0, wreg1;
     wreg0 = wreg1 = make_uint4(0, 0, 0, 0);
     auto fetch_in = [&](int c0, Stage& S) __attribute__((always_inline)) {   // inputs and depthwise taps of the step at channel c0: global -> registers
@@ -292,7 +281,6 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
             for (int i = 0; i < NFT; ++i) acc[m][i] = f32x4v{0.f, 0.f, 0.f, 0.f};
     };
     fetch_in(0, sa);
-    if (DEEP && nsteps > 1) fetch_in(kScKC, sb);
     fetch_w(0);
     if (hoist) stage_all_taps();     // (visible after the barrier that follows the first commit_in)
     int v = blockIdx.x;
@@ -306,12 +294,8 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
         };
         commit_in(sa);
         __syncthreads();
-        if (DEEP) {
-            if (nsteps > 2) fetch_in(2 * kScKC, sa);
-        } else {
-            if (nsteps > 1) fetch_in(kScKC, sa);
-            else if (more) next_tile_request();
-        }
+        if (nsteps > 1) fetch_in(kScKC, sa);
+        else if (more) next_tile_request();
         depthwise(y_s, 0);
         // iteration k: weights of step k and inputs of step k + 1 into LDS, requests for what comes next, then the matrix
         // work of step k beside the depthwise convolution of step k + 1
@@ -321,24 +305,13 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
             commit_in(S);
             __syncthreads();
             fetch_w((k + 1) * kScKC);
-            if (DEEP) {
-                if (k + 3 < nsteps) fetch_in((k + 3) * kScKC, S);
-            } else {
-                if (k + 2 < nsteps) fetch_in((k + 2) * kScKC, S);
-                else if (more) next_tile_request();
-            }
+            if (k + 2 < nsteps) fetch_in((k + 2) * kScKC, S);
+            else if (more) next_tile_request();
             if (RES && k == 0) zero_acc();
             pointwise(y_s + (k & 1) * kYh);
             depthwise(y_s + ((k + 1) & 1) * kYh, (k + 1) * kScKC);
         };
-        if (DEEP) {
-            for (int k = 0; k + 1 < nsteps; k += 2) {
-                iteration(k, sb);                             // step k + 1 (odd) lives in set b
-                if (k + 2 < nsteps) iteration(k + 1, sa);     // step k + 2 (even) in set a
-            }
-        } else {
-            for (int k = 0; k + 1 < nsteps; ++k) iteration(k, sa);
-        }
+        for (int k = 0; k + 1 < nsteps; ++k) iteration(k, sa);
         __syncthreads();
         commit_w();
         __syncthreads();
@@ -347,11 +320,9 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
         // each load sat behind an `s_waitcnt vmcnt(0)` in front of its use, and vmcnt counts stores on gfx950: every block
         // waited for the previous block's output stores to be acknowledged (the fp32 kernel's last step: 11.5 k cycles
         // against 5 k for the others, optflow.hip).
-        float4 bvs[QPWC_SC16_BIAS_EARLY ? NFT : 1];
-        if (QPWC_SC16_BIAS_EARLY) {
+        float4 bvs[NFT];
 #pragma unroll
-            for (int ft = 0; ft < NFT; ++ft) bvs[ft] = *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
-        }
+        for (int ft = 0; ft < NFT; ++ft) bvs[ft] = *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
         pointwise(y_s + ((nsteps - 1) & 1) * kYh);
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
@@ -360,35 +331,14 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
             const bool ok = gy < H && gx < W;
             __half* o = out + ((int64_t)(eb * H + gy) * W + gx) * F;
             auto finish = [&](int ft) __attribute__((always_inline)) {
-                const float4 bv = QPWC_SC16_BIAS_EARLY ? bvs[QPWC_SC16_BIAS_EARLY ? ft : 0]
-                                                       : *reinterpret_cast<const float4*>(bias + 16 * ft + 4 * g);
+                const float4 bv = bvs[ft];
                 float4 z = make_float4(acc[m][ft][0] + bv.x, acc[m][ft][1] + bv.y, acc[m][ft][2] + bv.z,
                                        acc[m][ft][3] + bv.w);
                 if (ACT_OUT) z = make_float4(mishf(z.x), mishf(z.y), mishf(z.z), mishf(z.w));
                 return z;
             };
-            if (QPWC_SC16_WIDE_STORES && NFT >= 2) {
-                // Round 4: 16-byte stores.  Lane (n, g) holds channels 16 ft + 4 g .. + 3 of blocks ft and ft + 1, 8 bytes
-                // each; the lanes of rows g and g ^ 1 (16 lanes apart, same pixel) trade one of the two through
-                // v_permlane16_swap (swaps the odd rows of its first operand with the even rows of its second) and
-                // each then owns 8 consecutive channels: even g those of block ft, odd g those of block ft + 1 --
-                // half the store instructions (16 -> 8 per lane at 128 outputs; the kernel is bound by their count).
-#pragma unroll
-                for (int fp = 0; fp < NFT / 2; ++fp) {
-                    const float4 z0 = finish(2 * fp), z1 = finish(2 * fp + 1);
-                    const __half2 a0 = __floats2half2_rn(z0.x, z0.y), a1 = __floats2half2_rn(z0.z, z0.w);
-                    const __half2 b0 = __floats2half2_rn(z1.x, z1.y), b1 = __floats2half2_rn(z1.z, z1.w);
-                    const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a0),
-                                                                     __builtin_bit_cast(unsigned, b0), false, false);
-                    const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a1),
-                                                                     __builtin_bit_cast(unsigned, b1), false, false);
-                    // even g: r*[0] = own block-ft pair, r*[1] = row g + 1's block-ft pair (channels 4 g + 4 ..)
-                    // odd g : r*[0] = row g - 1's block-(ft + 1) pair (channels 4 g - 4 ..), r*[1] = own
-                    const uint4 pk = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-                    const int ch = (g & 1) ? 16 * (2 * fp + 1) + 4 * (g - 1) : 16 * (2 * fp) + 4 * g;
-                    if (ok) *reinterpret_cast<uint4*>(o + ch) = pk;
-                }
-            } else if (ok) {
+            // (A/B, round 4: 16-byte output stores through v_permlane16_swap -- parity-green, +-0, config 5 step 1.679 vs 1.656 ms: not kept)
+            if (ok) {
 #pragma unroll
                 for (int ft = 0; ft < NFT; ++ft) st4(o + 16 * ft + 4 * g, finish(ft));
             }
@@ -396,13 +346,6 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
         if (more) fetch_w(0);
     } while (RES && (v += (int)gridDim.x) < n_work);
 }
-
-#ifndef QPWC_SC16_STREAM
-#define QPWC_SC16_STREAM 0   // lab note only: make ab ABSRC=optflow ABFLAGS=-DQPWC_SC16_STREAM=1
-#endif
-#if QPWC_SC16_STREAM
-#include "experimental/sepconv_f16_stream.inc"
-#endif
 
 #ifndef QPWC_SC16_RESIDENT
 #define QPWC_SC16_RESIDENT 512   // resident workgroups of the fp16 fused SeparableConv2D (0 = one workgroup per tile)
@@ -412,12 +355,6 @@ __global__ __launch_bounds__(256, (RES && WIDE && F <= 32) ? 3 : 2) void sepconv
                                  // one workgroup per tile (A/B build, one call): L4 F=32 65.4 vs 75.2, F=16 32.1 vs 35.4; L3 18.6 vs
                                  // 21.6, 10.5 vs 11.0 -- but F=64 170.8 vs 155.2 (172 registers: 2 instead of 3 waves per SIMD)
                                  // and F=128 266.8 vs 247.8: the narrow layers only, as in fp32
-#endif
-#ifndef QPWC_SC16_DIRECT
-#define QPWC_SC16_DIRECT 0   // lab note (experimental/sepconv_f16_direct.inc): parity-green, slower -- never in the product build
-#endif
-#if QPWC_SC16_DIRECT
-#include "experimental/sepconv_f16_direct.inc"
 #endif
 
 template <int F>
@@ -473,32 +410,6 @@ int sepconv3x3_f16_launch(const void* const* srcs, const int* chans, const int64
     const dim3 grid((unsigned)nblk);
     const __half* hp = (const __half*)pw;
     const float *fdw = (const float*)dw, *fb = (const float*)bias;
-#if QPWC_SC16_STREAM
-    // lab note (experimental/sepconv_f16_stream.inc): parity-green, slower -- never in the product build
-    if ((act & 1) == 0 && (int64_t)((W + kS2T - 1) / kS2T) * ((H + kS2T - 1) / kS2T) * B <= INT32_MAX) {
-        const bool oa = (act & 2) != 0;
-        switch (F) {
-            case 128: sepconv_f16_stream_dispatch<128>(d, wide, oa, fdw, hp, fb, (__half*)out, H, W, C, cpad, B, s); break;
-            case 64: sepconv_f16_stream_dispatch<64>(d, wide, oa, fdw, hp, fb, (__half*)out, H, W, C, cpad, B, s); break;
-            case 32: sepconv_f16_stream_dispatch<32>(d, wide, oa, fdw, hp, fb, (__half*)out, H, W, C, cpad, B, s); break;
-            case 16: sepconv_f16_stream_dispatch<16>(d, wide, oa, fdw, hp, fb, (__half*)out, H, W, C, cpad, B, s); break;
-            default: set_error("sepconv3x3_f16: unsupported filter count %d (16/32/64/128)", F); return QPWC_E_SHAPE;
-        }
-        return check_launch("sepconv3x3_f16_stream_kernel");
-    }
-#endif
-#if QPWC_SC16_DIRECT
-    if (F >= QPWC_SC16_DIRECT_MINF) {
-        switch (F) {
-            case 128: sepconv_f16_direct_dispatch<128>(d, wide, act, fdw, hp, fb, (__half*)out, H, W, C, cpad, tiles_x, tiles_y, grid, s); break;
-            case 64: sepconv_f16_direct_dispatch<64>(d, wide, act, fdw, hp, fb, (__half*)out, H, W, C, cpad, tiles_x, tiles_y, grid, s); break;
-            case 32: sepconv_f16_direct_dispatch<32>(d, wide, act, fdw, hp, fb, (__half*)out, H, W, C, cpad, tiles_x, tiles_y, grid, s); break;
-            case 16: sepconv_f16_direct_dispatch<16>(d, wide, act, fdw, hp, fb, (__half*)out, H, W, C, cpad, tiles_x, tiles_y, grid, s); break;
-            default: set_error("sepconv3x3_f16: unsupported filter count %d (16/32/64/128)", F); return QPWC_E_SHAPE;
-        }
-        return check_launch("sepconv3x3_f16_direct_kernel");
-    }
-#endif
     switch (F) {
         case 128: sepconv_f16_dispatch<128>(d, wide, act, fdw, hp, fb, (__half*)out, H, W, C, cpad, tiles_x, tiles_y, grid, s); break;
         case 64: sepconv_f16_dispatch<64>(d, wide, act, fdw, hp, fb, (__half*)out, H, W, C, cpad, tiles_x, tiles_y, grid, s); break;

@@ -107,9 +107,6 @@ class QpwcNet:
         self._sides = []
         # side stream of each decoder level in the two-stream forward (see _forward_two_streams)
         self.dec_stream_of = (0, 0, 0, 0)
-        # round 4 (tools/capture_crosswait.py): the two suspects of the capture SIGSEGV as switches
-        self.allow_returning_dec_streams = False    # a mapping like (0,1,0,1): two side streams waiting on each other
-        self.record_stream_under_capture = True     # Tensor.record_stream on private-pool tensors while capturing
         # the skip halves of the decoder's concat buffers copied under the encoder (_prefill): measured SLOWER -- 1.230 vs 1.133
         # ms/step (config 5: 1.781 vs 1.645; config 4: 30.0 vs 29.8): a fork that early turns the encoder's chain into one branch
         # of a two-branch graph for its whole length (tools/step_time.py prefill_skips=True).  Off.
@@ -246,8 +243,7 @@ class QpwcNet:
         with torch.cuda.stream(side):
             buf = self.dec[i].prefill_skip(f, c_in)
         if buf is not None:
-            if self.record_stream_under_capture or not torch.cuda.is_current_stream_capturing():
-                f.record_stream(side)
+            f.record_stream(side)
             self._prefilled[i] = buf
 
     def _encode_stacked(self, inputs, prefill=False):
@@ -311,12 +307,8 @@ class QpwcNet:
         # 0 on ITS stream; a mapping that RETURNS to an earlier stream, e.g. (0,1,0,1), makes two side streams wait on
         # each other alternately and the runtime dies with SIGSEGV while capturing / instantiating the graph -- the
         # round-1 "four staggered streams" crash.  Unsupported by this build: refused here.
-        if (any(b < a for a, b in zip(self.dec_stream_of, self.dec_stream_of[1:])) and
-                not self.allow_returning_dec_streams) or min(self.dec_stream_of) < 0:
+        if any(b < a for a, b in zip(self.dec_stream_of, self.dec_stream_of[1:])) or min(self.dec_stream_of) < 0:
             raise ValueError("dec_stream_of must be non-decreasing side-stream indices, got {}".format(self.dec_stream_of))
-        # tensors allocated under capture come from the graph's private pool and stay referenced (decs) until every
-        # stream has been joined: the graph's own edges order their reuse, the allocator needs no cross-stream note
-        note_streams = self.record_stream_under_capture or not torch.cuda.is_current_stream_capturing()
         n_side = max(self.dec_stream_of) + 1
         while len(self._sides) < n_side:
             self._sides.append(self._side if not self._sides else torch.cuda.Stream(device=encs[-1].device))
@@ -393,7 +385,7 @@ class QpwcNet:
                     # allocated on `side`, read by UpFlow on `main`: tell the caching allocator, so that the block
                     # is not handed to a later side-stream allocation while main may still be reading it (the
                     # join at the end orders main after side, not side's NEXT use after main's reads)
-                    for sd in ([main] + sides) if note_streams else ():
+                    for sd in [main] + sides:
                         if sd is not side:
                             f.record_stream(sd)
                     decs[i] = f

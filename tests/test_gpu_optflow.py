@@ -283,8 +283,8 @@ def test_sepconv3x3_wide_layers_many_tiles(chans, F, act):
     """The wide layers (F = 64 / 128) on a launch of 1183 ragged tiles (7 images of 100 x 200 pixels = 12.5 x 12.5 tiles:
     several rounds of workgroups per CU, partial tiles at the right / bottom edges), 1 / 2 / 4 / 5 steps per tile, a
     three-source first layer with the 2-channel flow tail: against the oracle, and BIT-IDENTICAL to the same images
-    launched one at a time (169 tiles).  Written for round 4's flat-pipeline kernel (csrc/experimental/sepconv_flat.inc,
-    not in the product build: it failed the bit-identity half of this test through a hardware hazard)."""
+    launched one at a time (169 tiles).  Written for round 4's flat-pipeline lab kernel (removed after 784aa79,
+    see git history: it failed the bit-identity half of this test through a hardware hazard)."""
     rng = np.random.default_rng(sum(chans) + F)
     B, H, W = 7, 100, 200
     assert B * ((H + 7) // 8) * ((W + 15) // 16) >= 1024 > ((H + 7) // 8) * ((W + 15) // 16)

@@ -4,7 +4,7 @@ C operand registers of an fp32 matrix instruction (v_mfma_f32_16x16x4_f32 with v
 fewer than 7 wait states after it.  The compiler inserts s_nop for LDS / memory returns into such registers, and for
 VALU writes after the XDL (low-precision) instructions, but not for this pair; on gfx950 the instruction reads C late
 when the matrix pipe is contended and the result loses its accumulated sum in the last columns
-(csrc/experimental/sepconv_flat.inc: found by a bit-identity test, round 4).
+(the flat-pipeline lab kernel, removed after 784aa79, see git history: found by a bit-identity test, round 4).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iqpwcnet_amd/csrc -S --cuda-device-only qpwcnet_amd/csrc/optflow.hip -o /tmp/optflow.s
     python tools/mfma_war_lint.py /tmp/optflow.s
