@@ -293,6 +293,37 @@ int qpwc_sepconv3x3_fwd(const void* const* src, const int* src_channels,
                         const void* dw, const void* pw, const void* bias, void* out,
                         int B, int H, int W, int F, void* stream);
 
+/* Floats of device scratch qpwc_sepconv3x3_bwd needs for C = sum(src_channels) input channels (the recomputed
+ * depthwise result and its gradient, (B*H*W, Cpad) each, gz (B*H*W, F), and the per-workgroup partials of the three
+ * weight gradients); negative QPWC_E_SHAPE for a non-positive extent, F outside {16,32,64,128} or a shape whose
+ * launch grids do not fit. */
+int64_t qpwc_sepconv3x3_bwd_workspace_floats(int B, int H, int W, int C, int F);
+
+/* Gradient of qpwc_sepconv3x3_fwd (fp32): what TF autograd takes through SeparableConv2D(3x3,'same')
+ * (non_layers.py:223-231) under qpwcnet/app/optical_flow/train.py.  With x = concat(src), a = Mish(x) if bit 0 of
+ * mish_flags else x, d = depthwise3x3(a), z = bias + pw d, out = Mish(z) if bit 1 else z, and g = grad_out =
+ * dL/d(what the forward stored), dense (B,H,W,F):
+ *   gz = g * Mish'(z) if bit 1 else g,   Mish'(t) = tanh(sp) + t (1 - tanh(sp)^2) sigmoid(t), sp = softplus(t)
+ *   grad_bias[f] = sum_p gz[p,f]
+ *   grad_pw[f,c] = sum_p gz[p,f] d[p,c]                        (F, Cpad); columns c >= C are written as 0
+ *   gd[p,c]      = sum_f gz[p,f] pw[f,c]
+ *   grad_dw[c,ky,kx] = sum_p gd[p,c] a[p+(ky-1,kx-1),c]         (C,3,3); pixels inside the image only
+ *   ga[p,c]      = sum_{ky,kx} dw[c,ky,kx] gd[p-(ky-1,kx-1),c]  (source pixels inside the image)
+ *   grad_src     = ga * Mish'(x) if bit 0 else ga, one dense (B,H,W,src_channels[i]) tensor per source
+ * d and z are recomputed from the sources (Mish is not invertible; nothing but the sources and weights is needed).
+ * src / src_channels / src_pixel_stride / dw / pw / bias / F as in the forward.  grad_src: n_src pointers, each may
+ * be NULL, as may the array; grad_dw, grad_pw, grad_bias may be NULL; not all outputs.  Work whose only consumer is
+ * a NULL output is skipped (no depthwise backward when only grad_pw / grad_bias are asked for).  All five outputs
+ * are bitwise reproducible: fixed-order two-stage reductions, no atomics.  workspace:
+ * qpwc_sepconv3x3_bwd_workspace_floats() floats.  Alignment: pw, grad_out, grad_pw and workspace 16 bytes (read and
+ * written as float4 / 16-byte rows), everything else 4.  Errors: QPWC_E_NULL, QPWC_E_SHAPE (extents, F, n_src,
+ * mish_flags, channels <= 0, pixel stride < channels), QPWC_E_ALIGN, QPWC_E_ALIAS (an output or the workspace
+ * overlapping an input or another output); qpwc_last_error() names the argument. */
+int qpwc_sepconv3x3_bwd(const void* const* src, const int* src_channels, const int64_t* src_pixel_stride,
+                        int n_src, int mish_flags, const void* dw, const void* pw, const void* bias,
+                        const void* grad_out, void* const* grad_src, void* grad_dw, void* grad_pw, void* grad_bias,
+                        void* workspace, int B, int H, int W, int F, void* stream);
+
 /* qpwc_sepconv3x3_fwd with the pointwise products on the bf16 matrix instructions ("bf16x3", csrc/split_bf16.h: both
  * operands split into three bf16 values, six partial products, fp32 accumulation; depthwise 3x3 in fp32 as before).
  * pw3: the (F, Cpad) fp32 matrix of qpwc_sepconv3x3_fwd split by qpwc_split_bf16x3_fwd = (3, F, Cpad) bf16.

@@ -33,6 +33,7 @@ SYMBOLS = (
     "qpwc_first_conv_mish_fwd", "qpwc_first_conv_mish_f16_fwd", "qpwc_conv3x3s2_mish_fwd", "qpwc_conv3x3s2_mish_c_fwd", "qpwc_conv3x3s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_fwd", "qpwc_upconv4x4s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_cat_fwd", "qpwc_upconv4x4s2_mish_cat_f16_fwd",
     "qpwc_cost_volume_bwd", "qpwc_warp_bwd_workspace_floats", "qpwc_warp_bwd",
     "qpwc_loss_workspace_floats", "qpwc_loss_fwd", "qpwc_loss_fwd_kernel", "qpwc_loss_bwd",
+    "qpwc_sepconv3x3_bwd_workspace_floats", "qpwc_sepconv3x3_bwd",
 )
 
 _lib = None
@@ -184,6 +185,11 @@ def lib():
     L.qpwc_loss_fwd_kernel.restype = ctypes.c_char_p
     L.qpwc_loss_bwd.argtypes = [pvp, vp, pvp, ctypes.POINTER(i64), pi, ci, vp]
     L.qpwc_loss_bwd.restype = ci
+    L.qpwc_sepconv3x3_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci]
+    L.qpwc_sepconv3x3_bwd_workspace_floats.restype = i64
+    L.qpwc_sepconv3x3_bwd.argtypes = [pvp, pi, ctypes.POINTER(i64), ci, ci, vp, vp, vp, vp, pvp, vp, vp, vp, vp,
+                                      ci, ci, ci, ci, vp]
+    L.qpwc_sepconv3x3_bwd.restype = ci
     _lib = L
     return L
 

@@ -113,6 +113,11 @@ const char* loss_fwd_kernel(int kind, int H, int W, const int* h, const int* w, 
 int loss_fwd_launch(int kind, float p0, float p1, const float* gt, int B, int H, int W, int C, int layout,
                     const void* const* pred, const int* h, const int* w, const int* pred_dtype, int n, float* out,
                     void* const* dpred, void* const* gt_out, float* ws, hipStream_t s);
+int64_t sepconv3x3_bwd_workspace_floats(int B, int H, int W, int C, int F);
+bool sepconv3x3_bwd_shape_ok(int B, int H, int W, int C, int F);
+int sepconv3x3_bwd_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src, int flags,
+                          const void* dw, const void* pw, const void* bias, const void* gout, void* const* gsrc,
+                          void* gdw, void* gpw, void* gbias, void* ws, int B, int H, int W, int F, hipStream_t s);
 int loss_bwd_launch(const void* const* dpred, const float* grad_losses, void* const* grad_pred, const int64_t* n_elems,
                     const int* pred_dtype, int n, hipStream_t s);
 
@@ -588,6 +593,81 @@ int qpwc_sepconv3x3_fwd(const void* const* src, const int* src_channels,
     if (mish_flags < 0 || mish_flags > 3) return fail(QPWC_E_SHAPE, "mish_flags %d outside [0,3]", mish_flags);
     return sepconv3x3_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, out, B,
                              H, W, F, (hipStream_t)stream);
+}
+
+static int sepconv_bwd_check_shape(int B, int H, int W, int64_t C, int F) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0)
+        return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d C=%lld", B, H, W, (long long)C);
+    if (F != 16 && F != 32 && F != 64 && F != 128) return fail(QPWC_E_SHAPE, "F=%d not in {16,32,64,128}", F);
+    if (C > (1 << 20) || !sepconv3x3_bwd_shape_ok(B, H, W, (int)C, F))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d C=%lld: too large for the backward's launch grids", B, H, W, (long long)C);
+    return QPWC_OK;
+}
+
+int64_t qpwc_sepconv3x3_bwd_workspace_floats(int B, int H, int W, int C, int F) {
+    const int rc = sepconv_bwd_check_shape(B, H, W, C, F);
+    return rc != QPWC_OK ? rc : sepconv3x3_bwd_workspace_floats(B, H, W, C, F);
+}
+
+int qpwc_sepconv3x3_bwd(const void* const* src, const int* src_channels, const int64_t* src_pixel_stride, int n_src,
+                        int mish_flags, const void* dw, const void* pw, const void* bias, const void* grad_out,
+                        void* const* grad_src, void* grad_dw, void* grad_pw, void* grad_bias, void* workspace, int B,
+                        int H, int W, int F, void* stream) {
+    if (!src) return fail(QPWC_E_NULL, "src is null");
+    if (!src_channels) return fail(QPWC_E_NULL, "src_channels is null");
+    if (!src_pixel_stride) return fail(QPWC_E_NULL, "src_pixel_stride is null");
+    if (!dw) return fail(QPWC_E_NULL, "dw is null");
+    if (!pw) return fail(QPWC_E_NULL, "pw is null");
+    if (!bias) return fail(QPWC_E_NULL, "bias is null");
+    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
+    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
+    if (n_src < 1 || n_src > 3) return fail(QPWC_E_SHAPE, "n_src %d outside [1,3]", n_src);
+    if (mish_flags < 0 || mish_flags > 3) return fail(QPWC_E_SHAPE, "mish_flags %d outside [0,3]", mish_flags);
+    int64_t C = 0;
+    bool any_out = grad_dw || grad_pw || grad_bias;
+    for (int i = 0; i < n_src; ++i) {
+        if (!src[i]) return fail(QPWC_E_NULL, "src[%d] is null", i);
+        if (src_channels[i] <= 0 || src_pixel_stride[i] < src_channels[i])
+            return fail(QPWC_E_SHAPE, "src[%d]: %d channels at pixel stride %lld", i, src_channels[i],
+                        (long long)src_pixel_stride[i]);
+        C += src_channels[i];
+        any_out |= grad_src && grad_src[i];
+    }
+    if (!any_out) return fail(QPWC_E_NULL, "grad_src, grad_dw, grad_pw and grad_bias are all null");
+    int rc = sepconv_bwd_check_shape(B, H, W, C, F);
+    if (rc != QPWC_OK) return rc;
+    const size_t M = (size_t)B * H * W, cpad = (size_t)(C + 31) / 32 * 32;
+    // buffers: inputs first, then outputs; name, extent in bytes, required alignment
+    struct Buf { const void* p; size_t n; size_t align; char name[16]; };
+    Buf bufs[14];
+    int n_in = 0, n_all;
+    auto add = [&](int& k, const void* p, size_t n, size_t align, const char* fmt, int i) {
+        bufs[k].p = p; bufs[k].n = n; bufs[k].align = align;
+        snprintf(bufs[k].name, sizeof(bufs[k].name), fmt, i);
+        ++k;
+    };
+    for (int i = 0; i < n_src; ++i)
+        add(n_in, src[i], ((M - 1) * (size_t)src_pixel_stride[i] + src_channels[i]) * 4, 4, "src[%d]", i);
+    add(n_in, dw, (size_t)C * 9 * 4, 4, "dw", 0);
+    add(n_in, pw, (size_t)F * cpad * 4, 16, "pw", 0);
+    add(n_in, bias, (size_t)F * 4, 4, "bias", 0);
+    add(n_in, grad_out, M * F * 4, 16, "grad_out", 0);
+    n_all = n_in;
+    for (int i = 0; i < n_src; ++i)
+        if (grad_src && grad_src[i]) add(n_all, grad_src[i], M * src_channels[i] * 4, 4, "grad_src[%d]", i);
+    if (grad_dw) add(n_all, grad_dw, (size_t)C * 9 * 4, 4, "grad_dw", 0);
+    if (grad_pw) add(n_all, grad_pw, (size_t)F * cpad * 4, 16, "grad_pw", 0);
+    if (grad_bias) add(n_all, grad_bias, (size_t)F * 4, 4, "grad_bias", 0);
+    add(n_all, workspace, (size_t)sepconv3x3_bwd_workspace_floats(B, H, W, (int)C, F) * 4, 16, "workspace", 0);
+    for (int k = 0; k < n_all; ++k)
+        if ((uintptr_t)bufs[k].p % bufs[k].align)
+            return fail(QPWC_E_ALIGN, "%s must be %d-byte aligned", bufs[k].name, (int)bufs[k].align);
+    for (int o = n_in; o < n_all; ++o)
+        for (int k = 0; k < o; ++k)
+            if (overlaps(bufs[o].p, bufs[o].n, bufs[k].p, bufs[k].n))
+                return fail(QPWC_E_ALIAS, "%s overlaps %s", bufs[o].name, bufs[k].name);
+    return sepconv3x3_bwd_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, grad_out, grad_src,
+                                 grad_dw, grad_pw, grad_bias, workspace, B, H, W, F, (hipStream_t)stream);
 }
 
 int qpwc_sepconv3x3_x3_fwd(const void* const* src, const int* src_channels, const int64_t* src_pixel_stride,

@@ -96,3 +96,57 @@ class WarpV2(_HotPathLayer):
     def forward(self, inputs):
         img, flo = self._unpack(inputs)
         return ops.warp(img, flo, "clamp", self.data_format)
+
+
+class _Kernel(torch.nn.Module):
+    """Holder of one `weight`, so that the state dict reads depthwise.weight / pointwise.weight like weights.py."""
+
+    def __init__(self, shape):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(shape))
+        torch.nn.init.xavier_uniform_(self.weight)   # Keras' glorot_uniform: the same fan_in + fan_out
+
+
+class SeparableConv2D(_HotPathLayer):
+    """tf.keras.layers.SeparableConv2D(filters, 3, padding='same', activation=...) as the reference uses it
+    (qpwcnet/core/non_layers.py:223-231, 291-294): depthwise 3x3 + pointwise 1x1 + bias (+ Mish) in the fused HIP
+    kernel, trainable through qpwc_sepconv3x3_bwd.  The call takes one tensor or a tuple / list of 1..3 sources that
+    are read as their channel concatenation (never materialised): SeparableConv2D(115, 128)((cost, prv, flo)).
+    Parameters in the torch layouts of weights.py: depthwise.weight (C,1,3,3), pointwise.weight (F,C,1,1), bias (F);
+    Keras' default initialisers (Glorot-uniform kernels, zero bias).  fp32 only."""
+
+    def __init__(self, in_channels, filters, activation="Mish", kernel_size=3, strides=1, padding="same",
+                 use_bias=True, depth_multiplier=1, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        fixed = (("kernel_size", kernel_size, (3, (3, 3), [3, 3])), ("strides", strides, (1, (1, 1), [1, 1])),
+                 ("padding", padding, ("same",)), ("use_bias", use_bias, (True,)),
+                 ("depth_multiplier", depth_multiplier, (1,)))
+        for key, value, allowed in fixed:
+            if not any(type(value) is type(a) and value == a for a in allowed):
+                raise ValueError("SeparableConv2D: {}={!r} is not supported (the reference uses {!r})".format(
+                    key, value, allowed[0]))
+        if activation not in ("Mish", None):
+            raise ValueError("SeparableConv2D: activation must be 'Mish' or None, got {!r}".format(activation))
+        if int(in_channels) < 1 or int(filters) not in (16, 32, 64, 128):
+            raise ValueError("SeparableConv2D: in_channels >= 1 and filters in (16, 32, 64, 128), got {} -> {}".format(
+                in_channels, filters))
+        self.in_channels, self.filters, self.activation = int(in_channels), int(filters), activation
+        self._config = {"in_channels": self.in_channels, "filters": self.filters, "activation": activation}
+        self.depthwise = _Kernel((self.in_channels, 1, 3, 3))
+        self.pointwise = _Kernel((self.filters, self.in_channels, 1, 1))
+        self.bias = torch.nn.Parameter(torch.zeros(self.filters))
+
+    def forward(self, inputs):
+        sources = list(inputs) if isinstance(inputs, (tuple, list)) else [inputs]
+        if not 1 <= len(sources) <= 3:
+            raise ValueError("SeparableConv2D takes 1..3 sources, got {}".format(len(sources)))
+        self.build([tuple(t.shape) for t in sources])
+        if sum(t.shape[self.axis] for t in sources) != self.in_channels:
+            raise ValueError("SeparableConv2D: the sources hold {} channels, the layer {}".format(
+                [t.shape[self.axis] for t in sources], self.in_channels))
+        if self.data_format == CHANNELS_FIRST:
+            # with grad the permuted view keeps the source in the autograd graph (ops makes it dense inside)
+            sources = [t.permute(0, 2, 3, 1) if ops._wants_grad(t) else ops._to_nhwc(t, CHANNELS_FIRST) for t in sources]
+        out = ops.sepconv3x3(sources, self.depthwise.weight, ops.pad_pointwise(self.pointwise.weight), self.bias,
+                             mish_on_load=False, mish_on_store=self.activation == "Mish")
+        return ops._from_nhwc(out, self.data_format)

@@ -828,6 +828,28 @@ class FrameInterpolate(_Weighted):
         return self._fmt(F.conv2d(x, w2, self.p("conv2.bias")))
 
 
+class SeparableConv2D(_Weighted):
+    """tf.keras.layers.SeparableConv2D(filters, 3, padding='same', activation=...) as OptFlow / FrameInterpolate use
+    it (qpwcnet/core/non_layers.py:223-231, 291-294) on its own: the functor twin of layers.SeparableConv2D.  Weights
+    `<prefix>depthwise.weight` (C,1,3,3), `<prefix>pointwise.weight` (F,C,1,1), `<prefix>bias` (F) from the params
+    dict; one tensor or 1..3 sources read as their channel concatenation; fp32, HIP only, differentiable in the
+    sources and the weights (ops.sepconv3x3)."""
+
+    def __init__(self, params, prefix, activation="Mish", *args, **kwargs):
+        super().__init__(params, prefix, *args, **kwargs)
+        if activation not in ("Mish", None):
+            raise ValueError("SeparableConv2D: activation must be 'Mish' or None, got {!r}".format(activation))
+        self.activation = activation
+
+    def __call__(self, inputs):
+        sources = list(inputs) if isinstance(inputs, (tuple, list)) else [inputs]
+        if self.data_format == CHANNELS_FIRST:
+            sources = [t.permute(0, 2, 3, 1) if ops._wants_grad(t) else ops._to_nhwc(t, CHANNELS_FIRST) for t in sources]
+        out = ops.sepconv3x3(sources, self.p("depthwise.weight"), ops.pad_pointwise(self.p("pointwise.weight")),
+                             self.p("bias"), mish_on_load=False, mish_on_store=self.activation == "Mish")
+        return ops._from_nhwc(out, self.data_format)
+
+
 class Flower(_Weighted):
     """qpwcnet/core/non_layers.py:452-505: the flow stack as one callable, so that
     ``build_interpolator`` can run it twice with shared weights (pwcnet.py:268-278).

@@ -944,12 +944,106 @@ def pad_pointwise(pw, dtype=torch.float32):
     return out
 
 
+def sepconv3x3_bwd(sources, dw, pw_padded, bias, grad_out, mish_on_load=False, mish_on_store=False,
+                   need=(True, True, True, True)):
+    """Gradients of sepconv3x3() (fp32, qpwc_sepconv3x3_bwd) for grad_out = dL/d(what the forward stored), dense
+    (B,H,W,F).  need = (sources, dw, pw, bias); `sources` one flag for all or one per source.
+    -> (list of per-source dense (B,H,W,c_i) gradients, grad_dw (C,3,3), grad_pw (F,Cpad), grad_bias (F)); whatever
+    is not asked for comes back as None."""
+    import ctypes
+    keep, c_ptrs, c_ch, c_st, B, H, W, C = _dw_sources(sources)
+    F_ = pw_padded.shape[-2]
+    w = dw.reshape(-1, 9)
+    cpad = (C + 31) // 32 * 32
+    if w.shape[0] != C or pw_padded.shape[-1] != cpad or bias.numel() != F_:
+        raise ValueError("weight shapes do not match C = {}".format(C))
+    for t in keep + [grad_out]:
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError("sepconv3x3_bwd takes fp32 device tensors")
+    for t in (w, pw_padded, bias):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("weights must be dense fp32 device tensors")
+    if tuple(grad_out.shape) != (B, H, W, F_):
+        raise ValueError("grad_out shape {} is not {}".format(tuple(grad_out.shape), (B, H, W, F_)))
+    grad_out = grad_out.contiguous()
+    need_src, need_dw, need_pw, need_b = need
+    if isinstance(need_src, bool):
+        need_src = (need_src,) * len(keep)
+    if len(need_src) != len(keep):
+        raise ValueError("need[0] must hold one flag per source")
+    dev = keep[0].device
+    L = _hip.lib()
+    nws = int(L.qpwc_sepconv3x3_bwd_workspace_floats(B, H, W, C, F_))
+    _hip.check(min(nws, 0))
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    gs = [torch.empty((B, H, W, t.shape[3]), dtype=torch.float32, device=dev) if n else None
+          for t, n in zip(keep, need_src)]
+    gdw = torch.empty((C, 3, 3), dtype=torch.float32, device=dev) if need_dw else None
+    gpw = torch.empty((F_, cpad), dtype=torch.float32, device=dev) if need_pw else None
+    gb = torch.empty((F_,), dtype=torch.float32, device=dev) if need_b else None
+    g_ptrs = (ctypes.c_void_p * len(keep))(*[g.data_ptr() if g is not None else None for g in gs])
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    flags = int(bool(mish_on_load)) | (2 if mish_on_store else 0)
+    with torch.cuda.device(dev), _timed("sepconv3x3_bwd", (B, H, W, C, F_)):
+        rc = L.qpwc_sepconv3x3_bwd(c_ptrs, c_ch, c_st, len(keep), flags, w.data_ptr(), pw_padded.data_ptr(),
+                                   bias.data_ptr(), grad_out.data_ptr(), g_ptrs, ptr(gdw), ptr(gpw), ptr(gb),
+                                   ws.data_ptr(), B, H, W, F_, _stream(grad_out))
+    _hip.check(rc)
+    return gs, gdw, gpw, gb
+
+
+class _SepConvFn(torch.autograd.Function):
+    """sepconv3x3() with qpwc_sepconv3x3_bwd as its gradient: the forward is the no-grad forward itself; the sources
+    and weights are saved, never the depthwise result or the pre-activation (the backward recomputes them)."""
+
+    @staticmethod
+    def forward(ctx, mish_on_load, mish_on_store, dw, pw_padded, bias, *sources):
+        _refuse_capture("the separable convolution")
+        out = sepconv3x3(sources, dw, pw_padded, bias, mish_on_load, mish_on_store)
+        ctx.save_for_backward(dw, pw_padded, bias, *sources)
+        ctx.cfg = (bool(mish_on_load), bool(mish_on_store))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the separable-convolution backward")
+        dw, pw_padded, bias = ctx.saved_tensors[:3]
+        sources = ctx.saved_tensors[3:]
+        on_load, on_store = ctx.cfg
+        nig = ctx.needs_input_grad
+        gs, gdw, gpw, gb = sepconv3x3_bwd(sources, dw, pw_padded, bias, grad_out.to(torch.float32), on_load, on_store,
+                                          (tuple(nig[5:]), nig[2], nig[3], nig[4]))
+        # a source handed in as a strided view (the 84-float cost volume) gets a dense gradient of its own shape
+        return (None, None, gdw.reshape(dw.shape) if gdw is not None else None, gpw,
+                gb.reshape(bias.shape) if gb is not None else None) + tuple(gs)
+
+
 def sepconv3x3(sources, dw, pw_padded, bias, mish_on_load=False, mish_on_store=False):
     """SeparableConv2D(3x3,'same'), fused (fp32): depthwise 3x3 over the virtual concat of 1..3
     channels-last sources, pointwise 1x1 + bias on the matrix cores
     (qpwcnet/core/non_layers.py:223-231).  pw_padded from pad_pointwise().
     -> (B,H,W,F): the pre-activation output, or Mish of it with mish_on_store (the layer's own
-    `activation='Mish'` applied once per element; the consumer then loads without Mish)."""
+    `activation='Mish'` applied once per element; the consumer then loads without Mish).
+    Differentiable (fp32) in the sources, dw, pw_padded and bias: with grad enabled and one of them requiring grad
+    the same forward runs inside an autograd Function whose backward is qpwc_sepconv3x3_bwd.  A source that is not
+    dense channels-last (the permuted view of a channels_first tensor) is copied dense in the forward and once more
+    in the backward: two transposes per step that channels-last training does not pay."""
+    if _wants_grad(dw, pw_padded, bias, *sources):
+        _refuse_capture("the separable convolution")
+        if not 1 <= len(sources) <= 3:
+            raise ValueError("takes 1..3 sources")
+        if any(isinstance(t, torch.Tensor) and t.dtype == torch.float16 for t in tuple(sources) + (pw_padded,)):
+            raise ValueError("sepconv3x3 has no gradient for fp16 storage: train in fp32")
+        if pw_padded.dtype == torch.bfloat16:
+            raise ValueError("sepconv3x3 has no gradient for a bf16x3 pointwise weight: pass pad_pointwise() itself")
+        for i, t in enumerate(sources):
+            _check_tensor("source %d" % i, t)
+        for name, t in (("dw", dw), ("pw_padded", pw_padded), ("bias", bias)):
+            if not t.is_cuda:
+                raise RuntimeError("qpwcnet_amd: {} is on '{}'; the hot path runs on a HIP device only "
+                                   "(no CPU fallback)".format(name, t.device))
+        return _SepConvFn.apply(bool(mish_on_load), bool(mish_on_store), dw, pw_padded, bias, *sources)
     keep, c_ptrs, c_ch, c_st, B, H, W, C = _dw_sources(sources)
     F_ = pw_padded.shape[-2]
     w = dw.reshape(-1, 9)
