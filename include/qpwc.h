@@ -357,6 +357,56 @@ int qpwc_flow_head_param_floats(void);
 int qpwc_flow_head_fwd(const void* z, const void* params, void* out, int B, int H, int W,
                        float scale, int dtype, int out_layout, void* stream);
 
+/* Training-mode BatchNormalization(fused=False) of the flow head (non_layers.py:242; the trainer calls
+ * model(ims, training=True), app/optical_flow/train.py:270), fp32 channels-last.  With m = Mish(z), a = W1 m + b1,
+ * u = Mish(a) over the M = B*H*W pixels:
+ *   mean[c] = sum_p u[p,c] / M,   var[c] = sum_p (u[p,c] - mean[c])^2 / M        (biased, as Keras' non-fused layer)
+ * in two stages: per-workgroup (count, mean, M2) partials of shifted sums, then a fixed-order Chan merge (accurate
+ * for |mean| >> std, bitwise reproducible, no atomics).  The merging launch also writes, on the device,
+ *   params (592 floats, what qpwc_flow_head_fwd takes): w1 | b1 | s | t | wf,  s = gamma / sqrt(var + eps),
+ *                                                        t = beta - mean s
+ *   stats (48 floats, may be NULL): mean | var | mean_lo -- what qpwc_flow_head_bwd takes; mean_lo is what the
+ *                                                        rounding of the batch mean to fp32 dropped
+ *   moving_mean / moving_var (16 floats each, both or neither NULL), in place:
+ *                                                        moving = moving * momentum + batch * (1 - momentum)
+ * so that the training forward is this call followed by qpwc_flow_head_fwd, with no host synchronisation.
+ * z: (B,H,W,16); w1 (16,16) (out,in); b1, gamma, beta (16); wf (3,3,16,2) (ky,kx,in,out).  workspace:
+ * qpwc_flow_head_stats_workspace_floats() floats (negative QPWC_E_SHAPE for a non-positive extent or more than
+ * 2^24 pixels).  z, w1, b1, params, stats and workspace 16-byte aligned (read or written as float4), the rest 4.
+ * Errors: QPWC_E_NULL, QPWC_E_SHAPE, QPWC_E_RANGE (eps <= 0, momentum outside [0,1]), QPWC_E_ALIGN, QPWC_E_ALIAS. */
+int64_t qpwc_flow_head_stats_workspace_floats(int B, int H, int W);
+int qpwc_flow_head_stats_fwd(const void* z, const void* w1, const void* b1, const void* gamma, const void* beta,
+                             const void* wf, void* moving_mean, void* moving_var, float momentum, float eps,
+                             void* params, void* stats, void* workspace, int B, int H, int W, void* stream);
+
+/* Gradient of qpwc_flow_head_fwd (fp32, channels-last output), in both BatchNorm modes.  Notation per pixel p:
+ *   m = Mish(z), a = W1 m + b1, u = Mish(a), h = s u + t, flow = scale conv3x3(h, wf) (zero 'same' padding)
+ * z, params (w1 | b1 | s | t | wf) and scale as in the forward; stats = mean | var | mean_lo (48 floats) that s and t
+ * were made from (those of qpwc_flow_head_stats_fwd, or the frozen moving ones with mean_lo = 0), eps the same;
+ * g = grad_out = dL/dflow (B,H,W,2).  u, a and m are recomputed from z (Mish is not invertible; the forward stores
+ * nothing).
+ *   gh[p,c]          = scale sum_k sum_o wf[k,c,o] g[p-k+1,o]            (g = 0 outside the image)
+ *   grad_wf[k,c,o]   = scale sum_p h[p+k-1,c] g[p,o]                     (3,3,16,2), h = 0 outside the image
+ *   xh = (u - mean - mean_lo) rstd, rstd = 1 / sqrt(var + eps)
+ *   grad_beta[c]     = sum_p gh[p,c]           grad_gamma[c] = sum_p gh[p,c] xh[p,c]
+ *   gu = s gh                                                             training == 0 (frozen statistics)
+ *   gu = s (gh - grad_beta / M - xh grad_gamma / M)                       training != 0 (batch statistics)
+ *   ga = gu Mish'(a)     grad_b1[f] = sum_p ga[p,f]     grad_w1[f,c] = sum_p ga[p,f] m[p,c]
+ *     (training != 0: sum_p gu = 0 identically, and grad_b1 is summed as sum_p gu (Mish'(a) - 1), which does not round
+ *      M cancelling terms)
+ *   grad_z = (W1^T ga) Mish'(z)
+ * Any of the six outputs may be NULL (not all); a pass whose only consumers are NULL is not launched.  Both 16 x 16
+ * products run on v_mfma_f32_16x16x4_f32.  Every output is bitwise reproducible and the same bits whatever else is
+ * asked for: per-workgroup partials in tile order, then a fixed-order sum; no atomics.  With training == 0 a pixel's
+ * grad_z depends on its own image only.  workspace: qpwc_flow_head_bwd_workspace_floats() floats.  z, params,
+ * stats, grad_z and workspace 16-byte aligned (float4 loads and stores), grad_out 8, the rest 4.  Errors:
+ * QPWC_E_NULL, QPWC_E_SHAPE, QPWC_E_RANGE (eps <= 0), QPWC_E_ALIGN, QPWC_E_ALIAS (an output or the workspace
+ * overlapping an input or another output). */
+int64_t qpwc_flow_head_bwd_workspace_floats(int B, int H, int W);
+int qpwc_flow_head_bwd(const void* z, const void* params, const void* stats, float eps, int training, float scale,
+                       const void* grad_out, void* grad_z, void* grad_w1, void* grad_b1, void* grad_gamma,
+                       void* grad_beta, void* grad_wf, void* workspace, int B, int H, int W, void* stream);
+
 /* Pointwise half of a SeparableConv2D whose depthwise half ran as qpwc_dwconv3x3_fwd (non_layers.py:223-231; the wide
  * first OptFlow layer of the coarsest levels, which stay split): out (M, F) = y (M, C) . weight^T + bias, fp32, on the
  * matrix cores, M = B*H*W pixels.  weight: (F, ceil(C/32)*32) row-major, zero padded (the layout qpwc_sepconv3x3_fwd
@@ -411,6 +461,12 @@ int qpwc_split_frames_pad_fwd(const void* in, void* out, int B, int H, int W, in
  * in (B,h,w,2); in_layout / out_layout QPWC_NCHW read (B,2,h,w) / write (B,2,2h,2w) instead. */
 int qpwc_upsample2x_flow_fwd(const void* in, void* out, int B, int h, int w, float scale, int dtype,
                              int in_layout, int out_layout, void* stream);
+
+/* Adjoint of qpwc_upsample2x_flow_fwd (fp32, channels-last): grad_out (B,2h,2w,2) -> grad_in (B,h,w,2), a gather.
+ * Per axis in[i] receives 0.75 (g[2i] + g[2i+1]) + 0.25 (g[2i-1] + g[2i+2]); at the borders the clamped tap's 0.25
+ * folds back onto the edge pixel (in[0] += 0.25 g[0], in[h-1] += 0.25 g[2h-1]).  The two axes are separable; the
+ * result is multiplied by scale.  One launch, no workspace, bitwise reproducible.  Both pointers 8-byte aligned. */
+int qpwc_upsample2x_flow_bwd(const void* grad_out, void* grad_in, int B, int h, int w, float scale, void* stream);
 
 /* inv_flow = -tf_warp(flow, flow) (occlusion.py:85; app/test/test_invert_flow.py:47): the flow
  * field sampled at its own targets with the tf_warp rules (warp.py:63-153), negated.

@@ -34,6 +34,8 @@ SYMBOLS = (
     "qpwc_cost_volume_bwd", "qpwc_warp_bwd_workspace_floats", "qpwc_warp_bwd",
     "qpwc_loss_workspace_floats", "qpwc_loss_fwd", "qpwc_loss_fwd_kernel", "qpwc_loss_bwd",
     "qpwc_sepconv3x3_bwd_workspace_floats", "qpwc_sepconv3x3_bwd",
+    "qpwc_flow_head_stats_workspace_floats", "qpwc_flow_head_stats_fwd", "qpwc_flow_head_bwd_workspace_floats",
+    "qpwc_flow_head_bwd", "qpwc_upsample2x_flow_bwd",
 )
 
 _lib = None
@@ -190,6 +192,16 @@ def lib():
     L.qpwc_sepconv3x3_bwd.argtypes = [pvp, pi, ctypes.POINTER(i64), ci, ci, vp, vp, vp, vp, pvp, vp, vp, vp, vp,
                                       ci, ci, ci, ci, vp]
     L.qpwc_sepconv3x3_bwd.restype = ci
+    L.qpwc_flow_head_stats_workspace_floats.argtypes = [ci, ci, ci]
+    L.qpwc_flow_head_stats_workspace_floats.restype = i64
+    L.qpwc_flow_head_stats_fwd.argtypes = [vp] * 8 + [cf, cf, vp, vp, vp, ci, ci, ci, vp]
+    L.qpwc_flow_head_stats_fwd.restype = ci
+    L.qpwc_flow_head_bwd_workspace_floats.argtypes = [ci, ci, ci]
+    L.qpwc_flow_head_bwd_workspace_floats.restype = i64
+    L.qpwc_flow_head_bwd.argtypes = [vp, vp, vp, cf, ci, cf, vp] + [vp] * 7 + [ci, ci, ci, vp]
+    L.qpwc_flow_head_bwd.restype = ci
+    L.qpwc_upsample2x_flow_bwd.argtypes = [vp, vp, ci, ci, ci, cf, vp]
+    L.qpwc_upsample2x_flow_bwd.restype = ci
     _lib = L
     return L
 

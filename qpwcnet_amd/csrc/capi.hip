@@ -118,6 +118,15 @@ bool sepconv3x3_bwd_shape_ok(int B, int H, int W, int C, int F);
 int sepconv3x3_bwd_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src, int flags,
                           const void* dw, const void* pw, const void* bias, const void* gout, void* const* gsrc,
                           void* gdw, void* gpw, void* gbias, void* ws, int B, int H, int W, int F, hipStream_t s);
+int64_t flow_head_stats_workspace_floats(int B, int H, int W);
+int64_t flow_head_bwd_workspace_floats(int B, int H, int W);
+int flow_head_stats_launch(const void* z, const void* w1, const void* b1, const void* gamma, const void* beta,
+                           const void* wf, void* moving_mean, void* moving_var, float momentum, float eps, void* params,
+                           void* stats, void* ws, int B, int H, int W, hipStream_t s);
+int flow_head_bwd_launch(const void* z, const void* params, const void* stats, float eps, int training, float scale,
+                         const void* gout, void* gz, void* gw1, void* gb1, void* ggamma, void* gbeta, void* gwf,
+                         void* ws, int B, int H, int W, hipStream_t s);
+int upsample2x_flow_bwd_launch(const void* gout, void* gin, int B, int h, int w, float scale, hipStream_t s);
 int loss_bwd_launch(const void* const* dpred, const float* grad_losses, void* const* grad_pred, const int64_t* n_elems,
                     const int* pred_dtype, int n, hipStream_t s);
 
@@ -202,6 +211,29 @@ static int loss_check_shapes(int kind, int B, int H, int W, int C, const int* h,
         if (kind == QPWC_LOSS_FLOW_MSE_V2 && (H % h[i] || W % w[i]))
             return fail(QPWC_E_SHAPE, "level %d: %dx%d is not a whole-block area reduction of %dx%d", i, h[i], w[i], H, W);
     }
+    return QPWC_OK;
+}
+
+// name, extent in bytes and required alignment of every buffer of an entry point: inputs first, then outputs
+struct BufCheck {
+    const void* p;
+    size_t n, align;
+    const char* name;
+};
+// every buffer aligned; no output (index >= n_in) overlapping a buffer listed before it
+static int check_bufs(const BufCheck* b, int n_in, int n_all) {
+    for (int k = 0; k < n_all; ++k)
+        if ((uintptr_t)b[k].p % b[k].align) return fail(QPWC_E_ALIGN, "%s must be %d-byte aligned", b[k].name, (int)b[k].align);
+    for (int o = n_in; o < n_all; ++o)
+        for (int k = 0; k < o; ++k)
+            if (overlaps(b[o].p, b[o].n, b[k].p, b[k].n)) return fail(QPWC_E_ALIAS, "%s overlaps %s", b[o].name, b[k].name);
+    return QPWC_OK;
+}
+
+static int flow_head_train_check_shape(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
+    if ((int64_t)B * H * W > (1 << 24))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: more than 2^24 pixels (the pixel counts are fp32)", B, H, W);
     return QPWC_OK;
 }
 
@@ -776,6 +808,95 @@ int qpwc_flow_head_fwd(const void* z, const void* params, void* out, int B, int 
     if (overlaps(out, (size_t)B * H * W * 2 * es, z, (size_t)B * H * W * 16 * es))
         return fail(QPWC_E_ALIAS, "out overlaps z");
     return flow_head_launch(z, params, out, B, H, W, scale, dtype, out_layout, (hipStream_t)stream);
+}
+
+int64_t qpwc_flow_head_stats_workspace_floats(int B, int H, int W) {
+    const int rc = flow_head_train_check_shape(B, H, W);
+    return rc != QPWC_OK ? rc : flow_head_stats_workspace_floats(B, H, W);
+}
+
+int qpwc_flow_head_stats_fwd(const void* z, const void* w1, const void* b1, const void* gamma, const void* beta,
+                             const void* wf, void* moving_mean, void* moving_var, float momentum, float eps,
+                             void* params, void* stats, void* workspace, int B, int H, int W, void* stream) {
+    const struct { const void* p; const char* name; } need[] = {{z, "z"}, {w1, "w1"}, {b1, "b1"}, {gamma, "gamma"},
+        {beta, "beta"}, {wf, "wf"}, {params, "params"}, {workspace, "workspace"}};
+    for (const auto& a : need)
+        if (!a.p) return fail(QPWC_E_NULL, "%s is null", a.name);
+    if (!moving_mean != !moving_var) return fail(QPWC_E_NULL, "moving_mean and moving_var: both or neither");
+    int rc = flow_head_train_check_shape(B, H, W);
+    if (rc != QPWC_OK) return rc;
+    if (!(eps > 0.0f)) return fail(QPWC_E_RANGE, "eps %g must be positive", (double)eps);
+    if (!(momentum >= 0.0f && momentum <= 1.0f)) return fail(QPWC_E_RANGE, "momentum %g outside [0,1]", (double)momentum);
+    const size_t M = (size_t)B * H * W;
+    BufCheck bufs[11];
+    int n_in = 0;
+    bufs[n_in++] = {z, M * 64, 16, "z"};
+    bufs[n_in++] = {w1, 1024, 16, "w1"};
+    bufs[n_in++] = {b1, 64, 16, "b1"};
+    bufs[n_in++] = {gamma, 64, 4, "gamma"};
+    bufs[n_in++] = {beta, 64, 4, "beta"};
+    bufs[n_in++] = {wf, 1152, 4, "wf"};
+    int n_all = n_in;
+    bufs[n_all++] = {params, 592 * 4, 16, "params"};
+    if (stats) bufs[n_all++] = {stats, 192, 16, "stats"};
+    if (moving_mean) {
+        bufs[n_all++] = {moving_mean, 64, 4, "moving_mean"};
+        bufs[n_all++] = {moving_var, 64, 4, "moving_var"};
+    }
+    bufs[n_all++] = {workspace, (size_t)flow_head_stats_workspace_floats(B, H, W) * 4, 16, "workspace"};
+    if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
+    return flow_head_stats_launch(z, w1, b1, gamma, beta, wf, moving_mean, moving_var, momentum, eps, params, stats,
+                                  workspace, B, H, W, (hipStream_t)stream);
+}
+
+int64_t qpwc_flow_head_bwd_workspace_floats(int B, int H, int W) {
+    const int rc = flow_head_train_check_shape(B, H, W);
+    return rc != QPWC_OK ? rc : flow_head_bwd_workspace_floats(B, H, W);
+}
+
+int qpwc_flow_head_bwd(const void* z, const void* params, const void* stats, float eps, int training, float scale,
+                       const void* grad_out, void* grad_z, void* grad_w1, void* grad_b1, void* grad_gamma,
+                       void* grad_beta, void* grad_wf, void* workspace, int B, int H, int W, void* stream) {
+    if (!z) return fail(QPWC_E_NULL, "z is null");
+    if (!params) return fail(QPWC_E_NULL, "params is null");
+    if (!stats) return fail(QPWC_E_NULL, "stats is null");
+    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
+    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
+    if (!grad_z && !grad_w1 && !grad_b1 && !grad_gamma && !grad_beta && !grad_wf)
+        return fail(QPWC_E_NULL, "grad_z, grad_w1, grad_b1, grad_gamma, grad_beta and grad_wf are all null");
+    int rc = flow_head_train_check_shape(B, H, W);
+    if (rc != QPWC_OK) return rc;
+    if (!(eps > 0.0f)) return fail(QPWC_E_RANGE, "eps %g must be positive", (double)eps);
+    const size_t M = (size_t)B * H * W;
+    BufCheck bufs[11];
+    int n_in = 0;
+    bufs[n_in++] = {z, M * 64, 16, "z"};
+    bufs[n_in++] = {params, 592 * 4, 16, "params"};
+    bufs[n_in++] = {stats, 192, 16, "stats"};
+    bufs[n_in++] = {grad_out, M * 8, 8, "grad_out"};
+    int n_all = n_in;
+    if (grad_z) bufs[n_all++] = {grad_z, M * 64, 16, "grad_z"};
+    if (grad_w1) bufs[n_all++] = {grad_w1, 1024, 4, "grad_w1"};
+    if (grad_b1) bufs[n_all++] = {grad_b1, 64, 4, "grad_b1"};
+    if (grad_gamma) bufs[n_all++] = {grad_gamma, 64, 4, "grad_gamma"};
+    if (grad_beta) bufs[n_all++] = {grad_beta, 64, 4, "grad_beta"};
+    if (grad_wf) bufs[n_all++] = {grad_wf, 1152, 4, "grad_wf"};
+    bufs[n_all++] = {workspace, (size_t)flow_head_bwd_workspace_floats(B, H, W) * 4, 16, "workspace"};
+    if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
+    return flow_head_bwd_launch(z, params, stats, eps, training, scale, grad_out, grad_z, grad_w1, grad_b1, grad_gamma,
+                                grad_beta, grad_wf, workspace, B, H, W, (hipStream_t)stream);
+}
+
+int qpwc_upsample2x_flow_bwd(const void* grad_out, void* grad_in, int B, int h, int w, float scale, void* stream) {
+    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
+    if (!grad_in) return fail(QPWC_E_NULL, "grad_in is null");
+    if (B <= 0 || h <= 0 || w <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d h=%d w=%d", B, h, w);
+    if (h > (1 << 29) || w > (1 << 29)) return fail(QPWC_E_SHAPE, "h=%d w=%d: the doubled extents must fit an int", h, w);
+    const size_t n = (size_t)B * h * w * 8;
+    const BufCheck bufs[2] = {{grad_out, 4 * n, 8, "grad_out"}, {grad_in, n, 8, "grad_in"}};
+    const int rc = check_bufs(bufs, 1, 2);
+    if (rc != QPWC_OK) return rc;
+    return upsample2x_flow_bwd_launch(grad_out, grad_in, B, h, w, scale, (hipStream_t)stream);
 }
 
 int qpwc_optflow_tail_fwd(const void* z2, const void* dw3, const void* pw3, const void* b3, const void* dw4,

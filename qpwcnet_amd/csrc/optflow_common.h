@@ -17,6 +17,36 @@ __device__ __forceinline__ float mishf(float x) {
     return m;
 }
 
+// Mish'(t) = tanh(sp) + t (1 - tanh(sp)^2) sigmoid(t), sp = softplus(t) (the derivative of t tanh(softplus(t)),
+// qpwcnet/core/mish.py:27-28).  With e = e^t and n = e (e + 2): tanh(sp) = n / (n + 2), 1 - tanh = 2 / (n + 2).
+// e is clamped at e^20 like mishf (tanh(sp) = 1 to 1 ulp there and the second term < 1e-14 |t|), so nothing overflows;
+// for t -> -inf e underflows to 0 and the result is 0.
+// Contraction is off: the compiler otherwise fuses `n + 2` and `1 + th` with the products that feed them in some
+// instantiations of the callers and not in others (where they are shared with mishf of the same value), and
+// grad_x would differ in its last bits with the set of outputs asked for.  Only the fmaf written here is fused.
+__device__ __forceinline__ float mish_grad(float t) {
+#pragma clang fp contract(off)
+    const float e = __builtin_amdgcn_exp2f(fminf(t, 20.0f) * 1.4426950408889634f);
+    const float n = e * (e + 2.0f);
+    const float r = __builtin_amdgcn_rcpf(n + 2.0f);
+    const float th = n * r;
+    const float sg = e * __builtin_amdgcn_rcpf(e + 1.0f);
+    return fmaf(t * sg, (2.0f * r) * (1.0f + th), th);
+}
+
+// Mish'(t) - 1 without the cancellation of computing Mish'(t) first: tanh(sp) - 1 = -2 / (n + 2) exactly, so
+// Mish'(t) - 1 = 2 r (t sigmoid(t) (1 + tanh(sp)) - 1), r = 1 / (n + 2).  Relative accuracy where Mish' is within 1e-6 of
+// 1 (t near 8), which a sum of g (Mish' - 1) over pixels needs when sum g = 0 (the BatchNorm backward's grad_b1).
+__device__ __forceinline__ float mish_grad_m1(float t) {
+#pragma clang fp contract(off)
+    const float e = __builtin_amdgcn_exp2f(fminf(t, 20.0f) * 1.4426950408889634f);
+    const float n = e * (e + 2.0f);
+    const float r = __builtin_amdgcn_rcpf(n + 2.0f);
+    const float th = n * r;
+    const float sg = e * __builtin_amdgcn_rcpf(e + 1.0f);
+    return (2.0f * r) * (fmaf(t * sg, 1.0f + th, -1.0f));
+}
+
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 #ifndef QPWC_DWSRC_REGS

@@ -36,23 +36,6 @@ constexpr int kScbDwSlots = 8;      // strips per workgroup trip of sepconv_bwd_
 constexpr int kScbDwBlocks = 1024;  // workgroups of sepconv_bwd_dw_kernel, shared likewise
 constexpr int kScbLd = kScKC + 4;   // LDS row of a 32-channel tile: 16-byte rows, 4 banks apart
 
-// Mish'(t) = tanh(sp) + t (1 - tanh(sp)^2) sigmoid(t), sp = softplus(t) (the derivative of t tanh(softplus(t)),
-// qpwcnet/core/mish.py:27-28).  With e = e^t and n = e (e + 2): tanh(sp) = n / (n + 2), 1 - tanh = 2 / (n + 2).
-// e is clamped at e^20 like mishf (tanh(sp) = 1 to 1 ulp there and the second term < 1e-14 |t|), so nothing overflows;
-// for t -> -inf e underflows to 0 and the result is 0.
-// Contraction is off: the compiler otherwise fuses `n + 2` and `1 + th` with the products that feed them in some
-// instantiations of the callers and not in others (where they are shared with mishf of the same value), and
-// grad_x would differ in its last bits with the set of outputs asked for.  Only the fmaf written here is fused.
-__device__ __forceinline__ float mish_grad(float t) {
-#pragma clang fp contract(off)
-    const float e = __builtin_amdgcn_exp2f(fminf(t, 20.0f) * 1.4426950408889634f);
-    const float n = e * (e + 2.0f);
-    const float r = __builtin_amdgcn_rcpf(n + 2.0f);
-    const float th = n * r;
-    const float sg = e * __builtin_amdgcn_rcpf(e + 1.0f);
-    return fmaf(t * sg, (2.0f * r) * (1.0f + th), th);
-}
-
 struct ScbGrad {
     float* ptr[3];  // dense (B,H,W,c_i) gradient of each source; NULL = not asked for
 };

@@ -1,8 +1,11 @@
 """``torch.nn.Module`` twins of the reference's Keras hot-path layers
 (qpwcnet/core/layers.py:32-186): ``CostVolume``, ``CostVolumeV2``, ``Warp``,
-``WarpV2``.  Same names, same constructor arguments, same ``layer((a, b))``
-call convention, same config round trip; the arithmetic runs in the gfx950 HIP
-kernels behind ``include/qpwc.h``.
+``WarpV2``, and trainable twins of the flow-estimator functors
+(qpwcnet/core/non_layers.py:183-193, 213-273, 315-387): ``SeparableConv2D``,
+``OptFlow``, ``Upsample``, ``Flow``, ``UpFlow``.  Same names, same constructor
+arguments, same ``layer((a, b))`` call convention, same config round trip; the
+arithmetic, forward and backward, runs in the gfx950 HIP kernels behind
+``include/qpwc.h``.
 
 Layout is read from the process-global ``image_data_format()`` at construction
 time exactly like the reference (layers.py:41,119,146,173); an explicit
@@ -150,3 +153,115 @@ class SeparableConv2D(_HotPathLayer):
         out = ops.sepconv3x3(sources, self.depthwise.weight, ops.pad_pointwise(self.pointwise.weight), self.bias,
                              mish_on_load=False, mish_on_store=self.activation == "Mish")
         return ops._from_nhwc(out, self.data_format)
+
+
+class _Conv(torch.nn.Module):
+    """Holder of a convolution's `weight` (and `bias`): conv.weight / conv.bias / flow.weight like weights.py."""
+
+    def __init__(self, shape, bias):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(shape))
+        torch.nn.init.xavier_uniform_(self.weight)   # Keras' glorot_uniform
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(shape[0]))
+
+
+class _BatchNorm(torch.nn.Module):
+    """Keras BatchNormalization's variables under the names of weights.py: gamma, beta; moving mean / var as buffers."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.gamma = torch.nn.Parameter(torch.ones(channels))
+        self.beta = torch.nn.Parameter(torch.zeros(channels))
+        self.register_buffer("mean", torch.zeros(channels))
+        self.register_buffer("var", torch.ones(channels))
+
+
+class OptFlow(_HotPathLayer):
+    """The flow estimator of one pyramid level (qpwcnet/core/non_layers.py:213-273), trainable: four
+    SeparableConv2D(3x3, 'same', Mish) -> Conv2D(1x1, Mish) -> BatchNormalization(fused=False) -> Conv2D(3x3, 2
+    filters, no bias) -> * scale, scale=None meaning sqrt(h^2 + w^2).  The last SeparableConv2D stores its
+    pre-activation and the head applies that layer's Mish on load, as the kernels expect.  The call takes one tensor
+    or a tuple / list of 1..3 sources read as their channel concatenation.  ``self.training`` selects the BatchNorm
+    mode: batch statistics and an in-place update of the moving buffers (Keras' momentum 0.99, epsilon 1e-3, biased
+    variance), or the moving statistics.  State-dict names are those of weights.py, so a converted checkpoint's
+    ``<prefix>flow.*`` entries load with load_state_dict.  fp32 only."""
+    MOMENTUM = 0.99
+    EPSILON = 1e-3
+
+    def __init__(self, in_channels, filters=(128, 64, 32, 16), scale=None, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        filters = tuple(int(f) for f in filters)
+        if not filters or filters[-1] != 16:
+            raise ValueError("OptFlow: the flow head takes 16 channels, got filters {}".format(filters))
+        self.in_channels, self.filters, self.scale = int(in_channels), filters, scale
+        self._config = {"in_channels": self.in_channels, "filters": filters, "scale": scale}
+        chans = (self.in_channels,) + filters
+        # the stack runs channels-last inside; this layer converts at its own boundary
+        self.feat = torch.nn.ModuleList(
+            SeparableConv2D(chans[i], f, activation="Mish" if i + 1 < len(filters) else None, data_format=CHANNELS_LAST)
+            for i, f in enumerate(filters))
+        self.conv = _Conv((16, 16, 1, 1), bias=True)
+        self.norm = _BatchNorm(16)
+        self.flow = _Conv((2, 16, 3, 3), bias=False)
+
+    def forward(self, inputs):
+        sources = list(inputs) if isinstance(inputs, (tuple, list)) else [inputs]
+        if not 1 <= len(sources) <= 3:
+            raise ValueError("OptFlow takes 1..3 sources, got {}".format(len(sources)))
+        self.build([tuple(t.shape) for t in sources])
+        if self.data_format == CHANNELS_FIRST:
+            sources = [t.permute(0, 2, 3, 1) if ops._wants_grad(t) else ops._to_nhwc(t, CHANNELS_FIRST) for t in sources]
+        scale = self.scale if self.scale is not None else float(self.h ** 2 + self.w ** 2) ** 0.5
+        z = sources
+        for layer in self.feat:
+            z = layer(z)
+        out = ops.flow_head_train(z, self.conv.weight, self.conv.bias, self.norm.gamma, self.norm.beta, self.norm.mean,
+                                  self.norm.var, self.flow.weight, scale, training=self.training,
+                                  momentum=self.MOMENTUM, eps=self.EPSILON)
+        return ops._from_nhwc(out, self.data_format)
+
+
+class Upsample(_HotPathLayer):
+    """qpwcnet/core/non_layers.py:183-193 on a flow: scale * UpSampling2D(2, 'bilinear'), differentiable."""
+
+    def __init__(self, scale=1.0, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.scale = float(scale)
+        self._config = {"scale": self.scale}
+
+    def forward(self, x):
+        return ops.upsample2x_flow(x, self.scale, self.data_format, self.data_format)
+
+
+class Flow(_HotPathLayer):
+    """First flow block (qpwcnet/core/non_layers.py:315-338), trainable: cost = CostVolumeV2(prv, nxt);
+    OptFlow(concat[cost, prv, nxt]).  in_channels: the channels of prv / nxt."""
+
+    def __init__(self, in_channels, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.in_channels = int(in_channels)
+        self._config = {"in_channels": self.in_channels}
+        self.cost_volume = CostVolumeV2(data_format=self.data_format)
+        self.flow = OptFlow(81 + 2 * self.in_channels, data_format=self.data_format)
+
+    def forward(self, inputs):
+        prv, nxt = inputs
+        return self.flow((self.cost_volume((prv, nxt)), prv, nxt))
+
+
+class UpFlow(_HotPathLayer):
+    """Refinement block (qpwcnet/core/non_layers.py:341-387), trainable: nxt_w = WarpV2(nxt, flo); cost =
+    CostVolumeV2(prv, nxt_w); OptFlow(concat[cost, prv, flo]).  in_channels: the channels of prv / nxt."""
+
+    def __init__(self, in_channels, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.in_channels = int(in_channels)
+        self._config = {"in_channels": self.in_channels}
+        self.warp = WarpV2(data_format=self.data_format)
+        self.cost_volume = CostVolumeV2(data_format=self.data_format)
+        self.flow = OptFlow(81 + self.in_channels + 2, data_format=self.data_format)
+
+    def forward(self, inputs):
+        prv, nxt, flo = inputs
+        return self.flow((self.cost_volume((prv, self.warp((nxt, flo)))), prv, flo))

@@ -625,14 +625,7 @@ class OptFlow(_Weighted):
         return self._fmt(scale * f)
 
 
-def pack_flow_head(w1, b1, gamma, beta, mean, var, eps, wf):
-    """Parameter vector of qpwc_flow_head_fwd (include/qpwc.h): w1[16][16] | b1 | bn_scale |
-    bn_shift | wf[ky][kx][in][out]; BatchNorm folded to scale/shift."""
-    w1, b1, gamma, beta, mean, var, wf = (t.float() for t in (w1, b1, gamma, beta, mean, var, wf))
-    bn_scale = gamma / torch.sqrt(var + eps)
-    bn_shift = beta - mean * bn_scale
-    return torch.cat([w1.reshape(16, 16).reshape(-1), b1.reshape(-1), bn_scale.reshape(-1),
-                      bn_shift.reshape(-1), wf.permute(2, 3, 1, 0).reshape(-1)]).contiguous()
+pack_flow_head = ops.pack_flow_head   # the parameter vector of qpwc_flow_head_fwd; lives beside its consumers
 
 
 class Flow(_Weighted):

@@ -576,6 +576,158 @@ def flow_head(z, params, scale, out_format=CHANNELS_LAST):
     return out
 
 
+def pack_flow_head(w1, b1, gamma, beta, mean, var, eps, wf):
+    """Parameter vector of qpwc_flow_head_fwd (include/qpwc.h): w1[16][16] | b1 | bn_scale |
+    bn_shift | wf[ky][kx][in][out]; BatchNorm folded to scale/shift."""
+    w1, b1, gamma, beta, mean, var, wf = (t.float() for t in (w1, b1, gamma, beta, mean, var, wf))
+    bn_scale = gamma / torch.sqrt(var + eps)
+    bn_shift = beta - mean * bn_scale
+    return torch.cat([w1.reshape(16, 16).reshape(-1), b1.reshape(-1), bn_scale.reshape(-1),
+                      bn_shift.reshape(-1), wf.permute(2, 3, 1, 0).reshape(-1)]).contiguous()
+
+
+def _head_operands(z, w1, b1, gamma, beta, mean, var, wf):
+    """Shape / dtype / device rules of the trainable flow head's operands (the torch layouts of weights.py)."""
+    _check_tensor("z", z)
+    if z.dtype != torch.float32 or z.shape[3] != 16:
+        raise ValueError("z must be an fp32 (B,H,W,16) tensor, got {} {}".format(z.dtype, tuple(z.shape)))
+    for name, t, numel in (("w1", w1, 256), ("b1", b1, 16), ("gamma", gamma, 16), ("beta", beta, 16), ("mean", mean, 16),
+                           ("var", var, 16), ("wf", wf, 288)):
+        if not isinstance(t, torch.Tensor) or t.device != z.device:
+            raise RuntimeError("qpwcnet_amd: {} must be a tensor on z's HIP device (no CPU fallback)".format(name))
+        if t.dtype != torch.float32 or t.numel() != numel:
+            raise ValueError("{} must hold {} fp32 values, got {} {}".format(name, numel, t.dtype, tuple(t.shape)))
+    if tuple(wf.shape) != (2, 16, 3, 3):
+        raise ValueError("wf must be the (2,16,3,3) kernel of the flow convolution, got {}".format(tuple(wf.shape)))
+
+
+def flow_head_stats(z, w1, b1, gamma, beta, mean, var, wf, momentum=0.99, eps=1e-3):
+    """Training-mode BatchNorm of the flow head (qpwc_flow_head_stats_fwd): the batch mean and biased variance of
+    Mish(W1 Mish(z) + b1) over all pixels of z (B,H,W,16) -> (params, stats): the 592-float vector flow_head() takes,
+    normalising with the batch statistics, and those statistics as mean | var | mean_lo (48 floats; mean_lo: what the
+    fp32 mean dropped, which keeps the backward's normalised activations centred when |mean| >> std).  mean / var (the layer's
+    moving buffers) are updated in place on the device, moving * momentum + batch * (1 - momentum); None for both
+    leaves out the update.  Two launches, no host synchronisation."""
+    moving = mean is not None
+    _head_operands(z, w1, b1, gamma, beta, mean if moving else b1, var if moving else b1, wf)
+    if moving and not (mean.is_contiguous() and var.is_contiguous()):
+        raise ValueError("the moving buffers are updated in place: dense tensors")
+    z = z.contiguous()
+    B, H, W, _ = z.shape
+    L = _hip.lib()
+    nws = int(L.qpwc_flow_head_stats_workspace_floats(B, H, W))
+    _hip.check(min(nws, 0))
+    ws = torch.empty(nws, dtype=torch.float32, device=z.device)
+    params = torch.empty(L.qpwc_flow_head_param_floats(), dtype=torch.float32, device=z.device)
+    stats = torch.empty(48, dtype=torch.float32, device=z.device)
+    w1c, b1c, gc, bc = (t.detach().contiguous() for t in (w1, b1, gamma, beta))
+    wfp = wf.detach().permute(2, 3, 1, 0).contiguous()
+    with torch.cuda.device(z.device), _timed("flow_head_stats", (B, H, W, 16)):
+        rc = L.qpwc_flow_head_stats_fwd(z.data_ptr(), w1c.data_ptr(), b1c.data_ptr(), gc.data_ptr(), bc.data_ptr(),
+                                        wfp.data_ptr(), mean.data_ptr() if moving else None,
+                                        var.data_ptr() if moving else None, float(momentum), float(eps),
+                                        params.data_ptr(), stats.data_ptr(), ws.data_ptr(), B, H, W, _stream(z))
+    _hip.check(rc)
+    return params, stats
+
+
+def frozen_stats(mean, var):
+    """mean | var | 0 (48 floats): the statistics operand of flow_head_bwd() for frozen (moving) statistics."""
+    return torch.cat([mean.reshape(-1).float(), var.reshape(-1).float(), torch.zeros_like(mean.reshape(-1)).float()])
+
+
+def flow_head_bwd(z, params, stats, scale, grad_out, training=False, eps=1e-3,
+                  need=(True, True, True, True, True, True)):
+    """Gradients of flow_head() (fp32 channels-last, qpwc_flow_head_bwd) for grad_out = dL/dflow (B,H,W,2).  params:
+    the vector the forward ran with, stats: mean | var | mean_lo (48 floats, frozen_stats() / flow_head_stats()) it was made from, training: whether those were the
+    batch statistics.  need = (z, w1, b1, gamma, beta, wf) -> (grad_z (B,H,W,16), grad_w1 (16,16), grad_b1 (16),
+    grad_gamma (16), grad_beta (16), grad_wf (3,3,16,2) as (ky,kx,in,out)); what is not asked for comes back as None."""
+    _check_tensor("z", z)
+    _check_tensor("grad_out", grad_out)
+    B, H, W, _ = z.shape
+    if z.dtype != torch.float32 or z.shape[3] != 16 or not z.is_contiguous():
+        raise ValueError("z must be a dense fp32 (B,H,W,16) tensor")
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (B, H, W, 2) or grad_out.device != z.device:
+        raise ValueError("grad_out must be fp32 {} on z's device, got {} {}".format(
+            (B, H, W, 2), grad_out.dtype, tuple(grad_out.shape)))
+    L = _hip.lib()
+    for name, t, numel in (("params", params, L.qpwc_flow_head_param_floats()), ("stats", stats, 48)):
+        if t.numel() != numel or t.dtype != torch.float32 or t.device != z.device or not t.is_contiguous():
+            raise ValueError("{} must be a dense fp32 vector of {} floats on z's device".format(name, numel))
+    if len(need) != 6 or not any(need):
+        raise ValueError("need holds six flags (z, w1, b1, gamma, beta, wf), at least one set")
+    grad_out = grad_out.contiguous()
+    nws = int(L.qpwc_flow_head_bwd_workspace_floats(B, H, W))
+    _hip.check(min(nws, 0))
+    ws = torch.empty(nws, dtype=torch.float32, device=z.device)
+    shapes = ((B, H, W, 16), (16, 16), (16,), (16,), (16,), (3, 3, 16, 2))
+    outs = [torch.empty(sh, dtype=torch.float32, device=z.device) if n else None for sh, n in zip(shapes, need)]
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(z.device), _timed("flow_head_bwd", (B, H, W, 16)):
+        rc = L.qpwc_flow_head_bwd(z.data_ptr(), params.data_ptr(), stats.data_ptr(), float(eps), int(bool(training)),
+                                  float(scale), grad_out.data_ptr(), *[ptr(t) for t in outs], ws.data_ptr(), B, H, W,
+                                  _stream(z))
+    _hip.check(rc)
+    return tuple(outs)
+
+
+class _FlowHeadFn(torch.autograd.Function):
+    """The flow head with qpwc_flow_head_bwd as its gradient.  The forward is flow_head() itself on a parameter vector
+    made from the moving statistics (inference mode) or by flow_head_stats() from the batch (training mode); z, that
+    vector and the statistics are saved, nothing else (the backward recomputes the activations)."""
+
+    @staticmethod
+    def forward(ctx, z, w1, b1, gamma, beta, wf, mean, var, scale, training, momentum, eps):
+        _refuse_capture("the flow head")
+        z = z.contiguous()
+        if training:
+            # mean / var are written in place through their raw pointers: no mark_dirty, no version bump.  They are
+            # buffers that never require grad and nothing here saves them for backward (the batch statistics travel
+            # in `stats`); a caller that saved them in another autograd node would not be warned of the update.
+            params, stats = flow_head_stats(z, w1, b1, gamma, beta, mean, var, wf, momentum, eps)
+        else:
+            params = pack_flow_head(w1, b1, gamma, beta, mean, var, eps, wf)
+            stats = frozen_stats(mean, var)
+        out = flow_head(z, params, scale)
+        ctx.save_for_backward(z, params, stats)
+        ctx.cfg = (float(scale), bool(training), float(eps), w1.shape, wf.shape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the flow-head backward")
+        z, params, stats = ctx.saved_tensors
+        scale, training, eps, w1_shape, wf_shape = ctx.cfg
+        gz, gw1, gb1, gg, gb, gwf = flow_head_bwd(z, params, stats, scale, grad_out.to(torch.float32), training, eps,
+                                                  tuple(ctx.needs_input_grad[:6]))
+        return (gz, gw1.reshape(w1_shape) if gw1 is not None else None, gb1, gg, gb,
+                gwf.permute(3, 2, 0, 1).reshape(wf_shape) if gwf is not None else None) + (None,) * 6
+
+
+def flow_head_train(z, w1, b1, gamma, beta, mean, var, wf, scale, training=False, momentum=0.99, eps=1e-3):
+    """The flow head on its own parameter tensors, trainable (fp32, channels-last): scale * conv3x3(BN(Mish(W1 Mish(z) +
+    b1)), wf) -> (B,H,W,2) for z (B,H,W,16), w1 (16,16,1,1), b1 / gamma / beta (16), wf (2,16,3,3), mean / var the
+    BatchNorm's moving buffers (16).  training=False normalises with the moving statistics: the launch, and the bits,
+    of flow_head(z, pack_flow_head(...)).  training=True normalises with the batch statistics and updates mean / var
+    in place, without grad, as Keras' BatchNormalization(fused=False) does: moving * momentum + batch * (1 - momentum),
+    biased variance (flow_head_stats()).  Differentiable in z, w1, b1, gamma, beta and wf: with grad enabled and one of
+    them requiring grad the same forward runs inside an autograd Function whose backward is qpwc_flow_head_bwd."""
+    if _wants_grad(z, w1, b1, gamma, beta, wf):
+        _refuse_capture("the flow head")
+        if isinstance(z, torch.Tensor) and z.dtype == torch.float16:
+            raise ValueError("the flow head has no gradient for fp16 storage: train in fp32")
+        _head_operands(z, w1, b1, gamma, beta, mean, var, wf)
+        return _FlowHeadFn.apply(z, w1, b1, gamma, beta, wf, mean, var, float(scale), bool(training), float(momentum),
+                                 float(eps))
+    if training:
+        if isinstance(z, torch.Tensor) and z.dtype == torch.float16:
+            raise ValueError("the flow head's batch statistics are fp32 only: train in fp32")
+        params, _ = flow_head_stats(z, w1, b1, gamma, beta, mean, var, wf, momentum, eps)
+        return flow_head(z.contiguous(), params, scale)
+    return flow_head(z, pack_flow_head(w1, b1, gamma, beta, mean, var, eps, wf), scale)
+
+
 def pointwise_bias(y, pw_padded, bias):
     """Pointwise 1x1 + bias of a split SeparableConv2D on the matrix cores (qpwc_pointwise_bias_fwd): y (..., C) fp32 dense
     -> (..., F) = y . W^T + bias, W = pw_padded (F, ceil(C/32)*32) from pad_pointwise().  The own replacement of the library
@@ -669,10 +821,54 @@ def bias_mish_(x_nhwc, bias=None):
     return x_nhwc
 
 
+def upsample2x_flow_bwd(grad_out, scale=1.0):
+    """Adjoint of upsample2x_flow() (fp32 channels-last, qpwc_upsample2x_flow_bwd): grad_out (B,2h,2w,2) -> (B,h,w,2)."""
+    _check_tensor("grad_out", grad_out)
+    B, H2, W2, C = grad_out.shape
+    if grad_out.dtype != torch.float32 or C != 2 or H2 % 2 or W2 % 2:
+        raise ValueError("upsample2x_flow_bwd takes an fp32 (B,2h,2w,2) gradient, got {} {}".format(
+            grad_out.dtype, tuple(grad_out.shape)))
+    g = grad_out.contiguous()
+    out = torch.empty((B, H2 // 2, W2 // 2, 2), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device), _timed("upsample2x_flow_bwd", (B, H2 // 2, W2 // 2, 2)):
+        rc = _hip.lib().qpwc_upsample2x_flow_bwd(g.data_ptr(), out.data_ptr(), B, H2 // 2, W2 // 2, float(scale),
+                                                  _stream(g))
+    _hip.check(rc)
+    return out
+
+
+class _UpsampleFn(torch.autograd.Function):
+    """upsample2x_flow() with qpwc_upsample2x_flow_bwd as its gradient: the forward is the no-grad forward itself."""
+
+    @staticmethod
+    def forward(ctx, flo, scale, in_format, out_format):
+        _refuse_capture("the flow upsampling")
+        ctx.cfg = (float(scale), in_format, out_format)
+        return upsample2x_flow(flo, scale, in_format, out_format)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the flow-upsampling backward")
+        scale, in_format, out_format = ctx.cfg
+        g = upsample2x_flow_bwd(_to_nhwc(grad_out.to(torch.float32), out_format), scale)
+        return _from_nhwc(g, in_format), None, None, None
+
+
 def upsample2x_flow(flo, scale=1.0, in_format=CHANNELS_LAST, out_format=CHANNELS_LAST):
     """scale * bilinear x2 upsampling of a flow (B,h,w,2) [(B,2,h,w) for in_format 'channels_first'] --
     the reference's Upsample functor (non_layers.py:183-193) as used on flows (pwcnet.py:55,60);
-    out (B,2h,2w,2) or (B,2,2h,2w) by out_format."""
+    out (B,2h,2w,2) or (B,2,2h,2w) by out_format.
+    Differentiable (fp32) in flo: with grad enabled and flo requiring grad the same forward runs inside an autograd
+    Function whose backward is qpwc_upsample2x_flow_bwd."""
+    if _wants_grad(flo):
+        _refuse_capture("the flow upsampling")
+        if flo.dtype == torch.float16:
+            raise ValueError("upsample2x_flow has no gradient for fp16 storage: train in fp32")
+        _check_tensor("flo", flo)
+        get_axis(in_format)
+        get_axis(out_format)
+        return _UpsampleFn.apply(flo, scale, in_format, out_format)
     _check_tensor("flo", flo)
     get_axis(in_format)
     get_axis(out_format)
