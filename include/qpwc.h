@@ -547,6 +547,45 @@ int qpwc_conv3x3s2_mish_x3_fwd(const void* x_padded, const void* weight3, const 
 int qpwc_conv3x3s2_mish_f16_fwd(const void* x_padded, const void* weight, const void* bias, void* out, int B,
                                 int H, int W, int C_in, void* stream);
 
+/* Conv2D(C_out, 3x3, strides=stride, padding='same') (+ Mish) of the encoder (non_layers.py:390-449) for any size, on
+ * the unpadded input: the training twin of the three forwards above.  fp32, channels-last, dense.
+ * TensorFlow 'SAME': Ho = ceil(H / stride), total = max((Ho - 1) stride + 3 - H, 0), pt = total / 2 rows of zeros above
+ * (stride 1: 1; stride 2: 0 for even H, with one row below, 1 for odd H); the same for W with pl.
+ *   z[n,oy,ox,o] = bias[o] + sum_{ky,kx,i} weight[ky*3+kx][o][i] x[n, oy stride + ky - pt, ox stride + kx - pl, i]
+ *   out = Mish(z) if mish else z                                  (terms outside the image are zero)
+ * x (B,H,W,C_in), C_in in {3,16,32,64,128,256}; weight (9, C_out, Cp) fp32 tap-major, Cp = C_in rounded up to 4 (the
+ * layouts of qpwc_conv3x3_mish_fwd and, for C_in = 3, qpwc_first_conv_mish_fwd); bias (C_out); out (B,Ho,Wo,C_out),
+ * C_out in {16,32,64,128,256}; stride in {1,2}; mish in {0,1}.  Implicit GEMM on the fp32 matrix instructions, one
+ * launch.  Alignment: weight, out 16 bytes, x 16 bytes (4 for the 12-byte pixels of C_in = 3), bias 4.
+ * Errors as qpwc_conv3x3_same_bwd. */
+int qpwc_conv3x3_same_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
+                          int C_in, int C_out, int stride, int mish, void* stream);
+
+/* Floats of device scratch qpwc_conv3x3_same_bwd needs: gz (B*Ho*Wo, C_out) and one partial of grad_w and grad_b per
+ * K-split of the pixel reduction; the number of splits comes from the shape alone.  Negative QPWC_E_SHAPE for a
+ * shape qpwc_conv3x3_same_bwd refuses. */
+int64_t qpwc_conv3x3_same_bwd_workspace_floats(int B, int H, int W, int C_in, int C_out, int stride);
+
+/* Gradient of qpwc_conv3x3_same_fwd (and of qpwc_conv3x3_mish_fwd / qpwc_conv3x3s2_mish_c_fwd / the first layer, which
+ * compute the same function).  With z and 'SAME' as above, g = grad_out = dL/d(out), dense (B,Ho,Wo,C_out), s = stride:
+ *   gz = g * Mish'(z) if mish else g,   Mish'(t) = tanh(sp) + t (1 - tanh(sp)^2) sigmoid(t), sp = softplus(t)
+ *   grad_b[o]           = sum_{n,oy,ox} gz[n,oy,ox,o]
+ *   grad_w[ky,kx][o][i] = sum_{n,oy,ox} gz[n,oy,ox,o] x[n, oy s + ky - pt, ox s + kx - pl, i]
+ *   grad_x[n,iy,ix,i]   = sum_{ky,kx,o} weight[ky,kx][o][i] gz[n, (iy + pt - ky) / s, (ix + pl - kx) / s, o]
+ *                         over the taps where both quotients are whole and in range
+ * (terms outside the image are zero).  z is recomputed from x (Mish is not invertible; only x, weight and bias are
+ * needed).  grad_x (B,H,W,C_in); grad_w (9, C_out, Cp) in the layout of weight, its pad slot (C_in = 3) written as 0;
+ * grad_b (C_out).  Any of the three may be NULL, not all; a stage whose only consumers are NULL is not launched.
+ * Every output is bitwise reproducible and has the same bits whatever else is asked for (fixed-order sums, no
+ * atomics, shape-only grids); grad_x of an image does not depend on the rest of the batch.  workspace:
+ * qpwc_conv3x3_same_bwd_workspace_floats() floats.  Alignment: weight, grad_out, grad_w, workspace 16 bytes; x and
+ * grad_x 16 bytes (4 for C_in = 3); bias, grad_b 4.  Errors: QPWC_E_NULL, QPWC_E_SHAPE (extents < 1, channel counts,
+ * stride, mish), QPWC_E_ALIGN, QPWC_E_ALIAS (an output or the workspace overlapping an input or another output);
+ * qpwc_last_error() names the argument. */
+int qpwc_conv3x3_same_bwd(const void* x, const void* weight, const void* bias, const void* grad_out, void* grad_x,
+                          void* grad_w, void* grad_b, void* workspace, int B, int H, int W, int C_in, int C_out,
+                          int stride, int mish, void* stream);
+
 /* UpConv of the decoder (non_layers.py:196-210): Conv2DTranspose(F, 4x4, strides 2, padding='same') + bias +
  * Mish of x (B,H,W,C), C in {64,128,256}, F % 16 == 0, written into channels [0, F) of `out`
  * (B, 2H, 2W, *) whose pixels are out_pixel_stride floats apart -- with out_pixel_stride = F + C_skip this is

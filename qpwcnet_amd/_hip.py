@@ -36,6 +36,7 @@ SYMBOLS = (
     "qpwc_sepconv3x3_bwd_workspace_floats", "qpwc_sepconv3x3_bwd",
     "qpwc_flow_head_stats_workspace_floats", "qpwc_flow_head_stats_fwd", "qpwc_flow_head_bwd_workspace_floats",
     "qpwc_flow_head_bwd", "qpwc_upsample2x_flow_bwd",
+    "qpwc_conv3x3_same_fwd", "qpwc_conv3x3_same_bwd_workspace_floats", "qpwc_conv3x3_same_bwd",
 )
 
 _lib = None
@@ -202,6 +203,12 @@ def lib():
     L.qpwc_flow_head_bwd.restype = ci
     L.qpwc_upsample2x_flow_bwd.argtypes = [vp, vp, ci, ci, ci, cf, vp]
     L.qpwc_upsample2x_flow_bwd.restype = ci
+    L.qpwc_conv3x3_same_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+    L.qpwc_conv3x3_same_fwd.restype = ci
+    L.qpwc_conv3x3_same_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.qpwc_conv3x3_same_bwd_workspace_floats.restype = i64
+    L.qpwc_conv3x3_same_bwd.argtypes = [vp] * 8 + [ci, ci, ci, ci, ci, ci, ci, vp]
+    L.qpwc_conv3x3_same_bwd.restype = ci
     _lib = L
     return L
 

@@ -118,6 +118,13 @@ bool sepconv3x3_bwd_shape_ok(int B, int H, int W, int C, int F);
 int sepconv3x3_bwd_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src, int flags,
                           const void* dw, const void* pw, const void* bias, const void* gout, void* const* gsrc,
                           void* gdw, void* gpw, void* gbias, void* ws, int B, int H, int W, int F, hipStream_t s);
+int64_t conv3x3_same_bwd_workspace_floats(int B, int H, int W, int cin, int cout, int s);
+bool conv3x3_same_shape_ok(int B, int H, int W, int cin, int cout, int s);
+int conv3x3_same_fwd_launch(const void* x, const void* w, const void* bias, void* out, int B, int H, int W, int cin,
+                            int cout, int stride, int mish, hipStream_t s);
+int conv3x3_same_bwd_launch(const void* x, const void* w, const void* bias, const void* gout, void* gx, void* gw,
+                            void* gb, void* ws, int B, int H, int W, int cin, int cout, int stride, int mish,
+                            hipStream_t s);
 int64_t flow_head_stats_workspace_floats(int B, int H, int W);
 int64_t flow_head_bwd_workspace_floats(int B, int H, int W);
 int flow_head_stats_launch(const void* z, const void* w1, const void* b1, const void* gamma, const void* beta,
@@ -1072,6 +1079,76 @@ int qpwc_conv3x3_mish_fwd(const void* x, const void* weight, const void* bias, v
     if (overlaps(out, (size_t)B * (H + pad_h) * (W + pad_w) * C * 4, x, (size_t)B * H * W * C * 4))
         return fail(QPWC_E_ALIAS, "out overlaps x");
     return conv3x3_mish_launch(x, weight, bias, out, B, H, W, C, pad_h, pad_w, (hipStream_t)stream);
+}
+
+static int conv_same_check_shape(int B, int H, int W, int C_in, int C_out, int stride) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
+    if (C_in != 3 && C_in != 16 && C_in != 32 && C_in != 64 && C_in != 128 && C_in != 256)
+        return fail(QPWC_E_SHAPE, "C_in=%d not in {3,16,32,64,128,256}", C_in);
+    if (C_out != 16 && C_out != 32 && C_out != 64 && C_out != 128 && C_out != 256)
+        return fail(QPWC_E_SHAPE, "C_out=%d not in {16,32,64,128,256}", C_out);
+    if (stride != 1 && stride != 2) return fail(QPWC_E_SHAPE, "stride=%d not in {1,2}", stride);
+    if (!conv3x3_same_shape_ok(B, H, W, C_in, C_out, stride))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: too large for the launch grids", B, H, W);
+    return QPWC_OK;
+}
+
+int qpwc_conv3x3_same_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
+                          int C_in, int C_out, int stride, int mish, void* stream) {
+    if (!x) return fail(QPWC_E_NULL, "x is null");
+    if (!weight) return fail(QPWC_E_NULL, "weight is null");
+    if (!bias) return fail(QPWC_E_NULL, "bias is null");
+    if (!out) return fail(QPWC_E_NULL, "out is null");
+    int rc = conv_same_check_shape(B, H, W, C_in, C_out, stride);
+    if (rc != QPWC_OK) return rc;
+    if (mish != 0 && mish != 1) return fail(QPWC_E_SHAPE, "mish=%d not in {0,1}", mish);
+    const size_t Ho = (size_t)(H + stride - 1) / stride, Wo = (size_t)(W + stride - 1) / stride;
+    const size_t cp = (size_t)(C_in + 3) / 4 * 4;
+    BufCheck bufs[4];
+    int n_in = 0;
+    bufs[n_in++] = {x, (size_t)B * H * W * C_in * 4, (size_t)(C_in % 4 ? 4 : 16), "x"};
+    bufs[n_in++] = {weight, 9 * (size_t)C_out * cp * 4, 16, "weight"};
+    bufs[n_in++] = {bias, (size_t)C_out * 4, 4, "bias"};
+    int n_all = n_in;
+    bufs[n_all++] = {out, (size_t)B * Ho * Wo * C_out * 4, 16, "out"};
+    if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
+    return conv3x3_same_fwd_launch(x, weight, bias, out, B, H, W, C_in, C_out, stride, mish, (hipStream_t)stream);
+}
+
+int64_t qpwc_conv3x3_same_bwd_workspace_floats(int B, int H, int W, int C_in, int C_out, int stride) {
+    const int rc = conv_same_check_shape(B, H, W, C_in, C_out, stride);
+    return rc != QPWC_OK ? rc : conv3x3_same_bwd_workspace_floats(B, H, W, C_in, C_out, stride);
+}
+
+int qpwc_conv3x3_same_bwd(const void* x, const void* weight, const void* bias, const void* grad_out, void* grad_x,
+                          void* grad_w, void* grad_b, void* workspace, int B, int H, int W, int C_in, int C_out,
+                          int stride, int mish, void* stream) {
+    if (!x) return fail(QPWC_E_NULL, "x is null");
+    if (!weight) return fail(QPWC_E_NULL, "weight is null");
+    if (!bias) return fail(QPWC_E_NULL, "bias is null");
+    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
+    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
+    if (!grad_x && !grad_w && !grad_b) return fail(QPWC_E_NULL, "grad_x, grad_w and grad_b are all null");
+    int rc = conv_same_check_shape(B, H, W, C_in, C_out, stride);
+    if (rc != QPWC_OK) return rc;
+    if (mish != 0 && mish != 1) return fail(QPWC_E_SHAPE, "mish=%d not in {0,1}", mish);
+    const size_t Ho = (size_t)(H + stride - 1) / stride, Wo = (size_t)(W + stride - 1) / stride;
+    const size_t cp = (size_t)(C_in + 3) / 4 * 4, xa = C_in % 4 ? 4 : 16;
+    BufCheck bufs[8];
+    int n_in = 0;
+    bufs[n_in++] = {x, (size_t)B * H * W * C_in * 4, xa, "x"};
+    bufs[n_in++] = {weight, 9 * (size_t)C_out * cp * 4, 16, "weight"};
+    bufs[n_in++] = {bias, (size_t)C_out * 4, 4, "bias"};
+    bufs[n_in++] = {grad_out, (size_t)B * Ho * Wo * C_out * 4, 16, "grad_out"};
+    int n_all = n_in;
+    if (grad_x) bufs[n_all++] = {grad_x, (size_t)B * H * W * C_in * 4, xa, "grad_x"};
+    if (grad_w) bufs[n_all++] = {grad_w, 9 * (size_t)C_out * cp * 4, 16, "grad_w"};
+    if (grad_b) bufs[n_all++] = {grad_b, (size_t)C_out * 4, 4, "grad_b"};
+    bufs[n_all++] = {workspace, (size_t)conv3x3_same_bwd_workspace_floats(B, H, W, C_in, C_out, stride) * 4, 16,
+                     "workspace"};
+    if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
+    return conv3x3_same_bwd_launch(x, weight, bias, grad_out, grad_x, grad_w, grad_b, workspace, B, H, W, C_in, C_out,
+                                   stride, mish, (hipStream_t)stream);
 }
 
 int qpwc_conv3x3_mish_x3_fwd(const void* x, const void* weight3, const void* bias, void* out, int B, int H,

@@ -2,7 +2,8 @@
 (qpwcnet/core/layers.py:32-186): ``CostVolume``, ``CostVolumeV2``, ``Warp``,
 ``WarpV2``, and trainable twins of the flow-estimator functors
 (qpwcnet/core/non_layers.py:183-193, 213-273, 315-387): ``SeparableConv2D``,
-``OptFlow``, ``Upsample``, ``Flow``, ``UpFlow``.  Same names, same constructor
+``OptFlow``, ``Upsample``, ``Flow``, ``UpFlow``, and of the encoder (non_layers.py:390-449, pwcnet.py:134-168):
+``DownConv``, ``Encoder``.  Same names, same constructor
 arguments, same ``layer((a, b))`` call convention, same config round trip; the
 arithmetic, forward and backward, runs in the gfx950 HIP kernels behind
 ``include/qpwc.h``.
@@ -265,3 +266,75 @@ class UpFlow(_HotPathLayer):
     def forward(self, inputs):
         prv, nxt, flo = inputs
         return self.flow((self.cost_volume((prv, self.warp((nxt, flo)))), prv, flo))
+
+
+class DownConv(_HotPathLayer):
+    """One encoder level (qpwcnet/core/non_layers.py:390-449 with use_normalizer=False, pwcnet.py:145-146), trainable:
+    Conv2D(filters, 3x3, strides 2, 'same', Mish) -> two Conv2D(filters, 3x3, 'same', Mish), forward and backward in
+    the HIP kernels behind ops.conv3x3_same.  State-dict names as weights.py: conv_a / conv_aa / conv_b .weight and
+    .bias in the torch layout; Keras' default initialisers (Glorot-uniform kernels, zero bias).  fp32 only."""
+
+    def __init__(self, in_channels, filters, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.in_channels, self.filters = int(in_channels), int(filters)
+        if self.in_channels not in ops._CONV_SAME_CIN or self.filters not in ops._CONV_SAME_COUT:
+            raise ValueError("DownConv: in_channels in {} and filters in {}, got {} -> {}".format(
+                ops._CONV_SAME_CIN, ops._CONV_SAME_COUT, in_channels, filters))
+        self._config = {"in_channels": self.in_channels, "filters": self.filters}
+        self.conv_a = _Conv((self.filters, self.in_channels, 3, 3), bias=True)
+        self.conv_aa = _Conv((self.filters, self.filters, 3, 3), bias=True)
+        self.conv_b = _Conv((self.filters, self.filters, 3, 3), bias=True)
+
+    def forward_nhwc(self, x):
+        x = ops.conv3x3_same(x, self.conv_a.weight, self.conv_a.bias, stride=2)
+        x = ops.conv3x3_same(x, self.conv_aa.weight, self.conv_aa.bias)
+        return ops.conv3x3_same(x, self.conv_b.weight, self.conv_b.bias)
+
+    def forward(self, x):
+        self.build((tuple(x.shape),))
+        if x.shape[self.axis] != self.in_channels:
+            raise ValueError("DownConv: the input holds {} channels, the layer {}".format(x.shape[self.axis],
+                                                                                         self.in_channels))
+        return ops._from_nhwc(self.forward_nhwc(_dense_nhwc(x, self.data_format)), self.data_format)
+
+
+def _dense_nhwc(t, data_format):
+    """Dense channels-last form of a layer input; with grad through torch's own copy, which autograd follows."""
+    if ops._wants_grad(t):
+        return (t if data_format == CHANNELS_LAST else t.permute(0, 2, 3, 1)).contiguous()
+    return ops._to_nhwc(t, data_format)
+
+
+class Encoder(_HotPathLayer):
+    """The feature pyramid (qpwcnet/core/pwcnet.py:134-168), trainable: one DownConv per entry of `filters`, shared by
+    both frames, which are stacked on the batch axis for one pass and split afterwards.  The call is
+    encoder((img_prv, img_nxt), output_features=False) -> (feature_prv, feature_nxt) of the coarsest level, or with
+    output_features the two lists [img, level 1, ..., level n].  State-dict names enc.{i}.conv_a.weight ... are those of
+    weights.py / synth.make_weights: a converted checkpoint loads with load_state_dict(strict=False).  The stack runs
+    channels-last inside; this layer converts at its own boundary."""
+
+    def __init__(self, filters=(16, 32, 64, 128, 256), in_channels=3, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.filters, self.in_channels = tuple(int(f) for f in filters), int(in_channels)
+        if not self.filters:
+            raise ValueError("Encoder: no filters")
+        self._config = {"filters": self.filters, "in_channels": self.in_channels}
+        chans = (self.in_channels,) + self.filters
+        self.enc = torch.nn.ModuleList(DownConv(chans[i], f, data_format=CHANNELS_LAST)
+                                       for i, f in enumerate(self.filters))
+
+    def forward(self, inputs, output_features=False):
+        img_prv, img_nxt = self._unpack(inputs)
+        if img_prv.shape != img_nxt.shape or img_prv.shape[self.axis] != self.in_channels:
+            raise ValueError("Encoder: two frames of one shape with {} channels, got {} and {}".format(
+                self.in_channels, tuple(img_prv.shape), tuple(img_nxt.shape)))
+        n = img_prv.shape[0]
+        f = _dense_nhwc(torch.cat([img_prv, img_nxt], dim=0), self.data_format)
+        feats_prv, feats_nxt = [img_prv], [img_nxt]
+        for layer in self.enc:
+            f = layer.forward_nhwc(f)
+            feats_prv.append(ops._from_nhwc(f[:n], self.data_format))
+            feats_nxt.append(ops._from_nhwc(f[n:], self.data_format))
+        if output_features:
+            return feats_prv, feats_nxt
+        return feats_prv[-1], feats_nxt[-1]

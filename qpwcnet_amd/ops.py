@@ -1339,6 +1339,147 @@ def conv3x3_mish(x_nhwc, taps, bias, pad_h=0, pad_w=0):
     return out
 
 
+def conv3x3_same_taps(weight):
+    """torch Conv2d weight (C_out, C_in, 3, 3) -> fp32 (9, C_out, Cp) [tap][out][in], Cp = C_in rounded up to 4 with
+    zero pad slots: conv3x3_taps() for the encoder's widths, first_conv_taps() for C_in = 3 (qpwc_conv3x3_same_*)."""
+    co, ci = weight.shape[0], weight.shape[1]
+    w = weight.to(torch.float32).permute(2, 3, 0, 1).reshape(9, co, ci)
+    if ci % 4 == 0:
+        return w.contiguous()
+    out = torch.zeros((9, co, (ci + 3) // 4 * 4), dtype=torch.float32, device=w.device)
+    out[..., :ci] = w
+    return out
+
+
+_CONV_SAME_CIN = (3, 16, 32, 64, 128, 256)
+_CONV_SAME_COUT = (16, 32, 64, 128, 256)
+
+
+def _conv_same_check(x, weight, bias, stride, what):
+    """The operand rules of qpwc_conv3x3_same_fwd / _bwd -> (B, H, W, C_in, C_out, Ho, Wo); weight in the torch layout
+    (C_out, C_in, 3, 3) or as its taps (9, C_out, Cp)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("{}: x must be a rank-4 (B,H,W,C) tensor".format(what))
+    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
+        if not t.is_cuda:
+            raise ValueError("{}: {} is on '{}'; the kernels run on a HIP device only (no CPU fallback)".format(
+                what, name, t.device))
+        if t.dtype == torch.float16:
+            raise ValueError("{}: no fp16 storage path, {} is fp16: train in fp32".format(what, name))
+        if t.dtype != torch.float32:
+            raise ValueError("{}: {} must be fp32, got {}".format(what, name, t.dtype))
+    if not x.is_contiguous():
+        raise ValueError("{}: x must be a dense channels-last tensor".format(what))
+    if stride not in (1, 2):
+        raise ValueError("{}: stride {} not in (1, 2)".format(what, stride))
+    B, H, W, ci = x.shape
+    taps = weight.dim() == 3
+    co = weight.shape[1] if taps else weight.shape[0]
+    if ci not in _CONV_SAME_CIN or co not in _CONV_SAME_COUT:
+        raise ValueError("{}: C_in {} -> C_out {} outside {} -> {}".format(what, ci, co, _CONV_SAME_CIN, _CONV_SAME_COUT))
+    want = (9, co, (ci + 3) // 4 * 4) if taps else (co, ci, 3, 3)
+    if tuple(weight.shape) != want or (taps and not weight.is_contiguous()) or bias.numel() != co or \
+            not bias.is_contiguous():
+        raise ValueError("{}: weight must hold (C_out, {}, 3, 3), bias (C_out)".format(what, ci))
+    if min(B, H, W) < 1:
+        raise ValueError("{}: empty input {}".format(what, tuple(x.shape)))
+    return B, H, W, ci, co, -(-H // stride), -(-W // stride)
+
+
+def _conv3x3_same_fwd(x, taps, bias, stride, mish):
+    """The forward launch of conv3x3_same(): the encoder's own kernels where their preconditions hold (stride 1 with
+    C_in = C_out: qpwc_conv3x3_mish_fwd; stride 2 with even H, W and C_out = 2 C_in: qpwc_conv3x3s2_mish_c_fwd on a
+    zero-bordered copy of x), else qpwc_conv3x3_same_fwd."""
+    B, H, W, ci, co, Ho, Wo = _conv_same_check(x, taps, bias, stride, "conv3x3_same")
+    if mish and stride == 1 and ci == co:
+        return conv3x3_mish(x, taps, bias)
+    if mish and stride == 2 and H % 2 == 0 and W % 2 == 0 and co == 2 * ci and ci in (16, 32, 64, 128):
+        return conv3x3s2_mish(torch.nn.functional.pad(x, (0, 0, 0, 1, 0, 1)), taps, bias)
+    out = torch.empty((B, Ho, Wo, co), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("conv3x3_same", (B, H, W, ci, co, stride)):
+        rc = _hip.lib().qpwc_conv3x3_same_fwd(x.data_ptr(), taps.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W,
+                                               ci, co, int(stride), int(bool(mish)), _stream(x))
+    _hip.check(rc)
+    return out
+
+
+def conv3x3_same_bwd(x_nhwc, taps, bias, grad_out, stride=1, mish=True, need=(True, True, True)):
+    """Gradients of conv3x3_same() (fp32, qpwc_conv3x3_same_bwd) for grad_out = dL/d(out), dense (B,Ho,Wo,C_out); taps
+    from conv3x3_same_taps().  need = (x, weight, bias) -> (grad_x (B,H,W,C_in), grad_taps (9,C_out,Cp) in the layout
+    of taps, grad_bias (C_out)); whatever is not asked for comes back as None and its pointer goes in as NULL."""
+    B, H, W, ci, co, Ho, Wo = _conv_same_check(x_nhwc, taps, bias, stride, "conv3x3_same_bwd")
+    if not isinstance(grad_out, torch.Tensor) or not grad_out.is_cuda or grad_out.dtype != torch.float32 or \
+            tuple(grad_out.shape) != (B, Ho, Wo, co):
+        raise ValueError("conv3x3_same_bwd: grad_out must be an fp32 device tensor of shape {}".format((B, Ho, Wo, co)))
+    if not any(need):
+        raise ValueError("conv3x3_same_bwd: nothing asked for")
+    grad_out = grad_out.contiguous()
+    dev = x_nhwc.device
+    L = _hip.lib()
+    nws = int(L.qpwc_conv3x3_same_bwd_workspace_floats(B, H, W, ci, co, int(stride)))
+    _hip.check(min(nws, 0))
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    gx = torch.empty((B, H, W, ci), dtype=torch.float32, device=dev) if need[0] else None
+    gw = torch.empty(tuple(taps.shape), dtype=torch.float32, device=dev) if need[1] else None
+    gb = torch.empty((co,), dtype=torch.float32, device=dev) if need[2] else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev), _timed("conv3x3_same_bwd", (B, H, W, ci, co, stride)):
+        rc = L.qpwc_conv3x3_same_bwd(x_nhwc.data_ptr(), taps.data_ptr(), bias.data_ptr(), grad_out.data_ptr(), ptr(gx),
+                                     ptr(gw), ptr(gb), ws.data_ptr(), B, H, W, ci, co, int(stride), int(bool(mish)),
+                                     _stream(grad_out))
+    _hip.check(rc)
+    return gx, gw, gb
+
+
+class _ConvSameFn(torch.autograd.Function):
+    """conv3x3_same() with qpwc_conv3x3_same_bwd as its gradient: the forward is the no-grad forward itself; x, weight
+    and bias are saved, never the pre-activation (the backward recomputes it)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, mish):
+        _refuse_capture("the 3x3 convolution")
+        out = _conv3x3_same_fwd(x, conv3x3_same_taps(weight), bias, stride, mish)
+        ctx.save_for_backward(x, weight, bias)
+        ctx.cfg = (int(stride), bool(mish))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the 3x3-convolution backward")
+        x, weight, bias = ctx.saved_tensors
+        stride, mish = ctx.cfg
+        nig = ctx.needs_input_grad
+        gx, gt, gb = conv3x3_same_bwd(x, conv3x3_same_taps(weight), bias, grad_out.to(torch.float32), stride, mish,
+                                      (nig[0], nig[1], nig[2]))
+        co, ci = weight.shape[0], weight.shape[1]
+        # the torch layout as a permuted view of the tap-major buffer (its pad slot, C_in = 3, left out)
+        gw = gt[..., :ci].reshape(3, 3, co, ci).permute(2, 3, 0, 1) if gt is not None else None
+        return gx, gw, gb.reshape(bias.shape) if gb is not None else None, None, None
+
+
+def conv3x3_same(x_nhwc, weight, bias, stride=1, mish=True, matmul="f32"):
+    """Conv2D(C_out, 3x3, strides=stride, padding='same') (+ Mish) of the encoder (qpwcnet/core/non_layers.py:390-449) on
+    a dense channels-last fp32 (B,H,W,C_in) tensor of any size, C_in in {3,16,32,64,128,256}, C_out in
+    {16,32,64,128,256}; weight in the torch layout (C_out, C_in, 3, 3), bias (C_out) -> (B, ceil(H/stride),
+    ceil(W/stride), C_out).  Differentiable in x, weight and bias: with grad enabled and one of them requiring grad the
+    same forward launch runs inside an autograd Function whose backward is qpwc_conv3x3_same_bwd (the workspace is
+    allocated per call); the result has the bits of the no-grad call."""
+    if matmul != "f32":
+        raise ValueError("conv3x3_same computes in fp32 only (matmul={!r}): no bf16x3 path, forward or gradient".format(
+            matmul))
+    for name, t in (("x", x_nhwc), ("weight", weight), ("bias", bias)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x_nhwc.dim() != 4 or weight.shape[1] != x_nhwc.shape[3]:
+        raise ValueError("conv3x3_same: weight {} does not fit x {}".format(tuple(weight.shape), tuple(x_nhwc.shape)))
+    if _wants_grad(x_nhwc, weight, bias):
+        _refuse_capture("the 3x3 convolution")
+        _conv_same_check(x_nhwc, weight, bias, stride, "conv3x3_same")   # the operand rules, before autograd sees the call
+        return _ConvSameFn.apply(x_nhwc, weight, bias, int(stride), bool(mish))
+    return _conv3x3_same_fwd(x_nhwc, conv3x3_same_taps(weight), bias, stride, mish)
+
+
 def split_bf16x3(t):
     """fp32 device tensor -> (3, *t.shape) bfloat16: the three-way split of csrc/split_bf16.h (qpwc_split_bf16x3_fwd);
     out[0] + out[1] + out[2] == t exactly (parts below the smallest normal fp32 flush to zero).  The weight operands of the *_x3 kernels."""
