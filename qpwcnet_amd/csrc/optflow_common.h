@@ -6,7 +6,12 @@ namespace qpwc {
 
 // mish(x) = x * tanh(softplus(x)) = x * t / (t + 2),  t = e^x (e^x + 2); x > 20 -> x
 // (torch's softplus threshold).  ~2 ulp with the fast exp/div.
+// Contraction is off, as in mish_grad below: with it the compiler fused `t + 2` with the product that forms t into
+// v_fma_f32(e, e + 2, 2) where it evaluated one value at a time (the fused SeparableConv2D's element-wise staging) and
+// not where it paired values for v_pk_mul_f32 (its 16-byte staging), and Mish-on-load of the same input differed in
+// the last bit between two instantiations of one kernel (tests/test_gpu_forward_scale.py).
 __device__ __forceinline__ float mishf(float x) {
+#pragma clang fp contract(off)
     // v_exp_f32 / v_rcp_f32 directly: hipcc lowers __expf with denormal range handling and __fdividef to
     // the full IEEE division sequence (div_scale / div_fmas / div_fixup), ~28 instructions per value
     const float e = __builtin_amdgcn_exp2f(fminf(x, 20.0f) * 1.4426950408889634f);
