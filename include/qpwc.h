@@ -617,6 +617,35 @@ int qpwc_upconv4x4s2_mish_cat_f16_fwd(const void* x, const void* weight, const v
                                       int64_t skip_batch_stride, int64_t skip_row_stride, int64_t skip_pixel_stride, void* out,
                                       int B, int H, int W, int C, int F, int64_t out_pixel_stride, void* stream);
 
+/* Floats of device scratch qpwc_upconv4x4s2_bwd needs: gz (B*2H*2W, F) and one partial of grad_w and grad_b per
+ * K-split of the pixel reduction; the number of splits comes from the shape alone.  Negative QPWC_E_SHAPE for a
+ * shape qpwc_upconv4x4s2_bwd refuses. */
+int64_t qpwc_upconv4x4s2_bwd_workspace_floats(int B, int H, int W, int C, int F);
+
+/* Gradient of qpwc_upconv4x4s2_mish_fwd / _cat_fwd: the layer Mish(Conv2DTranspose(F, 4x4, strides 2, 'same')(x) + bias),
+ * torch's conv_transpose2d(stride=2, padding=1) + Mish.  fp32, channels-last, dense.  x (B,H,W,C), C in {64,128,256};
+ * weight (16, F, C) tap-major, weight[ky*4+kx][f][c], F in {16,32,64,128}; bias (F).  With g = grad_out = dL/d(out)
+ * and terms outside the image equal to zero:
+ *   z[n,oy,ox,f]        = bias[f] + sum_{ky,kx,c} weight[ky,kx][f][c] x[n,iy,ix,c]
+ *                         over oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx   (an output of parity (py,px) meets 2x2 of the taps)
+ *   gz                  = g * Mish'(z) if mish else g
+ *   grad_b[f]           = sum_{n,oy,ox} gz[n,oy,ox,f]
+ *   grad_w[ky,kx][f][c] = sum_{n,iy,ix} gz[n, 2 iy - 1 + ky, 2 ix - 1 + kx, f] x[n,iy,ix,c]
+ *   grad_x[n,iy,ix,c]   = sum_{ky,kx,f} weight[ky,kx][f][c] gz[n, 2 iy - 1 + ky, 2 ix - 1 + kx, f]
+ * z is recomputed from x (the forward stores Mish(z) only; x, weight and bias are all that is needed).  grad_out is
+ * channels [0, F) of a (B,2H,2W,*) buffer whose pixels are grad_out_pixel_stride floats apart (>= F, a multiple of
+ * 4, at most 2^24): with F + C_skip it is the `up` half of the gradient of the decoder's concat([up, skip]), read in place.
+ * grad_x (B,H,W,C); grad_w (16, F, C) in the layout of weight; grad_b (F).  Any of the three may be NULL, not all; a
+ * stage whose only consumers are NULL is not launched.  Every output is bitwise reproducible and has the same bits
+ * whatever else is asked for (fixed-order sums, no atomics, shape-only grids); grad_x of an image does not depend on
+ * the rest of the batch.  workspace: qpwc_upconv4x4s2_bwd_workspace_floats() floats.  Alignment: x, weight, grad_out,
+ * grad_x, grad_w, workspace 16 bytes; bias, grad_b 4.  Errors: QPWC_E_NULL, QPWC_E_SHAPE (extents < 1, channel counts,
+ * mish, grad_out_pixel_stride), QPWC_E_ALIGN, QPWC_E_ALIAS (an output or the workspace overlapping an input or another
+ * output); qpwc_last_error() names the argument.  All of them are found before any HIP call. */
+int qpwc_upconv4x4s2_bwd(const void* x, const void* weight, const void* bias, const void* grad_out,
+                         int64_t grad_out_pixel_stride, void* grad_x, void* grad_w, void* grad_b, void* workspace,
+                         int B, int H, int W, int C, int F, int mish, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ SYMBOLS = (
     "qpwc_flow_head_stats_workspace_floats", "qpwc_flow_head_stats_fwd", "qpwc_flow_head_bwd_workspace_floats",
     "qpwc_flow_head_bwd", "qpwc_upsample2x_flow_bwd",
     "qpwc_conv3x3_same_fwd", "qpwc_conv3x3_same_bwd_workspace_floats", "qpwc_conv3x3_same_bwd",
+    "qpwc_upconv4x4s2_bwd_workspace_floats", "qpwc_upconv4x4s2_bwd",
 )
 
 _lib = None
@@ -209,6 +210,10 @@ def lib():
     L.qpwc_conv3x3_same_bwd_workspace_floats.restype = i64
     L.qpwc_conv3x3_same_bwd.argtypes = [vp] * 8 + [ci, ci, ci, ci, ci, ci, ci, vp]
     L.qpwc_conv3x3_same_bwd.restype = ci
+    L.qpwc_upconv4x4s2_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci]
+    L.qpwc_upconv4x4s2_bwd_workspace_floats.restype = i64
+    L.qpwc_upconv4x4s2_bwd.argtypes = [vp] * 4 + [i64] + [vp] * 4 + [ci, ci, ci, ci, ci, ci, vp]
+    L.qpwc_upconv4x4s2_bwd.restype = ci
     _lib = L
     return L
 

@@ -125,6 +125,11 @@ int conv3x3_same_fwd_launch(const void* x, const void* w, const void* bias, void
 int conv3x3_same_bwd_launch(const void* x, const void* w, const void* bias, const void* gout, void* gx, void* gw,
                             void* gb, void* ws, int B, int H, int W, int cin, int cout, int stride, int mish,
                             hipStream_t s);
+int64_t upconv4x4s2_bwd_workspace_floats(int B, int H, int W, int C, int F);
+bool upconv4x4s2_bwd_shape_ok(int B, int H, int W, int C, int F);
+int upconv4x4s2_bwd_launch(const void* x, const void* w, const void* bias, const void* gout, int64_t gout_stride,
+                           void* gx, void* gw, void* gb, void* ws, int B, int H, int W, int C, int F, int mish,
+                           hipStream_t s);
 int64_t flow_head_stats_workspace_floats(int B, int H, int W);
 int64_t flow_head_bwd_workspace_floats(int B, int H, int W);
 int flow_head_stats_launch(const void* z, const void* w1, const void* b1, const void* gamma, const void* beta,
@@ -1149,6 +1154,52 @@ int qpwc_conv3x3_same_bwd(const void* x, const void* weight, const void* bias, c
     if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
     return conv3x3_same_bwd_launch(x, weight, bias, grad_out, grad_x, grad_w, grad_b, workspace, B, H, W, C_in, C_out,
                                    stride, mish, (hipStream_t)stream);
+}
+
+static int upconv_bwd_check_shape(int B, int H, int W, int C, int F) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
+    if (C != 64 && C != 128 && C != 256) return fail(QPWC_E_SHAPE, "C=%d not in {64,128,256}", C);
+    if (F != 16 && F != 32 && F != 64 && F != 128) return fail(QPWC_E_SHAPE, "F=%d not in {16,32,64,128}", F);
+    if (!upconv4x4s2_bwd_shape_ok(B, H, W, C, F))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: too large for the launch grids", B, H, W);
+    return QPWC_OK;
+}
+
+int64_t qpwc_upconv4x4s2_bwd_workspace_floats(int B, int H, int W, int C, int F) {
+    const int rc = upconv_bwd_check_shape(B, H, W, C, F);
+    return rc != QPWC_OK ? rc : upconv4x4s2_bwd_workspace_floats(B, H, W, C, F);
+}
+
+int qpwc_upconv4x4s2_bwd(const void* x, const void* weight, const void* bias, const void* grad_out,
+                         int64_t grad_out_pixel_stride, void* grad_x, void* grad_w, void* grad_b, void* workspace,
+                         int B, int H, int W, int C, int F, int mish, void* stream) {
+    if (!x) return fail(QPWC_E_NULL, "x is null");
+    if (!weight) return fail(QPWC_E_NULL, "weight is null");
+    if (!bias) return fail(QPWC_E_NULL, "bias is null");
+    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
+    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
+    if (!grad_x && !grad_w && !grad_b) return fail(QPWC_E_NULL, "grad_x, grad_w and grad_b are all null");
+    int rc = upconv_bwd_check_shape(B, H, W, C, F);
+    if (rc != QPWC_OK) return rc;
+    if (mish != 0 && mish != 1) return fail(QPWC_E_SHAPE, "mish=%d not in {0,1}", mish);
+    if (grad_out_pixel_stride < F || grad_out_pixel_stride % 4 || grad_out_pixel_stride > ((int64_t)1 << 24))
+        return fail(QPWC_E_SHAPE, "grad_out_pixel_stride=%lld must be a multiple of 4 in [F=%d, 2^24]", (long long)grad_out_pixel_stride,
+                    F);
+    const size_t px = (size_t)B * H * W;
+    BufCheck bufs[8];
+    int n_in = 0;
+    bufs[n_in++] = {x, px * C * 4, 16, "x"};
+    bufs[n_in++] = {weight, 16 * (size_t)F * C * 4, 16, "weight"};
+    bufs[n_in++] = {bias, (size_t)F * 4, 4, "bias"};
+    bufs[n_in++] = {grad_out, ((4 * px - 1) * (size_t)grad_out_pixel_stride + F) * 4, 16, "grad_out"};
+    int n_all = n_in;
+    if (grad_x) bufs[n_all++] = {grad_x, px * C * 4, 16, "grad_x"};
+    if (grad_w) bufs[n_all++] = {grad_w, 16 * (size_t)F * C * 4, 16, "grad_w"};
+    if (grad_b) bufs[n_all++] = {grad_b, (size_t)F * 4, 4, "grad_b"};
+    bufs[n_all++] = {workspace, (size_t)upconv4x4s2_bwd_workspace_floats(B, H, W, C, F) * 4, 16, "workspace"};
+    if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
+    return upconv4x4s2_bwd_launch(x, weight, bias, grad_out, grad_out_pixel_stride, grad_x, grad_w, grad_b, workspace, B,
+                                  H, W, C, F, mish, (hipStream_t)stream);
 }
 
 int qpwc_conv3x3_mish_x3_fwd(const void* x, const void* weight3, const void* bias, void* out, int B, int H,

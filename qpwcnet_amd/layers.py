@@ -3,7 +3,8 @@
 ``WarpV2``, and trainable twins of the flow-estimator functors
 (qpwcnet/core/non_layers.py:183-193, 213-273, 315-387): ``SeparableConv2D``,
 ``OptFlow``, ``Upsample``, ``Flow``, ``UpFlow``, and of the encoder (non_layers.py:390-449, pwcnet.py:134-168):
-``DownConv``, ``Encoder``.  Same names, same constructor
+``DownConv``, ``Encoder``, of the decoder (non_layers.py:196-210, pwcnet.py:171-207): ``UpConv``, ``Decoder``, and of
+the whole ``build_flower`` network: ``FlowerModel``.  Same names, same constructor
 arguments, same ``layer((a, b))`` call convention, same config round trip; the
 arithmetic, forward and backward, runs in the gfx950 HIP kernels behind
 ``include/qpwc.h``.
@@ -338,3 +339,154 @@ class Encoder(_HotPathLayer):
         if output_features:
             return feats_prv, feats_nxt
         return feats_prv[-1], feats_nxt[-1]
+
+    def forward_stacked(self, frames):
+        """The pyramid of 2n stacked frames [prv; nxt] (dense channels-last, (2n,H,W,C)) -> [level 1, ..., level n],
+        stacked and channels-last as the levels compute them: what layers.Decoder.forward_stacked and FlowerModel
+        take, without the split and re-concatenation of forward()."""
+        return _encode_stacked(self.enc, frames)
+
+
+def _encode_stacked(levels, f):
+    feats = []
+    for layer in levels:
+        f = layer.forward_nhwc(f)
+        feats.append(f)
+    return feats
+
+
+class _ConvT(torch.nn.Module):
+    """Holder of a transposed convolution's `weight` (C_in, F, k, k) and `bias` (F): conv_up.weight / conv_up.bias."""
+
+    def __init__(self, shape):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(shape))
+        torch.nn.init.xavier_uniform_(self.weight)   # Keras' glorot_uniform: fan_in + fan_out = (C_in + F) k k either way
+        self.bias = torch.nn.Parameter(torch.zeros(shape[1]))
+
+
+class UpConv(_HotPathLayer):
+    """One decoder level (qpwcnet/core/non_layers.py:196-210), trainable: Conv2DTranspose(filters, 4x4, strides 2,
+    'same') + Mish, forward and backward in the HIP kernels behind ops.upconv4x4s2.  UpConv(x) -> the upsampled
+    features; UpConv.cat_skip(x, skip) -> concat([UpConv(x), skip]) on the channel axis (pwcnet.py:186-195), written by
+    the layer's own launch, with the gradient of the concat read in place.  State-dict names as weights.py:
+    conv_up.weight (C, F, 4, 4), conv_up.bias (F); Keras' default initialisers.  fp32 only."""
+
+    def __init__(self, in_channels, filters, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.in_channels, self.filters = int(in_channels), int(filters)
+        if self.in_channels not in ops._UPCONV_C or self.filters not in ops._UPCONV_F:
+            raise ValueError("UpConv: in_channels in {} and filters in {}, got {} -> {}".format(
+                ops._UPCONV_C, ops._UPCONV_F, in_channels, filters))
+        self._config = {"in_channels": self.in_channels, "filters": self.filters}
+        self.conv_up = _ConvT((self.in_channels, self.filters, 4, 4))
+
+    def forward_nhwc(self, x, skip=None):
+        return ops.upconv4x4s2(x, self.conv_up.weight, self.conv_up.bias, skip)
+
+    def _check(self, x):
+        self.build((tuple(x.shape),))
+        if x.shape[self.axis] != self.in_channels:
+            raise ValueError("UpConv: the input holds {} channels, the layer {}".format(x.shape[self.axis],
+                                                                                       self.in_channels))
+
+    def forward(self, x):
+        self._check(x)
+        return ops._from_nhwc(self.forward_nhwc(_dense_nhwc(x, self.data_format)), self.data_format)
+
+    def cat_skip(self, x, skip):
+        self._check(x)
+        if self.data_format == CHANNELS_FIRST:
+            skip = skip.permute(0, 2, 3, 1) if ops._wants_grad(skip) else ops._to_nhwc(skip, CHANNELS_FIRST)
+        return ops._from_nhwc(self.forward_nhwc(_dense_nhwc(x, self.data_format), skip), self.data_format)
+
+
+def _decode_stacked(levels, feats, use_skip):
+    f, decs = feats[-1], []
+    for i, layer in enumerate(levels):
+        f = layer.forward_nhwc(f, feats[-2 - i] if use_skip else None)
+        decs.append(f)
+    return decs
+
+
+class Decoder(_HotPathLayer):
+    """The feature decoder (qpwcnet/core/pwcnet.py:171-207), trainable: one UpConv per entry of `filters`, each
+    concatenated with the encoder feature of its resolution (`skip_channels`: that feature's channels per level; None
+    is the reference's use_skip=False).  The call is decoder((encs_prv, encs_nxt)) on the two feature lists of
+    Encoder(..., output_features=True) -> (decs_prv, decs_nxt); both frames go through one launch per level, stacked
+    on the batch axis.  A level's input width, in_channels or the concat of the level before, must be one the
+    transposed convolution takes (64, 128, 256).  State-dict names dec.{i}.conv_up.* are those of weights.py."""
+
+    def __init__(self, filters=(128, 64, 32, 16), in_channels=256, skip_channels=(128, 64, 32, 16), *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.filters, self.in_channels = tuple(int(f) for f in filters), int(in_channels)
+        self.skip_channels = None if skip_channels is None else tuple(int(c) for c in skip_channels)
+        if not self.filters or (self.skip_channels is not None and len(self.skip_channels) != len(self.filters)):
+            raise ValueError("Decoder: one skip width per filter, got {} and {}".format(filters, skip_channels))
+        self._config = {"filters": self.filters, "in_channels": self.in_channels, "skip_channels": self.skip_channels}
+        levels, c = [], self.in_channels
+        for i, f in enumerate(self.filters):
+            levels.append(UpConv(c, f, data_format=CHANNELS_LAST))
+            c = f + (self.skip_channels[i] if self.skip_channels is not None else 0)
+        self.dec = torch.nn.ModuleList(levels)
+
+    def forward_stacked(self, feats):
+        """Stacked channels-last encoder levels [..., level n] (Encoder.forward_stacked) -> the stacked decoder levels."""
+        return _decode_stacked(self.dec, feats, self.skip_channels is not None)
+
+    def forward(self, inputs):
+        encs_prv, encs_nxt = inputs
+        need = len(self.dec) + 1 if self.skip_channels is not None else 1
+        if len(encs_prv) != len(encs_nxt) or len(encs_prv) < need:
+            raise ValueError("Decoder: two feature lists of at least {} levels, got {} and {}".format(
+                need, len(encs_prv), len(encs_nxt)))
+        self.build((tuple(encs_prv[-1].shape),))
+        n = encs_prv[-1].shape[0]
+        feats = [_dense_nhwc(torch.cat([a, b], dim=0), self.data_format)
+                 for a, b in zip(encs_prv[-need:], encs_nxt[-need:])]
+        decs = self.forward_stacked(feats)
+        return ([ops._from_nhwc(d[:n], self.data_format) for d in decs],
+                [ops._from_nhwc(d[n:], self.data_format) for d in decs])
+
+
+class FlowerModel(_HotPathLayer):
+    """The whole flow network of build_flower (qpwcnet/core/pwcnet.py:210-244 with train=True), trainable: Encoder,
+    Decoder, the coarsest Flow and one UpFlow per decoder level with Upsample(2.0) between the levels and at the end.
+    The input is the frame pair (B,H,W,6), or (B,6,H,W) for channels_first; the result is the list of multi-scale flows,
+    coarse to fine, plus the final upsample-only one -- what loss.multiscale takes.  Every parameter receives a
+    gradient from HIP kernels.  State-dict names enc.*, dec.*, flow.flow.*, upflow.{i}.flow.* are those of weights.py /
+    synth.make_weights, so a converted checkpoint loads with load_state_dict.  train() / eval() select the BatchNorm
+    mode of every OptFlow.  The stack runs channels-last inside; this layer converts at its own boundary."""
+
+    def __init__(self, enc_filters=(16, 32, 64, 128, 256), dec_filters=(128, 64, 32, 16), *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.enc_filters = tuple(int(f) for f in enc_filters)
+        self.dec_filters = tuple(int(f) for f in dec_filters)
+        if not self.enc_filters or len(self.dec_filters) >= len(self.enc_filters):
+            raise ValueError("FlowerModel: fewer decoder levels than encoder levels, got {} and {}".format(
+                enc_filters, dec_filters))
+        self._config = {"enc_filters": self.enc_filters, "dec_filters": self.dec_filters}
+        skips = tuple(self.enc_filters[-2 - i] for i in range(len(self.dec_filters)))
+        self.enc = Encoder(self.enc_filters, data_format=CHANNELS_LAST).enc
+        self.dec = Decoder(self.dec_filters, self.enc_filters[-1], skips, data_format=CHANNELS_LAST).dec
+        self.flow = Flow(self.enc_filters[-1], data_format=CHANNELS_LAST)
+        self.upflow = torch.nn.ModuleList(UpFlow(f + c, data_format=CHANNELS_LAST)
+                                          for f, c in zip(self.dec_filters, skips))
+        self.up = Upsample(2.0, data_format=CHANNELS_LAST)
+
+    def forward(self, pairs):
+        if pairs.dim() != 4 or pairs.shape[self.axis] != 6:
+            raise ValueError("FlowerModel: a frame pair with 6 channels on axis {}, got {}".format(
+                self.axis, tuple(pairs.shape)))
+        self.build((tuple(pairs.shape),))
+        n = pairs.shape[0]
+        prv, nxt = torch.chunk(pairs, 2, dim=self.axis)
+        feats = _encode_stacked(self.enc, _dense_nhwc(torch.cat([prv, nxt], dim=0), self.data_format))
+        decs = _decode_stacked(self.dec, feats, True)
+        flo = self.flow((feats[-1][:n], feats[-1][n:]))
+        flows = [flo]
+        for d, upflow in zip(decs, self.upflow):
+            flo = upflow((d[:n], d[n:], self.up(flo)))
+            flows.append(flo)
+        flows.append(self.up(flo))
+        return [ops._from_nhwc(f, self.data_format) for f in flows]

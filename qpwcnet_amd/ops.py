@@ -1662,6 +1662,147 @@ def upconv4x4s2_mish_cat_into(x_nhwc, taps, bias, skip, dst):
     return dst
 
 
+_UPCONV_C = (64, 128, 256)
+_UPCONV_F = (16, 32, 64, 128)
+
+
+def _upconv_check(x, weight, bias, what):
+    """The operand rules of the differentiable transposed convolution / qpwc_upconv4x4s2_bwd -> (B, H, W, C, F); weight
+    in the torch layout (C, F, 4, 4) or as its taps (16, F, C)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("{}: x must be a rank-4 (B,H,W,C) tensor".format(what))
+    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
+        if not t.is_cuda:
+            raise ValueError("{}: {} is on '{}'; the kernels run on a HIP device only (no CPU fallback)".format(
+                what, name, t.device))
+        if t.dtype == torch.float16:
+            raise ValueError("{}: no fp16 storage path, {} is fp16: train in fp32".format(what, name))
+        if t.dtype != torch.float32:
+            raise ValueError("{}: {} must be fp32, got {}".format(what, name, t.dtype))
+    if not x.is_contiguous():
+        raise ValueError("{}: x must be a dense channels-last tensor".format(what))
+    B, H, W, C = x.shape
+    taps = weight.dim() == 3
+    F_ = weight.shape[1]
+    if C not in _UPCONV_C or F_ not in _UPCONV_F:
+        raise ValueError("{}: C {} -> F {} outside {} -> {}".format(what, C, F_, _UPCONV_C, _UPCONV_F))
+    want = (16, F_, C) if taps else (C, F_, 4, 4)
+    if tuple(weight.shape) != want or (taps and not weight.is_contiguous()) or bias.numel() != F_ or \
+            not bias.is_contiguous():
+        raise ValueError("{}: weight must hold ({}, F, 4, 4), bias (F)".format(what, C))
+    if min(B, H, W) < 1:
+        raise ValueError("{}: empty input {}".format(what, tuple(x.shape)))
+    return B, H, W, C, F_
+
+
+def _upconv4x4s2_fwd(x, taps, bias, skip):
+    """The forward launches of upconv4x4s2(): exactly those of the no-grad decoder (non_layers.UpConv.cat_skip)."""
+    B, H, W, C, F_ = _upconv_check(x, taps, bias, "upconv4x4s2")
+    if skip is None:
+        return upconv4x4s2_mish_into(x, taps, bias, torch.empty((B, 2 * H, 2 * W, F_), dtype=x.dtype, device=x.device))
+    buf = torch.empty((B, 2 * H, 2 * W, F_ + skip.shape[3]), dtype=x.dtype, device=x.device)
+    if upconv_cat_ok(x, taps, skip, buf):
+        return upconv4x4s2_mish_cat_into(x, taps, bias, skip, buf)
+    upconv4x4s2_mish_into(x, taps, bias, buf)
+    half = buf[..., F_:]
+    if copy_pixels_ok(skip, half):
+        copy_pixels(skip, half)
+    else:
+        half.copy_(skip)
+    return buf
+
+
+def upconv4x4s2_bwd(x_nhwc, taps, bias, grad_out, mish=True, need=(True, True, True)):
+    """Gradients of Mish(Conv2DTranspose(4x4, stride 2, 'same')(x) + bias) (fp32, qpwc_upconv4x4s2_bwd); taps from
+    upconv_taps().  grad_out = dL/d(out) is a dense (B,2H,2W,Ctot >= F) tensor whose first F channels are used, read in
+    place through its pixel stride Ctot (the gradient of the decoder's concat([up, skip]) as it is).  need = (x,
+    weight, bias) -> (grad_x (B,H,W,C), grad_taps (16,F,C) in the layout of taps, grad_bias (F)); whatever is not asked
+    for comes back as None and its pointer goes in as NULL."""
+    B, H, W, C, F_ = _upconv_check(x_nhwc, taps, bias, "upconv4x4s2_bwd")
+    if not isinstance(grad_out, torch.Tensor) or not grad_out.is_cuda or grad_out.dtype != torch.float32 or \
+            grad_out.dim() != 4 or tuple(grad_out.shape[:3]) != (B, 2 * H, 2 * W) or grad_out.shape[3] < F_ or \
+            grad_out.shape[3] % 4:
+        raise ValueError("upconv4x4s2_bwd: grad_out must be an fp32 device tensor of shape {} + (Ctot >= {}, "
+                         "Ctot % 4 == 0)".format((B, 2 * H, 2 * W), F_))
+    if not any(need):
+        raise ValueError("upconv4x4s2_bwd: nothing asked for")
+    grad_out = grad_out.contiguous()
+    dev = x_nhwc.device
+    L = _hip.lib()
+    nws = int(L.qpwc_upconv4x4s2_bwd_workspace_floats(B, H, W, C, F_))
+    _hip.check(min(nws, 0))
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    gx = torch.empty((B, H, W, C), dtype=torch.float32, device=dev) if need[0] else None
+    gw = torch.empty((16, F_, C), dtype=torch.float32, device=dev) if need[1] else None
+    gb = torch.empty((F_,), dtype=torch.float32, device=dev) if need[2] else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev), _timed("upconv4x4s2_bwd", (B, H, W, C, F_)):
+        rc = L.qpwc_upconv4x4s2_bwd(x_nhwc.data_ptr(), taps.data_ptr(), bias.data_ptr(), grad_out.data_ptr(),
+                                    grad_out.shape[3], ptr(gx), ptr(gw), ptr(gb), ws.data_ptr(), B, H, W, C, F_,
+                                    int(bool(mish)), _stream(grad_out))
+    _hip.check(rc)
+    return gx, gw, gb
+
+
+class _UpConvFn(torch.autograd.Function):
+    """upconv4x4s2() with qpwc_upconv4x4s2_bwd as its gradient: the forward is the no-grad forward itself; x, weight
+    and bias are saved, never the pre-activation (the backward recomputes it) nor the skip (its gradient is a view)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, skip):
+        _refuse_capture("the transposed convolution")
+        out = _upconv4x4s2_fwd(x, upconv_taps(weight), bias, skip)
+        ctx.save_for_backward(x, weight, bias)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the transposed-convolution backward")
+        x, weight, bias = ctx.saved_tensors
+        nig = ctx.needs_input_grad
+        C, F_ = weight.shape[0], weight.shape[1]
+        grad_out = grad_out.to(torch.float32).contiguous()   # the concat's gradient: its `up` half is read in place
+        gx = gw = gb = None
+        if nig[0] or nig[1] or nig[2]:
+            gx, gt, gb = upconv4x4s2_bwd(x, upconv_taps(weight), bias, grad_out, True, (nig[0], nig[1], nig[2]))
+            # the torch layout as a permuted view of the tap-major buffer
+            gw = gt.reshape(4, 4, F_, C).permute(3, 2, 0, 1) if gt is not None else None
+        gs = grad_out[..., F_:] if nig[3] else None
+        return gx, gw, gb.reshape(bias.shape) if gb is not None else None, gs
+
+
+def upconv4x4s2(x_nhwc, weight, bias, skip=None, matmul="f32"):
+    """Mish(Conv2DTranspose(F, 4x4, strides 2, 'same')(x) + bias) of the decoder (qpwcnet/core/non_layers.py:196-210) on
+    a dense channels-last fp32 (B,H,W,C) tensor, C in {64,128,256}, F in {16,32,64,128}; weight in the torch layout
+    (C, F, 4, 4), bias (F) -> (B,2H,2W,F), or with skip (B,2H,2W,S), S % 4 == 0, the concat([up, skip]) buffer
+    (B,2H,2W,F+S) of pwcnet.py:186-195.  The forward is the no-grad decoder's launches: upconv4x4s2_mish_cat_into where
+    upconv_cat_ok, else upconv4x4s2_mish_into plus the skip copy.  Differentiable in x, weight, bias and skip: with
+    grad enabled and one of them requiring grad the same launches run inside an autograd Function whose backward is
+    qpwc_upconv4x4s2_bwd on the concat's gradient in place (grad_skip is a view of it); the result has the bits of the
+    no-grad call."""
+    if matmul != "f32":
+        raise ValueError("upconv4x4s2 computes in fp32 only (matmul={!r}): no bf16x3 path with a gradient".format(matmul))
+    for name, t in (("x", x_nhwc), ("weight", weight), ("bias", bias)) + ((("skip", skip),) if skip is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4) or x_nhwc.dim() != 4 or weight.shape[0] != x_nhwc.shape[3]:
+        raise ValueError("upconv4x4s2: weight {} does not fit x {}".format(tuple(weight.shape), tuple(x_nhwc.shape)))
+    grad = _wants_grad(x_nhwc, weight, bias, skip)
+    if grad:
+        _refuse_capture("the transposed convolution")
+    _upconv_check(x_nhwc, weight, bias, "upconv4x4s2")   # the operand rules, before autograd sees the call
+    if skip is not None:
+        B, H, W, _ = x_nhwc.shape
+        if not skip.is_cuda or skip.dtype != torch.float32 or skip.dim() != 4 or \
+                tuple(skip.shape[:3]) != (B, 2 * H, 2 * W) or skip.shape[3] % 4 or skip.shape[3] < 4:
+            raise ValueError("upconv4x4s2: skip must be an fp32 device tensor of shape {} + (S, S % 4 == 0), got {} "
+                             "{}".format((B, 2 * H, 2 * W), tuple(skip.shape), skip.dtype))
+    if grad:
+        return _UpConvFn.apply(x_nhwc, weight, bias, skip)
+    return _upconv4x4s2_fwd(x_nhwc, upconv_taps(weight), bias, skip)
+
+
 def bias_mish_pad(x_nhwc, bias, pad_h, pad_w):
     """Mish(x + bias) written into a new (B, H+pad_h, W+pad_w, C) tensor whose border is zero:
     the activation epilogue and TensorFlow's 'SAME' padding of the following stride-2 conv
