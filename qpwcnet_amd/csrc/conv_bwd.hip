@@ -17,15 +17,20 @@
 //                                     registers across the workgroup's pixel blocks (grid-stride), one partial per
 //                                     workgroup; the tap-0 workgroups of the first C_in block also sum gz for grad_b
 //   R  conv_bwd_reduce_kernel         partials summed per output: 16 lanes stride over the workgroups, then a fixed tree
+//                                     (also stage R of upconv_bwd.hip, through conv_bwd_reduce_launch)
+// The lane layout of the matrix instruction, the B staging, the wave-order tile sum, the grad_b finish and the K-split
+// plan are those of conv_bwd_common.h, shared with upconv_bwd.hip.
 //
 // Determinism: every output element is a sum in a fixed order; no atomics; grids and the number of K-splits depend on the
 // shape only; what is asked for is a kernel argument and changes no arithmetic of the other outputs.  A row of the
 // GEMMs (a pixel of gz / grad_x) is accumulated independently of every other row: grad_x of an image does not depend
 // on the rest of the batch.
-#include "optflow_common.h"
+#include "conv_bwd_common.h"
 
 namespace qpwc {
 
+// This file's names of the tile constants, which the host-side guards of the tests read from here; the shared helpers
+// are written against those of conv_bwd_common.h, so the two sets must agree.
 constexpr int kCbPx = 64;           // pixels (GEMM rows) per block: 16 per wave, 4 waves
 constexpr int kCbKC = 32;           // K values staged per step
 constexpr int kCbLd = kCbKC + 4;    // LDS row of a staged tile: 16-byte rows, 4 banks apart
@@ -33,6 +38,9 @@ constexpr int kCbWBlocks = 1024;    // workgroups of conv_bwd_w_kernel, shared b
 constexpr int kCbWTile = 64;        // at most this many C_out x C_in per workgroup of conv_bwd_w_kernel
 constexpr int kCbWPad = 20;         // LDS row padding of its pixel-major tiles
 constexpr int kCbRedLanes = 16;     // lanes that share one output of conv_bwd_reduce_kernel
+static_assert(kCbPx == kCgPx && kCbKC == kCgKC && kCbLd == kCgLd && kCbWTile == kCgWTile && kCbWPad == kCgWPad &&
+                  kCbRedLanes == kCgRedLanes,
+              "the tile constants differ from those of conv_bwd_common.h");
 
 struct CbGeo {
     int H, W, Ho, Wo;    // input and output extent
@@ -47,8 +55,6 @@ enum { kCbStoreZ = 0, kCbStoreMish = 1, kCbStoreGz = 2 };
 // mode 1 (X): row = input pixel (n, iy, ix) of parity class blockIdx.z; A = gz at ((iy + pt - ky) / s, (ix + pl - kx) / s)
 //             over the taps where both are whole; K = cout; N = cin; B = w[t][k][n].
 // Workgroup = 64 rows x 16 NT columns (blockIdx.y); wave w owns rows 16 w .. 16 w + 15 and NT accumulators.
-// v_mfma_f32_16x16x4_f32: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; D register r of lane l
-// is row (l >> 4) * 4 + r, column l & 15.
 template <int NT>
 __global__ __launch_bounds__(256) void conv_bwd_gemm_kernel(const float* __restrict__ src, const float* __restrict__ w,
                                                             const float* __restrict__ bias,
@@ -73,25 +79,17 @@ __global__ __launch_bounds__(256) void conv_bwd_gemm_kernel(const float* __restr
     const int Hs = mode ? g.Ho : g.H, Ws = mode ? g.Wo : g.W;
     const int kc = K < kCbKC ? K : kCbKC, kq = kc >> 2;
     if (tid < kCbPx) {
-        const int64_t p = p0 + tid;
-        int n = -1, y = 0, x = 0;
-        if (p < Mr) {
-            x = (int)(p % Wr);
-            const int64_t q = p / Wr;
-            y = (int)(q % Hr);
-            n = (int)(q / Hr);
-            if (mode) {
-                y = y * g.s + cy;
-                x = x * g.s + cx;
-            }
+        int n, y, x;
+        cg_row_decode(p0 + tid, Mr, Hr, Wr, n, y, x);
+        if (mode && n >= 0) {
+            y = y * g.s + cy;
+            x = x * g.s + cx;
         }
         row_n[tid] = n;
         row_y[tid] = y;
         row_x[tid] = x;
     }
-    f32x4v acc[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[n] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4v acc[NT] = {};
     for (int ky = 0; ky < 3; ++ky)
         for (int kx = 0; kx < 3; ++kx) {
             // stride 2 gather: only the taps whose source row and column are whole
@@ -128,30 +126,9 @@ __global__ __launch_bounds__(256) void conv_bwd_gemm_kernel(const float* __restr
                     }
                     *reinterpret_cast<float4*>(&a_s[r * kCbLd + q * 4]) = v;
                 }
-                if (mode == 0) {  // b_s[j][k] = w[t][j0 + j][k0 + k], rows of w
-                    for (int i = tid; i < NB * kq; i += 256) {
-                        const int j = i / kq, q = i - j * kq;
-                        *reinterpret_cast<float4*>(&b_s[j * kCbLd + q * 4]) =
-                            ldg_f4(wt + (int64_t)(j0 + j) * g.cp + k0 + q * 4);
-                    }
-                } else {  // b_s[j][k] = w[t][k0 + k][j0 + j], columns of w; columns past cp are 0
-                    for (int i = tid; i < kc * (NB / 4); i += 256) {
-                        const int k = i / (NB / 4), j4 = (i % (NB / 4)) * 4;
-                        const float4 v = j0 + j4 < g.cp ? ldg_f4(wt + (int64_t)(k0 + k) * g.cp + j0 + j4)
-                                                        : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                        b_s[(j4 + 0) * kCbLd + k] = v.x;
-                        b_s[(j4 + 1) * kCbLd + k] = v.y;
-                        b_s[(j4 + 2) * kCbLd + k] = v.z;
-                        b_s[(j4 + 3) * kCbLd + k] = v.w;
-                    }
-                }
+                cg_stage_b<NB, true>(b_s, wt, g.cp, g.cp, j0, k0, kc, mode != 0, tid);  // mode 1: the N columns past cp are 0
                 __syncthreads();
-                for (int kk = 0; kk < kc; kk += 4) {
-                    const float a = a_s[(wave * 16 + li) * kCbLd + kk + lk];
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-                        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b_s[(n * 16 + li) * kCbLd + kk + lk], acc[n], 0, 0, 0);
-                }
+                cg_gemm_step<NT>(acc, a_s, b_s, kc, tid);
             }
         }
 #pragma unroll
@@ -177,8 +154,8 @@ __global__ __launch_bounds__(256) void conv_bwd_gemm_kernel(const float* __restr
 // ---- stage W: partial grad_w[t] = gz^T x_shifted(t), partial grad_b ---------------------------------------------------
 // grid (K-splits, C_out blocks x C_in blocks, taps).  A workgroup walks its pixel blocks in grid-stride order; wave w
 // owns pixels 16 w .. 16 w + 15 of a block (its K) and all NO x NI tiles, whose accumulators live across the walk (two
-// per tile, over alternate K steps, when the workgroup has one tile only).  At the end the four waves' tiles are added
-// in wave order through LDS.
+// per tile, over alternate K steps, when the workgroup has one tile only, added up at the end).  At the end the four
+// waves' tiles are added in wave order through LDS.
 template <int NO, int NI>
 __global__ __launch_bounds__(256) void conv_bwd_w_kernel(const float* __restrict__ gz, const float* __restrict__ x,
                                                          float* __restrict__ part_w, float* __restrict__ part_b,
@@ -189,18 +166,11 @@ __global__ __launch_bounds__(256) void conv_bwd_w_kernel(const float* __restrict
     constexpr int NS = NO * NI == 1 ? 2 : 1;
     __shared__ __attribute__((aligned(16))) float gz_s[kCbPx * SG];
     __shared__ __attribute__((aligned(16))) float x_s[kCbPx * SX];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int li = lane & 15, lk = lane >> 4;
+    const int tid = threadIdx.x;
     const int o0 = ((int)blockIdx.y / n_ib) * OB, i0 = ((int)blockIdx.y % n_ib) * IB;
     const int tap = blockIdx.z, ky = tap / 3, kx = tap % 3;
     const bool do_b = need_b && tap == 0 && i0 == 0;
-    f32x4v acc[NO][NI][NS];
-#pragma unroll
-    for (int n = 0; n < NO; ++n)
-#pragma unroll
-        for (int m = 0; m < NI; ++m)
-#pragma unroll
-            for (int h = 0; h < NS; ++h) acc[n][m][h] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4v acc[NS][NO][NI] = {};
     float bsum = 0.0f;
     for (int64_t pb = blockIdx.x; pb < n_pb; pb += gridDim.x) {
         const int64_t p0 = pb * kCbPx;
@@ -237,66 +207,21 @@ __global__ __launch_bounds__(256) void conv_bwd_w_kernel(const float* __restrict
                 *reinterpret_cast<float4*>(&x_s[r * SX + q * 4]) = v;
             }
         __syncthreads();
-        if (need_w) {
-#pragma unroll
-            for (int k = 0; k < 16; k += 4) {
-                const int row = wave * 16 + k + lk;
-                float a[NO], b[NI];
-#pragma unroll
-                for (int n = 0; n < NO; ++n) a[n] = gz_s[row * SG + n * 16 + li];
-#pragma unroll
-                for (int m = 0; m < NI; ++m) b[m] = x_s[row * SX + m * 16 + li];
-#pragma unroll
-                for (int n = 0; n < NO; ++n)
-#pragma unroll
-                    for (int m = 0; m < NI; ++m)
-                        acc[n][m][(k >> 2) % NS] =
-                            __builtin_amdgcn_mfma_f32_16x16x4f32(a[n], b[m], acc[n][m][(k >> 2) % NS], 0, 0, 0);
-            }
-        }
+        if (need_w) cg_w_mfma<NO, NI>(acc[0], acc[NS - 1], gz_s, x_s, tid);
         if (do_b)  // thread = (column, row group): 256 / OB groups of rows, each in row order
             for (int r = tid / OB; r < kCbPx; r += 256 / OB) bsum += gz_s[r * SG + tid % OB];
     }
     if (need_w) {
-        float* red = gz_s;  // OB x IB floats, smaller than the gz tile
-        for (int wv = 0; wv < 4; ++wv) {
-            __syncthreads();
-            if (wave == wv) {
-#pragma unroll
-                for (int n = 0; n < NO; ++n)
-#pragma unroll
-                    for (int m = 0; m < NI; ++m)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int i = (n * 16 + lk * 4 + r) * IB + m * 16 + li;
-                            float v = acc[n][m][0][r];
-                            if (NS == 2) v += acc[n][m][NS - 1][r];
-                            red[i] = wv == 0 ? v : red[i] + v;
-                        }
-            }
-        }
-        __syncthreads();
-        const int64_t base = ((int64_t)blockIdx.x * 9 + tap) * g.cout;
-        for (int i = tid; i < OB * IB; i += 256) {
-            const int o = i / IB, c = i % IB;
-            if (i0 + c < g.cp) part_w[(base + o0 + o) * g.cp + i0 + c] = red[i];
-        }
+        if (NS == 2) acc[0][0][0] += acc[NS - 1][0][0];
+        // red = gz_s: OB x IB floats, smaller than the gz tile
+        cg_tile_sum<NO, NI>(acc[0], gz_s, part_w, ((int64_t)blockIdx.x * 9 + tap) * g.cout + o0, g.cp, i0, g.cp, tid);
     }
-    if (do_b) {
-        __syncthreads();  // red is read
-        x_s[tid] = bsum;
-        __syncthreads();
-        if (tid < OB) {
-            float s = x_s[tid];
-            for (int j = 1; j < 256 / OB; ++j) s += x_s[j * OB + tid];
-            part_b[(int64_t)blockIdx.x * g.cout + o0 + tid] = s;
-        }
-    }
+    if (do_b) cg_bias_sum<OB>(bsum, x_s, part_b + (int64_t)blockIdx.x * g.cout + o0, tid);
 }
 
 // ---- stage R: out[i] = sum over the workgroups' partials ----------------------------------------------------------------
 // 16 outputs per workgroup, 16 lanes per output: lane j adds partials j, j + 16, ... in order, then a fixed binary tree
-// over the lanes.  The order depends on n_part only.
+// over the lanes.  The order depends on n_part only.  The one reduce kernel of the convolution backward passes.
 __global__ __launch_bounds__(256) void conv_bwd_reduce_kernel(const float* __restrict__ part, float* __restrict__ out,
                                                               int n_out, int n_part) {
     __shared__ float red[kCbRedLanes * 16];
@@ -317,8 +242,8 @@ __global__ __launch_bounds__(256) void conv_bwd_reduce_kernel(const float* __res
 struct CbPlan {
     CbGeo g;
     int64_t M_out, M_in, n_pb;
-    int w_ob, w_ib, n_ob, n_ib, nsplit;      // stage W: tile, blocks, K-splits
-    int64_t off_gz, off_pw, off_pb, total;   // workspace offsets, in floats, 16-byte aligned
+    int w_ob, w_ib, n_ob, n_ib;   // stage W: tile, blocks
+    CgSplit k;                    // its K-splits and the workspace
 };
 
 static CbPlan cb_plan(int B, int H, int W, int cin, int cout, int s) {
@@ -337,18 +262,12 @@ static CbPlan cb_plan(int B, int H, int W, int cin, int cout, int s) {
     p.w_ib = ci16 < kCbWTile ? ci16 : kCbWTile;
     p.n_ob = cout / p.w_ob;
     p.n_ib = ci16 / p.w_ib;
-    const int cap = kCbWBlocks / (9 * p.n_ob * p.n_ib) > 0 ? kCbWBlocks / (9 * p.n_ob * p.n_ib) : 1;
-    p.nsplit = (int)(p.n_pb < cap ? p.n_pb : cap);
-    auto up4 = [](int64_t n) { return (n + 3) / 4 * 4; };
-    p.off_gz = 0;
-    p.off_pw = p.off_gz + p.M_out * cout;
-    p.off_pb = p.off_pw + (int64_t)p.nsplit * 9 * cout * g.cp;
-    p.total = p.off_pb + up4((int64_t)p.nsplit * cout);
+    p.k = cg_split(p.n_pb, kCbWBlocks, 9, p.n_ob * p.n_ib, p.M_out * cout, (int64_t)9 * cout * g.cp, cout);
     return p;
 }
 
 int64_t conv3x3_same_bwd_workspace_floats(int B, int H, int W, int cin, int cout, int s) {
-    return cb_plan(B, H, W, cin, cout, s).total;
+    return cb_plan(B, H, W, cin, cout, s).k.total;
 }
 
 // whether the launch grids of a shape fit: one workgroup per 64 rows in stages Z and X
@@ -369,16 +288,14 @@ static int cb_gemm(const CbPlan& p, int B, const float* src, const float* w, con
         gz = (unsigned)(g.s * g.s);
     }
     const dim3 grid((unsigned)((rows + kCbPx - 1) / kCbPx), (unsigned)(N / (16 * nt)), gz);
-#define QPWC_CB_GEMM(NT) \
-    hipLaunchKernelGGL((conv_bwd_gemm_kernel<NT>), grid, dim3(256), 0, s, src, w, bias, gout, dst, g, B, mode, epi)
-    if (nt == 1) QPWC_CB_GEMM(1);
-    else if (nt == 2) QPWC_CB_GEMM(2);
-    else QPWC_CB_GEMM(4);
-#undef QPWC_CB_GEMM
+    cg_tiles(nt, [&](auto NT) {
+        hipLaunchKernelGGL((conv_bwd_gemm_kernel<decltype(NT)::value>), grid, dim3(256), 0, s, src, w, bias, gout, dst, g,
+                           B, mode, epi);
+    });
     return check_launch("conv_bwd_gemm_kernel");
 }
 
-static int cb_reduce(const float* part, float* out, int64_t n_out, int n_part, hipStream_t s) {
+int conv_bwd_reduce_launch(const float* part, float* out, int64_t n_out, int n_part, hipStream_t s) {
     hipLaunchKernelGGL(conv_bwd_reduce_kernel, dim3((unsigned)((n_out + 15) / 16)), dim3(256), 0, s, part, out,
                        (int)n_out, n_part);
     return check_launch("conv_bwd_reduce_kernel");
@@ -396,7 +313,7 @@ int conv3x3_same_bwd_launch(const void* x, const void* w, const void* bias, cons
                             hipStream_t s) {
     const CbPlan p = cb_plan(B, H, W, cin, cout, stride);
     float* wsf = (float*)ws;
-    float *gz_ws = wsf + p.off_gz, *part_w = wsf + p.off_pw, *part_b = wsf + p.off_pb;
+    float *gz_ws = wsf + p.k.off_gz, *part_w = wsf + p.k.off_pw, *part_b = wsf + p.k.off_pb;
     const float* gz = (const float*)gout;
     int rc;
     if (mish) {  // stage Z
@@ -408,25 +325,18 @@ int conv3x3_same_bwd_launch(const void* x, const void* w, const void* bias, cons
     if (gx && (rc = cb_gemm(p, B, gz, (const float*)w, nullptr, nullptr, (float*)gx, 1, 0, s))) return rc;  // stage X
     if (gw || gb) {  // stage W; only grad_b: the tap-0 workgroups of one C_in block
         const int n_ib = gw ? p.n_ib : 1;
-        const dim3 grid((unsigned)p.nsplit, (unsigned)(p.n_ob * n_ib), gw ? 9u : 1u);
-#define QPWC_CB_W(NO, NI)                                                                                              \
-    hipLaunchKernelGGL((conv_bwd_w_kernel<NO, NI>), grid, dim3(256), 0, s, gz, (const float*)x, part_w, part_b, p.g,  \
-                       p.M_out, p.n_pb, n_ib, (int)(gw != nullptr), (int)(gb != nullptr))
-        const int no = p.w_ob / 16, ni = p.w_ib / 16;
-        if (no == 1 && ni == 1) QPWC_CB_W(1, 1);
-        else if (no == 1 && ni == 2) QPWC_CB_W(1, 2);
-        else if (no == 1) QPWC_CB_W(1, 4);
-        else if (no == 2 && ni == 1) QPWC_CB_W(2, 1);
-        else if (no == 2 && ni == 2) QPWC_CB_W(2, 2);
-        else if (no == 2) QPWC_CB_W(2, 4);
-        else if (ni == 1) QPWC_CB_W(4, 1);
-        else if (ni == 2) QPWC_CB_W(4, 2);
-        else QPWC_CB_W(4, 4);
-#undef QPWC_CB_W
+        const dim3 grid((unsigned)p.k.nsplit, (unsigned)(p.n_ob * n_ib), gw ? 9u : 1u);
+        cg_tiles(p.w_ob / 16, [&](auto NO) {
+            cg_tiles(p.w_ib / 16, [&](auto NI) {
+                hipLaunchKernelGGL((conv_bwd_w_kernel<decltype(NO)::value, decltype(NI)::value>), grid, dim3(256), 0, s,
+                                   gz, (const float*)x, part_w, part_b, p.g, p.M_out, p.n_pb, n_ib, (int)(gw != nullptr),
+                                   (int)(gb != nullptr));
+            });
+        });
         if ((rc = check_launch("conv_bwd_w_kernel"))) return rc;
         // stage R
-        if (gw && (rc = cb_reduce(part_w, (float*)gw, (int64_t)9 * cout * p.g.cp, p.nsplit, s))) return rc;
-        if (gb && (rc = cb_reduce(part_b, (float*)gb, cout, p.nsplit, s))) return rc;
+        if (gw && (rc = conv_bwd_reduce_launch(part_w, (float*)gw, (int64_t)9 * cout * p.g.cp, p.k.nsplit, s))) return rc;
+        if (gb && (rc = conv_bwd_reduce_launch(part_b, (float*)gb, cout, p.k.nsplit, s))) return rc;
     }
     return QPWC_OK;
 }

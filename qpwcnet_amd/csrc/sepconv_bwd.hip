@@ -25,7 +25,7 @@
 // Determinism: every output element is a gather with a fixed summation order; the weight gradients are a two-stage
 // reduction (per workgroup: pixel blocks in grid-stride order, waves 0..3 / slots 0..7 in order; then stage D over the
 // workgroups in order).  No atomics.  A pixel's gz, gd and grad_x depend on its own image only.
-#include "optflow_common.h"
+#include "conv_bwd_common.h"
 
 namespace qpwc {
 
@@ -153,7 +153,8 @@ __global__ __launch_bounds__(256) void sepconv_bwd_gz_kernel(const float* __rest
 // ---- stage B2: gd = gz pw, partial grad_pw = gz^T d, partial grad_bias ---------------------------------------------
 // grid (pixel-block groups, 32-channel chunks).  A workgroup walks its pixel blocks in grid-stride order; wave w owns
 // pixels 16 w .. 16 w + 15 of a block: two gd tiles (K = F) and 2 F / 16 grad_pw tiles (K = its 16 pixels), whose
-// accumulators live across the walk.  At the end the four waves' grad_pw tiles are added in wave order through LDS.
+// accumulators live across the walk.  At the end the four waves' grad_pw tiles are added in wave order through LDS
+// (cg_tile_sum of conv_bwd_common.h, shared with the convolution backward passes).
 template <int F>
 __global__ __launch_bounds__(256) void sepconv_bwd_pw_kernel(const float* __restrict__ gz, const float* __restrict__ d,
                                                              const float* __restrict__ pw, float* __restrict__ gd,
@@ -228,26 +229,8 @@ __global__ __launch_bounds__(256) void sepconv_bwd_pw_kernel(const float* __rest
         if (do_b)
             for (int r = 0; r < kScbPx; ++r) bsum += gz_s[r * SG + tid];
     }
-    if (need_pw) {
-        float* red = gz_s;  // F x 32 floats, smaller than the gz tile
-        for (int w = 0; w < 4; ++w) {
-            __syncthreads();
-            if (wave == w) {
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int i = (n * 16 + lk * 4 + r) * kScKC + h * 16 + li;
-                            red[i] = w == 0 ? accw[n][h][r] : red[i] + accw[n][h][r];
-                        }
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < F * kScKC; i += 256)
-            part_pw[((int64_t)blockIdx.x * F + (i >> 5)) * cpad + c0 + (i & 31)] = red[i];
-    }
+    if (need_pw)  // red = gz_s: F x 32 floats, smaller than the gz tile; every column of the chunk lies within cpad
+        cg_tile_sum<NT, kScKC / 16>(accw, gz_s, part_pw, (int64_t)blockIdx.x * F, cpad, c0, cpad, tid);
     if (do_b) part_b[(int64_t)blockIdx.x * F + tid] = bsum;
 }
 

@@ -20,23 +20,31 @@
 //                                       across the workgroup's input-pixel blocks (grid-stride), one partial per
 //                                       workgroup; the tap-0 workgroups of the first C block also sum gz over the
 //                                       2 x 2 output pixels under each of their input pixels for grad_b
-//   R  upconv_bwd_reduce_kernel         partials summed per output: 16 lanes stride over the workgroups, then a fixed tree
+//   R  conv_bwd_reduce_kernel           partials summed per output: 16 lanes stride over the workgroups, then a fixed tree
+//                                       (the kernel of conv_bwd.hip, through conv_bwd_reduce_launch)
+// The lane layout of the matrix instruction, the B staging, the wave-order tile sum, the grad_b finish and the K-split
+// plan are those of conv_bwd_common.h, shared with conv_bwd.hip.
 //
 // Determinism: every output element is a sum in a fixed order; no atomics; grids and the number of K-splits depend on the
 // shape only; what is asked for is a kernel argument and changes no arithmetic of the other outputs.  A row of the
 // GEMMs (a pixel of gz / grad_x) is accumulated independently of every other row: grad_x of an image does not depend
 // on the rest of the batch.  Pixel offsets are 64-bit.
-#include "optflow_common.h"
+#include "conv_bwd_common.h"
 
 namespace qpwc {
 
+// This file's names of the tile constants, which the host-side guards of the tests read from here; the shared helpers
+// are written against those of conv_bwd_common.h, so the two sets must agree.
 constexpr int kUbPx = 64;           // pixels (GEMM rows) per block: 16 per wave, 4 waves
 constexpr int kUbKC = 32;           // K values staged per step
 constexpr int kUbLd = kUbKC + 4;    // LDS row of a staged tile: 16-byte rows, 4 banks apart
 constexpr int kUbWBlocks = 960;     // workgroups of upconv_bwd_w_kernel, shared between the K-splits, the blocks and the 16 taps
 constexpr int kUbWTile = 64;        // at most this many F x C per workgroup of upconv_bwd_w_kernel
 constexpr int kUbWPad = 20;         // LDS row padding of its pixel-major tiles
-constexpr int kUbRedLanes = 16;     // lanes that share one output of upconv_bwd_reduce_kernel
+constexpr int kUbRedLanes = 16;     // lanes that share one output of stage R (conv_bwd_reduce_kernel of conv_bwd.hip)
+static_assert(kUbPx == kCgPx && kUbKC == kCgKC && kUbLd == kCgLd && kUbWTile == kCgWTile && kUbWPad == kCgWPad &&
+                  kUbRedLanes == kCgRedLanes,
+              "the tile constants differ from those of conv_bwd_common.h");
 
 struct UbGeo {
     int H, W;       // input extent; the output is 2H x 2W
@@ -50,8 +58,6 @@ struct UbGeo {
 //             N = F; B = w[t][n][k].
 // mode 1 (X): row = input pixel (n, iy, ix); A = gz at (2 iy - 1 + ky, 2 ix - 1 + kx); K = F; N = C; B = w[t][k][n].
 // Workgroup = 64 rows x 16 NT columns (blockIdx.y); wave w owns rows 16 w .. 16 w + 15 and NT accumulators.
-// v_mfma_f32_16x16x4_f32: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; D register r of lane l
-// is row (l >> 4) * 4 + r, column l & 15.
 template <int NT>
 __global__ __launch_bounds__(256) void upconv_bwd_gemm_kernel(const float* __restrict__ src, const float* __restrict__ w,
                                                               const float* __restrict__ bias,
@@ -72,21 +78,13 @@ __global__ __launch_bounds__(256) void upconv_bwd_gemm_kernel(const float* __res
     const int Hs = mode ? 2 * g.H : g.H, Ws = mode ? 2 * g.W : g.W;
     const int kc = K < kUbKC ? K : kUbKC, kq = kc >> 2;
     if (tid < kUbPx) {
-        const int64_t p = p0 + tid;
-        int n = -1, y = 0, x = 0;
-        if (p < Mr) {
-            x = (int)(p % g.W);
-            const int64_t q = p / g.W;
-            y = (int)(q % g.H);
-            n = (int)(q / g.H);
-        }
+        int n, y, x;
+        cg_row_decode(p0 + tid, Mr, g.H, g.W, n, y, x);
         row_n[tid] = n;
         row_y[tid] = y;
         row_x[tid] = x;
     }
-    f32x4v acc[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[n] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4v acc[NT] = {};
     for (int ky = 0; ky < 4; ++ky)
         for (int kx = 0; kx < 4; ++kx) {
             // an output pixel of parity (py, px) meets the taps of the other parity only
@@ -105,29 +103,9 @@ __global__ __launch_bounds__(256) void upconv_bwd_gemm_kernel(const float* __res
                         v = ldg_f4(src + (((int64_t)n * Hs + sy) * Ws + sx) * ssrc + k0 + q * 4);
                     *reinterpret_cast<float4*>(&a_s[r * kUbLd + q * 4]) = v;
                 }
-                if (mode == 0) {  // b_s[j][k] = w[t][j0 + j][k0 + k], rows of w
-                    for (int i = tid; i < NB * kq; i += 256) {
-                        const int j = i / kq, q = i - j * kq;
-                        *reinterpret_cast<float4*>(&b_s[j * kUbLd + q * 4]) =
-                            ldg_f4(wt + (int64_t)(j0 + j) * g.C + k0 + q * 4);
-                    }
-                } else {  // b_s[j][k] = w[t][k0 + k][j0 + j], columns of w
-                    for (int i = tid; i < kc * (NB / 4); i += 256) {
-                        const int k = i / (NB / 4), j4 = (i % (NB / 4)) * 4;
-                        const float4 v = ldg_f4(wt + (int64_t)(k0 + k) * g.C + j0 + j4);
-                        b_s[(j4 + 0) * kUbLd + k] = v.x;
-                        b_s[(j4 + 1) * kUbLd + k] = v.y;
-                        b_s[(j4 + 2) * kUbLd + k] = v.z;
-                        b_s[(j4 + 3) * kUbLd + k] = v.w;
-                    }
-                }
+                cg_stage_b<NB, false>(b_s, wt, g.C, g.C, j0, k0, kc, mode != 0, tid);  // every N column lies within C
                 __syncthreads();
-                for (int kk = 0; kk < kc; kk += 4) {
-                    const float a = a_s[(wave * 16 + li) * kUbLd + kk + lk];
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-                        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b_s[(n * 16 + li) * kUbLd + kk + lk], acc[n], 0, 0, 0);
-                }
+                cg_gemm_step<NT>(acc, a_s, b_s, kc, tid);
             }
         }
 #pragma unroll
@@ -162,17 +140,12 @@ __global__ __launch_bounds__(256) void upconv_bwd_w_kernel(const float* __restri
     constexpr int SG = OB + kUbWPad, SX = IB + kUbWPad;
     __shared__ __attribute__((aligned(16))) float gz_s[kUbPx * SG];
     __shared__ __attribute__((aligned(16))) float x_s[kUbPx * SX];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int li = lane & 15, lk = lane >> 4;
+    const int tid = threadIdx.x;
     const int o0 = ((int)blockIdx.y / n_ib) * OB, i0 = ((int)blockIdx.y % n_ib) * IB;
     const int tap = blockIdx.z, ky = tap >> 2, kx = tap & 3;
     const bool do_b = need_b && tap == 0 && i0 == 0;
     const int Ho = 2 * g.H, Wo = 2 * g.W;
-    f32x4v acc[NO][NI];
-#pragma unroll
-    for (int n = 0; n < NO; ++n)
-#pragma unroll
-        for (int m = 0; m < NI; ++m) acc[n][m] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4v acc[NO][NI] = {};
     float bsum = 0.0f;
     for (int64_t pb = blockIdx.x; pb < n_pb; pb += gridDim.x) {
         const int64_t p0 = pb * kUbPx;
@@ -200,20 +173,7 @@ __global__ __launch_bounds__(256) void upconv_bwd_w_kernel(const float* __restri
                 *reinterpret_cast<float4*>(&x_s[r * SX + q * 4]) = v;
             }
             __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 16; k += 4) {
-                const int row = wave * 16 + k + lk;
-                float a[NO], b[NI];
-#pragma unroll
-                for (int n = 0; n < NO; ++n) a[n] = gz_s[row * SG + n * 16 + li];
-#pragma unroll
-                for (int m = 0; m < NI; ++m) b[m] = x_s[row * SX + m * 16 + li];
-#pragma unroll
-                for (int n = 0; n < NO; ++n)
-#pragma unroll
-                    for (int m = 0; m < NI; ++m)
-                        acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[n], b[m], acc[n][m], 0, 0, 0);
-            }
+            cg_w_mfma<NO, NI>(acc, acc, gz_s, x_s, tid);
         }
         if (do_b)  // thread = (column, row group): 256 / OB groups of rows, each in row order
             for (int r = tid / OB; r < kUbPx; r += 256 / OB) {
@@ -227,65 +187,16 @@ __global__ __launch_bounds__(256) void upconv_bwd_w_kernel(const float* __restri
                 bsum += (ldg_f1(q) + ldg_f1(q + g.gs)) + (ldg_f1(q + Wo * g.gs) + ldg_f1(q + (Wo + 1) * g.gs));
             }
     }
-    if (need_w) {
-        float* red = gz_s;  // OB x IB floats, no larger than the gz tile
-        for (int wv = 0; wv < 4; ++wv) {
-            __syncthreads();
-            if (wave == wv) {
-#pragma unroll
-                for (int n = 0; n < NO; ++n)
-#pragma unroll
-                    for (int m = 0; m < NI; ++m)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int i = (n * 16 + lk * 4 + r) * IB + m * 16 + li;
-                            red[i] = wv == 0 ? acc[n][m][r] : red[i] + acc[n][m][r];
-                        }
-            }
-        }
-        __syncthreads();
-        const int64_t base = ((int64_t)blockIdx.x * 16 + tap) * g.F;
-        for (int i = tid; i < OB * IB; i += 256) {
-            const int o = i / IB, c = i % IB;
-            part_w[(base + o0 + o) * g.C + i0 + c] = red[i];
-        }
-    }
-    if (do_b) {
-        __syncthreads();  // red is read
-        x_s[tid] = bsum;
-        __syncthreads();
-        if (tid < OB) {
-            float s = x_s[tid];
-            for (int j = 1; j < 256 / OB; ++j) s += x_s[j * OB + tid];
-            part_b[(int64_t)blockIdx.x * g.F + o0 + tid] = s;
-        }
-    }
-}
-
-// ---- stage R: out[i] = sum over the workgroups' partials ----------------------------------------------------------------
-// 16 outputs per workgroup, 16 lanes per output: lane j adds partials j, j + 16, ... in order, then a fixed binary tree
-// over the lanes.  The order depends on n_part only.
-__global__ __launch_bounds__(256) void upconv_bwd_reduce_kernel(const float* __restrict__ part, float* __restrict__ out,
-                                                                int n_out, int n_part) {
-    __shared__ float red[kUbRedLanes * 16];
-    const int tid = threadIdx.x, o = tid & 15, lane = tid >> 4;
-    const int i = blockIdx.x * 16 + o;
-    float s = 0.0f;
-    if (i < n_out)
-        for (int p = lane; p < n_part; p += kUbRedLanes) s += part[(int64_t)p * n_out + i];
-    red[lane * 16 + o] = s;
-    for (int h = kUbRedLanes / 2; h > 0; h >>= 1) {
-        __syncthreads();
-        if (lane < h) red[lane * 16 + o] += red[(lane + h) * 16 + o];
-    }
-    if (lane == 0 && i < n_out) out[i] = red[o];
+    if (need_w)  // red = gz_s: OB x IB floats, no larger than the gz tile
+        cg_tile_sum<NO, NI>(acc, gz_s, part_w, ((int64_t)blockIdx.x * 16 + tap) * g.F + o0, g.C, i0, g.C, tid);
+    if (do_b) cg_bias_sum<OB>(bsum, x_s, part_b + (int64_t)blockIdx.x * g.F + o0, tid);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 struct UbPlan {
     int64_t M_in, M_out, n_pb;
-    int w_ob, n_ob, n_ib, nsplit;            // stage W: F tile, blocks, K-splits (the C tile is kUbWTile)
-    int64_t off_gz, off_pw, off_pb, total;   // workspace offsets, in floats, 16-byte aligned
+    int w_ob, n_ob, n_ib;   // stage W: F tile, blocks (the C tile is kUbWTile)
+    CgSplit k;              // its K-splits and the workspace
 };
 
 static UbPlan ub_plan(int B, int H, int W, int C, int F) {
@@ -296,17 +207,11 @@ static UbPlan ub_plan(int B, int H, int W, int C, int F) {
     p.w_ob = F < kUbWTile ? F : kUbWTile;
     p.n_ob = F / p.w_ob;
     p.n_ib = C / kUbWTile;
-    const int cap = kUbWBlocks / (16 * p.n_ob * p.n_ib) > 0 ? kUbWBlocks / (16 * p.n_ob * p.n_ib) : 1;
-    p.nsplit = (int)(p.n_pb < cap ? p.n_pb : cap);
-    auto up4 = [](int64_t n) { return (n + 3) / 4 * 4; };
-    p.off_gz = 0;
-    p.off_pw = p.off_gz + p.M_out * F;
-    p.off_pb = p.off_pw + (int64_t)p.nsplit * 16 * F * C;
-    p.total = p.off_pb + up4((int64_t)p.nsplit * F);
+    p.k = cg_split(p.n_pb, kUbWBlocks, 16, p.n_ob * p.n_ib, p.M_out * F, (int64_t)16 * F * C, F);
     return p;
 }
 
-int64_t upconv4x4s2_bwd_workspace_floats(int B, int H, int W, int C, int F) { return ub_plan(B, H, W, C, F).total; }
+int64_t upconv4x4s2_bwd_workspace_floats(int B, int H, int W, int C, int F) { return ub_plan(B, H, W, C, F).k.total; }
 
 // whether the launch grids of a shape fit: one workgroup per 64 rows in stages Z and X
 bool upconv4x4s2_bwd_shape_ok(int B, int H, int W, int C, int F) {
@@ -320,20 +225,11 @@ static int ub_gemm(const UbGeo& g, int B, const float* src, const float* w, cons
     const int nt = N >= 64 ? 4 : N / 16;
     const int64_t rows = (int64_t)B * g.H * g.W;
     const dim3 grid((unsigned)((rows + kUbPx - 1) / kUbPx), (unsigned)(N / (16 * nt)), mode ? 1u : 4u);
-#define QPWC_UB_GEMM(NT)                                                                                               \
-    hipLaunchKernelGGL((upconv_bwd_gemm_kernel<NT>), grid, dim3(256), 0, s, src, w, bias, gout, gout_stride, dst, g, B, \
-                       mode)
-    if (nt == 1) QPWC_UB_GEMM(1);
-    else if (nt == 2) QPWC_UB_GEMM(2);
-    else QPWC_UB_GEMM(4);
-#undef QPWC_UB_GEMM
+    cg_tiles(nt, [&](auto NT) {
+        hipLaunchKernelGGL((upconv_bwd_gemm_kernel<decltype(NT)::value>), grid, dim3(256), 0, s, src, w, bias, gout,
+                           gout_stride, dst, g, B, mode);
+    });
     return check_launch("upconv_bwd_gemm_kernel");
-}
-
-static int ub_reduce(const float* part, float* out, int64_t n_out, int n_part, hipStream_t s) {
-    hipLaunchKernelGGL(upconv_bwd_reduce_kernel, dim3((unsigned)((n_out + 15) / 16)), dim3(256), 0, s, part, out,
-                       (int)n_out, n_part);
-    return check_launch("upconv_bwd_reduce_kernel");
 }
 
 int upconv4x4s2_bwd_launch(const void* x, const void* w, const void* bias, const void* gout, int64_t gout_stride,
@@ -341,7 +237,7 @@ int upconv4x4s2_bwd_launch(const void* x, const void* w, const void* bias, const
                            hipStream_t s) {
     const UbPlan p = ub_plan(B, H, W, C, F);
     float* wsf = (float*)ws;
-    float *gz_ws = wsf + p.off_gz, *part_w = wsf + p.off_pw, *part_b = wsf + p.off_pb;
+    float *gz_ws = wsf + p.k.off_gz, *part_w = wsf + p.k.off_pw, *part_b = wsf + p.k.off_pb;
     UbGeo g;
     g.H = H, g.W = W, g.C = C, g.F = F;
     g.gs = gout_stride;
@@ -357,19 +253,16 @@ int upconv4x4s2_bwd_launch(const void* x, const void* w, const void* bias, const
     if (gx && (rc = ub_gemm(g, B, gz, (const float*)w, nullptr, nullptr, 0, (float*)gx, 1, s))) return rc;  // stage X
     if (gw || gb) {  // stage W; only grad_b: the tap-0 workgroups of one C block
         const int n_ib = gw ? p.n_ib : 1;
-        const dim3 grid((unsigned)p.nsplit, (unsigned)(p.n_ob * n_ib), gw ? 16u : 1u);
-#define QPWC_UB_W(NO)                                                                                                  \
-    hipLaunchKernelGGL((upconv_bwd_w_kernel<NO, kUbWTile / 16>), grid, dim3(256), 0, s, gz, (const float*)x, part_w,  \
-                       part_b, g, p.M_in, p.n_pb, n_ib, (int)(gw != nullptr), (int)(gb != nullptr))
-        const int no = p.w_ob / 16;
-        if (no == 1) QPWC_UB_W(1);
-        else if (no == 2) QPWC_UB_W(2);
-        else QPWC_UB_W(4);
-#undef QPWC_UB_W
+        const dim3 grid((unsigned)p.k.nsplit, (unsigned)(p.n_ob * n_ib), gw ? 16u : 1u);
+        cg_tiles(p.w_ob / 16, [&](auto NO) {
+            hipLaunchKernelGGL((upconv_bwd_w_kernel<decltype(NO)::value, kUbWTile / 16>), grid, dim3(256), 0, s, gz,
+                               (const float*)x, part_w, part_b, g, p.M_in, p.n_pb, n_ib, (int)(gw != nullptr),
+                               (int)(gb != nullptr));
+        });
         if ((rc = check_launch("upconv_bwd_w_kernel"))) return rc;
         // stage R
-        if (gw && (rc = ub_reduce(part_w, (float*)gw, (int64_t)16 * F * C, p.nsplit, s))) return rc;
-        if (gb && (rc = ub_reduce(part_b, (float*)gb, F, p.nsplit, s))) return rc;
+        if (gw && (rc = conv_bwd_reduce_launch(part_w, (float*)gw, (int64_t)16 * F * C, p.k.nsplit, s))) return rc;
+        if (gb && (rc = conv_bwd_reduce_launch(part_b, (float*)gb, F, p.k.nsplit, s))) return rc;
     }
     return QPWC_OK;
 }

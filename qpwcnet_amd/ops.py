@@ -202,6 +202,33 @@ def _refuse_capture(what):
             "forward (torch.no_grad()) or run the training step eagerly".format(what))
 
 
+def _grad_operands_check(x, weight, bias, what):
+    """What the differentiable convolutions ask of their operands: a dense rank-4 channels-last x; x, weight and bias
+    fp32 on a HIP device."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("{}: x must be a rank-4 (B,H,W,C) tensor".format(what))
+    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
+        if not t.is_cuda:
+            raise ValueError("{}: {} is on '{}'; the kernels run on a HIP device only (no CPU fallback)".format(
+                what, name, t.device))
+        if t.dtype == torch.float16:
+            raise ValueError("{}: no fp16 storage path, {} is fp16: train in fp32".format(what, name))
+        if t.dtype != torch.float32:
+            raise ValueError("{}: {} must be fp32, got {}".format(what, name, t.dtype))
+    if not x.is_contiguous():
+        raise ValueError("{}: x must be a dense channels-last tensor".format(what))
+
+
+def _bwd_buffers(nws, shapes, need, dev):
+    """The buffers of a backward launch: the fp32 workspace of nws floats (a negative nws is the library's error code)
+    and one fp32 output per shape that is asked for -> (workspace, outputs with None for the rest, their pointers with
+    None = NULL for the rest)."""
+    _hip.check(min(int(nws), 0))
+    new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    outs = [new(tuple(sh)) if n else None for sh, n in zip(shapes, need)]
+    return new(int(nws)), outs, [t.data_ptr() if t is not None else None for t in outs]
+
+
 def _to_nhwc(t, data_format):
     """Dense (B,H,W,C) form of a layer operand or gradient for the channels-last backward kernels: a channels_first
     tensor that is physically NHWC (torch channels_last memory) through its permuted view, else transposed."""
@@ -657,15 +684,11 @@ def flow_head_bwd(z, params, stats, scale, grad_out, training=False, eps=1e-3,
     if len(need) != 6 or not any(need):
         raise ValueError("need holds six flags (z, w1, b1, gamma, beta, wf), at least one set")
     grad_out = grad_out.contiguous()
-    nws = int(L.qpwc_flow_head_bwd_workspace_floats(B, H, W))
-    _hip.check(min(nws, 0))
-    ws = torch.empty(nws, dtype=torch.float32, device=z.device)
-    shapes = ((B, H, W, 16), (16, 16), (16,), (16,), (16,), (3, 3, 16, 2))
-    outs = [torch.empty(sh, dtype=torch.float32, device=z.device) if n else None for sh, n in zip(shapes, need)]
-    ptr = lambda t: t.data_ptr() if t is not None else None
+    ws, outs, ptrs = _bwd_buffers(L.qpwc_flow_head_bwd_workspace_floats(B, H, W),
+                                  ((B, H, W, 16), (16, 16), (16,), (16,), (16,), (3, 3, 16, 2)), need, z.device)
     with torch.cuda.device(z.device), _timed("flow_head_bwd", (B, H, W, 16)):
         rc = L.qpwc_flow_head_bwd(z.data_ptr(), params.data_ptr(), stats.data_ptr(), float(eps), int(bool(training)),
-                                  float(scale), grad_out.data_ptr(), *[ptr(t) for t in outs], ws.data_ptr(), B, H, W,
+                                  float(scale), grad_out.data_ptr(), *ptrs, ws.data_ptr(), B, H, W,
                                   _stream(z))
     _hip.check(rc)
     return tuple(outs)
@@ -1169,21 +1192,16 @@ def sepconv3x3_bwd(sources, dw, pw_padded, bias, grad_out, mish_on_load=False, m
         raise ValueError("need[0] must hold one flag per source")
     dev = keep[0].device
     L = _hip.lib()
-    nws = int(L.qpwc_sepconv3x3_bwd_workspace_floats(B, H, W, C, F_))
-    _hip.check(min(nws, 0))
-    ws = torch.empty(nws, dtype=torch.float32, device=dev)
-    gs = [torch.empty((B, H, W, t.shape[3]), dtype=torch.float32, device=dev) if n else None
-          for t, n in zip(keep, need_src)]
-    gdw = torch.empty((C, 3, 3), dtype=torch.float32, device=dev) if need_dw else None
-    gpw = torch.empty((F_, cpad), dtype=torch.float32, device=dev) if need_pw else None
-    gb = torch.empty((F_,), dtype=torch.float32, device=dev) if need_b else None
-    g_ptrs = (ctypes.c_void_p * len(keep))(*[g.data_ptr() if g is not None else None for g in gs])
-    ptr = lambda t: t.data_ptr() if t is not None else None
+    ws, outs, ptrs = _bwd_buffers(L.qpwc_sepconv3x3_bwd_workspace_floats(B, H, W, C, F_),
+                                  [(B, H, W, t.shape[3]) for t in keep] + [(C, 3, 3), (F_, cpad), (F_,)],
+                                  tuple(need_src) + (need_dw, need_pw, need_b), dev)
+    gs, (gdw, gpw, gb) = outs[:-3], outs[-3:]
+    g_ptrs = (ctypes.c_void_p * len(keep))(*ptrs[:-3])
     flags = int(bool(mish_on_load)) | (2 if mish_on_store else 0)
     with torch.cuda.device(dev), _timed("sepconv3x3_bwd", (B, H, W, C, F_)):
         rc = L.qpwc_sepconv3x3_bwd(c_ptrs, c_ch, c_st, len(keep), flags, w.data_ptr(), pw_padded.data_ptr(),
-                                   bias.data_ptr(), grad_out.data_ptr(), g_ptrs, ptr(gdw), ptr(gpw), ptr(gb),
-                                   ws.data_ptr(), B, H, W, F_, _stream(grad_out))
+                                   bias.data_ptr(), grad_out.data_ptr(), g_ptrs, *ptrs[-3:], ws.data_ptr(), B, H, W, F_,
+                                   _stream(grad_out))
     _hip.check(rc)
     return gs, gdw, gpw, gb
 
@@ -1358,18 +1376,7 @@ _CONV_SAME_COUT = (16, 32, 64, 128, 256)
 def _conv_same_check(x, weight, bias, stride, what):
     """The operand rules of qpwc_conv3x3_same_fwd / _bwd -> (B, H, W, C_in, C_out, Ho, Wo); weight in the torch layout
     (C_out, C_in, 3, 3) or as its taps (9, C_out, Cp)."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError("{}: x must be a rank-4 (B,H,W,C) tensor".format(what))
-    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
-        if not t.is_cuda:
-            raise ValueError("{}: {} is on '{}'; the kernels run on a HIP device only (no CPU fallback)".format(
-                what, name, t.device))
-        if t.dtype == torch.float16:
-            raise ValueError("{}: no fp16 storage path, {} is fp16: train in fp32".format(what, name))
-        if t.dtype != torch.float32:
-            raise ValueError("{}: {} must be fp32, got {}".format(what, name, t.dtype))
-    if not x.is_contiguous():
-        raise ValueError("{}: x must be a dense channels-last tensor".format(what))
+    _grad_operands_check(x, weight, bias, what)
     if stride not in (1, 2):
         raise ValueError("{}: stride {} not in (1, 2)".format(what, stride))
     B, H, W, ci = x.shape
@@ -1416,19 +1423,13 @@ def conv3x3_same_bwd(x_nhwc, taps, bias, grad_out, stride=1, mish=True, need=(Tr
     grad_out = grad_out.contiguous()
     dev = x_nhwc.device
     L = _hip.lib()
-    nws = int(L.qpwc_conv3x3_same_bwd_workspace_floats(B, H, W, ci, co, int(stride)))
-    _hip.check(min(nws, 0))
-    ws = torch.empty(nws, dtype=torch.float32, device=dev)
-    gx = torch.empty((B, H, W, ci), dtype=torch.float32, device=dev) if need[0] else None
-    gw = torch.empty(tuple(taps.shape), dtype=torch.float32, device=dev) if need[1] else None
-    gb = torch.empty((co,), dtype=torch.float32, device=dev) if need[2] else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
+    ws, outs, ptrs = _bwd_buffers(L.qpwc_conv3x3_same_bwd_workspace_floats(B, H, W, ci, co, int(stride)),
+                                  ((B, H, W, ci), taps.shape, (co,)), need, dev)
     with torch.cuda.device(dev), _timed("conv3x3_same_bwd", (B, H, W, ci, co, stride)):
-        rc = L.qpwc_conv3x3_same_bwd(x_nhwc.data_ptr(), taps.data_ptr(), bias.data_ptr(), grad_out.data_ptr(), ptr(gx),
-                                     ptr(gw), ptr(gb), ws.data_ptr(), B, H, W, ci, co, int(stride), int(bool(mish)),
-                                     _stream(grad_out))
+        rc = L.qpwc_conv3x3_same_bwd(x_nhwc.data_ptr(), taps.data_ptr(), bias.data_ptr(), grad_out.data_ptr(), *ptrs,
+                                     ws.data_ptr(), B, H, W, ci, co, int(stride), int(bool(mish)), _stream(grad_out))
     _hip.check(rc)
-    return gx, gw, gb
+    return tuple(outs)
 
 
 class _ConvSameFn(torch.autograd.Function):
@@ -1669,18 +1670,7 @@ _UPCONV_F = (16, 32, 64, 128)
 def _upconv_check(x, weight, bias, what):
     """The operand rules of the differentiable transposed convolution / qpwc_upconv4x4s2_bwd -> (B, H, W, C, F); weight
     in the torch layout (C, F, 4, 4) or as its taps (16, F, C)."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError("{}: x must be a rank-4 (B,H,W,C) tensor".format(what))
-    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
-        if not t.is_cuda:
-            raise ValueError("{}: {} is on '{}'; the kernels run on a HIP device only (no CPU fallback)".format(
-                what, name, t.device))
-        if t.dtype == torch.float16:
-            raise ValueError("{}: no fp16 storage path, {} is fp16: train in fp32".format(what, name))
-        if t.dtype != torch.float32:
-            raise ValueError("{}: {} must be fp32, got {}".format(what, name, t.dtype))
-    if not x.is_contiguous():
-        raise ValueError("{}: x must be a dense channels-last tensor".format(what))
+    _grad_operands_check(x, weight, bias, what)
     B, H, W, C = x.shape
     taps = weight.dim() == 3
     F_ = weight.shape[1]
@@ -1729,19 +1719,14 @@ def upconv4x4s2_bwd(x_nhwc, taps, bias, grad_out, mish=True, need=(True, True, T
     grad_out = grad_out.contiguous()
     dev = x_nhwc.device
     L = _hip.lib()
-    nws = int(L.qpwc_upconv4x4s2_bwd_workspace_floats(B, H, W, C, F_))
-    _hip.check(min(nws, 0))
-    ws = torch.empty(nws, dtype=torch.float32, device=dev)
-    gx = torch.empty((B, H, W, C), dtype=torch.float32, device=dev) if need[0] else None
-    gw = torch.empty((16, F_, C), dtype=torch.float32, device=dev) if need[1] else None
-    gb = torch.empty((F_,), dtype=torch.float32, device=dev) if need[2] else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
+    ws, outs, ptrs = _bwd_buffers(L.qpwc_upconv4x4s2_bwd_workspace_floats(B, H, W, C, F_),
+                                  ((B, H, W, C), (16, F_, C), (F_,)), need, dev)
     with torch.cuda.device(dev), _timed("upconv4x4s2_bwd", (B, H, W, C, F_)):
         rc = L.qpwc_upconv4x4s2_bwd(x_nhwc.data_ptr(), taps.data_ptr(), bias.data_ptr(), grad_out.data_ptr(),
-                                    grad_out.shape[3], ptr(gx), ptr(gw), ptr(gb), ws.data_ptr(), B, H, W, C, F_,
-                                    int(bool(mish)), _stream(grad_out))
+                                    grad_out.shape[3], *ptrs, ws.data_ptr(), B, H, W, C, F_, int(bool(mish)),
+                                    _stream(grad_out))
     _hip.check(rc)
-    return gx, gw, gb
+    return tuple(outs)
 
 
 class _UpConvFn(torch.autograd.Function):

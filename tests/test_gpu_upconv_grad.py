@@ -24,7 +24,7 @@ from test_gpu_flow_head_grad import flow_mse_v2_composite, optflow_composite, up
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-# (B, H, W, C, F) at which the grid-stride loop of upconv_bwd_w_kernel and the lane loop of upconv_bwd_reduce_kernel make
+# (B, H, W, C, F) at which the grid-stride loop of upconv_bwd_w_kernel and the lane loop of conv_bwd_reduce_kernel make
 # more than one trip with an uneven last one, the last pixel block is partial and the K loops of upconv_bwd_gemm_kernel
 # make two steps (tests/test_upconv_grad_cpu.py checks this against the constants of csrc/upconv_bwd.hip)
 MULTI_TRIP = (2, 37, 53, 64, 16)
