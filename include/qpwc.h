@@ -33,6 +33,7 @@ extern "C" {
 /* storage dtype; arithmetic is always fp32 */
 #define QPWC_F32 0
 #define QPWC_F16 1
+#define QPWC_U8 2 /* source frames of qpwc_augment_fwd only: uint8 0..255 */
 
 /* warp border semantics */
 #define QPWC_WARP_CLAMP 0  /* WarpV2: tfa dense_image_warp, clamp-to-border */
@@ -205,6 +206,48 @@ const char* qpwc_loss_fwd_kernel(int kind, const void* y_true, int B, int H, int
  * grad_losses: n_levels fp32 on the device), stored in pred_dtype[l]. */
 int qpwc_loss_bwd(const void* const* dpred, const void* grad_losses, void* const* grad_pred, const int64_t* n_elems,
                   const int* pred_dtype, int n_levels, void* stream);
+
+/* ---- Training input pipeline (qpwcnet/data/augment.py:83-173 image_flip_ud / image_flip_lr / image_scale_and_crop /
+ * image_resize / image_augment_colors; app/optical_flow/train.py:54-94 preprocess / preprocess_no_op), batched.
+ * ims (B,H,W,6): two RGB frames per sample, channels-last, uint8 (QPWC_U8, taken times float32(1/255)) or fp32
+ * (QPWC_F32, taken as it is); flo (B,H,W,2) fp32 (u, v).  Per sample b, in this order:
+ *   flips       rows reversed and v negated (flip_ud), columns reversed and u negated (flip_lr);
+ *   scale+crop  all 8 channels resized to (rh, rw) with tf.image.resize(BILINEAR) (half-pixel centres, no antialias:
+ *               per axis src = (i + 0.5) * (in / float(out)) - 0.5, lo = max(floor(src), 0), hi = min(ceil(src), in - 1),
+ *               t = src - floor(src), value = a + (b - a) * t, rows after columns; a NaN neighbour poisons the pixel
+ *               even at weight 0), of which only the window [oy, oy + h) x [ox, ox + w) is computed;
+ *   flow        (u, v) * (mu, mv);
+ *   colours     (flag QPWC_AUGMENT_COLOR) on both frames with the same four scalars: x + brightness; HSV saturation *
+ *               saturation, clipped to [0, 1]; HSV hue + hue mod 1 (tf.image.rgb_to_hsv / hsv_to_rgb; no clipping of
+ *               RGB anywhere); (x - mean_c) * contrast + mean_c with mean_c the mean of colour channel c over the h * w
+ *               pixels of BOTH frames (the reference's 'h (w k) c' rearrangement: three means per sample);
+ *   offset      ims - 0.5;   scrub: NaN -> 0 in ims and flo, last (train.py:91-92).  Neither with QPWC_AUGMENT_RAW.
+ * Parameters, in device memory, read by the kernels (no host synchronisation):
+ *   iparams (B,6) int32 : rh, rw, oy, ox, flip_ud, flip_lr       (0 <= oy <= rh - h, 0 <= ox <= rw - w; flips 0 / 1)
+ *   fparams (B,6) fp32  : mu, mv, brightness, saturation, hue, contrast
+ * image_augment: rh, rw = int32(float32(H, W) * float32(scale)), mu = +-scale, mv = +-scale with the flip signs folded
+ * in.  image_resize / preprocess_no_op: rh = h, rw = w, offsets 0, mu = w / W, mv = h / H, flags 0.  Source indices
+ * are clamped into the image whatever the parameters hold; parameters outside the ranges above give unspecified
+ * values, never an access outside the buffers.
+ * out_ims (B,h,w,6) / (B,6,h,w) and out_flo (B,h,w,2) / (B,2,h,w) fp32 by `layout`, written in that layout by the
+ * kernels themselves.  workspace: qpwc_augment_workspace_floats() floats (the contrast partial sums; may be NULL
+ * with flags 0).  One launch with flags 0; with QPWC_AUGMENT_COLOR a second one folds the partial sums in a fixed
+ * order and applies contrast, offset and scrub in place.  No atomics: bitwise reproducible.
+ * Alignment: ims 2 bytes (uint8) / 8 (fp32), flo 8, everything else 4.  Errors: QPWC_E_MODE (unknown flag bits),
+ * QPWC_E_NULL, QPWC_E_DTYPE (ims_dtype), QPWC_E_LAYOUT, QPWC_E_SHAPE (an extent < 1; H * W or 6 * h * w or the number
+ * of 256-pixel workgroups B * ceil(h * w / 256) above 2^31 - 1 -- source offsets themselves are 64-bit), QPWC_E_ALIGN,
+ * QPWC_E_ALIAS (an output or the workspace overlapping an input or another output). */
+#define QPWC_AUGMENT_COLOR 1 /* flags: run the colour stage */
+#define QPWC_AUGMENT_RAW 2   /* flags: leave out the offset and the scrub (image_augment / image_resize on their own) */
+int64_t qpwc_augment_workspace_floats(int B, int h, int w);
+int qpwc_augment_fwd(const void* ims, int ims_dtype, const void* flo, int B, int H, int W, const void* iparams,
+                     const void* fparams, int h, int w, int flags, int layout, void* out_ims, void* out_flo,
+                     void* workspace, void* stream);
+
+/* The form of the first launch of qpwc_augment_fwd for these arguments (host only): "augment_pixel_kernel<vec4>" (h * w
+ * a multiple of 4 and both outputs 16-byte aligned: the workgroup's pixels leave through LDS as 16-byte stores) or
+ * "augment_pixel_kernel<scalar>" (4-byte stores); "" for arguments it refuses.  The second launch takes the same form. */
+const char* qpwc_augment_fwd_kernel(int B, int h, int w, const void* out_ims, const void* out_flo);
 
 /* UpFlow front end in one launch (non_layers.py:377-385):
  *   nxt_w = WarpV2(nxt, flo); cost = CostVolumeV2(prv, nxt_w)

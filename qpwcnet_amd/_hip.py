@@ -12,7 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QPWC_HIP_LIB") or os.path.join(_HERE, "csrc", "libqpwc_hip.so")
 
 NHWC, NCHW = 0, 1
-F32, F16 = 0, 1
+F32, F16, U8 = 0, 1, 2
+AUGMENT_COLOR, AUGMENT_RAW = 1, 2
 WARP_CLAMP, WARP_TFWARP = 0, 1
 BCAST_B, BCAST_H, BCAST_W = 1, 2, 4
 LOSS_FLOW_MSE_V2, LOSS_FLOW_MSE, LOSS_FLOW_FINETUNE, LOSS_AUTORESIZE_MSE = 0, 1, 2, 3
@@ -38,6 +39,7 @@ SYMBOLS = (
     "qpwc_flow_head_bwd", "qpwc_upsample2x_flow_bwd",
     "qpwc_conv3x3_same_fwd", "qpwc_conv3x3_same_bwd_workspace_floats", "qpwc_conv3x3_same_bwd",
     "qpwc_upconv4x4s2_bwd_workspace_floats", "qpwc_upconv4x4s2_bwd",
+    "qpwc_augment_workspace_floats", "qpwc_augment_fwd", "qpwc_augment_fwd_kernel",
 )
 
 _lib = None
@@ -214,6 +216,12 @@ def lib():
     L.qpwc_upconv4x4s2_bwd_workspace_floats.restype = i64
     L.qpwc_upconv4x4s2_bwd.argtypes = [vp] * 4 + [i64] + [vp] * 4 + [ci, ci, ci, ci, ci, ci, vp]
     L.qpwc_upconv4x4s2_bwd.restype = ci
+    L.qpwc_augment_workspace_floats.argtypes = [ci, ci, ci]
+    L.qpwc_augment_workspace_floats.restype = i64
+    L.qpwc_augment_fwd.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]
+    L.qpwc_augment_fwd.restype = ci
+    L.qpwc_augment_fwd_kernel.argtypes = [ci, ci, ci, vp, vp]
+    L.qpwc_augment_fwd_kernel.restype = ctypes.c_char_p
     _lib = L
     return L
 

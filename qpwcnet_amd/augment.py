@@ -1,0 +1,245 @@
+"""Training input pipeline of the reference, batched (qpwcnet/data/augment.py:83-173 ``image_flip_ud``,
+``image_flip_lr``, ``image_scale_and_crop``, ``image_resize``, ``image_augment_colors``, ``image_augment``;
+qpwcnet/app/optical_flow/train.py:54-94 ``preprocess``, ``preprocess_no_op``).
+
+The reference maps these over single samples on host threads; here a batch goes through at once.  Inputs are
+``(B,H,W,6)`` uint8 or float32 frames (two RGB frames per sample) and ``(B,H,W,2)`` float32 flow, dense and
+``channels_last`` as decoded frames are.  CUDA tensors run the gfx950 kernels behind ``ops.augment`` (one launch, two
+with the colour stage); CPU tensors run ``augment_torch``, the same chain composed from torch operators, which is
+also what ``tools/augbench.py`` times against the kernels.  Outputs are float32.
+
+The random draw is separate from the arithmetic: ``sample_params`` returns the per-sample parameters as two device
+tensors (``AugmentParams``), which the kernels read from device memory -- no host synchronisation anywhere.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import ops
+from .backend import CHANNELS_FIRST, CHANNELS_LAST, get_axis
+
+# iparams (B,6) int32: rh, rw, oy, ox, flip_ud, flip_lr; fparams (B,6) float32: mu, mv, brightness, saturation, hue,
+# contrast (include/qpwc.h, qpwc_augment_fwd)
+AugmentParams = collections.namedtuple("AugmentParams", "iparams fparams")
+
+SCALE_RANGE = (0.955, 1.05)     # augment.py:119-123, times base_scale
+HUE_RANGE = (-0.2, 0.2)         # augment.py:64-67
+BRIGHTNESS_RANGE = (-0.125, 0.125)
+SATURATION_RANGE = (0.5, 1.5)
+CONTRAST_RANGE = (0.5, 1.5)
+_INV255 = float(np.float32(1.0 / 255.0))
+
+
+def scaled_shape(H, W, scale):
+    """``tf.cast(tf.cast((H, W), tf.float32) * scale, tf.int32)`` (augment.py:130-131) for a float32 tensor of scales:
+    the product is rounded to float32 before it is truncated."""
+    scale = torch.as_tensor(scale, dtype=torch.float32)
+    hw = torch.tensor([float(H), float(W)], dtype=torch.float32, device=scale.device)
+    return (scale.reshape(-1, 1) * hw).to(torch.int32)
+
+
+def _scale_bounds(base_scale):
+    return np.float32(SCALE_RANGE[0] * base_scale), np.float32(SCALE_RANGE[1] * base_scale)
+
+
+def sample_params(batch, in_shape, out_shape, base_scale=1.0, generator=None, device=None):
+    """Draws one sample's parameters per batch entry as the reference does: flips Bernoulli(0.5), scale ~
+    U(0.955, 1.05) * base_scale, (rh, rw) = ``scaled_shape``, the crop offset uniform over the windows that fit, hue ~
+    U(-0.2, 0.2), brightness ~ U(-0.125, 0.125), saturation and contrast ~ U(0.5, 1.5).  The numbers come from
+    ``generator`` (on its own device; the default generator of ``device`` without one) and the result lives on
+    ``device``.  ValueError when a scale of the range leaves the resized image smaller than the crop (where TF's
+    random_crop asserts)."""
+    H, W = (int(v) for v in in_shape)
+    h, w = (int(v) for v in out_shape)
+    if batch <= 0 or min(H, W, h, w) <= 0:
+        raise ValueError("non-positive batch or shape: {} {} {}".format(batch, (H, W), (h, w)))
+    lo, hi = _scale_bounds(base_scale)
+    min_rh, min_rw = int(np.float32(H) * lo), int(np.float32(W) * lo)
+    if min_rh < h or min_rw < w:
+        raise ValueError("a {}x{} crop does not fit the smallest resized image {}x{} ({}x{} at scale {:.4f})".format(
+            h, w, min_rh, min_rw, H, W, float(lo)))
+    device = torch.device("cpu" if device is None else device)
+    draw = generator.device if generator is not None else device
+    u = torch.rand((int(batch), 9), generator=generator, device=draw, dtype=torch.float32)
+    scale = (float(lo) + u[:, 2] * float(hi - lo)).clamp(float(lo), float(hi))
+    r = scaled_shape(H, W, scale)
+    room = r - torch.tensor([h, w], dtype=torch.int32, device=draw)                  # >= 0 by the check above
+    off = torch.minimum((u[:, 3:5] * (room + 1).to(torch.float32)).to(torch.int32), room)
+    flip = (u[:, 0:2] < 0.5)
+    sign = 1.0 - 2.0 * flip.to(torch.float32)
+    uni = lambda col, rng: rng[0] + u[:, col] * (rng[1] - rng[0])
+    iparams = torch.cat([r, off, flip.to(torch.int32)], dim=1)
+    fparams = torch.stack([scale * sign[:, 1], scale * sign[:, 0], uni(6, BRIGHTNESS_RANGE), uni(7, SATURATION_RANGE),
+                           uni(5, HUE_RANGE), uni(8, CONTRAST_RANGE)], dim=1)
+    return AugmentParams(iparams.contiguous().to(device), fparams.contiguous().to(device))
+
+
+def resize_params(batch, in_shape, out_shape, device=None):
+    """The parameters of ``image_resize`` (augment.py:145-153): the whole image resized to out_shape, no flips, flow
+    times (w / W, h / H).  The colour entries are the identity settings (the colour stage is off for this path)."""
+    H, W = (int(v) for v in in_shape)
+    h, w = (int(v) for v in out_shape)
+    ip = torch.tensor([[h, w, 0, 0, 0, 0]], dtype=torch.int32).repeat(int(batch), 1)
+    fp = torch.tensor([[w / W, h / H, 0.0, 1.0, 0.0, 1.0]], dtype=torch.float32).repeat(int(batch), 1)
+    return AugmentParams(ip.to(device or "cpu"), fp.to(device or "cpu"))
+
+
+# ---- the chain composed from torch operators: the CPU path, and the baseline the kernels are timed against ---------
+def _rgb_to_hsv(x):
+    r, g, b = x.unbind(-1)
+    mx, mn = x.amax(-1), x.amin(-1)
+    rng = mx - mn
+    s = torch.where(mx > 0, rng / mx, torch.zeros_like(mx))
+    norm = 1.0 / (6.0 * rng)
+    hh = torch.where(r == mx, norm * (g - b),
+                     torch.where(g == mx, norm * (b - r) + 2.0 / 6.0, norm * (r - g) + 4.0 / 6.0))
+    hh = torch.where(rng > 0, hh, torch.zeros_like(hh))
+    hh = torch.where(hh < 0, hh + 1.0, hh)
+    nan = torch.isnan(x).any(-1)                     # amax / amin propagate NaN; keep the hue and saturation NaN too
+    hh = torch.where(nan, torch.full_like(hh, math.nan), hh)
+    return hh, s, mx
+
+
+def _hsv_to_rgb(hh, s, v):
+    dr = ((6.0 * hh - 3.0).abs() - 1.0).clamp(0.0, 1.0)
+    dg = (2.0 - (6.0 * hh - 2.0).abs()).clamp(0.0, 1.0)
+    db = (2.0 - (6.0 * hh - 4.0).abs()).clamp(0.0, 1.0)
+    d = torch.stack([dr, dg, db], dim=-1)
+    return ((d - 1.0) * s.unsqueeze(-1) + 1.0) * v.unsqueeze(-1)
+
+
+def _colours_torch(x, fparams):
+    """image_augment_colors on (B,h,w,6): both frames of a sample with that sample's four scalars."""
+    B, h, w, _ = x.shape
+    x = x.reshape(B, h, w, 2, 3)
+    col = lambda i: fparams[:, i].to(x.dtype).reshape(B, 1, 1, 1)
+    x = x + col(2).unsqueeze(-1)
+    hh, s, v = _rgb_to_hsv(x)
+    x = _hsv_to_rgb(hh, (s * col(3)).clamp(0.0, 1.0), v)
+    hh, s, v = _rgb_to_hsv(x)
+    hh = hh + col(4)
+    x = _hsv_to_rgb(hh - torch.floor(hh), s, v)
+    mean = x.mean(dim=(1, 2, 3), keepdim=True)       # per colour channel, over the pixels of BOTH frames
+    x = (x - mean) * col(5).unsqueeze(-1) + mean
+    return x.reshape(B, h, w, 6)
+
+
+def augment_torch(ims, flo, params, out_shape, colour=True, finish=True, data_format=CHANNELS_LAST):
+    """What ``ops.augment`` computes, composed from torch operators on the tensors' own device: flips and crop by
+    indexing, ``F.interpolate(mode='bilinear', align_corners=False, antialias=False)`` for the resize (one call when
+    (rh, rw) is the same for the whole batch, one per sample otherwise), elementwise operators for the colours.  The
+    resized (rh, rw) images are materialised and the sizes are read back to the host, as a composition has to."""
+    get_axis(data_format)
+    h, w = (int(v) for v in out_shape)
+    B = ims.shape[0]
+    ip = params.iparams.cpu().tolist()
+    fp = params.fparams.to(ims.device)
+    x = ims.to(torch.float32) * _INV255 if ims.dtype == torch.uint8 else ims
+    x = torch.cat([x, flo], dim=3).permute(0, 3, 1, 2)                       # (B,8,H,W) view
+    resize = lambda t, size: F.interpolate(t, size=size, mode="bilinear", align_corners=False, antialias=False)
+    if all(row[:2] == ip[0][:2] for row in ip):
+        for dim, col in ((2, 4), (3, 5)):
+            idx = [b for b in range(B) if ip[b][col]]
+            if idx:
+                x = x.index_copy(0, torch.tensor(idx, device=x.device), torch.flip(x[idx], [dim]))
+        out = resize(x, tuple(ip[0][:2]))
+        if all(row[2:4] == ip[0][2:4] for row in ip):
+            out = out[:, :, ip[0][2]:ip[0][2] + h, ip[0][3]:ip[0][3] + w]
+        else:
+            out = torch.stack([out[b, :, r[2]:r[2] + h, r[3]:r[3] + w] for b, r in enumerate(ip)], dim=0)
+    else:
+        rows = []
+        for b, (rh, rw, oy, ox, ud, lr) in enumerate(ip):
+            xb = x[b:b + 1]
+            dims = [d for d, f in ((2, ud), (3, lr)) if f]
+            if dims:
+                xb = torch.flip(xb, dims)
+            rows.append(resize(xb, (rh, rw))[:, :, oy:oy + h, ox:ox + w])
+        out = torch.cat(rows, dim=0)
+    out = out.permute(0, 2, 3, 1)
+    o_ims, o_flo = out[..., :6], out[..., 6:] * fp[:, None, None, 0:2]
+    if colour:
+        o_ims = _colours_torch(o_ims, fp)
+    if finish:
+        o_ims = o_ims - 0.5
+        o_ims = torch.where(torch.isnan(o_ims), torch.zeros_like(o_ims), o_ims)
+        o_flo = torch.where(torch.isnan(o_flo), torch.zeros_like(o_flo), o_flo)
+    if data_format == CHANNELS_FIRST:
+        return o_ims.permute(0, 3, 1, 2).contiguous(), o_flo.permute(0, 3, 1, 2).contiguous()
+    return o_ims.contiguous(), o_flo.contiguous()
+
+
+# ---- the reference's names ------------------------------------------------------------------------------------------
+def _check_inputs(ims, flo, dtypes):
+    for name, t, dt, c in (("ims", ims, dtypes, 6), ("flo", flo, (torch.float32,), 2)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if t.dtype not in dt:
+            raise ValueError("{}: unsupported dtype {}".format(name, t.dtype))
+        if t.dim() != 4 or t.shape[3] != c:
+            raise ValueError("{} must be (B,H,W,{}) channels_last, got shape {}".format(name, c, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("{} must be dense (contiguous) channels_last".format(name))
+    if tuple(flo.shape[:3]) != tuple(ims.shape[:3]):
+        raise ValueError("flo {} does not match ims {}".format(tuple(flo.shape), tuple(ims.shape)))
+    if flo.device != ims.device:
+        raise ValueError("ims is on {}, flo on {}".format(ims.device, flo.device))
+
+
+def _check_params(params, B, device):
+    if not isinstance(params, AugmentParams):
+        params = AugmentParams(*params)
+    for name, t, dt in (("iparams", params.iparams, torch.int32), ("fparams", params.fparams, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B, 6):
+            raise ValueError("params.{} must be a ({}, 6) {} tensor".format(name, B, dt))
+    return AugmentParams(params.iparams.to(device).contiguous(), params.fparams.to(device).contiguous())
+
+
+def _run(ims, flo, params, out_shape, colour, finish, data_format):
+    if ims.is_cuda:
+        return ops.augment(ims, flo, params.iparams, params.fparams, out_shape, colour=colour, finish=finish,
+                           data_format=data_format)
+    return augment_torch(ims, flo, params, out_shape, colour=colour, finish=finish, data_format=data_format)
+
+
+def _drawn(ims, out_shape, base_scale, params, generator):
+    B, H, W, _ = ims.shape
+    if params is None:
+        return sample_params(B, (H, W), out_shape, base_scale, generator=generator, device=ims.device)
+    return _check_params(params, B, ims.device)
+
+
+def image_augment(ims, flo, out_shape, base_scale=1.0, params=None, generator=None):
+    """augment.py:167-173: flips, scale and crop to out_shape, colours.  float32 frames in [0, 1] in, augmented frames
+    (not clipped) and flow out, channels_last.  ``params``: an ``AugmentParams`` (``sample_params``); None draws them
+    from ``generator``."""
+    _check_inputs(ims, flo, (torch.float32,))
+    return _run(ims, flo, _drawn(ims, out_shape, base_scale, params, generator), out_shape, True, False, CHANNELS_LAST)
+
+
+def image_resize(ims, flo, shape):
+    """augment.py:145-153: bilinear resize of frames and flow to ``shape``, flow times (w / W, h / H); channels_last."""
+    _check_inputs(ims, flo, (torch.float32,))
+    B, H, W, _ = ims.shape
+    return _run(ims, flo, resize_params(B, (H, W), shape, ims.device), shape, False, False, CHANNELS_LAST)
+
+
+def preprocess(ims, flo, data_format=CHANNELS_FIRST, base_scale=1.0, out_shape=(256, 512), params=None,
+               generator=None):
+    """train.py:71-94: uint8 frames times 1/255 (float32 frames as they are), ``image_augment``, - 0.5, the layout,
+    NaN -> 0 in frames and flow."""
+    get_axis(data_format)
+    _check_inputs(ims, flo, (torch.uint8, torch.float32))
+    return _run(ims, flo, _drawn(ims, out_shape, base_scale, params, generator), out_shape, True, True, data_format)
+
+
+def preprocess_no_op(ims, flo, data_format=CHANNELS_FIRST, out_shape=(256, 512)):
+    """train.py:54-68 (the validation path): uint8 frames times 1/255, ``image_resize`` to out_shape, - 0.5, the
+    layout; NaN -> 0 as in ``preprocess``."""
+    get_axis(data_format)
+    _check_inputs(ims, flo, (torch.uint8, torch.float32))
+    B, H, W, _ = ims.shape
+    return _run(ims, flo, resize_params(B, (H, W), out_shape, ims.device), out_shape, False, True, data_format)

@@ -1,0 +1,360 @@
+// Training input pipeline (qpwcnet/data/augment.py:83-173, app/optical_flow/train.py:54-94), batched: uint8 -> x 1/255,
+// flips, bilinear scale + crop, flow scaling, brightness / saturation / hue / contrast, - 0.5, NaN scrub and the layout
+// change, with every per-sample parameter read from device memory.
+//   pass 1 (augment_pixel_kernel): one output pixel per lane, 256 pixels per workgroup: flips, the four-neighbour
+//           gather of all 8 channels, flow scaling and the per-pixel colour stages.  With the colour stage on it
+//           writes the pre-contrast image and leaves the workgroup's sums of the three colour channels in the workspace;
+//           with it off it writes the final image.  The flow is final either way.  (Flag QPWC_AUGMENT_RAW leaves out
+//           the - 0.5 and the scrub: image_augment / image_resize on their own.)
+//   pass 2 (augment_contrast_kernel): folds a sample's partial sums in a fixed order, then contrast, - 0.5 and the NaN
+//           scrub in place.
+// Lanes of a wave read neighbouring source pixels (a 6-byte uint8 pixel is three 2-byte loads: pixel addresses are even,
+// never dword aligned) and, in the <vec4> form, the workgroup's 256 pixels leave through LDS in the output's own memory
+// order as 16-byte stores.  No atomics: two runs are bit-identical.
+#include "common.h"
+
+// a + (b - a) * t and u8 * (1/255) - 0.5 are separately rounded, as the reference's TF kernels round them
+#pragma clang fp contract(off)
+
+namespace qpwc {
+
+constexpr int kAugThreads = 256;
+constexpr int kAugPass2Pixels = 4096;   // pass 2: pixels of one sample per workgroup
+constexpr int kAugIParams = 6, kAugFParams = 6;
+
+typedef float aug_f32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+__device__ __forceinline__ float aug_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
+// index of floor / ceil of a source coordinate, clamped into the image whatever the parameters hold (NaN -> 0)
+__device__ __forceinline__ int aug_index(float v, int n) { return (int)fminf(fmaxf(v, 0.0f), (float)(n - 1)); }
+
+// the 6 colour channels of source pixel `pix` as fp32 in [0, 1]
+template <bool U8>
+__device__ __forceinline__ void aug_load_pixel(const void* ims, int64_t pix, float* v) {
+    if (U8) {
+        const uint16_t* p = reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(ims) + pix * 6);
+        const float k = 0.003921568859368563f;   // float32(1 / 255): a multiply, as train.py:56
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const unsigned w = p[i];
+            v[2 * i] = (float)(w & 0xffu) * k;
+            v[2 * i + 1] = (float)(w >> 8) * k;
+        }
+    } else {
+        const float2* p = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(ims) + pix * 6);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float2 w = p[i];
+            v[2 * i] = w.x;
+            v[2 * i + 1] = w.y;
+        }
+    }
+}
+
+// adjust_brightness, adjust_saturation and adjust_hue of one RGB pixel.  The reference makes two HSV round trips; the
+// second RGB -> HSV returns the first one's (h, s', v) (s' = range' / v' and the hue of the rebuilt pixel are those it
+// was built from, and a pixel with v <= 0 or s' = 0 is grey on both), so one round trip with both edits is the same
+// function.  A NaN channel makes the pixel NaN.
+__device__ __forceinline__ void aug_colour(float& r, float& g, float& b, float bright, float sat, float hue) {
+    r += bright;
+    g += bright;
+    b += bright;
+    const bool nan = r != r || g != g || b != b;
+    const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
+    const float range = mx - mn, v = mx;
+    float s = v > 0.0f ? range / v : 0.0f;
+    float h = 0.0f;
+    if (range > 0.0f) {
+        const float norm = 1.0f / (6.0f * range);
+        h = r == mx ? norm * (g - b) : (g == mx ? norm * (b - r) + 2.0f / 6.0f : norm * (r - g) + 4.0f / 6.0f);
+        if (h < 0.0f) h += 1.0f;
+    }
+    s = clip01(s * sat);
+    h += hue;
+    h -= floorf(h);
+    const float dr = clip01(fabsf(6.0f * h - 3.0f) - 1.0f);
+    const float dg = clip01(2.0f - fabsf(6.0f * h - 2.0f));
+    const float db = clip01(2.0f - fabsf(6.0f * h - 4.0f));
+    const float q = nan ? __builtin_nanf("") : v;
+    r = ((dr - 1.0f) * s + 1.0f) * q;
+    g = ((dg - 1.0f) * s + 1.0f) * q;
+    b = ((db - 1.0f) * s + 1.0f) * q;
+}
+
+__device__ __forceinline__ float aug_scrub(float v) { return v != v ? 0.0f : v; }
+
+}  // namespace
+
+// blockIdx.x = sample * nblk + chunk; the chunk's 256 consecutive pixels (row-major over the h x w output), one per lane.
+template <bool U8, int LAYOUT, bool VEC>
+__global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* __restrict__ ims,
+                                                                   const float* __restrict__ flo, int H, int W,
+                                                                   const int* __restrict__ iparams,
+                                                                   const float* __restrict__ fparams, int h, int w,
+                                                                   int nblk, int flags, float* __restrict__ out_ims,
+                                                                   float* __restrict__ out_flo,
+                                                                   float* __restrict__ partial) {
+    __shared__ aug_f32x4 stage4[kAugThreads * 8 / 4];   // <vec4>: the chunk in output order, image then flow (8 KB)
+    __shared__ float red[3][kAugThreads / 64];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / nblk, chunk = blockIdx.x - b * nblk;
+    const int hw = h * w;
+    const bool colour = flags & QPWC_AUGMENT_COLOR, raw = flags & QPWC_AUGMENT_RAW;
+    const int base = chunk * kAugThreads;                // first pixel of the chunk
+    const int pix = base + tid;
+    const bool valid = pix < hw;
+
+    const int* ip = iparams + (int64_t)b * kAugIParams;
+    const float* fp = fparams + (int64_t)b * kAugFParams;
+    const int rh = ip[0], rw = ip[1], oy = ip[2], ox = ip[3], flip_ud = ip[4], flip_lr = ip[5];
+    const float mu = fp[0], mv = fp[1], bright = fp[2], sat = fp[3], hue = fp[4];
+
+    float v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = 0.0f;
+    if (valid) {
+        const int y = pix / w, x = pix - y * w;
+        // tf.image.resize(BILINEAR): half-pixel centres, scale = in / float(out), no antialias
+        const float sy = ((float)(oy + y) + 0.5f) * ((float)H / (float)rh) - 0.5f;
+        const float sx = ((float)(ox + x) + 0.5f) * ((float)W / (float)rw) - 0.5f;
+        const float fy = floorf(sy), fx = floorf(sx);
+        const float ty = sy - fy, tx = sx - fx;
+        int y0 = aug_index(fy, H), y1 = aug_index(ceilf(sy), H);
+        int x0 = aug_index(fx, W), x1 = aug_index(ceilf(sx), W);
+        if (flip_ud) {
+            y0 = H - 1 - y0;
+            y1 = H - 1 - y1;
+        }
+        if (flip_lr) {
+            x0 = W - 1 - x0;
+            x1 = W - 1 - x1;
+        }
+        const int64_t img = (int64_t)b * H * W;
+        const int64_t p00 = img + (int64_t)y0 * W + x0, p01 = img + (int64_t)y0 * W + x1;
+        const int64_t p10 = img + (int64_t)y1 * W + x0, p11 = img + (int64_t)y1 * W + x1;
+        float a[8], bb[8], c_[8], d[8];
+        aug_load_pixel<U8>(ims, p00, a);
+        aug_load_pixel<U8>(ims, p01, bb);
+        aug_load_pixel<U8>(ims, p10, c_);
+        aug_load_pixel<U8>(ims, p11, d);
+        const float2* f2 = reinterpret_cast<const float2*>(flo);
+        const float2 fa = f2[p00], fb = f2[p01], fc = f2[p10], fd = f2[p11];
+        a[6] = fa.x; a[7] = fa.y;
+        bb[6] = fb.x; bb[7] = fb.y;
+        c_[6] = fc.x; c_[7] = fc.y;
+        d[6] = fd.x; d[7] = fd.y;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float top = a[c] + (bb[c] - a[c]) * tx;
+            const float bot = c_[c] + (d[c] - c_[c]) * tx;
+            v[c] = top + (bot - top) * ty;
+        }
+        v[6] *= mu;
+        v[7] *= mv;
+        if (!raw) {
+            v[6] = aug_scrub(v[6]);
+            v[7] = aug_scrub(v[7]);
+        }
+        if (colour) {
+            aug_colour(v[0], v[1], v[2], bright, sat, hue);
+            aug_colour(v[3], v[4], v[5], bright, sat, hue);
+        } else if (!raw) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) v[c] = aug_scrub(v[c] - 0.5f);
+        }
+    }
+
+    if (colour) {
+        // sums of the three colour channels over both frames (an invalid lane holds zeros), lanes then waves in order
+        const int lane = tid & 63, wid = tid >> 6;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float s = aug_wave_sum(v[c] + v[c + 3]);
+            if (lane == 0) red[c][wid] = s;
+        }
+        __syncthreads();
+        if (tid < 3) partial[((int64_t)b * 3 + tid) * nblk + chunk] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+    }
+
+    const int64_t obase = (int64_t)b * hw;
+    if (!VEC) {
+        if (!valid) return;
+        if (LAYOUT == QPWC_NHWC) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) out_ims[(obase + pix) * 6 + c] = v[c];
+            out_flo[(obase + pix) * 2] = v[6];
+            out_flo[(obase + pix) * 2 + 1] = v[7];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) out_ims[(obase * 6 + (int64_t)c * hw) + pix] = v[c];
+            out_flo[obase * 2 + pix] = v[6];
+            out_flo[obase * 2 + hw + pix] = v[7];
+        }
+        return;
+    }
+    // <vec4>: hw % 4 == 0, so the chunk holds n = a multiple of 4 valid pixels and every 16-byte piece is whole
+    float* stage = reinterpret_cast<float*>(stage4);
+    float* sflo = stage + kAugThreads * 6;
+    const int n = min(kAugThreads, hw - base);
+    if (LAYOUT == QPWC_NHWC) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) stage[tid * 6 + c] = v[c];
+        sflo[tid * 2] = v[6];
+        sflo[tid * 2 + 1] = v[7];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) stage[c * kAugThreads + tid] = v[c];
+        sflo[tid] = v[6];
+        sflo[kAugThreads + tid] = v[7];
+    }
+    __syncthreads();
+    aug_f32x4* o4 = reinterpret_cast<aug_f32x4*>(out_ims);
+    aug_f32x4* of4 = reinterpret_cast<aug_f32x4*>(out_flo);
+    const aug_f32x4* sflo4 = stage4 + kAugThreads * 6 / 4;
+    if (LAYOUT == QPWC_NHWC) {
+        const int64_t g = (obase + base) * 6 / 4;
+        for (int i = tid; i < n * 6 / 4; i += kAugThreads) o4[g + i] = stage4[i];
+        const int64_t gf = (obase + base) * 2 / 4;
+        if (tid < n * 2 / 4) of4[gf + tid] = sflo4[tid];
+    } else {
+        const int q = kAugThreads / 4;   // 16-byte pieces of one plane of the chunk
+        for (int i = tid; i < 6 * q; i += kAugThreads) {
+            const int c = i / q, j = i - c * q;
+            if (4 * j < n) o4[(obase * 6 + (int64_t)c * hw + base) / 4 + j] = stage4[i];
+        }
+        if (tid < 2 * q) {
+            const int c = tid / q, j = tid - c * q;
+            if (4 * j < n) of4[(obase * 2 + (int64_t)c * hw + base) / 4 + j] = sflo4[tid];
+        }
+    }
+}
+
+// blockIdx.x = sample * nblk2 + chunk of kAugPass2Pixels pixels: adjust_contrast with the mean of each colour channel
+// over both frames, then (unless raw) - 0.5 and NaN -> 0, in place.
+template <int LAYOUT, bool VEC>
+__global__ __launch_bounds__(kAugThreads) void augment_contrast_kernel(float* __restrict__ out_ims,
+                                                                      const float* __restrict__ partial,
+                                                                      const float* __restrict__ fparams, int h, int w,
+                                                                      int nblk, int nblk2, int raw) {
+    __shared__ float red[3][kAugThreads / 64];
+    __shared__ float mean_s[3];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / nblk2, chunk = blockIdx.x - b * nblk2;
+    const int hw = h * w;
+    const int lane = tid & 63, wid = tid >> 6;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* p = partial + ((int64_t)b * 3 + c) * nblk;
+        float s = 0.0f;
+        for (int i = tid; i < nblk; i += kAugThreads) s += p[i];
+        s = aug_wave_sum(s);
+        if (lane == 0) red[c][wid] = s;
+    }
+    __syncthreads();
+    if (tid < 3) mean_s[tid] = ((red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3])) / (2.0f * (float)hw);
+    __syncthreads();
+    const float m0 = mean_s[0], m1 = mean_s[1], m2 = mean_s[2];
+    const float factor = fparams[(int64_t)b * kAugFParams + 5];
+    auto fin = [&](float x, int c) -> float {
+        const float m = c == 0 ? m0 : (c == 1 ? m1 : m2);
+        const float r = (x - m) * factor + m;
+        return raw ? r : aug_scrub(r - 0.5f);
+    };
+    float* img = out_ims + (int64_t)b * hw * 6;
+    const int64_t e0 = (int64_t)chunk * kAugPass2Pixels * 6;
+    const int64_t e1 = min(e0 + (int64_t)kAugPass2Pixels * 6, (int64_t)hw * 6);
+    if (VEC) {
+        aug_f32x4* p4 = reinterpret_cast<aug_f32x4*>(img);
+        for (int64_t i = e0 / 4 + tid; i < e1 / 4; i += kAugThreads) {
+            aug_f32x4 x = p4[i];
+            if (LAYOUT == QPWC_NHWC) {
+                const int c = (int)((4 * i) % 6);   // 0, 4 or 2
+                x.x = fin(x.x, c % 3);
+                x.y = fin(x.y, (c + 1) % 3);
+                x.z = fin(x.z, (c + 2) % 3);
+                x.w = fin(x.w, c % 3);
+            } else {
+                const int c = (int)(((4 * i) / hw) % 3);   // hw % 4 == 0: one plane
+                x.x = fin(x.x, c);
+                x.y = fin(x.y, c);
+                x.z = fin(x.z, c);
+                x.w = fin(x.w, c);
+            }
+            p4[i] = x;
+        }
+        return;
+    }
+    for (int64_t i = e0 + tid; i < e1; i += kAugThreads) {
+        const int c = LAYOUT == QPWC_NHWC ? (int)(i % 3) : (int)((i / hw) % 3);
+        img[i] = fin(img[i], c);
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+
+static int64_t aug_nblk(int h, int w) { return ((int64_t)h * w + kAugThreads - 1) / kAugThreads; }
+
+// 3 partial sums per pass-1 workgroup
+int64_t augment_workspace_floats(int B, int h, int w) { return 3 * (int64_t)B * aug_nblk(h, w); }
+
+// both grids are one-dimensional over sample x chunk
+bool augment_shape_ok(int B, int H, int W, int h, int w) {
+    const int64_t lim = 0x7fffffff;
+    return (int64_t)H * W <= lim && (int64_t)h * w <= lim / 6 && (int64_t)B * aug_nblk(h, w) <= lim;
+}
+
+static bool aug_vec(int h, int w, const void* out_ims, const void* out_flo) {
+    return ((int64_t)h * w) % 4 == 0 && (uintptr_t)out_ims % 16 == 0 && (uintptr_t)out_flo % 16 == 0;
+}
+
+const char* augment_fwd_kernel(int h, int w, const void* out_ims, const void* out_flo) {
+    return aug_vec(h, w, out_ims, out_flo) ? "augment_pixel_kernel<vec4>" : "augment_pixel_kernel<scalar>";
+}
+
+int augment_fwd_launch(const void* ims, bool u8, const float* flo, int B, int H, int W, const int* iparams,
+                       const float* fparams, int h, int w, int flags, int layout, float* out_ims, float* out_flo,
+                       float* ws, hipStream_t s) {
+    const int nblk = (int)aug_nblk(h, w);
+    const bool vec = aug_vec(h, w, out_ims, out_flo);
+    const dim3 grid((unsigned)(B * nblk)), block(kAugThreads);
+#define QPWC_AUG_PIX(U, L, V)                                                                                          \
+    hipLaunchKernelGGL((augment_pixel_kernel<U, L, V>), grid, block, 0, s, ims, flo, H, W, iparams, fparams, h, w, nblk, \
+                       flags, out_ims, out_flo, ws)
+#define QPWC_AUG_PIX_LV(U)                                                                                             \
+    do {                                                                                                               \
+        if (layout == QPWC_NHWC) {                                                                                     \
+            if (vec) QPWC_AUG_PIX(U, QPWC_NHWC, true); else QPWC_AUG_PIX(U, QPWC_NHWC, false);                         \
+        } else {                                                                                                       \
+            if (vec) QPWC_AUG_PIX(U, QPWC_NCHW, true); else QPWC_AUG_PIX(U, QPWC_NCHW, false);                         \
+        }                                                                                                              \
+    } while (0)
+    if (u8) QPWC_AUG_PIX_LV(true);
+    else QPWC_AUG_PIX_LV(false);
+#undef QPWC_AUG_PIX_LV
+#undef QPWC_AUG_PIX
+    int rc = check_launch("augment_pixel_kernel");
+    if (rc != QPWC_OK || !(flags & QPWC_AUGMENT_COLOR)) return rc;
+    const int nblk2 = (int)(((int64_t)h * w + kAugPass2Pixels - 1) / kAugPass2Pixels);
+    const dim3 grid2((unsigned)(B * nblk2));
+#define QPWC_AUG_CON(L, V)                                                                                             \
+    hipLaunchKernelGGL((augment_contrast_kernel<L, V>), grid2, block, 0, s, out_ims, ws, fparams, h, w, nblk, nblk2,    \
+                       flags & QPWC_AUGMENT_RAW)
+    if (layout == QPWC_NHWC) {
+        if (vec) QPWC_AUG_CON(QPWC_NHWC, true); else QPWC_AUG_CON(QPWC_NHWC, false);
+    } else {
+        if (vec) QPWC_AUG_CON(QPWC_NCHW, true); else QPWC_AUG_CON(QPWC_NCHW, false);
+    }
+#undef QPWC_AUG_CON
+    return check_launch("augment_contrast_kernel");
+}
+
+}  // namespace qpwc

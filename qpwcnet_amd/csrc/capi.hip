@@ -142,6 +142,13 @@ int upsample2x_flow_bwd_launch(const void* gout, void* gin, int B, int h, int w,
 int loss_bwd_launch(const void* const* dpred, const float* grad_losses, void* const* grad_pred, const int64_t* n_elems,
                     const int* pred_dtype, int n, hipStream_t s);
 
+int64_t augment_workspace_floats(int B, int h, int w);
+bool augment_shape_ok(int B, int H, int W, int h, int w);
+const char* augment_fwd_kernel(int h, int w, const void* out_ims, const void* out_flo);
+int augment_fwd_launch(const void* ims, bool u8, const float* flo, int B, int H, int W, const int* iparams,
+                       const float* fparams, int h, int w, int flags, int layout, float* out_ims, float* out_flo,
+                       float* ws, hipStream_t s);
+
 // 16-byte-per-lane streaming copy: the box's achievable HBM ceiling (read + write) for bench.py's roofline
 // block.  tools/micro/copybench.hip on MI355X: one float4 per thread over a one-shot grid with non-temporal
 // loads and stores 6.5 TB/s (plain 6.1; 4 float4 per thread over a grid-strided loop 5.5-6.2; hipMemcpyAsync 5.3).
@@ -223,6 +230,15 @@ static int loss_check_shapes(int kind, int B, int H, int W, int C, const int* h,
         if (kind == QPWC_LOSS_FLOW_MSE_V2 && (H % h[i] || W % w[i]))
             return fail(QPWC_E_SHAPE, "level %d: %dx%d is not a whole-block area reduction of %dx%d", i, h[i], w[i], H, W);
     }
+    return QPWC_OK;
+}
+
+// the shape rules of the input pipeline, shared by qpwc_augment_workspace_floats / _fwd / _fwd_kernel
+static int augment_check_shapes(int B, int H, int W, int h, int w) {
+    if (B <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0)
+        return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d h=%d w=%d", B, H, W, h, w);
+    if (!augment_shape_ok(B, H, W, h, w))
+        return fail(QPWC_E_SHAPE, "B=%d %dx%d -> %dx%d: a pixel count or the launch grid overflows 32 bits", B, H, W, h, w);
     return QPWC_OK;
 }
 
@@ -569,6 +585,46 @@ int qpwc_loss_bwd(const void* const* dpred, const void* grad_losses, void* const
     }
     return loss_bwd_launch(dpred, (const float*)grad_losses, grad_pred, n_elems, pred_dtype, n_levels,
                            (hipStream_t)stream);
+}
+
+int64_t qpwc_augment_workspace_floats(int B, int h, int w) {
+    const int rc = augment_check_shapes(B, 1, 1, h, w);
+    return rc != QPWC_OK ? rc : augment_workspace_floats(B, h, w);
+}
+
+const char* qpwc_augment_fwd_kernel(int B, int h, int w, const void* out_ims, const void* out_flo) {
+    if (!out_ims || !out_flo || augment_check_shapes(B, 1, 1, h, w) != QPWC_OK) return "";
+    return augment_fwd_kernel(h, w, out_ims, out_flo);
+}
+
+int qpwc_augment_fwd(const void* ims, int ims_dtype, const void* flo, int B, int H, int W, const void* iparams,
+                     const void* fparams, int h, int w, int flags, int layout, void* out_ims, void* out_flo,
+                     void* workspace, void* stream) {
+    if (flags & ~(QPWC_AUGMENT_COLOR | QPWC_AUGMENT_RAW)) return fail(QPWC_E_MODE, "unknown augment flags 0x%x", flags);
+    const bool colour = flags & QPWC_AUGMENT_COLOR;
+    if (!ims || !flo || !iparams || !fparams || !out_ims || !out_flo || (colour && !workspace))
+        return fail(QPWC_E_NULL, "null pointer argument");
+    if (ims_dtype != QPWC_F32 && ims_dtype != QPWC_U8) return fail(QPWC_E_DTYPE, "unsupported image dtype %d", ims_dtype);
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    int rc = augment_check_shapes(B, H, W, h, w);
+    if (rc != QPWC_OK) return rc;
+    const bool u8 = ims_dtype == QPWC_U8;
+    const size_t src_px = (size_t)B * H * W, out_px = (size_t)B * h * w;
+    // a uint8 pixel is read as three 2-byte pieces, an fp32 pixel and a flow vector as 8-byte pieces
+    const BufCheck bufs[] = {
+        {ims, src_px * 6 * (u8 ? 1 : 4), u8 ? (size_t)2 : (size_t)8, "ims"},
+        {flo, src_px * 2 * 4, 8, "flo"},
+        {iparams, (size_t)B * 6 * 4, 4, "iparams"},
+        {fparams, (size_t)B * 6 * 4, 4, "fparams"},
+        {out_ims, out_px * 6 * 4, 4, "out_ims"},
+        {out_flo, out_px * 2 * 4, 4, "out_flo"},
+        {workspace, (size_t)augment_workspace_floats(B, h, w) * 4, 4, "workspace"},
+    };
+    rc = check_bufs(bufs, 4, colour ? 7 : 6);
+    if (rc != QPWC_OK) return rc;
+    return augment_fwd_launch(ims, u8, (const float*)flo, B, H, W, (const int*)iparams, (const float*)fparams, h, w,
+                              flags, layout, (float*)out_ims, (float*)out_flo, (float*)workspace,
+                              (hipStream_t)stream);
 }
 
 int qpwc_epe_workspace_floats(void) { return epe_workspace_floats(); }

@@ -994,6 +994,66 @@ def epe_multi(flows_true, flows_pred, out=None, data_format=CHANNELS_LAST):
     return out
 
 
+def augment_kernel(B, h, w, out_ims=None, out_flo=None):
+    """Form of the first launch of ``qpwc_augment_fwd`` for a (h, w) output ('augment_pixel_kernel<vec4>' /
+    'augment_pixel_kernel<scalar>'; host only).  Tensors or addresses for the outputs; None = 16-byte aligned, as
+    torch allocates.  '' for arguments the entry point refuses."""
+    ptr = lambda t: 1 << 20 if t is None else (t.data_ptr() if isinstance(t, torch.Tensor) else int(t))
+    name = _hip.lib().qpwc_augment_fwd_kernel(int(B), int(h), int(w), ptr(out_ims), ptr(out_flo))
+    return name.decode() if name else ""
+
+
+def augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, data_format=CHANNELS_LAST):
+    """The training input pipeline of one batch (qpwc_augment_fwd; qpwcnet/data/augment.py:83-173, train.py:54-94):
+    ims (B,H,W,6) uint8 (taken times 1/255) or float32, flo (B,H,W,2) float32, both dense channels-last on one HIP
+    device; iparams (B,6) int32 = rh, rw, oy, ox, flip_ud, flip_lr and fparams (B,6) float32 = mu, mv, brightness,
+    saturation, hue, contrast on the same device (include/qpwc.h) -> (ims, flo) fp32 of spatial size out_shape in
+    data_format, written in that layout by the kernels.  colour=False: no colour stage; finish=False: no - 0.5 and no
+    NaN scrub.  Enqueues and returns: no host synchronisation."""
+    get_axis(data_format)
+    for name, t, dt, c in (("ims", ims, (torch.uint8, torch.float32), 6), ("flo", flo, (torch.float32,), 2)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if not t.is_cuda:
+            raise RuntimeError("qpwcnet_amd: {} is on '{}'; ops.augment runs on a HIP device only (augment.* has the "
+                               "CPU path)".format(name, t.device))
+        if t.dtype not in dt:
+            raise ValueError("{}: unsupported dtype {}".format(name, t.dtype))
+        if t.dim() != 4 or t.shape[3] != c:
+            raise ValueError("{} must be (B,H,W,{}) channels_last, got shape {}".format(name, c, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("{} must be dense (contiguous) channels_last".format(name))
+    B, H, W, _ = ims.shape
+    if tuple(flo.shape[:3]) != (B, H, W):
+        raise ValueError("flo {} does not match ims {}".format(tuple(flo.shape), tuple(ims.shape)))
+    for name, t, dt in (("iparams", iparams, torch.int32), ("fparams", fparams, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B, 6) or not t.is_contiguous():
+            raise ValueError("{} must be a dense ({}, 6) {} tensor".format(name, B, dt))
+    if not (flo.device == ims.device == iparams.device == fparams.device):
+        raise ValueError("ims, flo, iparams and fparams must be on one device")
+    h, w = (int(v) for v in out_shape)
+    if h <= 0 or w <= 0:
+        raise ValueError("non-positive output shape {}".format((h, w)))
+    L = _hip.lib()
+    dev = ims.device
+    flags = (_hip.AUGMENT_COLOR if colour else 0) | (0 if finish else _hip.AUGMENT_RAW)
+    nhwc = data_format == CHANNELS_LAST
+    out_ims = torch.empty((B, h, w, 6) if nhwc else (B, 6, h, w), dtype=torch.float32, device=dev)
+    out_flo = torch.empty((B, h, w, 2) if nhwc else (B, 2, h, w), dtype=torch.float32, device=dev)
+    ws = None
+    if colour:
+        nws = L.qpwc_augment_workspace_floats(B, h, w)
+        _hip.check(min(int(nws), 0))
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("augment", (B, H, W, h, w)):
+        rc = L.qpwc_augment_fwd(ims.data_ptr(), _hip.U8 if ims.dtype == torch.uint8 else _hip.F32, flo.data_ptr(), B, H, W,
+                                iparams.data_ptr(), fparams.data_ptr(), h, w, flags,
+                                _hip.NHWC if nhwc else _hip.NCHW, out_ims.data_ptr(), out_flo.data_ptr(),
+                                None if ws is None else ws.data_ptr(), _stream(ims))
+    _hip.check(rc)
+    return out_ims, out_flo
+
+
 def _loss_layout(y_true, preds, data_format):
     """-> (y_true, preds, layout code, nhwc_view): 'channels_first' operands that are all physically NHWC (torch
     channels_last memory) are read through their permuted views; everything else dense in its declared layout."""
