@@ -689,6 +689,54 @@ int qpwc_upconv4x4s2_bwd(const void* x, const void* weight, const void* bias, co
                          int64_t grad_out_pixel_stride, void* grad_x, void* grad_w, void* grad_b, void* workspace,
                          int B, int H, int W, int C, int F, int mish, void* stream);
 
+/* ---- the interpolation stack (pwcnet.py:70-131): image head, Upsample of an image, the frame pyramid ----------------
+ * All fp32, channels-last, dense; one summation order per shape, no atomics, shape-only grids: every output is
+ * bitwise reproducible.  Every error below is found before any HIP call and qpwc_last_error() names the argument. */
+
+/* The image head of a FrameInterpolate block, Conv2D(3, 1x1) (non_layers.py:293, 311): out (M, 3) = z (M, 64) . w2^T
+ * + b2 over the M = B*H*W pixels.  w2 (3, 64) row-major, b2 (3).  z is whatever feeds the head (the stored Mish output
+ * of the block's SeparableConv2D): no activation is applied here.  z and w2 16-byte aligned (16-byte loads), b2 and
+ * out 4.  Errors: QPWC_E_NULL, QPWC_E_SHAPE (M < 1), QPWC_E_ALIGN, QPWC_E_ALIAS (out over an input). */
+int qpwc_image_head_fwd(const void* z, const void* w2, const void* b2, void* out, int64_t M, void* stream);
+
+/* Floats of device scratch qpwc_image_head_bwd needs: one partial of grad_w2 (192) and grad_b2 (3) per workgroup; the
+ * number of workgroups comes from M alone.  Negative QPWC_E_SHAPE for M < 1. */
+int64_t qpwc_image_head_bwd_workspace_floats(int64_t M);
+
+/* Gradient of qpwc_image_head_fwd for g = grad_out = dL/d(out), (M, 3):
+ *   grad_z[p,c]  = sum_k g[p,k] w2[k,c]       (M, 64)
+ *   grad_w2[k,c] = sum_p g[p,k] z[p,c]        (3, 64)
+ *   grad_b2[k]   = sum_p g[p,k]               (3)
+ * Any of the three may be NULL, not all; z is read only when grad_w2 or grad_b2 is asked for, and the reduce launches
+ * of an output that is NULL are skipped.  The weight gradients are per-workgroup partials over a grid-stride loop in a
+ * fixed order, then a sum over the workgroups in order; an output has the same bits whatever else is asked for, and
+ * grad_z of a pixel depends on that pixel alone.  workspace: qpwc_image_head_bwd_workspace_floats(M) floats.
+ * Alignment: z, w2, grad_z, workspace 16 bytes; grad_out, grad_w2, grad_b2 4.  Errors: QPWC_E_NULL, QPWC_E_SHAPE,
+ * QPWC_E_ALIGN, QPWC_E_ALIAS (an output or the workspace overlapping an input or another output). */
+int qpwc_image_head_bwd(const void* z, const void* w2, const void* grad_out, void* grad_z, void* grad_w2,
+                        void* grad_b2, void* workspace, int64_t M, void* stream);
+
+/* Upsample(scale) of an image (non_layers.py:183-193; pwcnet.py:108,124): out (B,2h,2w,C) = scale * bilinear x2
+ * upsampling (half-pixel centres, edge clamp: weights 0.25 / 0.75) of in (B,h,w,C), C in 1..4.  The arithmetic of
+ * qpwc_upsample2x_flow_fwd: for C = 2 the same bits.  Both pointers 4-byte aligned (16 for out with C = 4, 8 with
+ * C = 2).  Errors: QPWC_E_NULL, QPWC_E_SHAPE (extents < 1, C outside 1..4, h or w above 2^29), QPWC_E_ALIGN,
+ * QPWC_E_ALIAS. */
+int qpwc_upsample2x_image_fwd(const void* in, void* out, int B, int h, int w, int C, float scale, void* stream);
+
+/* Adjoint of qpwc_upsample2x_image_fwd: grad_out (B,2h,2w,C) -> grad_in (B,h,w,C), a gather over the 4 x 4 taps of
+ * each input pixel with the weights of qpwc_upsample2x_flow_bwd, times scale.  One launch, no workspace.  Both pointers
+ * 4-byte aligned.  Errors as the forward. */
+int qpwc_upsample2x_image_bwd(const void* grad_out, void* grad_in, int B, int h, int w, int C, float scale,
+                              void* stream);
+
+/* `levels` successive AvgPool2D(2, 'same') (non_layers.py:171-180; pwcnet.py:87-90) of x (B,H,W,C), C in 1..4, in one
+ * launch: out (B, H / 2^levels, W / 2^levels, C), the last level only.  Every level is the mean of its 2 x 2 window
+ * of the level before, ((a + b) + c + d) / 4 in row-major order -- a mean of means, not one flat block mean.  levels in
+ * 1..6; H and W multiples of 2^levels (no window is clipped): anything else is QPWC_E_SHAPE and the caller pools level
+ * by level.  x is read once, in 8-byte loads: x 8-byte aligned, out 4.  No gradient: the frames carry none.
+ * Errors: QPWC_E_NULL, QPWC_E_SHAPE, QPWC_E_ALIGN, QPWC_E_ALIAS. */
+int qpwc_avgpool_pyramid_fwd(const void* x, void* out, int B, int H, int W, int C, int levels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,8 @@ SYMBOLS = (
     "qpwc_conv3x3_same_fwd", "qpwc_conv3x3_same_bwd_workspace_floats", "qpwc_conv3x3_same_bwd",
     "qpwc_upconv4x4s2_bwd_workspace_floats", "qpwc_upconv4x4s2_bwd",
     "qpwc_augment_workspace_floats", "qpwc_augment_fwd", "qpwc_augment_fwd_kernel",
+    "qpwc_image_head_fwd", "qpwc_image_head_bwd_workspace_floats", "qpwc_image_head_bwd",
+    "qpwc_upsample2x_image_fwd", "qpwc_upsample2x_image_bwd", "qpwc_avgpool_pyramid_fwd",
 )
 
 _lib = None
@@ -222,6 +224,18 @@ def lib():
     L.qpwc_augment_fwd.restype = ci
     L.qpwc_augment_fwd_kernel.argtypes = [ci, ci, ci, vp, vp]
     L.qpwc_augment_fwd_kernel.restype = ctypes.c_char_p
+    L.qpwc_image_head_fwd.argtypes = [vp, vp, vp, vp, i64, vp]
+    L.qpwc_image_head_fwd.restype = ci
+    L.qpwc_image_head_bwd_workspace_floats.argtypes = [i64]
+    L.qpwc_image_head_bwd_workspace_floats.restype = i64
+    L.qpwc_image_head_bwd.argtypes = [vp] * 7 + [i64, vp]
+    L.qpwc_image_head_bwd.restype = ci
+    L.qpwc_upsample2x_image_fwd.argtypes = [vp, vp, ci, ci, ci, ci, cf, vp]
+    L.qpwc_upsample2x_image_fwd.restype = ci
+    L.qpwc_upsample2x_image_bwd.argtypes = [vp, vp, ci, ci, ci, ci, cf, vp]
+    L.qpwc_upsample2x_image_bwd.restype = ci
+    L.qpwc_avgpool_pyramid_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
+    L.qpwc_avgpool_pyramid_fwd.restype = ci
     _lib = L
     return L
 

@@ -149,6 +149,16 @@ int augment_fwd_launch(const void* ims, bool u8, const float* flo, int B, int H,
                        const float* fparams, int h, int w, int flags, int layout, float* out_ims, float* out_flo,
                        float* ws, hipStream_t s);
 
+int64_t image_head_bwd_workspace_floats(int64_t M);
+int image_head_fwd_launch(const void* z, const void* w2, const void* b2, void* out, int64_t M, hipStream_t s);
+int image_head_bwd_launch(const void* z, const void* w2, const void* gout, void* gz, void* gw2, void* gb2, void* ws,
+                          int64_t M, hipStream_t s);
+int upsample2x_image_launch(const void* in, void* out, int B, int h, int w, int C, float scale, hipStream_t s);
+int upsample2x_image_bwd_launch(const void* gout, void* gin, int B, int h, int w, int C, float scale, hipStream_t s);
+int avgpool_pyramid_max_levels();
+int64_t avgpool_pyramid_tiles(int B, int H, int W, int levels, int* tw_out);
+int avgpool_pyramid_launch(const void* x, void* out, int B, int H, int W, int C, int levels, hipStream_t s);
+
 // 16-byte-per-lane streaming copy: the box's achievable HBM ceiling (read + write) for bench.py's roofline
 // block.  tools/micro/copybench.hip on MI355X: one float4 per thread over a one-shot grid with non-temporal
 // loads and stores 6.5 TB/s (plain 6.1; 4 float4 per thread over a grid-strided loop 5.5-6.2; hipMemcpyAsync 5.3).
@@ -262,6 +272,19 @@ static int flow_head_train_check_shape(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
     if ((int64_t)B * H * W > (1 << 24))
         return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: more than 2^24 pixels (the pixel counts are fp32)", B, H, W);
+    return QPWC_OK;
+}
+
+static int image_head_check_m(int64_t M) {
+    if (M <= 0 || M > ((int64_t)1 << 40)) return fail(QPWC_E_SHAPE, "M=%lld outside [1, 2^40] pixels", (long long)M);
+    return QPWC_OK;
+}
+
+// the shape rules both directions of the image upsampling share
+static int upsample2x_image_check_shape(int B, int h, int w, int C) {
+    if (B <= 0 || h <= 0 || w <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d h=%d w=%d", B, h, w);
+    if (C < 1 || C > 4) return fail(QPWC_E_SHAPE, "C=%d outside 1..4", C);
+    if (h > (1 << 29) || w > (1 << 29)) return fail(QPWC_E_SHAPE, "h=%d w=%d: the doubled extents must fit an int", h, w);
     return QPWC_OK;
 }
 
@@ -1460,6 +1483,88 @@ int qpwc_upconv4x4s2_mish_cat_f16_fwd(const void* x, const void* weight, const v
                                       int B, int H, int W, int C, int F, int64_t out_pixel_stride, void* stream) {
     return upconv_cat_common(x, weight, bias, skip, skip_batch_stride, skip_row_stride, skip_pixel_stride, out, B, H, W, C, F,
                              out_pixel_stride, stream, 2);
+}
+
+int qpwc_image_head_fwd(const void* z, const void* w2, const void* b2, void* out, int64_t M, void* stream) {
+    if (!z) return fail(QPWC_E_NULL, "z is null");
+    if (!w2) return fail(QPWC_E_NULL, "w2 is null");
+    if (!b2) return fail(QPWC_E_NULL, "b2 is null");
+    if (!out) return fail(QPWC_E_NULL, "out is null");
+    int rc = image_head_check_m(M);
+    if (rc != QPWC_OK) return rc;
+    const BufCheck bufs[4] = {{z, (size_t)M * 256, 16, "z"}, {w2, 768, 16, "w2"}, {b2, 12, 4, "b2"},
+                              {out, (size_t)M * 12, 4, "out"}};
+    if ((rc = check_bufs(bufs, 3, 4)) != QPWC_OK) return rc;
+    return image_head_fwd_launch(z, w2, b2, out, M, (hipStream_t)stream);
+}
+
+int64_t qpwc_image_head_bwd_workspace_floats(int64_t M) {
+    const int rc = image_head_check_m(M);
+    return rc != QPWC_OK ? rc : image_head_bwd_workspace_floats(M);
+}
+
+int qpwc_image_head_bwd(const void* z, const void* w2, const void* grad_out, void* grad_z, void* grad_w2,
+                        void* grad_b2, void* workspace, int64_t M, void* stream) {
+    if (!z) return fail(QPWC_E_NULL, "z is null");
+    if (!w2) return fail(QPWC_E_NULL, "w2 is null");
+    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
+    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
+    if (!grad_z && !grad_w2 && !grad_b2) return fail(QPWC_E_NULL, "grad_z, grad_w2 and grad_b2 are all null");
+    int rc = image_head_check_m(M);
+    if (rc != QPWC_OK) return rc;
+    BufCheck bufs[7];
+    int n_in = 0;
+    bufs[n_in++] = {z, (size_t)M * 256, 16, "z"};
+    bufs[n_in++] = {w2, 768, 16, "w2"};
+    bufs[n_in++] = {grad_out, (size_t)M * 12, 4, "grad_out"};
+    int n_all = n_in;
+    if (grad_z) bufs[n_all++] = {grad_z, (size_t)M * 256, 16, "grad_z"};
+    if (grad_w2) bufs[n_all++] = {grad_w2, 768, 4, "grad_w2"};
+    if (grad_b2) bufs[n_all++] = {grad_b2, 12, 4, "grad_b2"};
+    bufs[n_all++] = {workspace, (size_t)image_head_bwd_workspace_floats(M) * 4, 16, "workspace"};
+    if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
+    return image_head_bwd_launch(z, w2, grad_out, grad_z, grad_w2, grad_b2, workspace, M, (hipStream_t)stream);
+}
+
+int qpwc_upsample2x_image_fwd(const void* in, void* out, int B, int h, int w, int C, float scale, void* stream) {
+    if (!in) return fail(QPWC_E_NULL, "in is null");
+    if (!out) return fail(QPWC_E_NULL, "out is null");
+    int rc = upsample2x_image_check_shape(B, h, w, C);
+    if (rc != QPWC_OK) return rc;
+    const size_t n = (size_t)B * h * w * C * 4;
+    const BufCheck bufs[2] = {{in, n, 4, "in"}, {out, 4 * n, (size_t)(C == 4 ? 16 : C == 2 ? 8 : 4), "out"}};
+    if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
+    return upsample2x_image_launch(in, out, B, h, w, C, scale, (hipStream_t)stream);
+}
+
+int qpwc_upsample2x_image_bwd(const void* grad_out, void* grad_in, int B, int h, int w, int C, float scale,
+                              void* stream) {
+    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
+    if (!grad_in) return fail(QPWC_E_NULL, "grad_in is null");
+    int rc = upsample2x_image_check_shape(B, h, w, C);
+    if (rc != QPWC_OK) return rc;
+    const size_t n = (size_t)B * h * w * C * 4;
+    const BufCheck bufs[2] = {{grad_out, 4 * n, 4, "grad_out"}, {grad_in, n, 4, "grad_in"}};
+    if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
+    return upsample2x_image_bwd_launch(grad_out, grad_in, B, h, w, C, scale, (hipStream_t)stream);
+}
+
+int qpwc_avgpool_pyramid_fwd(const void* x, void* out, int B, int H, int W, int C, int levels, void* stream) {
+    if (!x) return fail(QPWC_E_NULL, "x is null");
+    if (!out) return fail(QPWC_E_NULL, "out is null");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
+    if (C < 1 || C > 4) return fail(QPWC_E_SHAPE, "C=%d outside 1..4", C);
+    if (levels < 1 || levels > avgpool_pyramid_max_levels())
+        return fail(QPWC_E_SHAPE, "levels=%d outside 1..%d", levels, avgpool_pyramid_max_levels());
+    const int S = 1 << levels;
+    if (H % S || W % S) return fail(QPWC_E_SHAPE, "H=%d W=%d are not multiples of 2^levels = %d", H, W, S);
+    if (avgpool_pyramid_tiles(B, H, W, levels, nullptr) > INT32_MAX)
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d levels=%d: the launch grid overflows 32 bits", B, H, W, levels);
+    const size_t n = (size_t)B * H * W * C * 4;
+    const BufCheck bufs[2] = {{x, n, 8, "x"}, {out, n >> (2 * levels), 4, "out"}};
+    const int rc = check_bufs(bufs, 1, 2);
+    if (rc != QPWC_OK) return rc;
+    return avgpool_pyramid_launch(x, out, B, H, W, C, levels, (hipStream_t)stream);
 }
 
 }  // extern "C"

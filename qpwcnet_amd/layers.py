@@ -3,8 +3,9 @@
 ``WarpV2``, and trainable twins of the flow-estimator functors
 (qpwcnet/core/non_layers.py:183-193, 213-273, 315-387): ``SeparableConv2D``,
 ``OptFlow``, ``Upsample``, ``Flow``, ``UpFlow``, and of the encoder (non_layers.py:390-449, pwcnet.py:134-168):
-``DownConv``, ``Encoder``, of the decoder (non_layers.py:196-210, pwcnet.py:171-207): ``UpConv``, ``Decoder``, and of
-the whole ``build_flower`` network: ``FlowerModel``.  Same names, same constructor
+``DownConv``, ``Encoder``, of the decoder (non_layers.py:196-210, pwcnet.py:171-207): ``UpConv``, ``Decoder``, of
+the whole ``build_flower`` network: ``FlowerModel``, and of the frame interpolator (layers.py:356-402,
+pwcnet.py:70-131, 247-287): ``FrameInterpolate``, ``InterpolatorModel``.  Same names, same constructor
 arguments, same ``layer((a, b))`` call convention, same config round trip; the
 arithmetic, forward and backward, runs in the gfx950 HIP kernels behind
 ``include/qpwc.h``.
@@ -463,8 +464,8 @@ class FlowerModel(_HotPathLayer):
         self.enc_filters = tuple(int(f) for f in enc_filters)
         self.dec_filters = tuple(int(f) for f in dec_filters)
         if not self.enc_filters or len(self.dec_filters) >= len(self.enc_filters):
-            raise ValueError("FlowerModel: fewer decoder levels than encoder levels, got {} and {}".format(
-                enc_filters, dec_filters))
+            raise ValueError("{}: fewer decoder levels than encoder levels, got {} and {}".format(
+                type(self).__name__, enc_filters, dec_filters))
         self._config = {"enc_filters": self.enc_filters, "dec_filters": self.dec_filters}
         skips = tuple(self.enc_filters[-2 - i] for i in range(len(self.dec_filters)))
         self.enc = Encoder(self.enc_filters, data_format=CHANNELS_LAST).enc
@@ -474,19 +475,134 @@ class FlowerModel(_HotPathLayer):
                                           for f, c in zip(self.dec_filters, skips))
         self.up = Upsample(2.0, data_format=CHANNELS_LAST)
 
-    def forward(self, pairs):
+    def _pyramids(self, pairs):
+        """The frame pair -> (n, the 2n stacked channels-last frames [prv; nxt], their encoder levels, their decoder
+        levels)."""
         if pairs.dim() != 4 or pairs.shape[self.axis] != 6:
-            raise ValueError("FlowerModel: a frame pair with 6 channels on axis {}, got {}".format(
-                self.axis, tuple(pairs.shape)))
+            raise ValueError("{}: a frame pair with 6 channels on axis {}, got {}".format(
+                type(self).__name__, self.axis, tuple(pairs.shape)))
         self.build((tuple(pairs.shape),))
-        n = pairs.shape[0]
         prv, nxt = torch.chunk(pairs, 2, dim=self.axis)
-        feats = _encode_stacked(self.enc, _dense_nhwc(torch.cat([prv, nxt], dim=0), self.data_format))
-        decs = _decode_stacked(self.dec, feats, True)
-        flo = self.flow((feats[-1][:n], feats[-1][n:]))
+        frames = _dense_nhwc(torch.cat([prv, nxt], dim=0), self.data_format)
+        feats = _encode_stacked(self.enc, frames)
+        return pairs.shape[0], frames, feats, _decode_stacked(self.dec, feats, True)
+
+    def _flow_stack(self, enc_prv, enc_nxt, decs_prv, decs_nxt):
+        """The estimated flows of one direction, coarse to fine (pwcnet.py:28-64): Flow, then Upsample(2.0) + UpFlow per
+        decoder level."""
+        flo = self.flow((enc_prv, enc_nxt))
         flows = [flo]
-        for d, upflow in zip(decs, self.upflow):
-            flo = upflow((d[:n], d[n:], self.up(flo)))
+        for d_prv, d_nxt, upflow in zip(decs_prv, decs_nxt, self.upflow):
+            flo = upflow((d_prv, d_nxt, self.up(flo)))
             flows.append(flo)
-        flows.append(self.up(flo))
+        return flows
+
+    def forward(self, pairs):
+        n, _, feats, decs = self._pyramids(pairs)
+        flows = self._flow_stack(feats[-1][:n], feats[-1][n:], [d[:n] for d in decs], [d[n:] for d in decs])
+        flows.append(self.up(flows[-1]))
         return [ops._from_nhwc(f, self.data_format) for f in flows]
+
+
+class FrameInterpolate(_HotPathLayer):
+    """One block of the interpolation stack (qpwcnet/core/layers.py:356-402, non_layers.py:276-312), trainable: both
+    inputs warped half way along their flows, nxt_w = WarpV2(nxt, 0.5 flo_01) and prv_w = WarpV2(prv, 0.5 flo_10), then
+    concat [prv_w, nxt_w, flo_01, flo_10 (, img_u)] -> SeparableConv2D(64, 3x3, 'same', Mish) -> Conv2D(3, 1x1).  The
+    call takes (prv, nxt, flo_01, flo_10) or, with up=True, (prv, nxt, flo_01, flo_10, img_u), img_u being the
+    upsampled image of the level before.  The two warped members are read by the separable convolution as a virtual
+    concat; where in_channels is no multiple of 4 (the coarsest block, on the 3-channel frames) the concat is one dense
+    tensor.  State-dict names as weights.py: conv1.depthwise.weight, conv1.pointwise.weight, conv1.bias, conv2.weight
+    (3,64,1,1), conv2.bias; Keras' default initialisers.  in_channels: the channels of prv / nxt.  fp32 only."""
+    FILTERS = 64
+
+    def __init__(self, in_channels, up=False, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.in_channels, self.up = int(in_channels), bool(up)
+        if self.in_channels < 1:
+            raise ValueError("FrameInterpolate: in_channels >= 1, got {}".format(in_channels))
+        self._config = {"in_channels": self.in_channels, "up": self.up}
+        # the block runs channels-last inside; this layer converts at its own boundary
+        self.conv1 = SeparableConv2D(2 * self.in_channels + 4 + (3 if self.up else 0), self.FILTERS, "Mish",
+                                     data_format=CHANNELS_LAST)
+        self.conv2 = _Conv((3, self.FILTERS, 1, 1), bias=True)
+
+    def _head(self, prv_w, nxt_w, rest):
+        small = torch.cat(rest, dim=3)
+        if self.in_channels % 4:
+            sources = [torch.cat([prv_w, nxt_w, small], dim=3)]
+        else:
+            sources = [prv_w, nxt_w, small]
+        return ops.image_head(self.conv1(sources), self.conv2.weight, self.conv2.bias)
+
+    def _check(self, tensors, shape):
+        B, H, W = shape[0], shape[1], shape[2]
+        want = [(B, H, W, c) for c in (self.in_channels, self.in_channels, 2, 2, 3)][:len(tensors)]
+        if len(tensors) != (5 if self.up else 4) or [tuple(t.shape) for t in tensors] != want:
+            raise ValueError("FrameInterpolate(in_channels={}, up={}): got the shapes {}".format(
+                self.in_channels, self.up, [tuple(t.shape) for t in tensors]))
+
+    def forward_nhwc(self, prv, nxt, flo_01, flo_10, img_u=None):
+        nxt_w = ops.warp(nxt, 0.5 * flo_01, "clamp")
+        prv_w = ops.warp(prv, 0.5 * flo_10, "clamp")
+        return self._head(prv_w, nxt_w, [flo_01, flo_10] + ([img_u] if self.up else []))
+
+    def forward(self, inputs):
+        tensors = [_dense_nhwc(t, self.data_format) for t in inputs]
+        self.build((tuple(inputs[0].shape),))
+        self._check(tensors, tensors[0].shape)
+        return ops._from_nhwc(self.forward_nhwc(*tensors), self.data_format)
+
+    def forward_stacked(self, swapped, flows, img_u=None):
+        """The same block with both warps in one launch (non_layers.FrameInterpolate.call_stacked of the no-grad
+        network): `swapped` = [nxt; prv] and `flows` = [flo_01; flo_10] stacked on the batch axis (2n), dense
+        channels-last, img_u (n,H,W,3) with up=True.  The bits of the plain call."""
+        n = swapped.shape[0] // 2
+        rest = [flows[:n], flows[n:]] + ([img_u] if self.up else [])
+        self._check([swapped[n:], swapped[:n]] + rest, swapped[:n].shape)
+        w = ops.warp(swapped, 0.5 * flows, "clamp")     # [nxt_w; prv_w]
+        return self._head(w[n:], w[:n], rest)
+
+
+class InterpolatorModel(FlowerModel):
+    """The whole frame interpolator of build_interpolator (qpwcnet/core/pwcnet.py:247-287, 70-131), trainable: the
+    encoder, decoder and flow stack of FlowerModel, the flow stack run in both directions with the same modules --
+    flows_01 = flower(enc_nxt, enc_prv, decs_nxt, decs_prv), then flows_10 with the roles swapped, two passes in that
+    order in train() and eval() alike, so that every BatchNormalization takes its batch statistics per call and moves
+    its moving buffers twice per step as the reference's does -- and one FrameInterpolate block per level.  The coarsest
+    block reads the input frames pooled len(enc_filters) times (ops.avgpool_pyramid: the reference's n+1 poolings for
+    its own configuration, the coarsest feature size for any other), every finer one the decoder features of its level
+    and the upsampled image of the level before (ops.upsample2x_image); the last image is upsample-only.  The final
+    upsample-only flow of each direction is not needed and not computed.  The input is the frame pair (B,H,W,6), or
+    (B,6,H,W) for channels_first; the result is the list of len(dec_filters) + 2 images, coarse to fine -- what
+    loss.multiscale(loss.AutoResizeMseLoss(), ...) takes -- or with output_multiscale=False the last one.  State-dict
+    names enc.*, dec.*, flow.flow.*, upflow.{i}.flow.*, img.{k}.conv1.*, img.{k}.conv2.* are those of
+    synth.make_interpolator_weights; a FlowerModel state dict loads with strict=False and leaves img.* missing (the
+    reference's flow-to-interpolator weight transfer, pwcnet.py:276-279)."""
+
+    def __init__(self, enc_filters=(16, 32, 64, 128, 256), dec_filters=(128, 64, 32, 16), output_multiscale=True,
+                 *args, **kwargs):
+        super().__init__(enc_filters, dec_filters, *args, **kwargs)
+        self.output_multiscale = bool(output_multiscale)
+        self._config["output_multiscale"] = self.output_multiscale
+        self.img = torch.nn.ModuleList(
+            [FrameInterpolate(3, up=False, data_format=CHANNELS_LAST)] +
+            [FrameInterpolate(u.in_channels, up=True, data_format=CHANNELS_LAST) for u in self.upflow])
+
+    def forward(self, pairs):
+        n, frames, feats, decs = self._pyramids(pairs)
+        enc_prv, enc_nxt = feats[-1][:n], feats[-1][n:]
+        decs_prv, decs_nxt = [d[:n] for d in decs], [d[n:] for d in decs]
+        flows_01 = self._flow_stack(enc_nxt, enc_prv, decs_nxt, decs_prv)
+        flows_10 = self._flow_stack(enc_prv, enc_nxt, decs_prv, decs_nxt)
+        # the pooling is per image: the stacked [prv; nxt] frames give the reference's two pyramids in one launch
+        small = ops.avgpool_pyramid(frames.detach(), len(self.enc_filters))
+        img = self.img[0].forward_nhwc(small[:n], small[n:], flows_01[0], flows_10[0])
+        imgs = [img]
+        for i, block in enumerate(self.img[1:]):
+            img = block.forward_nhwc(decs_prv[i], decs_nxt[i], flows_01[i + 1], flows_10[i + 1],
+                                     ops.upsample2x_image(img))
+            imgs.append(img)
+        imgs.append(ops.upsample2x_image(img))
+        if not self.output_multiscale:
+            return ops._from_nhwc(imgs[-1], self.data_format)
+        return [ops._from_nhwc(t, self.data_format) for t in imgs]

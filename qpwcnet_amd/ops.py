@@ -913,6 +913,181 @@ def upsample2x_flow(flo, scale=1.0, in_format=CHANNELS_LAST, out_format=CHANNELS
     return out
 
 
+def _image_head_check(z, w2, b2, what):
+    """What the image head asks of its operands: z (B,H,W,64), w2 (3,64[,1,1]) and b2 (3; None in the backward, which
+    does not read it), fp32 on a HIP device."""
+    _check_tensor("z", z)
+    for name, t in (("z", z), ("w2", w2)) + ((("b2", b2),) if b2 is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if not t.is_cuda:
+            raise RuntimeError("qpwcnet_amd: {} is on '{}'; the hot path runs on a HIP device only "
+                               "(no CPU fallback)".format(name, t.device))
+        if t.dtype == torch.float16:
+            raise ValueError("{} has no fp16 storage path ({} is fp16): train in fp32".format(what, name))
+        if t.dtype != torch.float32:
+            raise ValueError("{}: {} must be fp32, got {}".format(what, name, t.dtype))
+    if z.shape[3] != 64 or w2.dim() < 2 or w2.shape[0] != 3 or w2.numel() != 192 or (b2 is not None and b2.numel() != 3):
+        raise ValueError("{} takes z (B,H,W,64), w2 (3,64) and b2 (3), got {}, {} and {}".format(
+            what, tuple(z.shape), tuple(w2.shape), None if b2 is None else tuple(b2.shape)))
+
+
+def image_head_bwd(z, w2, grad_out, need=(True, True, True)):
+    """Gradients of image_head() (fp32 channels-last, qpwc_image_head_bwd) for grad_out = dL/d(out), (B,H,W,3).
+    need = (z, w2, b2) -> (grad_z (B,H,W,64), grad_w2 (3,64), grad_b2 (3)); whatever is not asked for comes back as
+    None."""
+    _image_head_check(z, w2, None, "image_head_bwd")
+    _check_tensor("grad_out", grad_out)
+    B, H, W, _ = z.shape
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (B, H, W, 3):
+        raise ValueError("image_head_bwd: grad_out must be fp32 {}, got {} {}".format(
+            (B, H, W, 3), grad_out.dtype, tuple(grad_out.shape)))
+    if not any(need):
+        raise ValueError("image_head_bwd: nothing asked for")
+    z, w, g = z.contiguous(), w2.reshape(3, 64).contiguous(), grad_out.contiguous()
+    M = B * H * W
+    L = _hip.lib()
+    ws, outs, ptrs = _bwd_buffers(L.qpwc_image_head_bwd_workspace_floats(M), [(B, H, W, 64), (3, 64), (3,)], need,
+                                  z.device)
+    with torch.cuda.device(z.device), _timed("image_head_bwd", (B, H, W, 64)):
+        rc = L.qpwc_image_head_bwd(z.data_ptr(), w.data_ptr(), g.data_ptr(), *ptrs, ws.data_ptr(), M, _stream(z))
+    _hip.check(rc)
+    return tuple(outs)
+
+
+class _ImageHeadFn(torch.autograd.Function):
+    """image_head() with qpwc_image_head_bwd as its gradient: the forward is the no-grad forward itself; z and w2 are
+    saved."""
+
+    @staticmethod
+    def forward(ctx, z, w2, b2):
+        _refuse_capture("the image head")
+        out = image_head(z, w2, b2)
+        ctx.save_for_backward(z, w2)
+        ctx.b2_shape = tuple(b2.shape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the image-head backward")
+        z, w2 = ctx.saved_tensors
+        gz, gw, gb = image_head_bwd(z, w2, grad_out.to(torch.float32), tuple(ctx.needs_input_grad[:3]))
+        return (gz, gw.reshape(w2.shape) if gw is not None else None,
+                gb.reshape(ctx.b2_shape) if gb is not None else None)
+
+
+def image_head(z, w2, b2):
+    """The image head of a FrameInterpolate block, Conv2D(3, 1x1) on its 64 features (qpwcnet/core/non_layers.py:293,
+    311): z (B,H,W,64) fp32 channels-last, w2 (3,64) or the torch kernel (3,64,1,1), b2 (3) -> (B,H,W,3)
+    (qpwc_image_head_fwd).  No activation: z is what the block's SeparableConv2D stored.
+    Differentiable in z, w2 and b2: with grad enabled and one of them requiring grad the same forward runs inside an
+    autograd Function whose backward is qpwc_image_head_bwd."""
+    if _wants_grad(z, w2, b2):
+        _refuse_capture("the image head")
+        _image_head_check(z, w2, b2, "image_head")
+        return _ImageHeadFn.apply(z, w2, b2)
+    _image_head_check(z, w2, b2, "image_head")
+    zc, w, b = z.contiguous(), w2.reshape(3, 64).contiguous(), b2.contiguous()
+    B, H, W, _ = zc.shape
+    out = torch.empty((B, H, W, 3), dtype=torch.float32, device=zc.device)
+    with torch.cuda.device(zc.device), _timed("image_head", (B, H, W, 64)):
+        rc = _hip.lib().qpwc_image_head_fwd(zc.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W,
+                                             _stream(zc))
+    _hip.check(rc)
+    return out
+
+
+def _image_check(name, t, what):
+    """An fp32 channels-last image (B,h,w,C) of 1..4 channels on a HIP device."""
+    _check_tensor(name, t)
+    if t.dtype == torch.float16:
+        raise ValueError("{} has no fp16 storage path ({} is fp16): train in fp32".format(what, name))
+    if not 1 <= t.shape[3] <= 4:
+        raise ValueError("{} takes a channels-last image of 1..4 channels, got shape {}".format(what, tuple(t.shape)))
+
+
+def upsample2x_image_bwd(grad_out, scale=1.0):
+    """Adjoint of upsample2x_image() (fp32 channels-last, qpwc_upsample2x_image_bwd): grad_out (B,2h,2w,C) ->
+    (B,h,w,C)."""
+    _image_check("grad_out", grad_out, "upsample2x_image_bwd")
+    B, H2, W2, C = grad_out.shape
+    if H2 % 2 or W2 % 2:
+        raise ValueError("upsample2x_image_bwd takes a (B,2h,2w,C) gradient, got {}".format(tuple(grad_out.shape)))
+    g = grad_out.contiguous()
+    out = torch.empty((B, H2 // 2, W2 // 2, C), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device), _timed("upsample2x_image_bwd", (B, H2 // 2, W2 // 2, C)):
+        rc = _hip.lib().qpwc_upsample2x_image_bwd(g.data_ptr(), out.data_ptr(), B, H2 // 2, W2 // 2, C, float(scale),
+                                                   _stream(g))
+    _hip.check(rc)
+    return out
+
+
+class _UpsampleImageFn(torch.autograd.Function):
+    """upsample2x_image() with qpwc_upsample2x_image_bwd as its gradient: the forward is the no-grad forward itself."""
+
+    @staticmethod
+    def forward(ctx, img, scale):
+        _refuse_capture("the image upsampling")
+        ctx.scale = float(scale)
+        return upsample2x_image(img, scale)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        _refuse_capture("the image-upsampling backward")
+        return upsample2x_image_bwd(grad_out.to(torch.float32), ctx.scale), None
+
+
+def upsample2x_image(img, scale=1.0):
+    """scale * bilinear x2 upsampling of an image (B,h,w,C), C in 1..4, fp32 channels-last -> (B,2h,2w,C): the
+    reference's Upsample functor (non_layers.py:183-193) as the interpolator uses it on its 3-channel images
+    (pwcnet.py:108,124), one launch (qpwc_upsample2x_image_fwd).  Two channels come out with the bits of
+    upsample2x_flow().  Differentiable in img: with grad enabled and img requiring grad the same forward runs inside an
+    autograd Function whose backward is qpwc_upsample2x_image_bwd."""
+    if _wants_grad(img):
+        _refuse_capture("the image upsampling")
+        _image_check("img", img, "upsample2x_image")
+        return _UpsampleImageFn.apply(img, scale)
+    _image_check("img", img, "upsample2x_image")
+    x = img.contiguous()
+    B, h, w, C = x.shape
+    out = torch.empty((B, 2 * h, 2 * w, C), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("upsample2x_image", (B, h, w, C)):
+        rc = _hip.lib().qpwc_upsample2x_image_fwd(x.data_ptr(), out.data_ptr(), B, h, w, C, float(scale), _stream(x))
+    _hip.check(rc)
+    return out
+
+
+def avgpool_pyramid(x, levels):
+    """`levels` successive AvgPool2D(2, 'same') (non_layers.py:171-180) of x (B,H,W,C) fp32 channels-last, of which
+    only the last is returned, (B, ceil(H / 2^levels), ceil(W / 2^levels), C): how the interpolator brings its input
+    frames to the coarsest level (pwcnet.py:87-90, 101-102).  One launch (qpwc_avgpool_pyramid_fwd) for 1..4 channels
+    and H, W multiples of 2^levels; a shape the entry point refuses (QPWC_E_SHAPE) is pooled level by level by torch
+    with the clipped 'same' windows.  No gradient: the frames are data."""
+    _check_tensor("x", x)
+    if x.dtype != torch.float32:
+        raise ValueError("avgpool_pyramid has no fp16 storage path: x is {}".format(x.dtype))
+    if _wants_grad(x):
+        raise ValueError("avgpool_pyramid has no gradient: the frames it pools are data")
+    levels = int(levels)
+    if levels < 1 or x.numel() == 0:
+        raise ValueError("avgpool_pyramid takes levels >= 1 and a non-empty x, got {} and {}".format(
+            levels, tuple(x.shape)))
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    out = torch.empty((B, -(-H >> levels), -(-W >> levels), C), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("avgpool_pyramid", (B, H, W, C, levels)):
+        rc = _hip.lib().qpwc_avgpool_pyramid_fwd(x.data_ptr(), out.data_ptr(), B, H, W, C, levels, _stream(x))
+    if rc == _hip.E_SHAPE:
+        y = x.permute(0, 3, 1, 2)
+        for _ in range(levels):
+            y = torch.nn.functional.avg_pool2d(y, 2, stride=2, ceil_mode=True, count_include_pad=False)
+        return y.permute(0, 2, 3, 1).contiguous()
+    _hip.check(rc)
+    return out
+
+
 def _flow_dims(flow, data_format):
     get_axis(data_format)
     if flow.dim() != 4:
