@@ -22,27 +22,97 @@ E_NULL, E_LAYOUT, E_DTYPE, E_SHAPE, E_RANGE, E_MODE, E_ALIAS, E_LAUNCH, E_ALIGN,
     E_NODEVICE = range(-1, -12, -1)
 _ARGUMENT_ERRORS = {E_NULL, E_LAYOUT, E_DTYPE, E_SHAPE, E_RANGE, E_MODE, E_ALIAS, E_ALIGN, E_STRIDE}
 
-# every symbol include/qpwc.h declares
-SYMBOLS = (
-    "qpwc_version", "qpwc_last_error", "qpwc_strerror", "qpwc_build_info", "qpwc_device_copy", "qpwc_clock_probe", "qpwc_layout_transpose_fwd", "qpwc_copy_pixels_fwd",
-    "qpwc_cost_volume_fwd", "qpwc_cost_volume_fwd_strided", "qpwc_warp_fwd",
-    "qpwc_warp_cost_volume_fwd", "qpwc_cost_volume_kernel", "qpwc_epe_workspace_floats", "qpwc_epe_fwd",
-    "qpwc_dwconv3x3_fwd", "qpwc_flow_head_param_floats", "qpwc_flow_head_fwd", "qpwc_flow_head_up_fwd", "qpwc_pointwise_bias_fwd", "qpwc_optflow_tail_fwd", "qpwc_bias_mish_fwd",
-    "qpwc_upsample2x_flow_fwd", "qpwc_epe_multi_workspace_floats", "qpwc_epe_multi_fwd", "qpwc_epe_multi_mixed_fwd",
-    "qpwc_cost_volume_to_flow_fwd", "qpwc_sepconv3x3_fwd", "qpwc_sepconv3x3_f16_fwd", "qpwc_bias_mish_pad_fwd", "qpwc_split_frames_pad_fwd",
-    "qpwc_invert_flow_fwd", "qpwc_occlusion_fwd", "qpwc_conv3x3_mish_fwd", "qpwc_conv3x3_mish_f16_fwd", "qpwc_conv3x3_mish_x3_fwd", "qpwc_split_bf16x3_fwd", "qpwc_sepconv3x3_x3_fwd", "qpwc_conv3x3s2_mish_x3_fwd", "qpwc_upconv4x4s2_mish_x3_fwd",
-    "qpwc_first_conv_mish_fwd", "qpwc_first_conv_mish_f16_fwd", "qpwc_conv3x3s2_mish_fwd", "qpwc_conv3x3s2_mish_c_fwd", "qpwc_conv3x3s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_fwd", "qpwc_upconv4x4s2_mish_f16_fwd", "qpwc_upconv4x4s2_mish_cat_fwd", "qpwc_upconv4x4s2_mish_cat_f16_fwd",
-    "qpwc_cost_volume_bwd", "qpwc_warp_bwd_workspace_floats", "qpwc_warp_bwd",
-    "qpwc_loss_workspace_floats", "qpwc_loss_fwd", "qpwc_loss_fwd_kernel", "qpwc_loss_bwd",
-    "qpwc_sepconv3x3_bwd_workspace_floats", "qpwc_sepconv3x3_bwd",
-    "qpwc_flow_head_stats_workspace_floats", "qpwc_flow_head_stats_fwd", "qpwc_flow_head_bwd_workspace_floats",
-    "qpwc_flow_head_bwd", "qpwc_upsample2x_flow_bwd",
-    "qpwc_conv3x3_same_fwd", "qpwc_conv3x3_same_bwd_workspace_floats", "qpwc_conv3x3_same_bwd",
-    "qpwc_upconv4x4s2_bwd_workspace_floats", "qpwc_upconv4x4s2_bwd",
-    "qpwc_augment_workspace_floats", "qpwc_augment_fwd", "qpwc_augment_fwd_kernel",
-    "qpwc_image_head_fwd", "qpwc_image_head_bwd_workspace_floats", "qpwc_image_head_bwd",
-    "qpwc_upsample2x_image_fwd", "qpwc_upsample2x_image_bwd", "qpwc_avgpool_pyramid_fwd",
-)
+_vp, _ci, _cf, _i64, _str = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_char_p
+_pvp, _pi, _pi64 = ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_i64)
+_sepconv_fwd = [_pvp, _pi, _pi64, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]
+_upconv_fwd = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _vp]
+_upconv_cat_fwd = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _vp]
+
+# The C ABI, once: name -> (restype, argtypes) for every symbol include/qpwc.h declares, in the header's order.
+# lib() applies it; tests/test_capi_prototypes_cpu.py holds it to the header (an `int` where the header says
+# `int64_t` would corrupt an argument silently).
+PROTOTYPES = {
+    "qpwc_version": (_ci, []),
+    "qpwc_last_error": (_str, []),
+    "qpwc_strerror": (_str, [_ci]),
+    "qpwc_build_info": (_str, []),
+    "qpwc_layout_transpose_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_copy_pixels_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _pi64, _pi64, _ci, _vp]),
+    "qpwc_device_copy": (_ci, [_vp, _vp, _i64, _vp]),
+    "qpwc_clock_probe": (_ci, [_vp, _ci, _ci, _vp]),
+    "qpwc_cost_volume_fwd": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cf, _vp]),
+    "qpwc_cost_volume_fwd_strided": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cf, _i64, _i64, _vp]),
+    "qpwc_warp_fwd": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_cost_volume_bwd": (_ci, [_vp] * 6 + [_ci, _ci, _ci, _ci, _ci, _ci, _cf, _vp]),
+    "qpwc_warp_bwd_workspace_floats": (_i64, [_ci, _ci, _ci, _ci, _ci]),
+    "qpwc_warp_bwd": (_ci, [_vp] * 6 + [_ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_loss_workspace_floats": (_i64, [_ci, _ci, _ci, _ci, _ci, _pi, _pi, _ci]),
+    "qpwc_loss_fwd": (_ci, [_ci, _cf, _cf, _vp, _ci, _ci, _ci, _ci, _ci, _pvp, _pi, _pi, _pi, _ci, _vp, _pvp, _pvp,
+                            _vp, _vp]),
+    "qpwc_loss_fwd_kernel": (_str, [_ci, _vp, _ci, _ci, _ci, _ci, _pi, _pi, _ci]),
+    "qpwc_loss_bwd": (_ci, [_pvp, _vp, _pvp, _pi64, _pi, _ci, _vp]),
+    "qpwc_augment_workspace_floats": (_i64, [_ci, _ci, _ci]),
+    "qpwc_augment_fwd": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "qpwc_augment_fwd_kernel": (_str, [_ci, _ci, _ci, _vp, _vp]),
+    "qpwc_warp_cost_volume_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cf, _i64, _i64, _vp]),
+    "qpwc_cost_volume_kernel": (_str, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _i64, _ci]),
+    "qpwc_epe_workspace_floats": (_ci, []),
+    "qpwc_epe_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_epe_multi_workspace_floats": (_ci, []),
+    "qpwc_epe_multi_fwd": (_ci, [_pvp, _pvp, _pi64, _pi64, _ci, _vp, _vp, _vp]),
+    "qpwc_epe_multi_mixed_fwd": (_ci, [_pvp, _pvp, _pi64, _pi64, _pi, _ci, _vp, _vp, _vp]),
+    "qpwc_cost_volume_to_flow_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _i64, _ci, _ci, _vp]),
+    "qpwc_dwconv3x3_fwd": (_ci, [_pvp, _pi, _pi64, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_sepconv3x3_fwd": (_ci, _sepconv_fwd),
+    "qpwc_sepconv3x3_bwd_workspace_floats": (_i64, [_ci, _ci, _ci, _ci, _ci]),
+    "qpwc_sepconv3x3_bwd": (_ci, [_pvp, _pi, _pi64, _ci, _ci, _vp, _vp, _vp, _vp, _pvp, _vp, _vp, _vp, _vp,
+                                  _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_sepconv3x3_x3_fwd": (_ci, _sepconv_fwd),
+    "qpwc_sepconv3x3_f16_fwd": (_ci, _sepconv_fwd),
+    "qpwc_flow_head_param_floats": (_ci, []),
+    "qpwc_flow_head_fwd": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _cf, _ci, _ci, _vp]),
+    "qpwc_flow_head_stats_workspace_floats": (_i64, [_ci, _ci, _ci]),
+    "qpwc_flow_head_stats_fwd": (_ci, [_vp] * 8 + [_cf, _cf, _vp, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "qpwc_flow_head_bwd_workspace_floats": (_i64, [_ci, _ci, _ci]),
+    "qpwc_flow_head_bwd": (_ci, [_vp, _vp, _vp, _cf, _ci, _cf] + [_vp] * 8 + [_ci, _ci, _ci, _vp]),
+    "qpwc_pointwise_bias_fwd": (_ci, [_vp, _vp, _vp, _vp, _i64, _ci, _ci, _vp]),
+    "qpwc_flow_head_up_fwd": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _cf, _ci, _vp]),
+    "qpwc_optflow_tail_fwd": (_ci, [_vp] * 9 + [_ci, _ci, _ci, _cf, _ci, _ci, _vp]),
+    "qpwc_bias_mish_fwd": (_ci, [_vp, _vp, _i64, _ci, _ci, _vp]),
+    "qpwc_bias_mish_pad_fwd": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _i64, _ci, _vp]),
+    "qpwc_split_frames_pad_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_upsample2x_flow_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _cf, _ci, _ci, _ci, _vp]),
+    "qpwc_upsample2x_flow_bwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _cf, _vp]),
+    "qpwc_invert_flow_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_occlusion_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3_mish_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3_mish_x3_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_split_bf16x3_fwd": (_ci, [_vp, _vp, ctypes.c_longlong, _vp]),
+    "qpwc_conv3x3_mish_f16_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_first_conv_mish_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_first_conv_mish_f16_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3s2_mish_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3s2_mish_c_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3s2_mish_x3_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3s2_mish_f16_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3_same_fwd": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_conv3x3_same_bwd_workspace_floats": (_i64, [_ci, _ci, _ci, _ci, _ci, _ci]),
+    "qpwc_conv3x3_same_bwd": (_ci, [_vp] * 8 + [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_upconv4x4s2_mish_fwd": (_ci, _upconv_fwd),
+    "qpwc_upconv4x4s2_mish_x3_fwd": (_ci, _upconv_fwd),
+    "qpwc_upconv4x4s2_mish_f16_fwd": (_ci, _upconv_fwd),
+    "qpwc_upconv4x4s2_mish_cat_fwd": (_ci, _upconv_cat_fwd),
+    "qpwc_upconv4x4s2_mish_cat_f16_fwd": (_ci, _upconv_cat_fwd),
+    "qpwc_upconv4x4s2_bwd_workspace_floats": (_i64, [_ci, _ci, _ci, _ci, _ci]),
+    "qpwc_upconv4x4s2_bwd": (_ci, [_vp] * 4 + [_i64] + [_vp] * 4 + [_ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "qpwc_image_head_fwd": (_ci, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "qpwc_image_head_bwd_workspace_floats": (_i64, [_i64]),
+    "qpwc_image_head_bwd": (_ci, [_vp] * 7 + [_i64, _vp]),
+    "qpwc_upsample2x_image_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _cf, _vp]),
+    "qpwc_upsample2x_image_bwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _cf, _vp]),
+    "qpwc_avgpool_pyramid_fwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp]),
+}
+SYMBOLS = tuple(PROTOTYPES)
 
 _lib = None
 
@@ -75,167 +145,9 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
-    vp, ci, cf, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
-    L.qpwc_version.argtypes = []
-    L.qpwc_version.restype = ci
-    L.qpwc_last_error.argtypes = []
-    L.qpwc_last_error.restype = ctypes.c_char_p
-    L.qpwc_strerror.argtypes = [ci]
-    L.qpwc_strerror.restype = ctypes.c_char_p
-    L.qpwc_build_info.argtypes = []
-    L.qpwc_build_info.restype = ctypes.c_char_p
-    L.qpwc_layout_transpose_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_layout_transpose_fwd.restype = ci
-    L.qpwc_copy_pixels_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.POINTER(i64), ctypes.POINTER(i64), ci, vp]
-    L.qpwc_copy_pixels_fwd.restype = ci
-    L.qpwc_clock_probe.argtypes = [vp, ci, ci, vp]
-    L.qpwc_clock_probe.restype = ci
-    L.qpwc_device_copy.argtypes = [vp, vp, i64, vp]
-    L.qpwc_device_copy.restype = ci
-    L.qpwc_cost_volume_fwd.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp]
-    L.qpwc_cost_volume_fwd.restype = ci
-    L.qpwc_cost_volume_kernel.argtypes = [ci, ci, ci, ci, ci, ci, ci, i64, ci]
-    L.qpwc_cost_volume_kernel.restype = ctypes.c_char_p
-    L.qpwc_cost_volume_fwd_strided.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, i64, i64, vp]
-    L.qpwc_cost_volume_fwd_strided.restype = ci
-    L.qpwc_warp_fwd.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_warp_fwd.restype = ci
-    L.qpwc_warp_cost_volume_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, i64, i64, vp]
-    L.qpwc_warp_cost_volume_fwd.restype = ci
-    L.qpwc_epe_workspace_floats.argtypes = []
-    L.qpwc_epe_workspace_floats.restype = ci
-    L.qpwc_epe_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    L.qpwc_epe_fwd.restype = ci
-    L.qpwc_dwconv3x3_fwd.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(ci), ctypes.POINTER(i64),
-                                     ci, ci, vp, vp, ci, ci, ci, ci, vp]
-    L.qpwc_dwconv3x3_fwd.restype = ci
-    L.qpwc_flow_head_param_floats.argtypes = []
-    L.qpwc_flow_head_param_floats.restype = ci
-    L.qpwc_flow_head_fwd.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, vp]
-    L.qpwc_flow_head_fwd.restype = ci
-    L.qpwc_flow_head_up_fwd.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, cf, cf, ci, vp]
-    L.qpwc_flow_head_up_fwd.restype = ci
-    L.qpwc_pointwise_bias_fwd.argtypes = [vp, vp, vp, vp, i64, ci, ci, vp]
-    L.qpwc_pointwise_bias_fwd.restype = ci
-    L.qpwc_optflow_tail_fwd.argtypes = [vp] * 9 + [ci, ci, ci, cf, ci, ci, vp]
-    L.qpwc_optflow_tail_fwd.restype = ci
-    L.qpwc_bias_mish_fwd.argtypes = [vp, vp, i64, ci, ci, vp]
-    L.qpwc_bias_mish_fwd.restype = ci
-    L.qpwc_upsample2x_flow_fwd.argtypes = [vp, vp, ci, ci, ci, cf, ci, ci, ci, vp]
-    L.qpwc_upsample2x_flow_fwd.restype = ci
-    L.qpwc_epe_multi_workspace_floats.argtypes = []
-    L.qpwc_epe_multi_workspace_floats.restype = ci
-    L.qpwc_epe_multi_fwd.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
-                                     ctypes.POINTER(i64), ci, vp, vp, vp]
-    L.qpwc_epe_multi_fwd.restype = ci
-    L.qpwc_epe_multi_mixed_fwd.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
-                                           ctypes.POINTER(i64), ctypes.POINTER(ci), ci, vp, vp, vp]
-    L.qpwc_epe_multi_mixed_fwd.restype = ci
-    L.qpwc_sepconv3x3_fwd.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(ci), ctypes.POINTER(i64),
-                                      ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    L.qpwc_sepconv3x3_fwd.restype = ci
-    L.qpwc_sepconv3x3_f16_fwd.argtypes = L.qpwc_sepconv3x3_fwd.argtypes
-    L.qpwc_sepconv3x3_x3_fwd.argtypes = L.qpwc_sepconv3x3_fwd.argtypes
-    L.qpwc_sepconv3x3_x3_fwd.restype = ci
-    L.qpwc_cost_volume_to_flow_fwd.argtypes = [vp, vp, ci, ci, ci, ci, i64, ci, ci, vp]
-    L.qpwc_cost_volume_to_flow_fwd.restype = ci
-    L.qpwc_sepconv3x3_f16_fwd.restype = ci
-    L.qpwc_bias_mish_pad_fwd.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, i64, ci, vp]
-    L.qpwc_bias_mish_pad_fwd.restype = ci
-    L.qpwc_split_frames_pad_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_split_frames_pad_fwd.restype = ci
-    L.qpwc_invert_flow_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
-    L.qpwc_invert_flow_fwd.restype = ci
-    L.qpwc_occlusion_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
-    L.qpwc_occlusion_fwd.restype = ci
-    L.qpwc_conv3x3_mish_f16_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_conv3x3_mish_f16_fwd.restype = ci
-    L.qpwc_conv3x3_mish_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_conv3x3_mish_fwd.restype = ci
-    L.qpwc_conv3x3_mish_x3_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_conv3x3_mish_x3_fwd.restype = ci
-    L.qpwc_split_bf16x3_fwd.argtypes = [vp, vp, i64, vp]
-    L.qpwc_split_bf16x3_fwd.restype = ci
-    L.qpwc_first_conv_mish_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    L.qpwc_first_conv_mish_fwd.restype = ci
-    L.qpwc_first_conv_mish_f16_fwd.argtypes = L.qpwc_first_conv_mish_fwd.argtypes
-    L.qpwc_first_conv_mish_f16_fwd.restype = ci
-    L.qpwc_conv3x3s2_mish_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
-    L.qpwc_conv3x3s2_mish_fwd.restype = ci
-    L.qpwc_conv3x3s2_mish_c_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    L.qpwc_conv3x3s2_mish_c_fwd.restype = ci
-    L.qpwc_conv3x3s2_mish_f16_fwd.argtypes = L.qpwc_conv3x3s2_mish_c_fwd.argtypes
-    L.qpwc_conv3x3s2_mish_x3_fwd.argtypes = L.qpwc_conv3x3s2_mish_c_fwd.argtypes
-    L.qpwc_conv3x3s2_mish_x3_fwd.restype = ci
-    L.qpwc_conv3x3s2_mish_f16_fwd.restype = ci
-    L.qpwc_upconv4x4s2_mish_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, i64, vp]
-    L.qpwc_upconv4x4s2_mish_fwd.restype = ci
-    L.qpwc_upconv4x4s2_mish_f16_fwd.argtypes = L.qpwc_upconv4x4s2_mish_fwd.argtypes
-    L.qpwc_upconv4x4s2_mish_x3_fwd.argtypes = L.qpwc_upconv4x4s2_mish_fwd.argtypes
-    L.qpwc_upconv4x4s2_mish_x3_fwd.restype = ci
-    L.qpwc_upconv4x4s2_mish_f16_fwd.restype = ci
-    L.qpwc_upconv4x4s2_mish_cat_fwd.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, ci, ci, ci, ci, ci, i64, vp]
-    L.qpwc_upconv4x4s2_mish_cat_fwd.restype = ci
-    L.qpwc_upconv4x4s2_mish_cat_f16_fwd.argtypes = L.qpwc_upconv4x4s2_mish_cat_fwd.argtypes
-    L.qpwc_upconv4x4s2_mish_cat_f16_fwd.restype = ci
-    L.qpwc_cost_volume_bwd.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]
-    L.qpwc_cost_volume_bwd.restype = ci
-    L.qpwc_warp_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci]
-    L.qpwc_warp_bwd_workspace_floats.restype = i64
-    L.qpwc_warp_bwd.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_warp_bwd.restype = ci
-    pi, pvp = ctypes.POINTER(ci), ctypes.POINTER(vp)
-    L.qpwc_loss_workspace_floats.argtypes = [ci, ci, ci, ci, ci, pi, pi, ci]
-    L.qpwc_loss_workspace_floats.restype = i64
-    L.qpwc_loss_fwd.argtypes = [ci, cf, cf, vp, ci, ci, ci, ci, ci, pvp, pi, pi, pi, ci, vp, pvp, pvp, vp, vp]
-    L.qpwc_loss_fwd.restype = ci
-    L.qpwc_loss_fwd_kernel.argtypes = [ci, vp, ci, ci, ci, ci, pi, pi, ci]
-    L.qpwc_loss_fwd_kernel.restype = ctypes.c_char_p
-    L.qpwc_loss_bwd.argtypes = [pvp, vp, pvp, ctypes.POINTER(i64), pi, ci, vp]
-    L.qpwc_loss_bwd.restype = ci
-    L.qpwc_sepconv3x3_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci]
-    L.qpwc_sepconv3x3_bwd_workspace_floats.restype = i64
-    L.qpwc_sepconv3x3_bwd.argtypes = [pvp, pi, ctypes.POINTER(i64), ci, ci, vp, vp, vp, vp, pvp, vp, vp, vp, vp,
-                                      ci, ci, ci, ci, vp]
-    L.qpwc_sepconv3x3_bwd.restype = ci
-    L.qpwc_flow_head_stats_workspace_floats.argtypes = [ci, ci, ci]
-    L.qpwc_flow_head_stats_workspace_floats.restype = i64
-    L.qpwc_flow_head_stats_fwd.argtypes = [vp] * 8 + [cf, cf, vp, vp, vp, ci, ci, ci, vp]
-    L.qpwc_flow_head_stats_fwd.restype = ci
-    L.qpwc_flow_head_bwd_workspace_floats.argtypes = [ci, ci, ci]
-    L.qpwc_flow_head_bwd_workspace_floats.restype = i64
-    L.qpwc_flow_head_bwd.argtypes = [vp, vp, vp, cf, ci, cf, vp] + [vp] * 7 + [ci, ci, ci, vp]
-    L.qpwc_flow_head_bwd.restype = ci
-    L.qpwc_upsample2x_flow_bwd.argtypes = [vp, vp, ci, ci, ci, cf, vp]
-    L.qpwc_upsample2x_flow_bwd.restype = ci
-    L.qpwc_conv3x3_same_fwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_conv3x3_same_fwd.restype = ci
-    L.qpwc_conv3x3_same_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci, ci]
-    L.qpwc_conv3x3_same_bwd_workspace_floats.restype = i64
-    L.qpwc_conv3x3_same_bwd.argtypes = [vp] * 8 + [ci, ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_conv3x3_same_bwd.restype = ci
-    L.qpwc_upconv4x4s2_bwd_workspace_floats.argtypes = [ci, ci, ci, ci, ci]
-    L.qpwc_upconv4x4s2_bwd_workspace_floats.restype = i64
-    L.qpwc_upconv4x4s2_bwd.argtypes = [vp] * 4 + [i64] + [vp] * 4 + [ci, ci, ci, ci, ci, ci, vp]
-    L.qpwc_upconv4x4s2_bwd.restype = ci
-    L.qpwc_augment_workspace_floats.argtypes = [ci, ci, ci]
-    L.qpwc_augment_workspace_floats.restype = i64
-    L.qpwc_augment_fwd.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]
-    L.qpwc_augment_fwd.restype = ci
-    L.qpwc_augment_fwd_kernel.argtypes = [ci, ci, ci, vp, vp]
-    L.qpwc_augment_fwd_kernel.restype = ctypes.c_char_p
-    L.qpwc_image_head_fwd.argtypes = [vp, vp, vp, vp, i64, vp]
-    L.qpwc_image_head_fwd.restype = ci
-    L.qpwc_image_head_bwd_workspace_floats.argtypes = [i64]
-    L.qpwc_image_head_bwd_workspace_floats.restype = i64
-    L.qpwc_image_head_bwd.argtypes = [vp] * 7 + [i64, vp]
-    L.qpwc_image_head_bwd.restype = ci
-    L.qpwc_upsample2x_image_fwd.argtypes = [vp, vp, ci, ci, ci, ci, cf, vp]
-    L.qpwc_upsample2x_image_fwd.restype = ci
-    L.qpwc_upsample2x_image_bwd.argtypes = [vp, vp, ci, ci, ci, ci, cf, vp]
-    L.qpwc_upsample2x_image_bwd.restype = ci
-    L.qpwc_avgpool_pyramid_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
-    L.qpwc_avgpool_pyramid_fwd.restype = ci
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
     return L
 

@@ -12,6 +12,7 @@
 // never dword aligned) and, in the <vec4> form, the workgroup's 256 pixels leave through LDS in the output's own memory
 // order as 16-byte stores.  No atomics: two runs are bit-identical.
 #include "common.h"
+#include "launch.h"
 
 // a + (b - a) * t and u8 * (1/255) - 0.5 are separately rounded, as the reference's TF kernels round them
 #pragma clang fp contract(off)

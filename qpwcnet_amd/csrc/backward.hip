@@ -13,6 +13,7 @@
 //
 // Compiled with -ffp-contract=off semantics inside the helpers, like the forward (`#pragma clang fp contract(off)`).
 #include "common.h"
+#include "launch.h"
 
 namespace qpwc {
 

@@ -4,7 +4,9 @@
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "common.h"
+#include <initializer_list>
+
+#include "launch.h"
 
 namespace qpwc {
 
@@ -27,137 +29,6 @@ int check_launch(const char* what) {
     }
     return QPWC_OK;
 }
-
-int cost_volume_launch(const void* prv, const void* nxt, const void* flo, void* out, int B, int H,
-                       int W, int C, int r, int layout, int dtype, int64_t ops, float slope,
-                       bool fuse, bool pad84, hipStream_t s);
-int warp_launch(const void* img, const void* flo, void* out, int B, int H, int W, int C,
-                int flo_bcast_mask, int layout, int dtype, int mode, hipStream_t s);
-int epe_workspace_floats();
-int epe_launch(const float* a, const float* b, float* out, float* ws, int B, int H, int W,
-               int layout, hipStream_t s);
-
-int epe_multi_workspace_floats();
-int epe_multi_launch(const void* const* a, const void* const* b, const int64_t* npix, const int64_t* plane,
-                     const int* pred_dtype, int n_levels, float* out, float* ws, hipStream_t s);
-int layout_transpose_launch(const void* in, void* out, int B, int H, int W, int C, int to_layout, int dtype,
-                            hipStream_t s);
-int copy_pixels_launch(const void* src, void* dst, int B, int H, int W, int64_t row_bytes, int64_t sb, int64_t sy,
-                       int64_t sx, int64_t db, int64_t dy, int64_t dx, hipStream_t s);
-int dwconv3x3_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src,
-                     int act, const void* weight, void* out, int B, int H, int W, int dtype,
-                     hipStream_t s);
-int cost_volume_to_flow_launch(const void* cvol, float* flow, int B, int H, int W, int D, int64_t pix_stride,
-                               int layout, int dtype, hipStream_t s);
-int sepconv3x3_f16_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src, int act,
-                          const void* dw, const void* pw, const void* bias, void* out, int B, int H, int W,
-                          int F, hipStream_t s);
-int sepconv3x3_x3_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src, int act,
-                         const void* dw, const void* pw3, const void* bias, void* out, int B, int H, int W, int F,
-                         hipStream_t s);
-int sepconv3x3_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src,
-                      int act, const void* dw, const void* pw, const void* bias, void* out, int B, int H,
-                      int W, int F, hipStream_t s);
-int flow_head_launch(const void* z, const void* params, void* out, int B, int H, int W, float scale,
-                     int dtype, int out_layout, hipStream_t s);
-int flow_head_param_floats();
-int pointwise_bias_launch(const void* y, const void* w, const void* bias, void* out, int64_t M, int C, int cpad, int F,
-                          hipStream_t s);
-int flow_head_up_launch(const void* z, const void* params, void* out, void* out_up, void* out_up_f32, int B, int H, int W,
-                        float scale, float up_scale, int dtype, hipStream_t s);
-int optflow_tail_launch(const void* z2, const void* dw3, const void* pw3, const void* b3, const void* dw4,
-                        const void* pw4, const void* b4, const void* head, void* out, int B, int H, int W,
-                        float scale, int act_in, int out_layout, hipStream_t s);
-int upsample2x_flow_launch(const void* in, void* out, int B, int h, int w, float scale, int dtype,
-                           int in_layout, int out_layout, hipStream_t s);
-int bias_mish_pad_launch(const void* src, const void* bias, void* dst, int B, int H, int W, int C,
-                         int pad_h, int pad_w, int64_t dst_pixel_stride, int dtype, hipStream_t s);
-int split_frames_pad_launch(const void* in, void* out, int B, int H, int W, int pad_h, int pad_w, int dtype,
-                            hipStream_t s);
-int invert_flow_launch(const void* flow, void* out, int B, int H, int W, int layout, int dtype,
-                       hipStream_t s);
-int occlusion_launch(const void* flow, void* out, int B, int H, int W, int layout, int dtype,
-                     hipStream_t s);
-int upconv4x4s2_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W, int C,
-                            int F, int out_pixel_stride, hipStream_t s, const void* skip = nullptr, int64_t skip_bs = 0,
-                            int64_t skip_rs = 0, int64_t skip_ps = 0);
-int upconv4x4s2_mish_f16_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W, int C,
-                            int F, int out_pixel_stride, hipStream_t s, const void* skip = nullptr, int64_t skip_bs = 0,
-                            int64_t skip_rs = 0, int64_t skip_ps = 0);
-int conv3x3s2_mish_any_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
-                              int CI, hipStream_t s);
-int conv3x3s2_mish_f16_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
-                              int CI, hipStream_t s);
-int conv3x3_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
-                        int C, int pad_h, int pad_w, hipStream_t s);
-int conv3x3_mish_x3_launch(const void* x, const void* w3, const void* bias, void* out, int B, int H, int W, int C,
-                           int pad_h, int pad_w, hipStream_t s);
-int split_bf16x3_launch(const void* src, void* out, int64_t n, hipStream_t s);
-int conv3x3s2_mish_x3_launch(const void* x, const void* w3, const void* bias, void* out, int B, int H, int W, int CI,
-                             hipStream_t s);
-int upconv4x4s2_mish_x3_launch(const void* x, const void* w3, const void* bias, void* out, int B, int H, int W, int C,
-                               int F, int out_pixel_stride, hipStream_t s);
-int conv3x3_mish_f16_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
-                        int C, int pad_h, int pad_w, hipStream_t s);
-int first_conv_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
-                           int layout, int dtype, hipStream_t s);
-int conv3x3s2_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
-                          hipStream_t s);
-int bias_mish_launch(void* x, const void* bias, int64_t n_pixels, int C, int dtype, hipStream_t s);
-int cost_volume_bwd_launch(const void* prv, const void* nxt, const void* out, const void* gout, void* gprv,
-                           void* gnxt, int B, int H, int W, int C, int r, int dtype, float slope, hipStream_t s);
-int warp_bwd_launch(const void* img, const void* flo, const void* gout, void* gimg, void* gflo, void* ws, int B,
-                    int H, int W, int C, int dtype, int mode, hipStream_t s);
-int64_t loss_workspace_floats(int n_levels);
-const char* loss_fwd_kernel(int kind, int H, int W, const int* h, const int* w, int n, const void* gt);
-int loss_fwd_launch(int kind, float p0, float p1, const float* gt, int B, int H, int W, int C, int layout,
-                    const void* const* pred, const int* h, const int* w, const int* pred_dtype, int n, float* out,
-                    void* const* dpred, void* const* gt_out, float* ws, hipStream_t s);
-int64_t sepconv3x3_bwd_workspace_floats(int B, int H, int W, int C, int F);
-bool sepconv3x3_bwd_shape_ok(int B, int H, int W, int C, int F);
-int sepconv3x3_bwd_launch(const void* const* srcs, const int* chans, const int64_t* strides, int n_src, int flags,
-                          const void* dw, const void* pw, const void* bias, const void* gout, void* const* gsrc,
-                          void* gdw, void* gpw, void* gbias, void* ws, int B, int H, int W, int F, hipStream_t s);
-int64_t conv3x3_same_bwd_workspace_floats(int B, int H, int W, int cin, int cout, int s);
-bool conv3x3_same_shape_ok(int B, int H, int W, int cin, int cout, int s);
-int conv3x3_same_fwd_launch(const void* x, const void* w, const void* bias, void* out, int B, int H, int W, int cin,
-                            int cout, int stride, int mish, hipStream_t s);
-int conv3x3_same_bwd_launch(const void* x, const void* w, const void* bias, const void* gout, void* gx, void* gw,
-                            void* gb, void* ws, int B, int H, int W, int cin, int cout, int stride, int mish,
-                            hipStream_t s);
-int64_t upconv4x4s2_bwd_workspace_floats(int B, int H, int W, int C, int F);
-bool upconv4x4s2_bwd_shape_ok(int B, int H, int W, int C, int F);
-int upconv4x4s2_bwd_launch(const void* x, const void* w, const void* bias, const void* gout, int64_t gout_stride,
-                           void* gx, void* gw, void* gb, void* ws, int B, int H, int W, int C, int F, int mish,
-                           hipStream_t s);
-int64_t flow_head_stats_workspace_floats(int B, int H, int W);
-int64_t flow_head_bwd_workspace_floats(int B, int H, int W);
-int flow_head_stats_launch(const void* z, const void* w1, const void* b1, const void* gamma, const void* beta,
-                           const void* wf, void* moving_mean, void* moving_var, float momentum, float eps, void* params,
-                           void* stats, void* ws, int B, int H, int W, hipStream_t s);
-int flow_head_bwd_launch(const void* z, const void* params, const void* stats, float eps, int training, float scale,
-                         const void* gout, void* gz, void* gw1, void* gb1, void* ggamma, void* gbeta, void* gwf,
-                         void* ws, int B, int H, int W, hipStream_t s);
-int upsample2x_flow_bwd_launch(const void* gout, void* gin, int B, int h, int w, float scale, hipStream_t s);
-int loss_bwd_launch(const void* const* dpred, const float* grad_losses, void* const* grad_pred, const int64_t* n_elems,
-                    const int* pred_dtype, int n, hipStream_t s);
-
-int64_t augment_workspace_floats(int B, int h, int w);
-bool augment_shape_ok(int B, int H, int W, int h, int w);
-const char* augment_fwd_kernel(int h, int w, const void* out_ims, const void* out_flo);
-int augment_fwd_launch(const void* ims, bool u8, const float* flo, int B, int H, int W, const int* iparams,
-                       const float* fparams, int h, int w, int flags, int layout, float* out_ims, float* out_flo,
-                       float* ws, hipStream_t s);
-
-int64_t image_head_bwd_workspace_floats(int64_t M);
-int image_head_fwd_launch(const void* z, const void* w2, const void* b2, void* out, int64_t M, hipStream_t s);
-int image_head_bwd_launch(const void* z, const void* w2, const void* gout, void* gz, void* gw2, void* gb2, void* ws,
-                          int64_t M, hipStream_t s);
-int upsample2x_image_launch(const void* in, void* out, int B, int h, int w, int C, float scale, hipStream_t s);
-int upsample2x_image_bwd_launch(const void* gout, void* gin, int B, int h, int w, int C, float scale, hipStream_t s);
-int avgpool_pyramid_max_levels();
-int64_t avgpool_pyramid_tiles(int B, int H, int W, int levels, int* tw_out);
-int avgpool_pyramid_launch(const void* x, void* out, int B, int H, int W, int C, int levels, hipStream_t s);
 
 // 16-byte-per-lane streaming copy: the box's achievable HBM ceiling (read + write) for bench.py's roofline
 // block.  tools/micro/copybench.hip on MI355X: one float4 per thread over a one-shot grid with non-temporal
@@ -252,12 +123,29 @@ static int augment_check_shapes(int B, int H, int W, int h, int w) {
     return QPWC_OK;
 }
 
+// the first null pointer of a {pointer, name} list fails, by name
+struct PtrName {
+    const void* p;
+    const char* name;
+};
+static int check_nonnull(std::initializer_list<PtrName> need) {
+    for (const PtrName& a : need)
+        if (!a.p) return fail(QPWC_E_NULL, "%s is null", a.name);
+    return QPWC_OK;
+}
+
 // name, extent in bytes and required alignment of every buffer of an entry point: inputs first, then outputs
 struct BufCheck {
     const void* p;
     size_t n, align;
-    const char* name;
+    char name[16];
 };
+// a buffer whose name carries an index: src[1], grad_src[2]
+static BufCheck indexed_buf(const void* p, size_t n, size_t align, const char* fmt, int i) {
+    BufCheck b = {p, n, align, ""};
+    snprintf(b.name, sizeof(b.name), fmt, i);
+    return b;
+}
 // every buffer aligned; no output (index >= n_in) overlapping a buffer listed before it
 static int check_bufs(const BufCheck* b, int n_in, int n_all) {
     for (int k = 0; k < n_all; ++k)
@@ -643,8 +531,7 @@ int qpwc_augment_fwd(const void* ims, int ims_dtype, const void* flo, int B, int
         {out_flo, out_px * 2 * 4, 4, "out_flo"},
         {workspace, (size_t)augment_workspace_floats(B, h, w) * 4, 4, "workspace"},
     };
-    rc = check_bufs(bufs, 4, colour ? 7 : 6);
-    if (rc != QPWC_OK) return rc;
+    if ((rc = check_bufs(bufs, 4, colour ? 7 : 6)) != QPWC_OK) return rc;
     return augment_fwd_launch(ims, u8, (const float*)flo, B, H, W, (const int*)iparams, (const float*)fparams, h, w,
                               flags, layout, (float*)out_ims, (float*)out_flo, (float*)workspace,
                               (hipStream_t)stream);
@@ -692,10 +579,12 @@ int qpwc_dwconv3x3_fwd(const void* const* src, const int* src_channels,
                             H, W, dtype, (hipStream_t)stream);
 }
 
-int qpwc_sepconv3x3_fwd(const void* const* src, const int* src_channels,
-                        const int64_t* src_pixel_stride, int n_src, int mish_flags, const void* dw,
-                        const void* pw, const void* bias, void* out, int B, int H, int W, int F,
-                        void* stream) {
+// The fused SeparableConv2D forwards.  es: the element size of the sources and of out (4: fp32 and bf16x3, 2: fp16);
+// pw_name: what the messages call the pointwise operand.  The order is part of the contract: null, stride, alignment
+// and aliasing source by source, only then the alignment of out / pw / bias, and mish_flags last.
+static int sepconv_fwd_check(const void* const* src, const int* src_channels, const int64_t* src_pixel_stride, int n_src,
+                             int mish_flags, const void* dw, const void* pw, const void* bias, const void* out, int B,
+                             int H, int W, int F, size_t es, const char* pw_name) {
     if (!src || !src_channels || !src_pixel_stride || !dw || !pw || !bias || !out)
         return fail(QPWC_E_NULL, "null pointer argument");
     if (n_src < 1 || n_src > 3) return fail(QPWC_E_SHAPE, "n_src %d outside [1,3]", n_src);
@@ -704,18 +593,38 @@ int qpwc_sepconv3x3_fwd(const void* const* src, const int* src_channels,
     for (int i = 0; i < n_src; ++i) {
         if (!src[i]) return fail(QPWC_E_NULL, "null source %d", i);
         if (src_channels[i] <= 0 || src_pixel_stride[i] < src_channels[i])
-            return fail(QPWC_E_STRIDE, "source %d: %d channels at pixel stride %lld", i,
-                        src_channels[i], (long long)src_pixel_stride[i]);
-        if ((uintptr_t)src[i] % 4) return fail(QPWC_E_ALIGN, "source %d not 4-byte aligned", i);
-        if (overlaps(out, (size_t)B * H * W * F * 4, src[i],
-                     (((size_t)B * H * W - 1) * src_pixel_stride[i] + src_channels[i]) * 4))
+            return fail(QPWC_E_STRIDE, "source %d: %d channels at pixel stride %lld", i, src_channels[i],
+                        (long long)src_pixel_stride[i]);
+        if (es == 2) {
+            // 8-byte loads of 4 channels: every source but a short (< 4 channel) last one
+            const bool tail = i + 1 == n_src && src_channels[i] < 4;
+            if (!tail && (src_channels[i] % 4 || src_pixel_stride[i] % 4 || (uintptr_t)src[i] % 8))
+                return fail(QPWC_E_ALIGN, "source %d: %d channels at stride %lld must be multiples of 4, 8-byte aligned",
+                            i, src_channels[i], (long long)src_pixel_stride[i]);
+            if ((uintptr_t)src[i] % 2) return fail(QPWC_E_ALIGN, "source %d not element aligned", i);
+        } else if ((uintptr_t)src[i] % 4) {
+            return fail(QPWC_E_ALIGN, "source %d not 4-byte aligned", i);
+        }
+        if (overlaps(out, (size_t)B * H * W * F * es, src[i],
+                     (((size_t)B * H * W - 1) * src_pixel_stride[i] + src_channels[i]) * es))
             return fail(QPWC_E_ALIAS, "out overlaps source %d", i);
+        if (es == 2 && (int64_t)H * W * src_pixel_stride[i] > INT32_MAX) return fail(QPWC_E_SHAPE, "image too large");
     }
     if ((uintptr_t)out % 16 || (uintptr_t)pw % 16 || (uintptr_t)bias % 16 || (uintptr_t)dw % 4)
-        return fail(QPWC_E_ALIGN, "out, pw, bias must be 16-byte aligned");
+        return fail(QPWC_E_ALIGN, "out, %s, bias must be 16-byte aligned", pw_name);
     if (mish_flags < 0 || mish_flags > 3) return fail(QPWC_E_SHAPE, "mish_flags %d outside [0,3]", mish_flags);
-    return sepconv3x3_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, out, B,
-                             H, W, F, (hipStream_t)stream);
+    return QPWC_OK;
+}
+
+int qpwc_sepconv3x3_fwd(const void* const* src, const int* src_channels,
+                        const int64_t* src_pixel_stride, int n_src, int mish_flags, const void* dw,
+                        const void* pw, const void* bias, void* out, int B, int H, int W, int F,
+                        void* stream) {
+    const int rc = sepconv_fwd_check(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, out, B, H, W,
+                                     F, 4, "pw");
+    return rc != QPWC_OK ? rc
+                         : sepconv3x3_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, out,
+                                             B, H, W, F, (hipStream_t)stream);
 }
 
 static int sepconv_bwd_check_shape(int B, int H, int W, int64_t C, int F) {
@@ -736,14 +645,9 @@ int qpwc_sepconv3x3_bwd(const void* const* src, const int* src_channels, const i
                         int mish_flags, const void* dw, const void* pw, const void* bias, const void* grad_out,
                         void* const* grad_src, void* grad_dw, void* grad_pw, void* grad_bias, void* workspace, int B,
                         int H, int W, int F, void* stream) {
-    if (!src) return fail(QPWC_E_NULL, "src is null");
-    if (!src_channels) return fail(QPWC_E_NULL, "src_channels is null");
-    if (!src_pixel_stride) return fail(QPWC_E_NULL, "src_pixel_stride is null");
-    if (!dw) return fail(QPWC_E_NULL, "dw is null");
-    if (!pw) return fail(QPWC_E_NULL, "pw is null");
-    if (!bias) return fail(QPWC_E_NULL, "bias is null");
-    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
-    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
+    int rc = check_nonnull({{src, "src"}, {src_channels, "src_channels"}, {src_pixel_stride, "src_pixel_stride"},
+                            {dw, "dw"}, {pw, "pw"}, {bias, "bias"}, {grad_out, "grad_out"}, {workspace, "workspace"}});
+    if (rc != QPWC_OK) return rc;
     if (n_src < 1 || n_src > 3) return fail(QPWC_E_SHAPE, "n_src %d outside [1,3]", n_src);
     if (mish_flags < 0 || mish_flags > 3) return fail(QPWC_E_SHAPE, "mish_flags %d outside [0,3]", mish_flags);
     int64_t C = 0;
@@ -757,38 +661,25 @@ int qpwc_sepconv3x3_bwd(const void* const* src, const int* src_channels, const i
         any_out |= grad_src && grad_src[i];
     }
     if (!any_out) return fail(QPWC_E_NULL, "grad_src, grad_dw, grad_pw and grad_bias are all null");
-    int rc = sepconv_bwd_check_shape(B, H, W, C, F);
-    if (rc != QPWC_OK) return rc;
+    if ((rc = sepconv_bwd_check_shape(B, H, W, C, F)) != QPWC_OK) return rc;
     const size_t M = (size_t)B * H * W, cpad = (size_t)(C + 31) / 32 * 32;
-    // buffers: inputs first, then outputs; name, extent in bytes, required alignment
-    struct Buf { const void* p; size_t n; size_t align; char name[16]; };
-    Buf bufs[14];
-    int n_in = 0, n_all;
-    auto add = [&](int& k, const void* p, size_t n, size_t align, const char* fmt, int i) {
-        bufs[k].p = p; bufs[k].n = n; bufs[k].align = align;
-        snprintf(bufs[k].name, sizeof(bufs[k].name), fmt, i);
-        ++k;
-    };
+    BufCheck bufs[14];
+    int n_in = 0;
     for (int i = 0; i < n_src; ++i)
-        add(n_in, src[i], ((M - 1) * (size_t)src_pixel_stride[i] + src_channels[i]) * 4, 4, "src[%d]", i);
-    add(n_in, dw, (size_t)C * 9 * 4, 4, "dw", 0);
-    add(n_in, pw, (size_t)F * cpad * 4, 16, "pw", 0);
-    add(n_in, bias, (size_t)F * 4, 4, "bias", 0);
-    add(n_in, grad_out, M * F * 4, 16, "grad_out", 0);
-    n_all = n_in;
+        bufs[n_in++] = indexed_buf(src[i], ((M - 1) * (size_t)src_pixel_stride[i] + src_channels[i]) * 4, 4, "src[%d]", i);
+    bufs[n_in++] = {dw, (size_t)C * 9 * 4, 4, "dw"};
+    bufs[n_in++] = {pw, (size_t)F * cpad * 4, 16, "pw"};
+    bufs[n_in++] = {bias, (size_t)F * 4, 4, "bias"};
+    bufs[n_in++] = {grad_out, M * F * 4, 16, "grad_out"};
+    int n_all = n_in;
     for (int i = 0; i < n_src; ++i)
-        if (grad_src && grad_src[i]) add(n_all, grad_src[i], M * src_channels[i] * 4, 4, "grad_src[%d]", i);
-    if (grad_dw) add(n_all, grad_dw, (size_t)C * 9 * 4, 4, "grad_dw", 0);
-    if (grad_pw) add(n_all, grad_pw, (size_t)F * cpad * 4, 16, "grad_pw", 0);
-    if (grad_bias) add(n_all, grad_bias, (size_t)F * 4, 4, "grad_bias", 0);
-    add(n_all, workspace, (size_t)sepconv3x3_bwd_workspace_floats(B, H, W, (int)C, F) * 4, 16, "workspace", 0);
-    for (int k = 0; k < n_all; ++k)
-        if ((uintptr_t)bufs[k].p % bufs[k].align)
-            return fail(QPWC_E_ALIGN, "%s must be %d-byte aligned", bufs[k].name, (int)bufs[k].align);
-    for (int o = n_in; o < n_all; ++o)
-        for (int k = 0; k < o; ++k)
-            if (overlaps(bufs[o].p, bufs[o].n, bufs[k].p, bufs[k].n))
-                return fail(QPWC_E_ALIAS, "%s overlaps %s", bufs[o].name, bufs[k].name);
+        if (grad_src && grad_src[i])
+            bufs[n_all++] = indexed_buf(grad_src[i], M * src_channels[i] * 4, 4, "grad_src[%d]", i);
+    if (grad_dw) bufs[n_all++] = {grad_dw, (size_t)C * 9 * 4, 4, "grad_dw"};
+    if (grad_pw) bufs[n_all++] = {grad_pw, (size_t)F * cpad * 4, 16, "grad_pw"};
+    if (grad_bias) bufs[n_all++] = {grad_bias, (size_t)F * 4, 4, "grad_bias"};
+    bufs[n_all++] = {workspace, (size_t)sepconv3x3_bwd_workspace_floats(B, H, W, (int)C, F) * 4, 16, "workspace"};
+    if ((rc = check_bufs(bufs, n_in, n_all)) != QPWC_OK) return rc;
     return sepconv3x3_bwd_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, grad_out, grad_src,
                                  grad_dw, grad_pw, grad_bias, workspace, B, H, W, F, (hipStream_t)stream);
 }
@@ -796,57 +687,21 @@ int qpwc_sepconv3x3_bwd(const void* const* src, const int* src_channels, const i
 int qpwc_sepconv3x3_x3_fwd(const void* const* src, const int* src_channels, const int64_t* src_pixel_stride,
                            int n_src, int mish_flags, const void* dw, const void* pw3, const void* bias, void* out,
                            int B, int H, int W, int F, void* stream) {
-    if (!src || !src_channels || !src_pixel_stride || !dw || !pw3 || !bias || !out)
-        return fail(QPWC_E_NULL, "null pointer argument");
-    if (n_src < 1 || n_src > 3) return fail(QPWC_E_SHAPE, "n_src %d outside [1,3]", n_src);
-    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
-    if (F != 16 && F != 32 && F != 64 && F != 128) return fail(QPWC_E_SHAPE, "F=%d not in {16,32,64,128}", F);
-    for (int i = 0; i < n_src; ++i) {
-        if (!src[i]) return fail(QPWC_E_NULL, "null source %d", i);
-        if (src_channels[i] <= 0 || src_pixel_stride[i] < src_channels[i])
-            return fail(QPWC_E_STRIDE, "source %d: %d channels at pixel stride %lld", i, src_channels[i],
-                        (long long)src_pixel_stride[i]);
-        if ((uintptr_t)src[i] % 4) return fail(QPWC_E_ALIGN, "source %d not 4-byte aligned", i);
-        if (overlaps(out, (size_t)B * H * W * F * 4, src[i],
-                     (((size_t)B * H * W - 1) * src_pixel_stride[i] + src_channels[i]) * 4))
-            return fail(QPWC_E_ALIAS, "out overlaps source %d", i);
-    }
-    if ((uintptr_t)out % 16 || (uintptr_t)pw3 % 16 || (uintptr_t)bias % 16 || (uintptr_t)dw % 4)
-        return fail(QPWC_E_ALIGN, "out, pw3, bias must be 16-byte aligned");
-    if (mish_flags < 0 || mish_flags > 3) return fail(QPWC_E_SHAPE, "mish_flags %d outside [0,3]", mish_flags);
-    return sepconv3x3_x3_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw3, bias, out, B, H, W, F,
-                                (hipStream_t)stream);
+    const int rc = sepconv_fwd_check(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw3, bias, out, B, H,
+                                     W, F, 4, "pw3");
+    return rc != QPWC_OK ? rc
+                         : sepconv3x3_x3_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw3, bias,
+                                                out, B, H, W, F, (hipStream_t)stream);
 }
 
 int qpwc_sepconv3x3_f16_fwd(const void* const* src, const int* src_channels, const int64_t* src_pixel_stride,
                             int n_src, int mish_flags, const void* dw, const void* pw, const void* bias,
                             void* out, int B, int H, int W, int F, void* stream) {
-    if (!src || !src_channels || !src_pixel_stride || !dw || !pw || !bias || !out)
-        return fail(QPWC_E_NULL, "null pointer argument");
-    if (n_src < 1 || n_src > 3) return fail(QPWC_E_SHAPE, "n_src %d outside [1,3]", n_src);
-    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
-    if (F != 16 && F != 32 && F != 64 && F != 128) return fail(QPWC_E_SHAPE, "F=%d not in {16,32,64,128}", F);
-    for (int i = 0; i < n_src; ++i) {
-        if (!src[i]) return fail(QPWC_E_NULL, "null source %d", i);
-        if (src_channels[i] <= 0 || src_pixel_stride[i] < src_channels[i])
-            return fail(QPWC_E_STRIDE, "source %d: %d channels at pixel stride %lld", i, src_channels[i],
-                        (long long)src_pixel_stride[i]);
-        // 8-byte loads of 4 channels: every source but a short (< 4 channel) last one
-        const bool tail = i + 1 == n_src && src_channels[i] < 4;
-        if (!tail && (src_channels[i] % 4 || src_pixel_stride[i] % 4 || (uintptr_t)src[i] % 8))
-            return fail(QPWC_E_ALIGN, "source %d: %d channels at stride %lld must be multiples of 4, 8-byte aligned",
-                        i, src_channels[i], (long long)src_pixel_stride[i]);
-        if ((uintptr_t)src[i] % 2) return fail(QPWC_E_ALIGN, "source %d not element aligned", i);
-        if (overlaps(out, (size_t)B * H * W * F * 2, src[i],
-                     (((size_t)B * H * W - 1) * src_pixel_stride[i] + src_channels[i]) * 2))
-            return fail(QPWC_E_ALIAS, "out overlaps source %d", i);
-        if ((int64_t)H * W * src_pixel_stride[i] > INT32_MAX) return fail(QPWC_E_SHAPE, "image too large");
-    }
-    if ((uintptr_t)out % 16 || (uintptr_t)pw % 16 || (uintptr_t)bias % 16 || (uintptr_t)dw % 4)
-        return fail(QPWC_E_ALIGN, "out, pw, bias must be 16-byte aligned");
-    if (mish_flags < 0 || mish_flags > 3) return fail(QPWC_E_SHAPE, "mish_flags %d outside [0,3]", mish_flags);
-    return sepconv3x3_f16_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, out, B,
-                                 H, W, F, (hipStream_t)stream);
+    const int rc = sepconv_fwd_check(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias, out, B, H, W,
+                                     F, 2, "pw");
+    return rc != QPWC_OK ? rc
+                         : sepconv3x3_f16_launch(src, src_channels, src_pixel_stride, n_src, mish_flags, dw, pw, bias,
+                                                 out, B, H, W, F, (hipStream_t)stream);
 }
 
 int qpwc_pointwise_bias_fwd(const void* y, const void* weight, const void* bias, void* out, int64_t M, int C, int F,
@@ -909,13 +764,11 @@ int64_t qpwc_flow_head_stats_workspace_floats(int B, int H, int W) {
 int qpwc_flow_head_stats_fwd(const void* z, const void* w1, const void* b1, const void* gamma, const void* beta,
                              const void* wf, void* moving_mean, void* moving_var, float momentum, float eps,
                              void* params, void* stats, void* workspace, int B, int H, int W, void* stream) {
-    const struct { const void* p; const char* name; } need[] = {{z, "z"}, {w1, "w1"}, {b1, "b1"}, {gamma, "gamma"},
-        {beta, "beta"}, {wf, "wf"}, {params, "params"}, {workspace, "workspace"}};
-    for (const auto& a : need)
-        if (!a.p) return fail(QPWC_E_NULL, "%s is null", a.name);
-    if (!moving_mean != !moving_var) return fail(QPWC_E_NULL, "moving_mean and moving_var: both or neither");
-    int rc = flow_head_train_check_shape(B, H, W);
+    int rc = check_nonnull({{z, "z"}, {w1, "w1"}, {b1, "b1"}, {gamma, "gamma"}, {beta, "beta"}, {wf, "wf"},
+                            {params, "params"}, {workspace, "workspace"}});
     if (rc != QPWC_OK) return rc;
+    if (!moving_mean != !moving_var) return fail(QPWC_E_NULL, "moving_mean and moving_var: both or neither");
+    if ((rc = flow_head_train_check_shape(B, H, W)) != QPWC_OK) return rc;
     if (!(eps > 0.0f)) return fail(QPWC_E_RANGE, "eps %g must be positive", (double)eps);
     if (!(momentum >= 0.0f && momentum <= 1.0f)) return fail(QPWC_E_RANGE, "momentum %g outside [0,1]", (double)momentum);
     const size_t M = (size_t)B * H * W;
@@ -948,15 +801,12 @@ int64_t qpwc_flow_head_bwd_workspace_floats(int B, int H, int W) {
 int qpwc_flow_head_bwd(const void* z, const void* params, const void* stats, float eps, int training, float scale,
                        const void* grad_out, void* grad_z, void* grad_w1, void* grad_b1, void* grad_gamma,
                        void* grad_beta, void* grad_wf, void* workspace, int B, int H, int W, void* stream) {
-    if (!z) return fail(QPWC_E_NULL, "z is null");
-    if (!params) return fail(QPWC_E_NULL, "params is null");
-    if (!stats) return fail(QPWC_E_NULL, "stats is null");
-    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
-    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
+    int rc = check_nonnull({{z, "z"}, {params, "params"}, {stats, "stats"}, {grad_out, "grad_out"},
+                            {workspace, "workspace"}});
+    if (rc != QPWC_OK) return rc;
     if (!grad_z && !grad_w1 && !grad_b1 && !grad_gamma && !grad_beta && !grad_wf)
         return fail(QPWC_E_NULL, "grad_z, grad_w1, grad_b1, grad_gamma, grad_beta and grad_wf are all null");
-    int rc = flow_head_train_check_shape(B, H, W);
-    if (rc != QPWC_OK) return rc;
+    if ((rc = flow_head_train_check_shape(B, H, W)) != QPWC_OK) return rc;
     if (!(eps > 0.0f)) return fail(QPWC_E_RANGE, "eps %g must be positive", (double)eps);
     const size_t M = (size_t)B * H * W;
     BufCheck bufs[11];
@@ -979,14 +829,13 @@ int qpwc_flow_head_bwd(const void* z, const void* params, const void* stats, flo
 }
 
 int qpwc_upsample2x_flow_bwd(const void* grad_out, void* grad_in, int B, int h, int w, float scale, void* stream) {
-    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
-    if (!grad_in) return fail(QPWC_E_NULL, "grad_in is null");
+    int rc = check_nonnull({{grad_out, "grad_out"}, {grad_in, "grad_in"}});
+    if (rc != QPWC_OK) return rc;
     if (B <= 0 || h <= 0 || w <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d h=%d w=%d", B, h, w);
     if (h > (1 << 29) || w > (1 << 29)) return fail(QPWC_E_SHAPE, "h=%d w=%d: the doubled extents must fit an int", h, w);
     const size_t n = (size_t)B * h * w * 8;
     const BufCheck bufs[2] = {{grad_out, 4 * n, 8, "grad_out"}, {grad_in, n, 8, "grad_in"}};
-    const int rc = check_bufs(bufs, 1, 2);
-    if (rc != QPWC_OK) return rc;
+    if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
     return upsample2x_flow_bwd_launch(grad_out, grad_in, B, h, w, scale, (hipStream_t)stream);
 }
 
@@ -1063,47 +912,42 @@ int qpwc_upsample2x_flow_fwd(const void* in, void* out, int B, int h, int w, flo
 
 int qpwc_epe_multi_workspace_floats(void) { return epe_multi_workspace_floats(); }
 
-int qpwc_epe_multi_fwd(const void* const* y_true, const void* const* y_pred, const int64_t* n_pixels,
-                       const int64_t* plane_pixels, int n_levels, void* out_means, void* workspace,
-                       void* stream) {
-    if (!y_true || !y_pred || !n_pixels || !out_means || !workspace)
+// pred_dtype: one storage dtype per prediction (mixed), or null for all fp32
+static int epe_multi_checked(const void* const* y_true, const void* const* y_pred, const int64_t* n_pixels,
+                             const int64_t* plane_pixels, const int* pred_dtype, bool mixed, int n_levels,
+                             void* out_means, void* workspace, void* stream) {
+    if (!y_true || !y_pred || !n_pixels || (mixed && !pred_dtype) || !out_means || !workspace)
         return fail(QPWC_E_NULL, "null pointer argument");
     if (n_levels < 1 || n_levels > 8) return fail(QPWC_E_SHAPE, "n_levels %d outside [1,8]", n_levels);
     for (int i = 0; i < n_levels; ++i) {
         if (!y_true[i] || !y_pred[i]) return fail(QPWC_E_NULL, "null flow pointer at level %d", i);
-        if (n_pixels[i] <= 0) return fail(QPWC_E_SHAPE, "level %d has no pixels", i);
-        const bool planar = plane_pixels && plane_pixels[i] > 0;
-        if (planar && n_pixels[i] % plane_pixels[i])
-            return fail(QPWC_E_SHAPE, "level %d: %lld pixels are not whole planes of %lld", i,
-                        (long long)n_pixels[i], (long long)plane_pixels[i]);
-        if ((uintptr_t)y_true[i] % (planar ? 4 : 8) || (uintptr_t)y_pred[i] % (planar ? 4 : 8))
-            return fail(QPWC_E_ALIGN, "flow pointers must be 8-byte (pixels) / 4-byte (planes) aligned");
-    }
-    return epe_multi_launch(y_true, y_pred, n_pixels, plane_pixels, nullptr, n_levels, (float*)out_means,
-                            (float*)workspace, (hipStream_t)stream);
-}
-
-int qpwc_epe_multi_mixed_fwd(const void* const* y_true, const void* const* y_pred, const int64_t* n_pixels,
-                             const int64_t* plane_pixels, const int* pred_dtype, int n_levels, void* out_means,
-                             void* workspace, void* stream) {
-    if (!y_true || !y_pred || !n_pixels || !pred_dtype || !out_means || !workspace)
-        return fail(QPWC_E_NULL, "null pointer argument");
-    if (n_levels < 1 || n_levels > 8) return fail(QPWC_E_SHAPE, "n_levels %d outside [1,8]", n_levels);
-    for (int i = 0; i < n_levels; ++i) {
-        if (!y_true[i] || !y_pred[i]) return fail(QPWC_E_NULL, "null flow pointer at level %d", i);
-        if (pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
+        if (mixed && pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
             return fail(QPWC_E_DTYPE, "level %d: unsupported prediction dtype %d", i, pred_dtype[i]);
         if (n_pixels[i] <= 0) return fail(QPWC_E_SHAPE, "level %d has no pixels", i);
         const bool planar = plane_pixels && plane_pixels[i] > 0;
         if (planar && n_pixels[i] % plane_pixels[i])
             return fail(QPWC_E_SHAPE, "level %d: %lld pixels are not whole planes of %lld", i,
                         (long long)n_pixels[i], (long long)plane_pixels[i]);
-        const int pes = pred_dtype[i] == QPWC_F16 ? 2 : 4;
+        const int pes = mixed && pred_dtype[i] == QPWC_F16 ? 2 : 4;
         if ((uintptr_t)y_true[i] % (planar ? 4 : 8) || (uintptr_t)y_pred[i] % (planar ? pes : 2 * pes))
-            return fail(QPWC_E_ALIGN, "flow pointers must be aligned to a pixel (channels-last) / an element (planes)");
+            return fail(QPWC_E_ALIGN, mixed ? "flow pointers must be aligned to a pixel (channels-last) / an element (planes)"
+                                            : "flow pointers must be 8-byte (pixels) / 4-byte (planes) aligned");
     }
     return epe_multi_launch(y_true, y_pred, n_pixels, plane_pixels, pred_dtype, n_levels, (float*)out_means,
                             (float*)workspace, (hipStream_t)stream);
+}
+
+int qpwc_epe_multi_fwd(const void* const* y_true, const void* const* y_pred, const int64_t* n_pixels,
+                       const int64_t* plane_pixels, int n_levels, void* out_means, void* workspace,
+                       void* stream) {
+    return epe_multi_checked(y_true, y_pred, n_pixels, plane_pixels, nullptr, false, n_levels, out_means, workspace, stream);
+}
+
+int qpwc_epe_multi_mixed_fwd(const void* const* y_true, const void* const* y_pred, const int64_t* n_pixels,
+                             const int64_t* plane_pixels, const int* pred_dtype, int n_levels, void* out_means,
+                             void* workspace, void* stream) {
+    return epe_multi_checked(y_true, y_pred, n_pixels, plane_pixels, pred_dtype, true, n_levels, out_means, workspace,
+                             stream);
 }
 
 int qpwc_cost_volume_to_flow_fwd(const void* cvol, void* flow, int B, int H, int W, int D,
@@ -1151,18 +995,41 @@ int qpwc_occlusion_fwd(const void* flow, void* out, int B, int H, int W, int lay
     return occlusion_launch(flow, out, B, H, W, layout, dtype, (hipStream_t)stream);
 }
 
-int qpwc_conv3x3_mish_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H,
-                          int W, int C, int pad_h, int pad_w, void* stream) {
+// ---- The encoder and decoder forwards: one checker per layer, an export per arithmetic (fp32, bf16x3, fp16).
+// es: the element size of x and out (4: fp32 and bf16x3, 2: fp16); w_name: what the messages call the weight operand.
+
+static int conv3x3_mish_check(const void* x, const void* weight, const void* bias, const void* out, int B, int H, int W,
+                              int C, int pad_h, int pad_w, size_t es, const char* w_name) {
     if (!x || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
     if (C != 16 && C != 32 && C != 64 && C != 128 && C != 256)
         return fail(QPWC_E_SHAPE, "C=%d not in {16,32,64,128,256}", C);
     if (B <= 0 || H <= 0 || W <= 0 || pad_h < 0 || pad_w < 0 || pad_h > 8 || pad_w > 8)
         return fail(QPWC_E_SHAPE, "bad shape B=%d H=%d W=%d pad=%d,%d", B, H, W, pad_h, pad_w);
     if ((uintptr_t)x % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * (H + pad_h) * (W + pad_w) * C * 4, x, (size_t)B * H * W * C * 4))
+        return fail(QPWC_E_ALIGN, "x, %s, bias, out must be 16-byte aligned", w_name);
+    if (overlaps(out, (size_t)B * (H + pad_h) * (W + pad_w) * C * es, x, (size_t)B * H * W * C * es))
         return fail(QPWC_E_ALIAS, "out overlaps x");
-    return conv3x3_mish_launch(x, weight, bias, out, B, H, W, C, pad_h, pad_w, (hipStream_t)stream);
+    return QPWC_OK;
+}
+
+int qpwc_conv3x3_mish_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H,
+                          int W, int C, int pad_h, int pad_w, void* stream) {
+    const int rc = conv3x3_mish_check(x, weight, bias, out, B, H, W, C, pad_h, pad_w, 4, "weight");
+    return rc != QPWC_OK ? rc : conv3x3_mish_launch(x, weight, bias, out, B, H, W, C, pad_h, pad_w, (hipStream_t)stream);
+}
+
+int qpwc_conv3x3_mish_x3_fwd(const void* x, const void* weight3, const void* bias, void* out, int B, int H,
+                             int W, int C, int pad_h, int pad_w, void* stream) {
+    const int rc = conv3x3_mish_check(x, weight3, bias, out, B, H, W, C, pad_h, pad_w, 4, "weight3");
+    return rc != QPWC_OK ? rc
+                         : conv3x3_mish_x3_launch(x, weight3, bias, out, B, H, W, C, pad_h, pad_w, (hipStream_t)stream);
+}
+
+int qpwc_conv3x3_mish_f16_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H,
+                              int W, int C, int pad_h, int pad_w, void* stream) {
+    const int rc = conv3x3_mish_check(x, weight, bias, out, B, H, W, C, pad_h, pad_w, 2, "weight");
+    return rc != QPWC_OK ? rc
+                         : conv3x3_mish_f16_launch(x, weight, bias, out, B, H, W, C, pad_h, pad_w, (hipStream_t)stream);
 }
 
 static int conv_same_check_shape(int B, int H, int W, int C_in, int C_out, int stride) {
@@ -1179,12 +1046,9 @@ static int conv_same_check_shape(int B, int H, int W, int C_in, int C_out, int s
 
 int qpwc_conv3x3_same_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                           int C_in, int C_out, int stride, int mish, void* stream) {
-    if (!x) return fail(QPWC_E_NULL, "x is null");
-    if (!weight) return fail(QPWC_E_NULL, "weight is null");
-    if (!bias) return fail(QPWC_E_NULL, "bias is null");
-    if (!out) return fail(QPWC_E_NULL, "out is null");
-    int rc = conv_same_check_shape(B, H, W, C_in, C_out, stride);
+    int rc = check_nonnull({{x, "x"}, {weight, "weight"}, {bias, "bias"}, {out, "out"}});
     if (rc != QPWC_OK) return rc;
+    if ((rc = conv_same_check_shape(B, H, W, C_in, C_out, stride)) != QPWC_OK) return rc;
     if (mish != 0 && mish != 1) return fail(QPWC_E_SHAPE, "mish=%d not in {0,1}", mish);
     const size_t Ho = (size_t)(H + stride - 1) / stride, Wo = (size_t)(W + stride - 1) / stride;
     const size_t cp = (size_t)(C_in + 3) / 4 * 4;
@@ -1207,14 +1071,11 @@ int64_t qpwc_conv3x3_same_bwd_workspace_floats(int B, int H, int W, int C_in, in
 int qpwc_conv3x3_same_bwd(const void* x, const void* weight, const void* bias, const void* grad_out, void* grad_x,
                           void* grad_w, void* grad_b, void* workspace, int B, int H, int W, int C_in, int C_out,
                           int stride, int mish, void* stream) {
-    if (!x) return fail(QPWC_E_NULL, "x is null");
-    if (!weight) return fail(QPWC_E_NULL, "weight is null");
-    if (!bias) return fail(QPWC_E_NULL, "bias is null");
-    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
-    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
-    if (!grad_x && !grad_w && !grad_b) return fail(QPWC_E_NULL, "grad_x, grad_w and grad_b are all null");
-    int rc = conv_same_check_shape(B, H, W, C_in, C_out, stride);
+    int rc = check_nonnull({{x, "x"}, {weight, "weight"}, {bias, "bias"}, {grad_out, "grad_out"},
+                            {workspace, "workspace"}});
     if (rc != QPWC_OK) return rc;
+    if (!grad_x && !grad_w && !grad_b) return fail(QPWC_E_NULL, "grad_x, grad_w and grad_b are all null");
+    if ((rc = conv_same_check_shape(B, H, W, C_in, C_out, stride)) != QPWC_OK) return rc;
     if (mish != 0 && mish != 1) return fail(QPWC_E_SHAPE, "mish=%d not in {0,1}", mish);
     const size_t Ho = (size_t)(H + stride - 1) / stride, Wo = (size_t)(W + stride - 1) / stride;
     const size_t cp = (size_t)(C_in + 3) / 4 * 4, xa = C_in % 4 ? 4 : 16;
@@ -1252,14 +1113,11 @@ int64_t qpwc_upconv4x4s2_bwd_workspace_floats(int B, int H, int W, int C, int F)
 int qpwc_upconv4x4s2_bwd(const void* x, const void* weight, const void* bias, const void* grad_out,
                          int64_t grad_out_pixel_stride, void* grad_x, void* grad_w, void* grad_b, void* workspace,
                          int B, int H, int W, int C, int F, int mish, void* stream) {
-    if (!x) return fail(QPWC_E_NULL, "x is null");
-    if (!weight) return fail(QPWC_E_NULL, "weight is null");
-    if (!bias) return fail(QPWC_E_NULL, "bias is null");
-    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
-    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
-    if (!grad_x && !grad_w && !grad_b) return fail(QPWC_E_NULL, "grad_x, grad_w and grad_b are all null");
-    int rc = upconv_bwd_check_shape(B, H, W, C, F);
+    int rc = check_nonnull({{x, "x"}, {weight, "weight"}, {bias, "bias"}, {grad_out, "grad_out"},
+                            {workspace, "workspace"}});
     if (rc != QPWC_OK) return rc;
+    if (!grad_x && !grad_w && !grad_b) return fail(QPWC_E_NULL, "grad_x, grad_w and grad_b are all null");
+    if ((rc = upconv_bwd_check_shape(B, H, W, C, F)) != QPWC_OK) return rc;
     if (mish != 0 && mish != 1) return fail(QPWC_E_SHAPE, "mish=%d not in {0,1}", mish);
     if (grad_out_pixel_stride < F || grad_out_pixel_stride % 4 || grad_out_pixel_stride > ((int64_t)1 << 24))
         return fail(QPWC_E_SHAPE, "grad_out_pixel_stride=%lld must be a multiple of 4 in [F=%d, 2^24]", (long long)grad_out_pixel_stride,
@@ -1281,20 +1139,6 @@ int qpwc_upconv4x4s2_bwd(const void* x, const void* weight, const void* bias, co
                                   H, W, C, F, mish, (hipStream_t)stream);
 }
 
-int qpwc_conv3x3_mish_x3_fwd(const void* x, const void* weight3, const void* bias, void* out, int B, int H,
-                             int W, int C, int pad_h, int pad_w, void* stream) {
-    if (!x || !weight3 || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C != 16 && C != 32 && C != 64 && C != 128 && C != 256)
-        return fail(QPWC_E_SHAPE, "C=%d not in {16,32,64,128,256}", C);
-    if (B <= 0 || H <= 0 || W <= 0 || pad_h < 0 || pad_w < 0 || pad_h > 8 || pad_w > 8)
-        return fail(QPWC_E_SHAPE, "bad shape B=%d H=%d W=%d pad=%d,%d", B, H, W, pad_h, pad_w);
-    if ((uintptr_t)x % 16 || (uintptr_t)weight3 % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight3, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * (H + pad_h) * (W + pad_w) * C * 4, x, (size_t)B * H * W * C * 4))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return conv3x3_mish_x3_launch(x, weight3, bias, out, B, H, W, C, pad_h, pad_w, (hipStream_t)stream);
-}
-
 int qpwc_split_bf16x3_fwd(const void* src, void* out, long long n, void* stream) {
     if (!src || !out) return fail(QPWC_E_NULL, "null pointer argument");
     if (n <= 0 || n > ((long long)1 << 40)) return fail(QPWC_E_SHAPE, "n=%lld out of range", n);
@@ -1303,195 +1147,154 @@ int qpwc_split_bf16x3_fwd(const void* src, void* out, long long n, void* stream)
     return split_bf16x3_launch(src, out, (int64_t)n, (hipStream_t)stream);
 }
 
-int qpwc_conv3x3_mish_f16_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H,
-                              int W, int C, int pad_h, int pad_w, void* stream) {
-    if (!x || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C != 16 && C != 32 && C != 64 && C != 128 && C != 256)
-        return fail(QPWC_E_SHAPE, "C=%d not in {16,32,64,128,256}", C);
-    if (B <= 0 || H <= 0 || W <= 0 || pad_h < 0 || pad_w < 0 || pad_h > 8 || pad_w > 8)
-        return fail(QPWC_E_SHAPE, "bad shape B=%d H=%d W=%d pad=%d,%d", B, H, W, pad_h, pad_w);
-    if ((uintptr_t)x % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * (H + pad_h) * (W + pad_w) * C * 2, x, (size_t)B * H * W * C * 2))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return conv3x3_mish_f16_launch(x, weight, bias, out, B, H, W, C, pad_h, pad_w, (hipStream_t)stream);
+// pairs are read two elements, out is written four elements at a time
+static int first_conv_mish_checked(const void* pairs, const void* weight, const void* bias, void* out, int B, int H,
+                                   int W, int layout, int dtype, void* stream) {
+    if (!pairs || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: H and W must be even and >= 2", B, H, W);
+    const size_t es = esize(dtype);
+    if ((uintptr_t)pairs % (2 * es) || (uintptr_t)weight % 4 || (uintptr_t)bias % 16 || (uintptr_t)out % (4 * es))
+        return fail(QPWC_E_ALIGN, dtype == QPWC_F32 ? "pairs must be 8-byte, bias and out 16-byte aligned"
+                                                    : "pairs must be 4-byte, bias 16-byte and out 8-byte aligned");
+    if (overlaps(out, (size_t)2 * B * (H / 2) * (W / 2) * 16 * es, pairs, (size_t)B * H * W * 6 * es))
+        return fail(QPWC_E_ALIAS, "out overlaps pairs");
+    return first_conv_mish_launch(pairs, weight, bias, out, B, H, W, layout, dtype, (hipStream_t)stream);
 }
 
 int qpwc_first_conv_mish_fwd(const void* pairs, const void* weight, const void* bias, void* out, int B,
                              int H, int W, int layout, void* stream) {
-    if (!pairs || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
-    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1))
-        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: H and W must be even and >= 2", B, H, W);
-    if ((uintptr_t)pairs % 8 || (uintptr_t)weight % 4 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "pairs must be 8-byte, bias and out 16-byte aligned");
-    if (overlaps(out, (size_t)2 * B * (H / 2) * (W / 2) * 16 * 4, pairs, (size_t)B * H * W * 6 * 4))
-        return fail(QPWC_E_ALIAS, "out overlaps pairs");
-    return first_conv_mish_launch(pairs, weight, bias, out, B, H, W, layout, QPWC_F32, (hipStream_t)stream);
+    return first_conv_mish_checked(pairs, weight, bias, out, B, H, W, layout, QPWC_F32, stream);
 }
 
 int qpwc_first_conv_mish_f16_fwd(const void* pairs, const void* weight, const void* bias, void* out, int B,
                                  int H, int W, int layout, void* stream) {
-    if (!pairs || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    return first_conv_mish_checked(pairs, weight, bias, out, B, H, W, layout, QPWC_F16, stream);
+}
+
+// C_in a power of two in [c_min, 128]: c_min 16, or 32 for the bf16x3 form
+static int conv3x3s2_mish_check(const void* x_padded, const void* weight, const void* bias, const void* out, int B,
+                                int H, int W, int C_in, int c_min, size_t es, const char* w_name) {
+    if (!x_padded || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
+    if ((C_in != 16 && C_in != 32 && C_in != 64 && C_in != 128) || C_in < c_min)
+        return fail(QPWC_E_SHAPE, "C_in=%d not in {%s32,64,128}", C_in, c_min == 16 ? "16," : "");
     if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1))
         return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: H and W must be even and >= 2", B, H, W);
-    if ((uintptr_t)pairs % 4 || (uintptr_t)weight % 4 || (uintptr_t)bias % 16 || (uintptr_t)out % 8)
-        return fail(QPWC_E_ALIGN, "pairs must be 4-byte, bias 16-byte and out 8-byte aligned");
-    if (overlaps(out, (size_t)2 * B * (H / 2) * (W / 2) * 16 * 2, pairs, (size_t)B * H * W * 6 * 2))
-        return fail(QPWC_E_ALIAS, "out overlaps pairs");
-    return first_conv_mish_launch(pairs, weight, bias, out, B, H, W, layout, QPWC_F16, (hipStream_t)stream);
+    if ((uintptr_t)x_padded % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
+        return fail(QPWC_E_ALIGN, "x, %s, bias, out must be 16-byte aligned", w_name);
+    if (overlaps(out, (size_t)B * (H / 2) * (W / 2) * 2 * C_in * es, x_padded,
+                 (size_t)B * (H + 1) * (W + 1) * C_in * es))
+        return fail(QPWC_E_ALIAS, "out overlaps x");
+    return QPWC_OK;
 }
 
 int qpwc_conv3x3s2_mish_fwd(const void* x_padded, const void* weight, const void* bias, void* out, int B,
                             int H, int W, void* stream) {
-    if (!x_padded || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1))
-        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: H and W must be even and >= 2", B, H, W);
-    if ((uintptr_t)x_padded % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * (H / 2) * (W / 2) * 32 * 4, x_padded, (size_t)B * (H + 1) * (W + 1) * 16 * 4))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return conv3x3s2_mish_launch(x_padded, weight, bias, out, B, H, W, (hipStream_t)stream);
-}
-
-int qpwc_conv3x3s2_mish_x3_fwd(const void* x_padded, const void* weight3, const void* bias, void* out, int B,
-                               int H, int W, int C_in, void* stream) {
-    if (!x_padded || !weight3 || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C_in != 32 && C_in != 64 && C_in != 128) return fail(QPWC_E_SHAPE, "C_in=%d not in {32,64,128}", C_in);
-    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1))
-        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: H and W must be even and >= 2", B, H, W);
-    if ((uintptr_t)x_padded % 16 || (uintptr_t)weight3 % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight3, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * (H / 2) * (W / 2) * 2 * C_in * 4, x_padded,
-                 (size_t)B * (H + 1) * (W + 1) * C_in * 4))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return conv3x3s2_mish_x3_launch(x_padded, weight3, bias, out, B, H, W, C_in, (hipStream_t)stream);
+    const int rc = conv3x3s2_mish_check(x_padded, weight, bias, out, B, H, W, 16, 16, 4, "weight");
+    return rc != QPWC_OK ? rc : conv3x3s2_mish_launch(x_padded, weight, bias, out, B, H, W, (hipStream_t)stream);
 }
 
 int qpwc_conv3x3s2_mish_c_fwd(const void* x_padded, const void* weight, const void* bias, void* out, int B,
                               int H, int W, int C_in, void* stream) {
-    if (!x_padded || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C_in != 16 && C_in != 32 && C_in != 64 && C_in != 128)
-        return fail(QPWC_E_SHAPE, "C_in=%d not in {16,32,64,128}", C_in);
-    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1))
-        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: H and W must be even and >= 2", B, H, W);
-    if ((uintptr_t)x_padded % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * (H / 2) * (W / 2) * 2 * C_in * 4, x_padded,
-                 (size_t)B * (H + 1) * (W + 1) * C_in * 4))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return conv3x3s2_mish_any_launch(x_padded, weight, bias, out, B, H, W, C_in, (hipStream_t)stream);
+    const int rc = conv3x3s2_mish_check(x_padded, weight, bias, out, B, H, W, C_in, 16, 4, "weight");
+    return rc != QPWC_OK ? rc
+                         : conv3x3s2_mish_any_launch(x_padded, weight, bias, out, B, H, W, C_in, (hipStream_t)stream);
+}
+
+int qpwc_conv3x3s2_mish_x3_fwd(const void* x_padded, const void* weight3, const void* bias, void* out, int B,
+                               int H, int W, int C_in, void* stream) {
+    const int rc = conv3x3s2_mish_check(x_padded, weight3, bias, out, B, H, W, C_in, 32, 4, "weight3");
+    return rc != QPWC_OK ? rc
+                         : conv3x3s2_mish_x3_launch(x_padded, weight3, bias, out, B, H, W, C_in, (hipStream_t)stream);
 }
 
 int qpwc_conv3x3s2_mish_f16_fwd(const void* x_padded, const void* weight, const void* bias, void* out, int B,
                                 int H, int W, int C_in, void* stream) {
-    if (!x_padded || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C_in != 16 && C_in != 32 && C_in != 64 && C_in != 128)
-        return fail(QPWC_E_SHAPE, "C_in=%d not in {16,32,64,128}", C_in);
-    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1))
-        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: H and W must be even and >= 2", B, H, W);
-    if ((uintptr_t)x_padded % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * (H / 2) * (W / 2) * 2 * C_in * 2, x_padded,
-                 (size_t)B * (H + 1) * (W + 1) * C_in * 2))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return conv3x3s2_mish_f16_launch(x_padded, weight, bias, out, B, H, W, C_in, (hipStream_t)stream);
+    const int rc = conv3x3s2_mish_check(x_padded, weight, bias, out, B, H, W, C_in, 16, 2, "weight");
+    return rc != QPWC_OK ? rc
+                         : conv3x3s2_mish_f16_launch(x_padded, weight, bias, out, B, H, W, C_in, (hipStream_t)stream);
 }
 
-int qpwc_upconv4x4s2_mish_x3_fwd(const void* x, const void* weight3, const void* bias, void* out, int B, int H, int W,
-                                 int C, int F, int64_t out_pixel_stride, void* stream) {
-    if (!x || !weight3 || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
+// UpConv, alone (skip == nullptr, cat == false) or with the skip half of concat([up, skip]) in the same launch
+// (include/qpwc.h): with a skip the pixel holds 2 F channels, and skip is checked like out
+static int upconv_check(const void* x, const void* weight, const void* bias, const void* skip, bool cat, int64_t skip_bs,
+                        int64_t skip_rs, int64_t skip_ps, const void* out, int B, int H, int W, int C, int F,
+                        int64_t out_pixel_stride, size_t es, const char* w_name) {
+    if (!x || !weight || !bias || !out || (cat && !skip)) return fail(QPWC_E_NULL, "null pointer argument");
     if (C != 64 && C != 128 && C != 256) return fail(QPWC_E_SHAPE, "C=%d not in {64,128,256}", C);
     if (F <= 0 || F % 16) return fail(QPWC_E_SHAPE, "F=%d must be a positive multiple of 16", F);
     if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
-    if (out_pixel_stride < F || out_pixel_stride % 4 || out_pixel_stride > (1 << 20))
-        return fail(QPWC_E_STRIDE, "out_pixel_stride %lld must be >= F and a multiple of 4", (long long)out_pixel_stride);
-    if ((uintptr_t)x % 16 || (uintptr_t)weight3 % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight3, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * 4 * H * W * out_pixel_stride * 4, x, (size_t)B * H * W * C * 4))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return upconv4x4s2_mish_x3_launch(x, weight3, bias, out, B, H, W, C, F, (int)out_pixel_stride, (hipStream_t)stream);
+    if (out_pixel_stride < (cat ? 2 : 1) * (int64_t)F || out_pixel_stride % 4 || out_pixel_stride > (1 << 20))
+        return fail(QPWC_E_STRIDE, "out_pixel_stride %lld must be >= %s and a multiple of 4", (long long)out_pixel_stride,
+                    cat ? "2 F" : "F");
+    if (cat && (skip_ps < F || skip_ps % 4 || skip_rs % 4 || skip_bs % 4 || skip_rs < 2 * (int64_t)W * skip_ps ||
+                skip_bs < 2 * (int64_t)H * skip_rs))
+        return fail(QPWC_E_STRIDE, "skip strides (%lld, %lld, %lld) must describe (B, 2H, 2W, >= F) in multiples of 4 elements",
+                    (long long)skip_bs, (long long)skip_rs, (long long)skip_ps);
+    const int oa = es == 4 ? 16 : 8;
+    if ((uintptr_t)x % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % oa ||
+        (cat && (uintptr_t)skip % oa)) {
+        if (cat) return fail(QPWC_E_ALIGN, "x, weight, bias must be 16-byte aligned, out and skip %d-byte", oa);
+        if (es == 2) return fail(QPWC_E_ALIGN, "x, weight, bias must be 16-byte aligned, out 8-byte");
+        return fail(QPWC_E_ALIGN, "x, %s, bias, out must be 16-byte aligned", w_name);
+    }
+    const size_t out_bytes = (size_t)B * 4 * H * W * out_pixel_stride * es;
+    if (overlaps(out, out_bytes, x, (size_t)B * H * W * C * es)) return fail(QPWC_E_ALIAS, "out overlaps x");
+    if (cat && overlaps(out, out_bytes, skip, (size_t)B * skip_bs * es)) return fail(QPWC_E_ALIAS, "out overlaps skip");
+    return QPWC_OK;
 }
 
 int qpwc_upconv4x4s2_mish_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                               int C, int F, int64_t out_pixel_stride, void* stream) {
-    if (!x || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C != 64 && C != 128 && C != 256) return fail(QPWC_E_SHAPE, "C=%d not in {64,128,256}", C);
-    if (F <= 0 || F % 16) return fail(QPWC_E_SHAPE, "F=%d must be a positive multiple of 16", F);
-    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
-    if (out_pixel_stride < F || out_pixel_stride % 4 || out_pixel_stride > (1 << 20))
-        return fail(QPWC_E_STRIDE, "out_pixel_stride %lld must be >= F and a multiple of 4", (long long)out_pixel_stride);
-    if ((uintptr_t)x % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 16)
-        return fail(QPWC_E_ALIGN, "x, weight, bias, out must be 16-byte aligned");
-    if (overlaps(out, (size_t)B * 4 * H * W * out_pixel_stride * 4, x, (size_t)B * H * W * C * 4))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return upconv4x4s2_mish_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride, (hipStream_t)stream);
+    const int rc = upconv_check(x, weight, bias, nullptr, false, 0, 0, 0, out, B, H, W, C, F, out_pixel_stride, 4, "weight");
+    return rc != QPWC_OK ? rc
+                         : upconv4x4s2_mish_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride,
+                                                   (hipStream_t)stream);
+}
+
+int qpwc_upconv4x4s2_mish_x3_fwd(const void* x, const void* weight3, const void* bias, void* out, int B, int H, int W,
+                                 int C, int F, int64_t out_pixel_stride, void* stream) {
+    const int rc = upconv_check(x, weight3, bias, nullptr, false, 0, 0, 0, out, B, H, W, C, F, out_pixel_stride, 4, "weight3");
+    return rc != QPWC_OK ? rc
+                         : upconv4x4s2_mish_x3_launch(x, weight3, bias, out, B, H, W, C, F, (int)out_pixel_stride,
+                                                      (hipStream_t)stream);
 }
 
 int qpwc_upconv4x4s2_mish_f16_fwd(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                                   int C, int F, int64_t out_pixel_stride, void* stream) {
-    if (!x || !weight || !bias || !out) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C != 64 && C != 128 && C != 256) return fail(QPWC_E_SHAPE, "C=%d not in {64,128,256}", C);
-    if (F <= 0 || F % 16) return fail(QPWC_E_SHAPE, "F=%d must be a positive multiple of 16", F);
-    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
-    if (out_pixel_stride < F || out_pixel_stride % 4 || out_pixel_stride > (1 << 20))
-        return fail(QPWC_E_STRIDE, "out_pixel_stride %lld must be >= F and a multiple of 4", (long long)out_pixel_stride);
-    if ((uintptr_t)x % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % 8)
-        return fail(QPWC_E_ALIGN, "x, weight, bias must be 16-byte aligned, out 8-byte");
-    if (overlaps(out, (size_t)B * 4 * H * W * out_pixel_stride * 2, x, (size_t)B * H * W * C * 2))
-        return fail(QPWC_E_ALIAS, "out overlaps x");
-    return upconv4x4s2_mish_f16_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride, (hipStream_t)stream);
-}
-
-// UpConv + the skip half of concat([up, skip]) in one launch (round 4; include/qpwc.h)
-static int upconv_cat_common(const void* x, const void* weight, const void* bias, const void* skip, int64_t skip_bs,
-                             int64_t skip_rs, int64_t skip_ps, void* out, int B, int H, int W, int C, int F,
-                             int64_t out_pixel_stride, void* stream, int esize) {
-    if (!x || !weight || !bias || !out || !skip) return fail(QPWC_E_NULL, "null pointer argument");
-    if (C != 64 && C != 128 && C != 256) return fail(QPWC_E_SHAPE, "C=%d not in {64,128,256}", C);
-    if (F <= 0 || F % 16) return fail(QPWC_E_SHAPE, "F=%d must be a positive multiple of 16", F);
-    if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
-    if (out_pixel_stride < 2 * (int64_t)F || out_pixel_stride % 4 || out_pixel_stride > (1 << 20))
-        return fail(QPWC_E_STRIDE, "out_pixel_stride %lld must be >= 2 F and a multiple of 4", (long long)out_pixel_stride);
-    if (skip_ps < F || skip_ps % 4 || skip_rs % 4 || skip_bs % 4 || skip_rs < 2 * (int64_t)W * skip_ps ||
-        skip_bs < 2 * (int64_t)H * skip_rs)
-        return fail(QPWC_E_STRIDE, "skip strides (%lld, %lld, %lld) must describe (B, 2H, 2W, >= F) in multiples of 4 elements",
-                    (long long)skip_bs, (long long)skip_rs, (long long)skip_ps);
-    const int oa = esize == 4 ? 16 : 8;
-    if ((uintptr_t)x % 16 || (uintptr_t)weight % 16 || (uintptr_t)bias % 16 || (uintptr_t)out % oa || (uintptr_t)skip % oa)
-        return fail(QPWC_E_ALIGN, "x, weight, bias must be 16-byte aligned, out and skip %d-byte", oa);
-    const size_t out_bytes = (size_t)B * 4 * H * W * out_pixel_stride * esize;
-    if (overlaps(out, out_bytes, x, (size_t)B * H * W * C * esize)) return fail(QPWC_E_ALIAS, "out overlaps x");
-    if (overlaps(out, out_bytes, skip, (size_t)B * skip_bs * esize)) return fail(QPWC_E_ALIAS, "out overlaps skip");
-    if (esize == 4)
-        return upconv4x4s2_mish_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride, (hipStream_t)stream, skip,
-                                       skip_bs, skip_rs, skip_ps);
-    return upconv4x4s2_mish_f16_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride, (hipStream_t)stream, skip,
-                                       skip_bs, skip_rs, skip_ps);
+    const int rc = upconv_check(x, weight, bias, nullptr, false, 0, 0, 0, out, B, H, W, C, F, out_pixel_stride, 2, "weight");
+    return rc != QPWC_OK ? rc
+                         : upconv4x4s2_mish_f16_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride,
+                                                       (hipStream_t)stream);
 }
 
 int qpwc_upconv4x4s2_mish_cat_fwd(const void* x, const void* weight, const void* bias, const void* skip,
                                   int64_t skip_batch_stride, int64_t skip_row_stride, int64_t skip_pixel_stride, void* out,
                                   int B, int H, int W, int C, int F, int64_t out_pixel_stride, void* stream) {
-    return upconv_cat_common(x, weight, bias, skip, skip_batch_stride, skip_row_stride, skip_pixel_stride, out, B, H, W, C, F,
-                             out_pixel_stride, stream, 4);
+    const int rc = upconv_check(x, weight, bias, skip, true, skip_batch_stride, skip_row_stride, skip_pixel_stride, out, B,
+                                H, W, C, F, out_pixel_stride, 4, "weight");
+    return rc != QPWC_OK ? rc
+                         : upconv4x4s2_mish_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride,
+                                                   (hipStream_t)stream, skip, skip_batch_stride, skip_row_stride,
+                                                   skip_pixel_stride);
 }
 
 int qpwc_upconv4x4s2_mish_cat_f16_fwd(const void* x, const void* weight, const void* bias, const void* skip,
                                       int64_t skip_batch_stride, int64_t skip_row_stride, int64_t skip_pixel_stride, void* out,
                                       int B, int H, int W, int C, int F, int64_t out_pixel_stride, void* stream) {
-    return upconv_cat_common(x, weight, bias, skip, skip_batch_stride, skip_row_stride, skip_pixel_stride, out, B, H, W, C, F,
-                             out_pixel_stride, stream, 2);
+    const int rc = upconv_check(x, weight, bias, skip, true, skip_batch_stride, skip_row_stride, skip_pixel_stride, out, B,
+                                H, W, C, F, out_pixel_stride, 2, "weight");
+    return rc != QPWC_OK ? rc
+                         : upconv4x4s2_mish_f16_launch(x, weight, bias, out, B, H, W, C, F, (int)out_pixel_stride,
+                                                       (hipStream_t)stream, skip, skip_batch_stride, skip_row_stride,
+                                                       skip_pixel_stride);
 }
 
 int qpwc_image_head_fwd(const void* z, const void* w2, const void* b2, void* out, int64_t M, void* stream) {
-    if (!z) return fail(QPWC_E_NULL, "z is null");
-    if (!w2) return fail(QPWC_E_NULL, "w2 is null");
-    if (!b2) return fail(QPWC_E_NULL, "b2 is null");
-    if (!out) return fail(QPWC_E_NULL, "out is null");
-    int rc = image_head_check_m(M);
+    int rc = check_nonnull({{z, "z"}, {w2, "w2"}, {b2, "b2"}, {out, "out"}});
     if (rc != QPWC_OK) return rc;
+    if ((rc = image_head_check_m(M)) != QPWC_OK) return rc;
     const BufCheck bufs[4] = {{z, (size_t)M * 256, 16, "z"}, {w2, 768, 16, "w2"}, {b2, 12, 4, "b2"},
                               {out, (size_t)M * 12, 4, "out"}};
     if ((rc = check_bufs(bufs, 3, 4)) != QPWC_OK) return rc;
@@ -1505,13 +1308,10 @@ int64_t qpwc_image_head_bwd_workspace_floats(int64_t M) {
 
 int qpwc_image_head_bwd(const void* z, const void* w2, const void* grad_out, void* grad_z, void* grad_w2,
                         void* grad_b2, void* workspace, int64_t M, void* stream) {
-    if (!z) return fail(QPWC_E_NULL, "z is null");
-    if (!w2) return fail(QPWC_E_NULL, "w2 is null");
-    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
-    if (!workspace) return fail(QPWC_E_NULL, "workspace is null");
-    if (!grad_z && !grad_w2 && !grad_b2) return fail(QPWC_E_NULL, "grad_z, grad_w2 and grad_b2 are all null");
-    int rc = image_head_check_m(M);
+    int rc = check_nonnull({{z, "z"}, {w2, "w2"}, {grad_out, "grad_out"}, {workspace, "workspace"}});
     if (rc != QPWC_OK) return rc;
+    if (!grad_z && !grad_w2 && !grad_b2) return fail(QPWC_E_NULL, "grad_z, grad_w2 and grad_b2 are all null");
+    if ((rc = image_head_check_m(M)) != QPWC_OK) return rc;
     BufCheck bufs[7];
     int n_in = 0;
     bufs[n_in++] = {z, (size_t)M * 256, 16, "z"};
@@ -1527,10 +1327,9 @@ int qpwc_image_head_bwd(const void* z, const void* w2, const void* grad_out, voi
 }
 
 int qpwc_upsample2x_image_fwd(const void* in, void* out, int B, int h, int w, int C, float scale, void* stream) {
-    if (!in) return fail(QPWC_E_NULL, "in is null");
-    if (!out) return fail(QPWC_E_NULL, "out is null");
-    int rc = upsample2x_image_check_shape(B, h, w, C);
+    int rc = check_nonnull({{in, "in"}, {out, "out"}});
     if (rc != QPWC_OK) return rc;
+    if ((rc = upsample2x_image_check_shape(B, h, w, C)) != QPWC_OK) return rc;
     const size_t n = (size_t)B * h * w * C * 4;
     const BufCheck bufs[2] = {{in, n, 4, "in"}, {out, 4 * n, (size_t)(C == 4 ? 16 : C == 2 ? 8 : 4), "out"}};
     if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
@@ -1539,10 +1338,9 @@ int qpwc_upsample2x_image_fwd(const void* in, void* out, int B, int h, int w, in
 
 int qpwc_upsample2x_image_bwd(const void* grad_out, void* grad_in, int B, int h, int w, int C, float scale,
                               void* stream) {
-    if (!grad_out) return fail(QPWC_E_NULL, "grad_out is null");
-    if (!grad_in) return fail(QPWC_E_NULL, "grad_in is null");
-    int rc = upsample2x_image_check_shape(B, h, w, C);
+    int rc = check_nonnull({{grad_out, "grad_out"}, {grad_in, "grad_in"}});
     if (rc != QPWC_OK) return rc;
+    if ((rc = upsample2x_image_check_shape(B, h, w, C)) != QPWC_OK) return rc;
     const size_t n = (size_t)B * h * w * C * 4;
     const BufCheck bufs[2] = {{grad_out, 4 * n, 4, "grad_out"}, {grad_in, n, 4, "grad_in"}};
     if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
@@ -1550,8 +1348,8 @@ int qpwc_upsample2x_image_bwd(const void* grad_out, void* grad_in, int B, int h,
 }
 
 int qpwc_avgpool_pyramid_fwd(const void* x, void* out, int B, int H, int W, int C, int levels, void* stream) {
-    if (!x) return fail(QPWC_E_NULL, "x is null");
-    if (!out) return fail(QPWC_E_NULL, "out is null");
+    int rc = check_nonnull({{x, "x"}, {out, "out"}});
+    if (rc != QPWC_OK) return rc;
     if (B <= 0 || H <= 0 || W <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
     if (C < 1 || C > 4) return fail(QPWC_E_SHAPE, "C=%d outside 1..4", C);
     if (levels < 1 || levels > avgpool_pyramid_max_levels())
@@ -1562,8 +1360,7 @@ int qpwc_avgpool_pyramid_fwd(const void* x, void* out, int B, int H, int W, int 
         return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d levels=%d: the launch grid overflows 32 bits", B, H, W, levels);
     const size_t n = (size_t)B * H * W * C * 4;
     const BufCheck bufs[2] = {{x, n, 8, "x"}, {out, n >> (2 * levels), 4, "out"}};
-    const int rc = check_bufs(bufs, 1, 2);
-    if (rc != QPWC_OK) return rc;
+    if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
     return avgpool_pyramid_launch(x, out, B, H, W, C, levels, (hipStream_t)stream);
 }
 

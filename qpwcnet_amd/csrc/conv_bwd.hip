@@ -26,6 +26,7 @@
 // GEMMs (a pixel of gz / grad_x) is accumulated independently of every other row: grad_x of an image does not depend
 // on the rest of the batch.
 #include "conv_bwd_common.h"
+#include "launch.h"
 
 namespace qpwc {
 

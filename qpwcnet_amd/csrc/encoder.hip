@@ -19,6 +19,7 @@
 // and a double-buffered LDS image need 144 / 196 registers (loop-invariant addresses stay live): 34.7 us
 // at C = 16, 34.8 (from 31.8) at C = 32 -- not kept.
 #include "common.h"
+#include "launch.h"
 
 namespace qpwc {
 

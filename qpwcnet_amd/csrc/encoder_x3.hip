@@ -10,6 +10,7 @@
 // kernels); the weights are split once on the host side of the boundary (qpwc_split_bf16x3_fwd) and streamed as
 // 16-byte operands.
 #include "common.h"
+#include "launch.h"
 #include "split_bf16.h"
 
 namespace qpwc {

@@ -2,6 +2,7 @@
 //   mean over (b,y,x) of || y_true - y_pred ||_2 along the 2-channel flow axis.
 // Deterministic two-stage sum: kEpeBlocks partials, then one block folds them.
 #include "common.h"
+#include "launch.h"
 
 namespace qpwc {
 

@@ -30,6 +30,7 @@
 // subset, so an output's bits do not depend on its neighbours.  Contraction is off in the kernels (every fused
 // multiply-add is written out) so that gh is the same bits in both passes.
 #include "optflow_common.h"
+#include "launch.h"
 
 namespace qpwc {
 

@@ -21,6 +21,7 @@
 // cg_tile_sum of conv_bwd_common.h adds matrix-instruction tiles and has nothing to add here: the 3 x 64 product is
 // 12 multiply-adds per lane.
 #include "conv_bwd_common.h"
+#include "launch.h"
 
 namespace qpwc {
 

@@ -8,6 +8,7 @@
 // in runs of >= 128 bytes (NCHW side: 64 consecutive pixels of one channel plane; NHWC side: 32
 // consecutive channels of one pixel), LDS rows padded to 65 floats (conflict free both ways).
 #include "common.h"
+#include "launch.h"
 
 namespace qpwc {
 

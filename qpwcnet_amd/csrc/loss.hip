@@ -6,6 +6,7 @@
 // Deterministic by construction: grids depend on the shapes only, every thread sums in a fixed order, the partial sums
 // are folded by shuffles and a fixed-order LDS step; no atomics.
 #include "common.h"
+#include "launch.h"
 
 namespace qpwc {
 

@@ -15,6 +15,7 @@
 // to its target -- all writers of one target store the same value, the result does not depend on
 // the order (no atomics needed).  Both passes are ~12 B per pixel: HBM/launch-latency bound.
 #include "common.h"
+#include "launch.h"
 
 namespace qpwc {
 

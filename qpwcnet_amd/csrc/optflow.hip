@@ -20,6 +20,7 @@
 // 16->2 (no bias) -> * scale   (non_layers.py:238-254, 268-273) in one launch; the
 // normalised 16-channel tile (+1 halo, zero outside the image) lives in LDS.
 #include "optflow_common.h"
+#include "launch.h"
 #include "split_bf16.h"
 
 namespace qpwc {

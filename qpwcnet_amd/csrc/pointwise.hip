@@ -11,6 +11,7 @@
 // (311 KB at L0) from L2.  OptFlow.own_pointwise is off; the entry point stays, tested, for callers without a GEMM library.
 // W: (F, cpad) row-major, zero padded to cpad = ceil(C / 32) * 32 (ops.pad_pointwise); F % 16 == 0, F <= 256.
 #include "common.h"
+#include "launch.h"
 
 namespace qpwc {
 

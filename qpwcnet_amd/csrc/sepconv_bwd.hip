@@ -26,6 +26,7 @@
 // reduction (per workgroup: pixel blocks in grid-stride order, waves 0..3 / slots 0..7 in order; then stage D over the
 // workgroups in order).  No atomics.  A pixel's gz, gd and grad_x depend on its own image only.
 #include "conv_bwd_common.h"
+#include "launch.h"
 
 namespace qpwc {
 

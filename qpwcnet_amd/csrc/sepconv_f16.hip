@@ -5,6 +5,7 @@
                             // 242-248 vs 238-244 us; config 5 step 1.619-1.624 vs 1.609-1.611 ms): this file keeps the if-chain
 #endif
 #include "optflow_common.h"
+#include "launch.h"
 
 namespace qpwc {
 

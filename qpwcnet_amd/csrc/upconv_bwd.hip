@@ -30,6 +30,7 @@
 // GEMMs (a pixel of gz / grad_x) is accumulated independently of every other row: grad_x of an image does not depend
 // on the rest of the batch.  Pixel offsets are 64-bit.
 #include "conv_bwd_common.h"
+#include "launch.h"
 
 namespace qpwc {
 
