@@ -114,6 +114,13 @@ PROTOTYPES = {
 }
 SYMBOLS = tuple(PROTOTYPES)
 
+# The trainer's update step, declared in include/qpwc_optim.h: a table of its own, applied after PROTOTYPES and held
+# to its header by tests/test_optim_cpu.py.
+OPTIM_PROTOTYPES = {
+    "qpwc_agc_adam_step": (_ci, [_vp, _ci, _vp, _i64, _cf, _cf, _cf, _cf, _cf, _cf, _vp]),
+    "qpwc_agc_adam_step_kernel": (_str, [_i64]),
+}
+
 _lib = None
 
 
@@ -145,7 +152,9 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()):
+        if name in OPTIM_PROTOTYPES and not hasattr(L, name):
+            continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L

@@ -6,6 +6,7 @@
 
 #include <initializer_list>
 
+#include "../../include/qpwc_optim.h"
 #include "launch.h"
 
 namespace qpwc {
@@ -1362,6 +1363,31 @@ int qpwc_avgpool_pyramid_fwd(const void* x, void* out, int B, int H, int W, int 
     const BufCheck bufs[2] = {{x, n, 8, "x"}, {out, n >> (2 * levels), 4, "out"}};
     if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
     return avgpool_pyramid_launch(x, out, B, H, W, C, levels, (hipStream_t)stream);
+}
+
+const char* qpwc_agc_adam_step_kernel(int64_t n_units) {
+    if (n_units < 1 || n_units > agc_adam_max_units()) return "";
+    return agc_adam_step_kernel(n_units);
+}
+
+int qpwc_agc_adam_step(const void* tensors, int n_tensors, const void* units, int64_t n_units, float alpha, float beta1,
+                       float beta2, float epsilon, float clip_factor, float agc_eps, void* stream) {
+    int rc = check_nonnull({{tensors, "tensors"}, {units, "units"}});
+    if (rc != QPWC_OK) return rc;
+    if (n_tensors < 1) return fail(QPWC_E_SHAPE, "n_tensors=%d < 1", n_tensors);
+    if (n_units < 1 || n_units > agc_adam_max_units())
+        return fail(QPWC_E_SHAPE, "n_units=%lld outside [1, %lld]", (long long)n_units, (long long)agc_adam_max_units());
+    // written so that a NaN fails each test
+    if (!(beta1 >= 0.0f && beta1 < 1.0f)) return fail(QPWC_E_RANGE, "beta1=%g outside [0, 1)", beta1);
+    if (!(beta2 >= 0.0f && beta2 < 1.0f)) return fail(QPWC_E_RANGE, "beta2=%g outside [0, 1)", beta2);
+    if (!(epsilon > 0.0f)) return fail(QPWC_E_RANGE, "epsilon=%g must be > 0", epsilon);
+    if (!(agc_eps > 0.0f)) return fail(QPWC_E_RANGE, "agc_eps=%g must be > 0", agc_eps);
+    if (!(alpha - alpha == 0.0f)) return fail(QPWC_E_RANGE, "alpha=%g is not finite", alpha);
+    // both tables are inputs, but one written through the other's pointers would be a caller's bug: no overlap
+    const BufCheck bufs[2] = {{tensors, (size_t)n_tensors * 32, 8, "tensors"}, {units, (size_t)n_units * 24, 8, "units"}};
+    if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
+    return agc_adam_step_launch(tensors, n_tensors, units, n_units, alpha, beta1, beta2, epsilon, clip_factor, agc_eps,
+                                (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -159,4 +159,10 @@ int avgpool_pyramid_max_levels();
 int64_t avgpool_pyramid_tiles(int B, int H, int W, int levels, int* tw_out);
 int avgpool_pyramid_launch(const void* x, void* out, int B, int H, int W, int C, int levels, hipStream_t s);
 
+// optim.hip (include/qpwc_optim.h)
+int64_t agc_adam_max_units();
+const char* agc_adam_step_kernel(int64_t n_units);
+int agc_adam_step_launch(const void* tensors, int n_tensors, const void* units, int64_t n_units, float alpha,
+                         float beta1, float beta2, float epsilon, float clip_factor, float agc_eps, hipStream_t s);
+
 }  // namespace qpwc
