@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("QPWC_HIP_LIB") or os.path.join(_HERE, "csrc", "libqpw
 NHWC, NCHW = 0, 1
 F32, F16, U8 = 0, 1, 2
 AUGMENT_COLOR, AUGMENT_RAW = 1, 2
+TRIPLET_RAW = 1
 WARP_CLAMP, WARP_TFWARP = 0, 1
 BCAST_B, BCAST_H, BCAST_W = 1, 2, 4
 LOSS_FLOW_MSE_V2, LOSS_FLOW_MSE, LOSS_FLOW_FINETUNE, LOSS_AUTORESIZE_MSE = 0, 1, 2, 3
@@ -121,6 +122,13 @@ OPTIM_PROTOTYPES = {
     "qpwc_agc_adam_step_kernel": (_str, [_i64]),
 }
 
+# The frame interpolator's input pipeline, declared in include/qpwc_triplet.h: a table of its own under the same rules,
+# held to its header by tests/test_triplet_cpu.py.
+TRIPLET_PROTOTYPES = {
+    "qpwc_augment_triplet_fwd": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "qpwc_augment_triplet_fwd_kernel": (_str, [_ci, _ci, _ci, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -152,8 +160,9 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()):
-        if name in OPTIM_PROTOTYPES and not hasattr(L, name):
+    later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES)
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
+        if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)

@@ -10,6 +10,10 @@ also what ``tools/augbench.py`` times against the kernels.  Outputs are float32.
 
 The random draw is separate from the arithmetic: ``sample_params`` returns the per-sample parameters as two device
 tensors (``AugmentParams``), which the kernels read from device memory -- no host synchronisation anywhere.
+
+The frame interpolator's pipeline is the second half of the module: three ``(B,H,W,3)`` frames per sample through
+``preprocess_triplet`` / ``augment_triplet`` (one launch behind ``ops.augment_triplet``; ``triplet_torch`` on the
+CPU), with ``sample_triplet_params`` / ``identity_triplet_params`` as its draws.
 """
 import collections
 import math
@@ -243,3 +247,176 @@ def preprocess_no_op(ims, flo, data_format=CHANNELS_FIRST, out_shape=(256, 512))
     _check_inputs(ims, flo, (torch.uint8, torch.float32))
     B, H, W, _ = ims.shape
     return _run(ims, flo, resize_params(B, (H, W), out_shape, ims.device), out_shape, False, True, data_format)
+
+
+# ---- the frame interpolator's triplets (qpwcnet/data/triplet_dataset_ops.py, data/augment.py:10-59,
+# app/frame_interpolation/pre_train.py:110-124) ------------------------------------------------------------------------
+# iparams (B,4) int32: flip_ud, flip_lr, key0, key1; fparams (B,16) float32: R row-major, scale, txn, sigma
+# (include/qpwc_triplet.h, qpwc_augment_triplet_fwd)
+TripletParams = collections.namedtuple("TripletParams", "iparams fparams")
+
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+_M32 = 0xFFFFFFFF
+
+
+def rotation_matrix_from_euler(x):
+    """augment.py:10-25: (..., 3) Euler angles (x, y, z) -> (..., 3, 3) = Rz(z) . Ry(y) . Rx(x)."""
+    x = torch.as_tensor(x)
+    (cx, cy, cz), (sx, sy, sz) = torch.cos(x).unbind(-1), torch.sin(x).unbind(-1)
+    R = [cy * cz, sx * sy * cz - cx * sz, cx * sy * cz + sx * sz,
+         cy * sz, sx * sy * sz + cx * cz, cx * sy * sz - sx * cz,
+         -sy, sx * cy, cx * cy]
+    return torch.stack(R, dim=-1).reshape(x.shape[:-1] + (3, 3))
+
+
+def sample_triplet_params(batch, max_txn=0.3, max_rxn=0.3, max_scale=0.3, noise=0.02, generator=None, device=None):
+    """One draw per batch entry as ``augment_triplet(batch_size=B)`` makes it: txn ~ U(-max_txn, max_txn)^3, Euler
+    angles ~ U(-max_rxn, max_rxn)^3, scale = exp(U(-max_scale, max_scale))^3, flips Bernoulli(0.5), sigma = noise, and
+    two random 32-bit words as the key of the sample's noise field.  The numbers come from ``generator`` (on its own
+    device; the default generator of ``device`` without one) and the result lives on ``device``."""
+    if batch <= 0:
+        raise ValueError("non-positive batch: {}".format(batch))
+    device = torch.device("cpu" if device is None else device)
+    draw = generator.device if generator is not None else device
+    B = int(batch)
+    u = torch.rand((B, 11), generator=generator, device=draw, dtype=torch.float32) * 2.0 - 1.0     # U[-1, 1)
+    keys = torch.randint(-(1 << 31), 1 << 31, (B, 2), generator=generator, device=draw, dtype=torch.int64)
+    R = rotation_matrix_from_euler(u[:, 3:6] * max_rxn).reshape(B, 9)
+    sigma = torch.full((B, 1), float(noise), dtype=torch.float32, device=draw)
+    fparams = torch.cat([R, torch.exp(u[:, 6:9] * max_scale), u[:, 0:3] * max_txn, sigma], dim=1)
+    iparams = torch.cat([(u[:, 9:11] < 0.0).to(torch.int32), keys.to(torch.int32)], dim=1)
+    return TripletParams(iparams.contiguous().to(device), fparams.contiguous().to(device))
+
+
+def identity_triplet_params(batch, device=None):
+    """The validation path (``read_triplet_dataset(augment=False)``): R = I, scale 1, txn 0, sigma 0, no flips."""
+    fp = torch.tensor([[1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0]], dtype=torch.float32).repeat(int(batch), 1)
+    return TripletParams(torch.zeros((int(batch), 4), dtype=torch.int32).to(device or "cpu"), fp.to(device or "cpu"))
+
+
+def _mul32(m, c):
+    """(hi, lo) words of the 64-bit product of the 32-bit constant m and int64 tensor c in [0, 2^32), without leaving
+    int64: c by 16-bit halves."""
+    p, q = m * (c & 0xFFFF), m * (c >> 16)                   # < 2^48 each; the product is (q << 16) + p
+    s = p + ((q & 0xFFFF) << 16)
+    return (q >> 16) + (s >> 32), s & _M32
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85)
+    from integer torch operators, on any device: counter (..., 4) and key (..., 2) integer tensors whose entries are
+    taken modulo 2^32 (so int32 bit patterns serve) -> (..., 4) int64 words in [0, 2^32)."""
+    c = [t & _M32 for t in torch.as_tensor(counter).to(torch.int64).unbind(-1)]
+    k = [t & _M32 for t in torch.as_tensor(key).to(torch.int64).unbind(-1)]
+    for _ in range(10):
+        hi0, lo0 = _mul32(_PHILOX_M[0], c[0])
+        hi1, lo1 = _mul32(_PHILOX_M[1], c[2])
+        c = [hi1 ^ c[1] ^ k[0], lo1, hi0 ^ c[3] ^ k[1], lo0]
+        k = [(k[0] + _PHILOX_W[0]) & _M32, (k[1] + _PHILOX_W[1]) & _M32]
+    return torch.stack(torch.broadcast_tensors(*c), dim=-1)
+
+
+def triplet_noise(keys, h, w):
+    """The noise field of qpwc_augment_triplet_fwd before the flips and before sigma: keys (B,2) integer -> (B,h,w,3)
+    float32 standard normals, pixel (y, x) from Philox counter (y * w + x, 0, 0, 0) by Box-Muller on uniforms that are
+    exact in fp32 (include/qpwc_triplet.h)."""
+    keys = torch.as_tensor(keys)
+    B, n = keys.shape[0], int(h) * int(w)
+    counter = torch.zeros((1, n, 4), dtype=torch.int64, device=keys.device)
+    counter[0, :, 0] = torch.arange(n, device=keys.device)
+    r = philox4x32(counter, keys.reshape(B, 1, 2))
+    k = 2.0 ** -24
+    u1, u2 = ((r[..., 0::2] >> 8) + 1).to(torch.float32) * k, (r[..., 1::2] >> 8).to(torch.float32) * k
+    rad = torch.sqrt(-2.0 * torch.log(u1))
+    ang = float(np.float32(2.0 * math.pi)) * u2
+    z = torch.stack([rad[..., 0] * torch.cos(ang[..., 0]), rad[..., 0] * torch.sin(ang[..., 0]),
+                     rad[..., 1] * torch.cos(ang[..., 1])], dim=-1)
+    return z.reshape(B, int(h), int(w), 3)
+
+
+def triplet_torch(a, b, c, params, dsize, finish=True, data_format=CHANNELS_LAST, noise=None):
+    """What ``ops.augment_triplet`` computes, composed from torch operators on the tensors' own device, step by step as
+    the reference does it: times 1/255, ``F.interpolate(mode='bilinear', align_corners=False, antialias=False)``, the
+    colour einsum, the noise field (``triplet_noise``: the same numbers as the kernel's), both flips, - 0.5, concat
+    and the layout.  The CPU path.  ``noise``: a callable (B, h, w) -> (B,h,w,3) standard normals to draw the field
+    with instead (tools/tripletbench.py times the composition with ``torch.randn``, as the reference would run it)."""
+    get_axis(data_format)
+    h, w = (int(v) for v in dsize)
+    B, H, W, _ = a.shape
+    ip, fp = params.iparams.to(a.device), params.fparams.to(a.device)
+    x = torch.stack([a, b, c], dim=0)                                          # (3,B,H,W,3)
+    x = x.to(torch.float32) * _INV255 if x.dtype == torch.uint8 else x
+    if (H, W) != (h, w):
+        x = F.interpolate(x.reshape(3 * B, H, W, 3).permute(0, 3, 1, 2), size=(h, w), mode="bilinear",
+                          align_corners=False, antialias=False).permute(0, 2, 3, 1).reshape(3, B, h, w, 3)
+    per = lambda t: t.reshape(1, B, 1, 1, 3)
+    y = torch.einsum("nab,fnhwb->fnhwa", fp[:, 0:9].reshape(B, 3, 3), x) * per(fp[:, 9:12]) + per(fp[:, 12:15])
+    z = triplet_noise(ip[:, 2:4], h, w) if noise is None else noise(B, h, w)
+    y = y + (fp[:, 15].reshape(B, 1, 1, 1) * z).unsqueeze(0)
+    for col, axis in ((0, 2), (1, 3)):
+        y = torch.where((ip[:, col] != 0).reshape(1, B, 1, 1, 1), torch.flip(y, [axis]), y)
+    if finish:
+        y = y - 0.5
+    pair, mid = torch.cat([y[0], y[2]], dim=-1), y[1]
+    if data_format == CHANNELS_FIRST:
+        return pair.permute(0, 3, 1, 2).contiguous(), mid.permute(0, 3, 1, 2).contiguous()
+    return pair.contiguous(), mid.contiguous()
+
+
+def _check_triplet(a, b, c):
+    for name, t in (("a", a), ("b", b), ("c", c)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("{}: unsupported dtype {}".format(name, t.dtype))
+        if t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError("{} must be (B,H,W,3) channels_last, got shape {}".format(name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("{} must be dense (contiguous) channels_last".format(name))
+        if t.shape != a.shape or t.dtype != a.dtype or t.device != a.device:
+            raise ValueError("{} ({}, {}, {}) does not match a ({}, {}, {})".format(
+                name, tuple(t.shape), t.dtype, t.device, tuple(a.shape), a.dtype, a.device))
+
+
+def _triplet_params(params, B, device, generator, augment=True):
+    if not augment:
+        return identity_triplet_params(B, device)
+    if params is None:
+        return sample_triplet_params(B, generator=generator, device=device)
+    if not isinstance(params, TripletParams):
+        params = TripletParams(*params)
+    for name, t, dt, n in (("iparams", params.iparams, torch.int32, 4), ("fparams", params.fparams, torch.float32, 16)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B, n):
+            raise ValueError("params.{} must be a ({}, {}) {} tensor".format(name, B, n, dt))
+    return TripletParams(params.iparams.to(device).contiguous(), params.fparams.to(device).contiguous())
+
+
+def _run_triplet(a, b, c, params, dsize, finish, data_format):
+    if a.is_cuda:
+        return ops.augment_triplet(a, b, c, params.iparams, params.fparams, dsize, finish=finish,
+                                   data_format=data_format)
+    return triplet_torch(a, b, c, params, dsize, finish=finish, data_format=data_format)
+
+
+def augment_triplet(a, b, c, dsize, params=None, generator=None):
+    """triplet_dataset_ops.py:20-54 on a batch, after read_and_resize's resize to ``dsize``: one colour rotation, scale
+    and offset, one noise field and one pair of flips per sample for the three frames -> three (B,h,w,3) float32
+    images, channels_last, not offset and not clipped (views of the kernel's two outputs).  ``params``: a
+    ``TripletParams`` (``sample_triplet_params``); None draws them from ``generator``."""
+    _check_triplet(a, b, c)
+    pair, mid = _run_triplet(a, b, c, _triplet_params(params, a.shape[0], a.device, generator), dsize, False,
+                             CHANNELS_LAST)
+    return pair[..., 0:3], mid, pair[..., 3:6]
+
+
+def preprocess_triplet(a, b, c, dsize=(256, 512), data_format=CHANNELS_FIRST, augment=True, params=None,
+                       generator=None):
+    """read_and_resize's conversion and resize, ``augment_triplet`` (augment=False: the validation path, the resize
+    alone) and pre_train.py:110-124: uint8 frames times 1/255 (float32 frames as they are), - 0.5, img_pair =
+    concat([img0, img2]) -> (img_pair, img1) in data_format, what InterpolatorModel and
+    ``loss.multiscale(AutoResizeMseLoss())`` take."""
+    get_axis(data_format)
+    _check_triplet(a, b, c)
+    return _run_triplet(a, b, c, _triplet_params(params, a.shape[0], a.device, generator, augment), dsize, True,
+                        data_format)

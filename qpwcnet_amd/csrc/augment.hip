@@ -11,19 +11,13 @@
 // Lanes of a wave read neighbouring source pixels (a 6-byte uint8 pixel is three 2-byte loads: pixel addresses are even,
 // never dword aligned) and, in the <vec4> form, the workgroup's 256 pixels leave through LDS in the output's own memory
 // order as 16-byte stores.  No atomics: two runs are bit-identical.
-#include "common.h"
+#include "augment_common.h"
 #include "launch.h"
-
-// a + (b - a) * t and u8 * (1/255) - 0.5 are separately rounded, as the reference's TF kernels round them
-#pragma clang fp contract(off)
 
 namespace qpwc {
 
-constexpr int kAugThreads = 256;
 constexpr int kAugPass2Pixels = 4096;   // pass 2: pixels of one sample per workgroup
 constexpr int kAugIParams = 6, kAugFParams = 6;
-
-typedef float aug_f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -34,32 +28,6 @@ __device__ __forceinline__ float aug_wave_sum(float v) {
 }
 
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
-
-// index of floor / ceil of a source coordinate, clamped into the image whatever the parameters hold (NaN -> 0)
-__device__ __forceinline__ int aug_index(float v, int n) { return (int)fminf(fmaxf(v, 0.0f), (float)(n - 1)); }
-
-// the 6 colour channels of source pixel `pix` as fp32 in [0, 1]
-template <bool U8>
-__device__ __forceinline__ void aug_load_pixel(const void* ims, int64_t pix, float* v) {
-    if (U8) {
-        const uint16_t* p = reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(ims) + pix * 6);
-        const float k = 0.003921568859368563f;   // float32(1 / 255): a multiply, as train.py:56
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const unsigned w = p[i];
-            v[2 * i] = (float)(w & 0xffu) * k;
-            v[2 * i + 1] = (float)(w >> 8) * k;
-        }
-    } else {
-        const float2* p = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(ims) + pix * 6);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float2 w = p[i];
-            v[2 * i] = w.x;
-            v[2 * i + 1] = w.y;
-        }
-    }
-}
 
 // adjust_brightness, adjust_saturation and adjust_hue of one RGB pixel.  The reference makes two HSV round trips; the
 // second RGB -> HSV returns the first one's (h, s', v) (s' = range' / v' and the hue of the rebuilt pixel are those it
@@ -124,13 +92,9 @@ __global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* 
     for (int c = 0; c < 8; ++c) v[c] = 0.0f;
     if (valid) {
         const int y = pix / w, x = pix - y * w;
-        // tf.image.resize(BILINEAR): half-pixel centres, scale = in / float(out), no antialias
-        const float sy = ((float)(oy + y) + 0.5f) * ((float)H / (float)rh) - 0.5f;
-        const float sx = ((float)(ox + x) + 0.5f) * ((float)W / (float)rw) - 0.5f;
-        const float fy = floorf(sy), fx = floorf(sx);
-        const float ty = sy - fy, tx = sx - fx;
-        int y0 = aug_index(fy, H), y1 = aug_index(ceilf(sy), H);
-        int x0 = aug_index(fx, W), x1 = aug_index(ceilf(sx), W);
+        const AugAxis ay = aug_axis(oy + y, H, rh), ax = aug_axis(ox + x, W, rw);
+        const float ty = ay.t, tx = ax.t;
+        int y0 = ay.lo, y1 = ay.hi, x0 = ax.lo, x1 = ax.hi;
         if (flip_ud) {
             y0 = H - 1 - y0;
             y1 = H - 1 - y1;
@@ -154,11 +118,7 @@ __global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* 
         c_[6] = fc.x; c_[7] = fc.y;
         d[6] = fd.x; d[7] = fd.y;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float top = a[c] + (bb[c] - a[c]) * tx;
-            const float bot = c_[c] + (d[c] - c_[c]) * tx;
-            v[c] = top + (bot - top) * ty;
-        }
+        for (int c = 0; c < 8; ++c) v[c] = aug_lerp2(a[c], bb[c], c_[c], d[c], tx, ty);
         v[6] *= mu;
         v[7] *= mv;
         if (!raw) {

@@ -7,6 +7,7 @@
 #include <initializer_list>
 
 #include "../../include/qpwc_optim.h"
+#include "../../include/qpwc_triplet.h"
 #include "launch.h"
 
 namespace qpwc {
@@ -123,6 +124,10 @@ static int augment_check_shapes(int B, int H, int W, int h, int w) {
         return fail(QPWC_E_SHAPE, "B=%d %dx%d -> %dx%d: a pixel count or the launch grid overflows 32 bits", B, H, W, h, w);
     return QPWC_OK;
 }
+
+// the shape rules of the interpolator's input pipeline, shared by qpwc_augment_triplet_fwd / _fwd_kernel: its launch is
+// augment_pixel_kernel's (one-dimensional over sample x 256-pixel chunk, 6 floats per pixel in the larger output)
+static int triplet_check_shapes(int B, int H, int W, int h, int w) { return augment_check_shapes(B, H, W, h, w); }
 
 // the first null pointer of a {pointer, name} list fails, by name
 struct PtrName {
@@ -1388,6 +1393,38 @@ int qpwc_agc_adam_step(const void* tensors, int n_tensors, const void* units, in
     if ((rc = check_bufs(bufs, 1, 2)) != QPWC_OK) return rc;
     return agc_adam_step_launch(tensors, n_tensors, units, n_units, alpha, beta1, beta2, epsilon, clip_factor, agc_eps,
                                 (hipStream_t)stream);
+}
+
+const char* qpwc_augment_triplet_fwd_kernel(int B, int h, int w, const void* out_pair, const void* out_mid) {
+    if (!out_pair || !out_mid || triplet_check_shapes(B, 1, 1, h, w) != QPWC_OK) return "";
+    return augment_triplet_fwd_kernel(h, w, out_pair, out_mid);
+}
+
+int qpwc_augment_triplet_fwd(const void* a, const void* b, const void* c, int dtype, int B, int H, int W,
+                             const void* iparams, const void* fparams, int h, int w, int flags, int layout,
+                             void* out_pair, void* out_mid, void* stream) {
+    if (flags & ~QPWC_TRIPLET_RAW) return fail(QPWC_E_MODE, "unknown triplet flags 0x%x", flags);
+    int rc = check_nonnull({{a, "a"}, {b, "b"}, {c, "c"}, {iparams, "iparams"}, {fparams, "fparams"},
+                            {out_pair, "out_pair"}, {out_mid, "out_mid"}});
+    if (rc != QPWC_OK) return rc;
+    if (dtype != QPWC_F32 && dtype != QPWC_U8) return fail(QPWC_E_DTYPE, "unsupported frame dtype %d", dtype);
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if ((rc = triplet_check_shapes(B, H, W, h, w)) != QPWC_OK) return rc;
+    const bool u8 = dtype == QPWC_U8;
+    // a uint8 pixel is read byte by byte, an fp32 pixel dword by dword; the three frames may be one buffer
+    const size_t src_n = (size_t)B * H * W * 3 * (u8 ? 1 : 4), src_al = u8 ? 1 : 4, out_px = (size_t)B * h * w;
+    const BufCheck bufs[] = {
+        {a, src_n, src_al, "a"},
+        {b, src_n, src_al, "b"},
+        {c, src_n, src_al, "c"},
+        {iparams, (size_t)B * 4 * 4, 4, "iparams"},
+        {fparams, (size_t)B * 16 * 4, 4, "fparams"},
+        {out_pair, out_px * 6 * 4, 4, "out_pair"},
+        {out_mid, out_px * 3 * 4, 4, "out_mid"},
+    };
+    if ((rc = check_bufs(bufs, 5, 7)) != QPWC_OK) return rc;
+    return augment_triplet_fwd_launch(a, b, c, u8, B, H, W, (const int*)iparams, (const float*)fparams, h, w, flags,
+                                      layout, (float*)out_pair, (float*)out_mid, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -165,4 +165,11 @@ const char* agc_adam_step_kernel(int64_t n_units);
 int agc_adam_step_launch(const void* tensors, int n_tensors, const void* units, int64_t n_units, float alpha,
                          float beta1, float beta2, float epsilon, float clip_factor, float agc_eps, hipStream_t s);
 
+
+// triplet.hip (include/qpwc_triplet.h)
+const char* augment_triplet_fwd_kernel(int h, int w, const void* out_pair, const void* out_mid);
+int augment_triplet_fwd_launch(const void* a, const void* b, const void* c, bool u8, int B, int H, int W,
+                               const int* iparams, const float* fparams, int h, int w, int flags, int layout,
+                               float* out_pair, float* out_mid, hipStream_t s);
+
 }  // namespace qpwc

@@ -1229,6 +1229,60 @@ def augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, dat
     return out_ims, out_flo
 
 
+def augment_triplet_kernel(B, h, w, out_pair=None, out_mid=None):
+    """Launch form of ``qpwc_augment_triplet_fwd`` for a (h, w) output ('triplet_pixel_kernel<vec4>' /
+    'triplet_pixel_kernel<scalar>'; host only).  Tensors or addresses for the outputs; None = 16-byte aligned, as
+    torch allocates.  '' for arguments the entry point refuses."""
+    ptr = lambda t: 1 << 20 if t is None else (t.data_ptr() if isinstance(t, torch.Tensor) else int(t))
+    name = _hip.lib().qpwc_augment_triplet_fwd_kernel(int(B), int(h), int(w), ptr(out_pair), ptr(out_mid))
+    return name.decode() if name else ""
+
+
+def augment_triplet(a, b, c, iparams, fparams, dsize, finish=True, data_format=CHANNELS_LAST):
+    """The frame interpolator's input pipeline of one batch in one launch (qpwc_augment_triplet_fwd;
+    qpwcnet/data/triplet_dataset_ops.py, app/frame_interpolation/pre_train.py:110-124): a, b, c (B,H,W,3) uint8 (taken
+    times 1/255) or float32, the first, middle and last frames, dense channels-last on one HIP device; iparams (B,4)
+    int32 = flip_ud, flip_lr, key0, key1 and fparams (B,16) float32 = R, scale, txn, sigma on the same device
+    (include/qpwc_triplet.h) -> (img_pair, img1) fp32 of spatial size dsize with 6 and 3 channels in data_format,
+    written in that layout by the kernel.  finish=False: no - 0.5.  Enqueues and returns: no host synchronisation."""
+    get_axis(data_format)
+    for name, t in (("a", a), ("b", b), ("c", c)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if not t.is_cuda:
+            raise RuntimeError("qpwcnet_amd: {} is on '{}'; ops.augment_triplet runs on a HIP device only (augment.* "
+                               "has the CPU path)".format(name, t.device))
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("{}: unsupported dtype {}".format(name, t.dtype))
+        if t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError("{} must be (B,H,W,3) channels_last, got shape {}".format(name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("{} must be dense (contiguous) channels_last".format(name))
+        if t.shape != a.shape or t.dtype != a.dtype:
+            raise ValueError("{} {} {} does not match a {} {}".format(name, tuple(t.shape), t.dtype, tuple(a.shape),
+                                                                     a.dtype))
+    B, H, W, _ = a.shape
+    for name, t, dt, n in (("iparams", iparams, torch.int32, 4), ("fparams", fparams, torch.float32, 16)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B, n) or not t.is_contiguous():
+            raise ValueError("{} must be a dense ({}, {}) {} tensor".format(name, B, n, dt))
+    if not (a.device == b.device == c.device == iparams.device == fparams.device):
+        raise ValueError("a, b, c, iparams and fparams must be on one device")
+    h, w = (int(v) for v in dsize)
+    if h <= 0 or w <= 0:
+        raise ValueError("non-positive output shape {}".format((h, w)))
+    dev = a.device
+    nhwc = data_format == CHANNELS_LAST
+    out_pair = torch.empty((B, h, w, 6) if nhwc else (B, 6, h, w), dtype=torch.float32, device=dev)
+    out_mid = torch.empty((B, h, w, 3) if nhwc else (B, 3, h, w), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("augment_triplet", (B, H, W, h, w)):
+        rc = _hip.lib().qpwc_augment_triplet_fwd(
+            a.data_ptr(), b.data_ptr(), c.data_ptr(), _hip.U8 if a.dtype == torch.uint8 else _hip.F32, B, H, W,
+            iparams.data_ptr(), fparams.data_ptr(), h, w, 0 if finish else _hip.TRIPLET_RAW,
+            _hip.NHWC if nhwc else _hip.NCHW, out_pair.data_ptr(), out_mid.data_ptr(), _stream(a))
+    _hip.check(rc)
+    return out_pair, out_mid
+
+
 def _loss_layout(y_true, preds, data_format):
     """-> (y_true, preds, layout code, nhwc_view): 'channels_first' operands that are all physically NHWC (torch
     channels_last memory) are read through their permuted views; everything else dense in its declared layout."""
