@@ -15,6 +15,7 @@ NHWC, NCHW = 0, 1
 F32, F16, U8 = 0, 1, 2
 AUGMENT_COLOR, AUGMENT_RAW = 1, 2
 TRIPLET_RAW = 1
+VIS_MAX_TILE, VIS_TILE = 2048, 1024     # csrc/vis.hip: source pixels per partial maximum, output pixels per workgroup
 WARP_CLAMP, WARP_TFWARP = 0, 1
 BCAST_B, BCAST_H, BCAST_W = 1, 2, 4
 LOSS_FLOW_MSE_V2, LOSS_FLOW_MSE, LOSS_FLOW_FINETUNE, LOSS_AUTORESIZE_MSE = 0, 1, 2, 3
@@ -129,6 +130,14 @@ TRIPLET_PROTOTYPES = {
     "qpwc_augment_triplet_fwd_kernel": (_str, [_ci, _ci, _ci, _vp, _vp]),
 }
 
+# The trainer's flow panels, declared in include/qpwc_vis.h: a table of its own under the same rules, held to its header
+# by tests/test_vis_capi_cpu.py.
+VIS_PROTOTYPES = {
+    "qpwc_flow_to_image_workspace_floats": (_i64, [_ci, _ci, _pi, _pi]),
+    "qpwc_flow_to_image_fwd": (_ci, [_pvp, _pi, _pi, _pi, _ci, _ci, _ci, _pvp, _pi, _pi, _ci, _ci, _vp, _vp]),
+    "qpwc_flow_to_image_fwd_kernel": (_str, [_ci, _ci, _pi, _pi, _ci, _ci, _pvp]),
+}
+
 _lib = None
 
 
@@ -160,7 +169,7 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
-    later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES)
+    later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
         if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)

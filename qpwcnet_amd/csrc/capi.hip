@@ -8,6 +8,7 @@
 
 #include "../../include/qpwc_optim.h"
 #include "../../include/qpwc_triplet.h"
+#include "../../include/qpwc_vis.h"
 #include "launch.h"
 
 namespace qpwc {
@@ -128,6 +129,21 @@ static int augment_check_shapes(int B, int H, int W, int h, int w) {
 // the shape rules of the interpolator's input pipeline, shared by qpwc_augment_triplet_fwd / _fwd_kernel: its launch is
 // augment_pixel_kernel's (one-dimensional over sample x 256-pixel chunk, 6 floats per pixel in the larger output)
 static int triplet_check_shapes(int B, int H, int W, int h, int w) { return augment_check_shapes(B, H, W, h, w); }
+
+// the shape rules of the flow panels, shared by qpwc_flow_to_image_workspace_floats / _fwd / _fwd_kernel; oh, ow may be
+// NULL (the workspace depends on the flows' own sizes only)
+static int vis_check_shapes(int n, int B, const int* h, const int* w, const int* oh, const int* ow) {
+    if (n < 1 || n > 8) return fail(QPWC_E_SHAPE, "n %d outside [1,8]", n);
+    if (B <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d", B);
+    for (int l = 0; l < n; ++l) {
+        if (h[l] <= 0 || w[l] <= 0) return fail(QPWC_E_SHAPE, "level %d: non-positive extent %dx%d", l, h[l], w[l]);
+        if (oh && (oh[l] <= 0 || ow[l] <= 0))
+            return fail(QPWC_E_SHAPE, "level %d: non-positive output extent %dx%d", l, oh[l], ow[l]);
+    }
+    if (!flow_to_image_shape_ok(n, B, h, w, oh, ow))
+        return fail(QPWC_E_SHAPE, "B=%d: an element count or a launch grid overflows 32 bits", B);
+    return QPWC_OK;
+}
 
 // the first null pointer of a {pointer, name} list fails, by name
 struct PtrName {
@@ -1425,6 +1441,62 @@ int qpwc_augment_triplet_fwd(const void* a, const void* b, const void* c, int dt
     if ((rc = check_bufs(bufs, 5, 7)) != QPWC_OK) return rc;
     return augment_triplet_fwd_launch(a, b, c, u8, B, H, W, (const int*)iparams, (const float*)fparams, h, w, flags,
                                       layout, (float*)out_pair, (float*)out_mid, (hipStream_t)stream);
+}
+
+int64_t qpwc_flow_to_image_workspace_floats(int n, int B, const int* h, const int* w) {
+    if (!h || !w) return fail(QPWC_E_NULL, "null pointer argument");
+    const int rc = vis_check_shapes(n, B, h, w, nullptr, nullptr);
+    if (rc != QPWC_OK) return rc;
+    return flow_to_image_workspace_floats(n, B, h, w);
+}
+
+const char* qpwc_flow_to_image_fwd_kernel(int n, int B, const int* oh, const int* ow, int out_dtype, int out_layout,
+                                          const void* const* outs) {
+    if (!oh || !ow || !outs || n < 1 || n > 8) return "";
+    if (out_dtype != QPWC_F32 && out_dtype != QPWC_U8) return "";
+    if (out_layout != QPWC_NHWC && out_layout != QPWC_NCHW) return "";
+    for (int l = 0; l < n; ++l)
+        if (!outs[l]) return "";
+    // the picture's size stands in for the flow's own: only the outputs decide the store form
+    if (vis_check_shapes(n, B, oh, ow, oh, ow) != QPWC_OK) return "";
+    return flow_to_image_fwd_kernel(n, oh, ow, outs);
+}
+
+int qpwc_flow_to_image_fwd(const void* const* flows, const int* flow_dtype, const int* h, const int* w, int n, int B,
+                           int in_layout, void* const* outs, const int* oh, const int* ow, int out_dtype,
+                           int out_layout, void* ws, void* stream) {
+    int rc = check_nonnull({{flows, "flows"}, {flow_dtype, "flow_dtype"}, {h, "h"}, {w, "w"}, {outs, "outs"},
+                            {oh, "oh"}, {ow, "ow"}, {ws, "ws"}});
+    if (rc != QPWC_OK) return rc;
+    // the arrays hold n entries: read them only for an n the entry point takes (n itself fails below, as a shape)
+    const int nn = n < 1 || n > 8 ? 0 : n;
+    for (int l = 0; l < nn; ++l) {
+        if (!flows[l]) return fail(QPWC_E_NULL, "flows[%d] is null", l);
+        if (!outs[l]) return fail(QPWC_E_NULL, "outs[%d] is null", l);
+    }
+    for (int l = 0; l < nn; ++l)
+        if (flow_dtype[l] != QPWC_F32 && flow_dtype[l] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "flows[%d]: unsupported dtype %d", l, flow_dtype[l]);
+    if (out_dtype != QPWC_F32 && out_dtype != QPWC_U8) return fail(QPWC_E_DTYPE, "unsupported output dtype %d", out_dtype);
+    if (in_layout != QPWC_NHWC && in_layout != QPWC_NCHW)
+        return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", in_layout);
+    if (out_layout != QPWC_NHWC && out_layout != QPWC_NCHW)
+        return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", out_layout);
+    if ((rc = vis_check_shapes(n, B, h, w, oh, ow)) != QPWC_OK) return rc;
+    const bool u8 = out_dtype == QPWC_U8;
+    // the flows are only read and may be one buffer; the workspace and the outputs are written
+    BufCheck bufs[2 * 8 + 1];
+    int f16[8];
+    for (int l = 0; l < n; ++l) {
+        f16[l] = flow_dtype[l] == QPWC_F16;
+        const size_t es = f16[l] ? 2 : 4;
+        bufs[l] = indexed_buf(flows[l], (size_t)B * h[l] * w[l] * 2 * es, es, "flows[%d]", l);
+        bufs[n + 1 + l] = indexed_buf(outs[l], (size_t)B * oh[l] * ow[l] * 3 * (u8 ? 1 : 4), u8 ? 1 : 4, "outs[%d]", l);
+    }
+    bufs[n] = indexed_buf(ws, (size_t)flow_to_image_workspace_floats(n, B, h, w) * 4, 4, "ws", 0);
+    if ((rc = check_bufs(bufs, n, 2 * n + 1)) != QPWC_OK) return rc;
+    return flow_to_image_fwd_launch(flows, f16, h, w, n, B, in_layout, outs, oh, ow, u8, out_layout, (float*)ws,
+                                    (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -172,4 +172,12 @@ int augment_triplet_fwd_launch(const void* a, const void* b, const void* c, bool
                                const int* iparams, const float* fparams, int h, int w, int flags, int layout,
                                float* out_pair, float* out_mid, hipStream_t s);
 
+// vis.hip (include/qpwc_vis.h)
+bool flow_to_image_shape_ok(int n, int B, const int* h, const int* w, const int* oh, const int* ow);
+int64_t flow_to_image_workspace_floats(int n, int B, const int* h, const int* w);
+const char* flow_to_image_fwd_kernel(int n, const int* oh, const int* ow, const void* const* outs);
+int flow_to_image_fwd_launch(const void* const* flows, const int* f16, const int* h, const int* w, int n, int B,
+                             int in_layout, void* const* outs, const int* oh, const int* ow, bool u8, int out_layout,
+                             float* ws, hipStream_t s);
+
 }  // namespace qpwc

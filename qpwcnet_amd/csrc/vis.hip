@@ -1,0 +1,331 @@
+// The trainer's flow panels (qpwcnet/core/vis.py:37-76 flow_to_image; app/train.py ShowImageCallback / train_custom:
+// every flow coloured, nearest-resized to the label's size and converted for tf.summary.image), for up to 8 flows of
+// different sizes in two launches (include/qpwc_vis.h):
+//   flow_mag_max_kernel   one workgroup per (level, image, tile of 2048 source pixels) writes the tile's largest
+//                         magnitude to the workspace;
+//   flow_to_image_kernel  one workgroup per (level, image, tile of 1024 output pixels) folds the partials of its
+//                         (level, image) -- 64 floats at 256x512 -- and colours its pixels, gathering each from its
+//                         nearest source pixel.  In the <vec4> form the tile leaves through LDS in the output's own
+//                         memory order: 16-byte stores for fp32, packed dwords for uint8.
+// No atomics and no state between calls: a max does not depend on the order, two runs are bit-identical, and a captured
+// graph replays both launches unchanged.  A workgroup's level is found from blockIdx.x by scalar code and every field of
+// the by-value level table is then read at that uniform index (no per-lane selection).
+#include <limits.h>
+
+#include "../../include/qpwc_vis.h"
+#include "common.h"
+#include "launch.h"
+
+// (1 - s) + s * d and the hue are separately rounded products and sums, as include/qpwc_vis.h states them
+#pragma clang fp contract(off)
+
+namespace qpwc {
+
+constexpr int kVisThreads = 256;
+constexpr int kVisMaxLevels = 8;
+
+typedef float vis_f32x4 __attribute__((ext_vector_type(4)));
+
+struct VisLevels {
+    const void* flow[kVisMaxLevels];
+    void* out[kVisMaxLevels];
+    int h[kVisMaxLevels], w[kVisMaxLevels];      // the flow's own size
+    int oh[kVisMaxLevels], ow[kVisMaxLevels];    // the picture's size
+    int f16[kVisMaxLevels];
+    int pair[kVisMaxLevels];                     // NHWC and the flow aligned to a whole pixel: one load per pixel
+    float ry[kVisMaxLevels], rx[kVisMaxLevels];  // (float)h / oh, (float)w / ow
+    int step_y[kVisMaxLevels], step_x[kVisMaxLevels];   // 256 output pixels further: 256 / ow rows and 256 % ow columns
+    int mtiles[kVisMaxLevels];                   // max-tiles per image
+    int ctiles[kVisMaxLevels];                   // colour tiles per image
+    int mblk0[kVisMaxLevels];                    // the level's first workgroup of the max launch = its first partial
+    int cblk0[kVisMaxLevels];                    // the level's first workgroup of the colour launch
+};                                               // unused levels: mblk0 = cblk0 = INT_MAX
+
+namespace {
+
+// the level of a workgroup: the last one whose first workgroup is not after it (scalar compares on blockIdx.x)
+__device__ __forceinline__ int vis_level(const int* blk0, int bid) {
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < kVisMaxLevels; ++k) l += bid >= blk0[k] ? 1 : 0;
+    return l;
+}
+
+// (fx, fy) of pixel `pix` of image n of a (B,h,w,2) / (B,2,h,w) flow with hw pixels per image
+template <int IN_LAYOUT>
+__device__ __forceinline__ float2 vis_load(const void* flow, int f16, int pair, int64_t n, int pix, int hw) {
+    if (IN_LAYOUT == QPWC_NHWC) {
+        const int64_t o = (n * hw + pix) * 2;
+        if (f16) {
+            const __half* p = reinterpret_cast<const __half*>(flow) + o;
+            if (pair) return __half22float2(*reinterpret_cast<const __half2*>(p));
+            return make_float2(__half2float(p[0]), __half2float(p[1]));
+        }
+        const float* p = reinterpret_cast<const float*>(flow) + o;
+        if (pair) return *reinterpret_cast<const float2*>(p);
+        return make_float2(p[0], p[1]);
+    }
+    const int64_t o = n * 2 * hw + pix;
+    if (f16) {
+        const __half* p = reinterpret_cast<const __half*>(flow) + o;
+        return make_float2(__half2float(p[0]), __half2float(p[hw]));
+    }
+    const float* p = reinterpret_cast<const float*>(flow) + o;
+    return make_float2(p[0], p[hw]);
+}
+
+// |f|^2 as both kernels form it: the colour kernel's magnitude never exceeds the maximum it is divided by
+__device__ __forceinline__ float vis_mag2(float2 f) { return __fmaf_rn(f.x, f.x, f.y * f.y); }
+
+__device__ __forceinline__ float vis_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// the maximum of a workgroup's values, in every lane; `red` holds one float per wave
+__device__ __forceinline__ float vis_block_max(float v, float* red) {
+    v = vis_wave_max(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+__device__ __forceinline__ float vis_clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
+// tf.image.hsv_to_rgb's functor at v = 1
+__device__ __forceinline__ void vis_colour(float2 f, float denom, float* rgb) {
+    const float pi = 3.1415927410125732f, two_pi = 6.2831854820251465f;   // float32(pi), float32(2 pi)
+    const float hue = (atan2f(f.y, f.x) + pi) / two_pi;
+    const float s = sqrtf(vis_mag2(f)) / denom;
+    const float dh = 6.0f * hue;
+    const float d[3] = {vis_clamp01(fabsf(dh - 3.0f) - 1.0f), vis_clamp01(2.0f - fabsf(dh - 2.0f)),
+                        vis_clamp01(2.0f - fabsf(dh - 4.0f))};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = (1.0f - s) + s * d[c];
+}
+
+// tf.image.convert_image_dtype(uint8, saturate=True)
+__device__ __forceinline__ uint8_t vis_u8(float x) { return (uint8_t)fminf(fmaxf(truncf(x * 255.5f), 0.0f), 255.0f); }
+
+}  // namespace
+
+constexpr int kVisMaxPix = 8;                            // source pixels per lane of the max launch
+constexpr int kVisMaxTile = kVisThreads * kVisMaxPix;    // 2048
+constexpr int kVisPix = 4;                               // output pixels per lane of the colour launch
+constexpr int kVisTile = kVisThreads * kVisPix;          // 1024
+
+// blockIdx.x = mblk0[level] + image * mtiles[level] + tile; ws[blockIdx.x] = the tile's largest magnitude
+template <int IN_LAYOUT>
+__global__ __launch_bounds__(kVisThreads) void flow_mag_max_kernel(VisLevels lv, float* __restrict__ ws) {
+    __shared__ float red[kVisThreads / 64];
+    const int bid = blockIdx.x;
+    const int l = vis_level(lv.mblk0, bid);
+    const int rel = bid - lv.mblk0[l], mt = lv.mtiles[l];
+    const int n = rel / mt, tile = rel - n * mt;
+    const int hw = lv.h[l] * lv.w[l];
+    const void* flow = lv.flow[l];
+    const int f16 = lv.f16[l], pair = lv.pair[l];
+    float m2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kVisMaxPix; ++k) {
+        const int pix = tile * kVisMaxTile + k * kVisThreads + (int)threadIdx.x;
+        if (pix < hw) m2 = fmaxf(m2, vis_mag2(vis_load<IN_LAYOUT>(flow, f16, pair, n, pix, hw)));
+    }
+    m2 = vis_block_max(m2, red);
+    // the square root is monotone: the root of the largest square is the largest magnitude, bit for bit
+    if (threadIdx.x == 0) ws[bid] = sqrtf(m2);
+}
+
+// blockIdx.x = cblk0[level] + image * ctiles[level] + tile; the tile's 1024 consecutive output pixels (row-major over
+// oh x ow), lane t at pixels t, t + 256, t + 512, t + 768 of it.
+template <int IN_LAYOUT, int OUT_LAYOUT, bool U8, bool VEC>
+__global__ __launch_bounds__(kVisThreads) void flow_to_image_kernel(VisLevels lv, const float* __restrict__ ws) {
+    __shared__ float red[kVisThreads / 64];
+    __shared__ vis_f32x4 stage4[VEC ? kVisTile * 3 / (U8 ? 16 : 4) : 1];   // <vec4>: the tile in output order
+    const int tid = threadIdx.x;
+    const int bid = blockIdx.x;
+    const int l = vis_level(lv.cblk0, bid);
+    const int rel = bid - lv.cblk0[l], ct = lv.ctiles[l];
+    const int n = rel / ct, tile = rel - n * ct;
+    const int h = lv.h[l], w = lv.w[l], oh = lv.oh[l], ow = lv.ow[l];
+    const int hw = h * w, ohw = oh * ow;
+    const float ry = lv.ry[l], rx = lv.rx[l];
+    const int step_y = lv.step_y[l], step_x = lv.step_x[l];
+    const void* flow = lv.flow[l];
+    const int f16 = lv.f16[l], pair = lv.pair[l];
+
+    // the image's maximum: its mtiles partials, written by the launch before this one
+    const int mt = lv.mtiles[l];
+    const float* part = ws + lv.mblk0[l] + (int64_t)n * mt;
+    float smax = 0.0f;
+    for (int i = tid; i < mt; i += kVisThreads) smax = fmaxf(smax, part[i]);
+    smax = vis_block_max(smax, red);
+    const float denom = smax + 1e-6f;
+
+    const int base = tile * kVisTile;       // first pixel of the tile
+    const int64_t obase = (int64_t)n * ohw;  // first pixel of the image
+    float* stage = reinterpret_cast<float*>(stage4);
+    uint8_t* stage_b = reinterpret_cast<uint8_t*>(stage4);
+    float* outf = reinterpret_cast<float*>(lv.out[l]);
+    uint8_t* outb = reinterpret_cast<uint8_t*>(lv.out[l]);
+
+    // one division per lane: its further pixels lie 256 = step_y * ow + step_x pixels on
+    int Y = (base + tid) / ow, X = (base + tid) - Y * ow;
+#pragma unroll
+    for (int k = 0; k < kVisPix; ++k, Y += step_y, X += step_x) {
+        const int t = k * kVisThreads + tid, pix = base + t;
+        if (X >= ow) {
+            X -= ow;
+            ++Y;
+        }
+        if (pix >= ohw) continue;
+        const int sy = min((int)floorf(((float)Y + 0.5f) * ry), h - 1);
+        const int sx = min((int)floorf(((float)X + 0.5f) * rx), w - 1);
+        float rgb[3];
+        vis_colour(vis_load<IN_LAYOUT>(flow, f16, pair, n, sy * w + sx, hw), denom, rgb);
+        if (VEC) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int at = OUT_LAYOUT == QPWC_NHWC ? t * 3 + c : c * kVisTile + t;
+                if (U8) stage_b[at] = vis_u8(rgb[c]);
+                else stage[at] = rgb[c];
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int64_t at = OUT_LAYOUT == QPWC_NHWC ? (obase + pix) * 3 + c : (obase * 3 + (int64_t)c * ohw) + pix;
+                if (U8) outb[at] = vis_u8(rgb[c]);
+                else outf[at] = rgb[c];
+            }
+        }
+    }
+    if (!VEC) return;
+    // <vec4>: ohw % 4 == 0, so the tile holds cnt = a multiple of 4 pixels: whole 16-byte pieces of fp32 in either
+    // layout, whole dwords of uint8; the output and with it every image, plane and tile start 16-byte (fp32) / 4-byte
+    // (uint8) aligned
+    __syncthreads();
+    const int cnt = min(kVisTile, ohw - base);
+    if (!U8) {
+        vis_f32x4* o4 = reinterpret_cast<vis_f32x4*>(outf);
+        if (OUT_LAYOUT == QPWC_NHWC) {
+            const int64_t g = (obase + base) * 3 / 4;
+            for (int i = tid; i < cnt * 3 / 4; i += kVisThreads) o4[g + i] = stage4[i];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int64_t g = (obase * 3 + (int64_t)c * ohw + base) / 4;
+                if (4 * tid < cnt) o4[g + tid] = stage4[c * (kVisTile / 4) + tid];
+            }
+        }
+    } else {
+        uint32_t* o1 = reinterpret_cast<uint32_t*>(outb);
+        const uint32_t* stage1 = reinterpret_cast<const uint32_t*>(stage4);
+        if (OUT_LAYOUT == QPWC_NHWC) {
+            const int64_t g = (obase + base) * 3 / 4;
+            for (int i = tid; i < cnt * 3 / 4; i += kVisThreads) o1[g + i] = stage1[i];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int64_t g = (obase * 3 + (int64_t)c * ohw + base) / 4;
+                if (4 * tid < cnt) o1[g + tid] = stage1[c * (kVisTile / 4) + tid];
+            }
+        }
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+
+static int64_t vis_tiles(int a, int b, int tile) { return ((int64_t)a * b + tile - 1) / tile; }
+
+// every count the launches index with fits 32 bits: 2 * B * h * w and 3 * B * oh * ow of each level (oh, ow may be
+// NULL: the workspace query) and the workgroups of both launches
+bool flow_to_image_shape_ok(int n, int B, const int* h, const int* w, const int* oh, const int* ow) {
+    int64_t mblk = 0, cblk = 0;
+    for (int l = 0; l < n; ++l) {
+        if (2 * (int64_t)B * h[l] * w[l] > INT32_MAX) return false;
+        mblk += B * vis_tiles(h[l], w[l], kVisMaxTile);
+        if (oh) {
+            if (3 * (int64_t)B * oh[l] * ow[l] > INT32_MAX) return false;
+            cblk += B * vis_tiles(oh[l], ow[l], kVisTile);
+        }
+    }
+    return mblk <= INT32_MAX && cblk <= INT32_MAX;
+}
+
+int64_t flow_to_image_workspace_floats(int n, int B, const int* h, const int* w) {
+    int64_t f = 0;
+    for (int l = 0; l < n; ++l) f += B * vis_tiles(h[l], w[l], kVisMaxTile);
+    return f;
+}
+
+static bool vis_vec(int n, const int* oh, const int* ow, const void* const* outs) {
+    for (int l = 0; l < n; ++l)
+        if (((int64_t)oh[l] * ow[l]) % 4 || (uintptr_t)outs[l] % 16) return false;
+    return true;
+}
+
+const char* flow_to_image_fwd_kernel(int n, const int* oh, const int* ow, const void* const* outs) {
+    return vis_vec(n, oh, ow, outs) ? "flow_to_image_kernel<vec4>" : "flow_to_image_kernel<scalar>";
+}
+
+int flow_to_image_fwd_launch(const void* const* flows, const int* f16, const int* h, const int* w, int n, int B,
+                             int in_layout, void* const* outs, const int* oh, const int* ow, bool u8, int out_layout,
+                             float* ws, hipStream_t s) {
+    VisLevels lv = {};
+    int mblk = 0, cblk = 0;
+    for (int l = 0; l < kVisMaxLevels; ++l) {
+        lv.mblk0[l] = lv.cblk0[l] = INT_MAX;
+        if (l >= n) continue;
+        lv.flow[l] = flows[l];
+        lv.out[l] = outs[l];
+        lv.h[l] = h[l];
+        lv.w[l] = w[l];
+        lv.oh[l] = oh[l];
+        lv.ow[l] = ow[l];
+        lv.f16[l] = f16[l];
+        lv.pair[l] = in_layout == QPWC_NHWC && (uintptr_t)flows[l] % (f16[l] ? 4 : 8) == 0;
+        lv.ry[l] = (float)h[l] / (float)oh[l];
+        lv.rx[l] = (float)w[l] / (float)ow[l];
+        lv.step_y[l] = kVisThreads / ow[l];
+        lv.step_x[l] = kVisThreads % ow[l];
+        lv.mtiles[l] = (int)vis_tiles(h[l], w[l], kVisMaxTile);
+        lv.ctiles[l] = (int)vis_tiles(oh[l], ow[l], kVisTile);
+        lv.mblk0[l] = mblk;
+        lv.cblk0[l] = cblk;
+        mblk += B * lv.mtiles[l];
+        cblk += B * lv.ctiles[l];
+    }
+    const dim3 block(kVisThreads);
+    if (in_layout == QPWC_NHWC)
+        hipLaunchKernelGGL((flow_mag_max_kernel<QPWC_NHWC>), dim3((unsigned)mblk), block, 0, s, lv, ws);
+    else
+        hipLaunchKernelGGL((flow_mag_max_kernel<QPWC_NCHW>), dim3((unsigned)mblk), block, 0, s, lv, ws);
+    int rc = check_launch("flow_mag_max_kernel");
+    if (rc != QPWC_OK) return rc;
+
+    const bool vec = vis_vec(n, oh, ow, outs);
+    const dim3 grid((unsigned)cblk);
+#define QPWC_VIS(I, O, U, V) \
+    hipLaunchKernelGGL((flow_to_image_kernel<I, O, U, V>), grid, block, 0, s, lv, (const float*)ws)
+#define QPWC_VIS_UV(I, O)                                                          \
+    do {                                                                           \
+        if (u8) {                                                                  \
+            if (vec) QPWC_VIS(I, O, true, true); else QPWC_VIS(I, O, true, false); \
+        } else {                                                                   \
+            if (vec) QPWC_VIS(I, O, false, true); else QPWC_VIS(I, O, false, false); \
+        }                                                                          \
+    } while (0)
+    if (in_layout == QPWC_NHWC) {
+        if (out_layout == QPWC_NHWC) QPWC_VIS_UV(QPWC_NHWC, QPWC_NHWC);
+        else QPWC_VIS_UV(QPWC_NHWC, QPWC_NCHW);
+    } else {
+        if (out_layout == QPWC_NHWC) QPWC_VIS_UV(QPWC_NCHW, QPWC_NHWC);
+        else QPWC_VIS_UV(QPWC_NCHW, QPWC_NCHW);
+    }
+#undef QPWC_VIS_UV
+#undef QPWC_VIS
+    return check_launch("flow_to_image_kernel");
+}
+
+}  // namespace qpwc

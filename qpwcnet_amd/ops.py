@@ -1283,6 +1283,83 @@ def augment_triplet(a, b, c, iparams, fparams, dsize, finish=True, data_format=C
     return out_pair, out_mid
 
 
+def flow_to_image_kernel(B, sizes, out_dtype=torch.uint8, out_layout=CHANNELS_LAST, outs=None):
+    """Store form of ``qpwc_flow_to_image_fwd`` for pictures of these (oh, ow) sizes ('flow_to_image_kernel<vec4>' /
+    'flow_to_image_kernel<scalar>'; host only).  Tensors or addresses for the outputs; None = 16-byte aligned, as
+    torch allocates.  '' for arguments the entry point refuses."""
+    sizes = [tuple(int(v) for v in s) for s in sizes]
+    n = len(sizes)
+    ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else int(t)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*([1 << 20] * n if outs is None else [ptr(t) for t in outs]))
+    oh, ow = (ctypes.c_int * max(n, 1))(*[s[0] for s in sizes]), (ctypes.c_int * max(n, 1))(*[s[1] for s in sizes])
+    name = _hip.lib().qpwc_flow_to_image_fwd_kernel(
+        n, int(B), oh, ow, {torch.uint8: _hip.U8, torch.float32: _hip.F32}.get(out_dtype, -1),
+        {CHANNELS_LAST: _hip.NHWC, CHANNELS_FIRST: _hip.NCHW}.get(out_layout, -1), ptrs)
+    return name.decode() if name else ""
+
+
+def flow_to_image(flows, sizes=None, in_layout=CHANNELS_LAST, out_dtype=torch.float32, out_layout=CHANNELS_LAST):
+    """1..8 flows of one batch size and different spatial sizes -> their pictures, in two launches for all of them
+    (qpwc_flow_to_image_fwd, include/qpwc_vis.h; qpwcnet/core/vis.py:37-76 and the nearest resize and uint8 conversion
+    of app/train.py's ShowImageCallback).  flows[l] (B,h,w,2) / (B,2,h,w) by in_layout, fp32 or fp16, dense, on one HIP
+    device; sizes[l] = (oh, ow) or None for the flow's own size (sizes=None: all of them); -> a list of (B,oh,ow,3) /
+    (B,3,oh,ow) tensors by out_layout, float32 or uint8 by out_dtype, each coloured by its own per-image maximum.  The
+    workspace comes from torch's allocator on the current stream.  Enqueues and returns: no host synchronisation."""
+    get_axis(in_layout)
+    get_axis(out_layout)
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError("out_dtype must be torch.float32 or torch.uint8, got {}".format(out_dtype))
+    flows = list(flows)
+    n = len(flows)
+    if not 1 <= n <= 8:
+        raise ValueError("flow_to_image takes 1..8 flows, got {}".format(n))
+    sizes = [None] * n if sizes is None else list(sizes)
+    if len(sizes) != n:
+        raise ValueError("{} sizes for {} flows".format(len(sizes), n))
+    nhwc_in, nhwc_out = in_layout == CHANNELS_LAST, out_layout == CHANNELS_LAST
+    hs, ws_, ohs, ows = [], [], [], []
+    for i, f in enumerate(flows):
+        name = "flows[%d]" % i
+        if not isinstance(f, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if not f.is_cuda:
+            raise RuntimeError("qpwcnet_amd: {} is on '{}'; ops.flow_to_image runs on a HIP device only (vis.* has "
+                               "the CPU path)".format(name, f.device))
+        if f.dtype not in _DTYPES:
+            raise ValueError("{}: unsupported dtype {}".format(name, f.dtype))
+        if f.dim() != 4 or f.shape[3 if nhwc_in else 1] != 2:
+            raise ValueError("{} must be {}, got shape {}".format(name, "(B,h,w,2)" if nhwc_in else "(B,2,h,w)",
+                                                                  tuple(f.shape)))
+        if f.device != flows[0].device or f.shape[0] != flows[0].shape[0]:
+            raise ValueError("{}: every flow must be on one device and of one batch size".format(name))
+        flows[i] = f = f.contiguous()
+        h, w = (f.shape[1], f.shape[2]) if nhwc_in else (f.shape[2], f.shape[3])
+        oh, ow = (h, w) if sizes[i] is None else (int(v) for v in sizes[i])
+        if min(h, w, oh, ow) <= 0:
+            raise ValueError("{}: non-positive extent {}x{} -> {}x{}".format(name, h, w, oh, ow))
+        hs.append(int(h)), ws_.append(int(w)), ohs.append(oh), ows.append(ow)
+    B, dev = int(flows[0].shape[0]), flows[0].device
+    if B <= 0:
+        raise ValueError("empty batch")
+    L = _hip.lib()
+    arr = lambda v: (ctypes.c_int * n)(*v)
+    ha, wa, oha, owa = arr(hs), arr(ws_), arr(ohs), arr(ows)
+    nws = L.qpwc_flow_to_image_workspace_floats(n, B, ha, wa)
+    _hip.check(min(int(nws), 0))
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+        outs = [torch.empty((B, oh, ow, 3) if nhwc_out else (B, 3, oh, ow), dtype=out_dtype, device=dev)
+                for oh, ow in zip(ohs, ows)]
+        with _timed("flow_to_image", (n, B, ohs[0], ows[0])):
+            rc = L.qpwc_flow_to_image_fwd(
+                (ctypes.c_void_p * n)(*[f.data_ptr() for f in flows]), arr([_DTYPES[f.dtype] for f in flows]), ha, wa, n,
+                B, _hip.NHWC if nhwc_in else _hip.NCHW, (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), oha, owa,
+                _hip.U8 if out_dtype == torch.uint8 else _hip.F32, _hip.NHWC if nhwc_out else _hip.NCHW,
+                ws.data_ptr(), _stream(flows[0]))
+    _hip.check(rc)
+    return outs
+
+
 def _loss_layout(y_true, preds, data_format):
     """-> (y_true, preds, layout code, nhwc_view): 'channels_first' operands that are all physically NHWC (torch
     channels_last memory) are read through their permuted views; everything else dense in its declared layout."""
