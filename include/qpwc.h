@@ -254,6 +254,9 @@ const char* qpwc_augment_fwd_kernel(int B, int h, int w, const void* out_ims, co
  * without materialising nxt_w.  NHWC, mode CLAMP, flo dense (B,H,W,2) fp32,
  * search_range 4, C % 4 == 0.  Output addressing as in
  * qpwc_cost_volume_fwd_strided (pass stride d*d, offset 0 for a dense result).
+ * ALIGNMENT: prv and nxt must be 16-byte aligned (every fused kernel gathers them as 16-byte vectors and there is no
+ * element-wise form): QPWC_E_ALIGN otherwise, qpwc_last_error() names the operand.  flo (4 bytes) and out (its
+ * element) are element-aligned like everywhere else.
  * PERFORMANCE NOTE: this entry point always computes what it is asked.  Where the matrix-core
  * kernels do not apply (qpwc_cost_volume_kernel(..., fused=1) names the choice: anything but
  * "cost_volume_mfma_lds*" means fewer than 256 regions of 8x8 pixels, C % 32 != 0, or a generic

@@ -93,6 +93,12 @@ static int cost_volume_checked(const void* prv, const void* nxt, const void* flo
     if (overlaps(out, n_out, prv, n_in) || overlaps(out, n_out, nxt, n_in) ||
         (fuse && overlaps(out, n_out, flo, (size_t)B * H * W * 2 * 4)))
         return fail(QPWC_E_ALIAS, "out overlaps an input");
+    // every fused kernel reads prv and nxt as 16-byte vectors and there is no element-wise form behind them
+    // (cost_volume_impl); a shape they do not take (C % 4, search_range) stays the launcher's to answer
+    if (fuse && r == 4 && C % 4 == 0) {
+        if ((uintptr_t)prv % 16) return fail(QPWC_E_ALIGN, "prv must be 16-byte aligned for the fused warp+cost volume");
+        if ((uintptr_t)nxt % 16) return fail(QPWC_E_ALIGN, "nxt must be 16-byte aligned for the fused warp+cost volume");
+    }
     char* o = (char*)out + (size_t)off * es;
     // 84-float pixels holding the 81 channels at offset 0: the 3 pad channels are written as zeros
     const bool pad84 = strided && r == 4 && ops == 84 && off == 0;
