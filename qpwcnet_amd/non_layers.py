@@ -9,6 +9,7 @@ Tensors cross every block boundary in the declared data format, like the
 reference.  Convolutions run on logical-NCHW views; for ``channels_last`` those
 views are torch channels_last memory, i.e. nothing is transposed or copied.
 """
+import collections
 import math
 
 import torch
@@ -82,9 +83,9 @@ class Warp(_Functor):
 class WarpV2(_Functor):
     """qpwcnet/core/non_layers.py:137-158 -> tfa dense_image_warp(img, -flo[..., ::-1])."""
 
-    def __call__(self, inputs):
+    def __call__(self, inputs, flo32=None):
         img, flo = inputs
-        return ops.warp(img, flo, "clamp", self.data_format)
+        return ops.warp(img, flo, "clamp", self.data_format, flo32=flo32)
 
 
 # --------------------------------------------------------------------------
@@ -160,14 +161,21 @@ class _Weighted(_Functor):
     def p(self, name):
         return self.params[self.prefix + name]
 
-    def p32(self, name):
-        """fp32 copy of a (small) parameter, converted once: the HIP epilogues take fp32
-        biases whatever the storage dtype of the activations."""
-        key = self.prefix + name + "#f32"
+    def _memo(self, key, make):
         t = self.params.get(key)
         if t is None:
-            t = self.params[key] = self.params[self.prefix + name].float().contiguous()
+            t = self.params[key] = make()
         return t
+
+    def derived(self, name, make):
+        """A tensor (or tuple of tensors) computed from this block's parameters, made once by make() and kept beside
+        them under `<prefix>#<name>`: functors on the same dict and prefix share the one copy."""
+        return self._memo(self.prefix + "#" + name, make)
+
+    def p32(self, name):
+        """fp32 copy of a (small) parameter, converted once (kept as `<prefix><name>#f32`): the HIP epilogues take fp32
+        biases whatever the storage dtype of the activations."""
+        return self._memo(self.prefix + name + "#f32", lambda: self.p(name).float().contiguous())
 
 
 def _hip_act_ok(y_nchw, data_format):
@@ -237,16 +245,11 @@ class UpConv(_Weighted):
         (skip half already in place; ordering it before this call is the caller's business)."""
         if self._hip_upconv_ok(x, skip):
             # own transposed-convolution kernel: bias + Mish fused, written straight into the concat buffer
-            key = self.prefix + ("#taps_up" if x.dtype == torch.float32 else "#taps_up_f16")
-            t = self.params.get(key)
-            if t is None:
-                t = self.params[key] = ops.upconv_taps(self.p("conv_up.weight"), x.dtype)
+            t = self.derived("taps_up" if x.dtype == torch.float32 else "taps_up_f16",
+                             lambda: ops.upconv_taps(self.p("conv_up.weight"), x.dtype))
             n_up = t.shape[1]
             if self.matmul == "bf16x3" and x.dtype == torch.float32 and x.shape[3] in self.x3_channels:
-                t3 = self.params.get(self.prefix + "#taps_up_x3")
-                if t3 is None:
-                    t3 = self.params[self.prefix + "#taps_up_x3"] = ops.split_bf16x3(t)
-                t = t3
+                t = self.derived("taps_up_x3", lambda: ops.split_bf16x3(t))
             prefilled = buf is not None
             if prefilled and (tuple(buf.shape) != tuple(skip.shape[:3]) + (n_up + skip.shape[3],) or buf.dtype != x.dtype):
                 raise ValueError("prefilled concat buffer {} does not fit this level".format(tuple(buf.shape)))
@@ -315,15 +318,11 @@ class DownConv(_Weighted):
         `after_a`: Mish(conv_a(x) + bias) already computed (channels-last), conv_a is skipped."""
         if after_a is None and padded_in is not None and self._hip_s2_ok(padded_in):
             # second level: stride-2 conv + bias + Mish in one HIP launch on the zero-bordered input
-            key = self.prefix + ("#taps_a" if padded_in.dtype == torch.float32 else "#taps_a_f16")
-            t = self.params.get(key)
-            if t is None:
-                t = self.params[key] = ops.conv3x3_taps(self.p("conv_a.weight"), padded_in.dtype)
+            t = self.derived("taps_a" if padded_in.dtype == torch.float32 else "taps_a_f16",
+                             lambda: ops.conv3x3_taps(self.p("conv_a.weight"), padded_in.dtype))
             if self.matmul == "bf16x3" and self.x3_stride2 and padded_in.dtype == torch.float32 and \
                     padded_in.shape[3] in (32, 64, 128):
-                t3 = self.params.get(self.prefix + "#taps_a_x3")
-                if t3 is None:
-                    t3 = self.params[self.prefix + "#taps_a_x3"] = ops.split_bf16x3(t)
+                t3 = self.derived("taps_a_x3", lambda: ops.split_bf16x3(t))
                 after_a = ops.conv3x3s2_mish_x3(padded_in, t3, self.p32("conv_a.bias"))
             else:
                 after_a = ops.conv3x3s2_mish(padded_in, t, self.p32("conv_a.bias"))
@@ -392,26 +391,21 @@ class DownConv(_Weighted):
                 pairs.dtype in (torch.float32, torch.float16) and tuple(w.shape) == (16, 3, 3, 3) and
                 hh % 2 == 0 and ww % 2 == 0 and cc == 6):
             return None
-        key = self.prefix + "#taps_a"
-        t = self.params.get(key)
-        if t is None:
-            t = self.params[key] = ops.first_conv_taps(w)
+        t = self.derived("taps_a", lambda: ops.first_conv_taps(w))
         return ops.first_conv_mish(pairs.contiguous(), t, self.p32("conv_a.bias"), pf)
 
     def _taps(self, dtype=torch.float32):
-        key = self.prefix + ("#taps" if dtype == torch.float32 else "#taps_f16")
-        t = self.params.get(key)
-        if t is None:
-            t = self.params[key] = (ops.conv3x3_taps(self.p("conv_aa.weight"), dtype),
-                                    ops.conv3x3_taps(self.p("conv_b.weight"), dtype))
-        return t
+        return self.derived("taps" if dtype == torch.float32 else "taps_f16",
+                            lambda: (ops.conv3x3_taps(self.p("conv_aa.weight"), dtype),
+                                     ops.conv3x3_taps(self.p("conv_b.weight"), dtype)))
 
     def _taps_x3(self):
-        key = self.prefix + "#taps_x3"
-        t = self.params.get(key)
-        if t is None:
-            t = self.params[key] = tuple(ops.split_bf16x3(w) for w in self._taps(torch.float32))
-        return t
+        return self.derived("taps_x3", lambda: tuple(ops.split_bf16x3(w) for w in self._taps(torch.float32)))
+
+
+# What a level of the flow chain hands on: its flow and, where the flow head's launch wrote them too (ops.flow_head_up),
+# the Upsample(2.0) of it and -- fp16 storage -- that once more as fp32, the next level's warp coordinates; else None.
+FlowLevel = collections.namedtuple("FlowLevel", "flow up up32", defaults=(None, None))
 
 
 class OptFlow(_Weighted):
@@ -472,11 +466,13 @@ class OptFlow(_Weighted):
         super().__init__(params, prefix, *args, **kwargs)
         self.filters = tuple(filters)
         self.scale = scale
+        self.out_format = self.data_format   # QpwcNet: 'channels_first' for a channels_first model on channels-last blocks
+        self._hip_ready = False
 
     # ---- HIP path: multi-source depthwise kernel (no concat, Mish
     # fused on load), pointwise convs as library GEMMs, fused flow head ---------------
     def _prepare_hip(self):
-        if getattr(self, "_hip_ready", False):
+        if self._hip_ready:
             return
         self._pw_t, self._pw_b, self._dw = [], [], []
         for i in range(len(self.filters)):
@@ -531,15 +527,20 @@ class OptFlow(_Weighted):
         return (self.data_format == CHANNELS_LAST and self.filters[-1] == 16 and
                 all(t.is_cuda and t.dtype in (torch.float32, torch.float16) for t in sources))
 
-    def from_sources(self, sources):
-        """OptFlow on the virtual concat of `sources` ((B,H,W,Ci) each, channels_last)."""
+    def from_sources(self, sources, want_up=False):
+        """OptFlow on the virtual concat of `sources` ((B,H,W,Ci) each, channels_last): the flow, or level()'s FlowLevel."""
+        lvl = self.level(sources, want_up)
+        return lvl if want_up else lvl.flow
+
+    def level(self, sources, want_up=False):
+        """from_sources() as a FlowLevel.  want_up: the caller upsamples the flow next (QpwcNet's flow chain), so where
+        fuse_upsample applies the flow head's launch writes `up` (and `up32`) too; everywhere else they are None."""
         if not self.can_use_hip(sources):
             y = self(torch.cat(list(sources), dim=self.axis))
-            out_format = getattr(self, "out_format", self.data_format)
-            if out_format != self.data_format:   # a channels_first model on channels-last blocks wants (B,2,h,w)
-                y = y.permute(0, 3, 1, 2) if out_format == CHANNELS_FIRST else y.permute(0, 2, 3, 1)
+            if self.out_format != self.data_format:   # a channels_first model on channels-last blocks wants (B,2,h,w)
+                y = y.permute(0, 3, 1, 2) if self.out_format == CHANNELS_FIRST else y.permute(0, 2, 3, 1)
                 y = y.contiguous()
-            return y
+            return FlowLevel(y)
         self._prepare_hip()
         B, H, W = sources[0].shape[:3]
         scale = self.scale if self.scale is not None else float(H ** 2 + W ** 2) ** 0.5
@@ -565,9 +566,8 @@ class OptFlow(_Weighted):
         for i in range(n_layers):
             if use_tail and i == 2:   # z = the second layer's output
                 dw = self._dw
-                return ops.optflow_tail(z, dw[2], self._pw3, self._pw_b32[2], dw[3], self._pw4, self._pw_b32[3],
-                                        self._head, scale, mish_on_load=not z_act,
-                                        out_format=getattr(self, "out_format", CHANNELS_LAST))
+                return FlowLevel(ops.optflow_tail(z, dw[2], self._pw3, self._pw_b32[2], dw[3], self._pw4, self._pw_b32[3],
+                                                  self._head, scale, mish_on_load=not z_act, out_format=self.out_format))
             src = sources if i == 0 else [z]
             act_in = i > 0 and not z_act
             first84 = i == 0 and padded_cost
@@ -597,14 +597,11 @@ class OptFlow(_Weighted):
                     z = torch.addmm(self._pw_b[i], y.view(B * H * W, -1),
                                     self._pw_t84 if first84 else self._pw_t[i]).view(B, H, W, -1)
                 z_act = False
-        out_format = getattr(self, "out_format", CHANNELS_LAST)
-        if self.fuse_upsample and out_format == CHANNELS_LAST and B * H * W <= self.fuse_upsample_max_pixels:
-            # round 4: the Upsample(2.0) that follows every level in QpwcNet's flow chain, by the flow head's own launch; the
-            # caller finds it on the returned flow (QpwcNet._up)
-            out, up = ops.flow_head_up(z, self._head, scale, 2.0)
-            out._qpwc_up2 = up
-            return out
-        return ops.flow_head(z, self._head, scale, out_format)
+        if (want_up and self.fuse_upsample and self.out_format == CHANNELS_LAST and
+                B * H * W <= self.fuse_upsample_max_pixels):
+            # round 4: the Upsample(2.0) that follows every level in QpwcNet's flow chain, by the flow head's own launch
+            return FlowLevel(*ops.flow_head_up(z, self._head, scale, 2.0))
+        return FlowLevel(ops.flow_head(z, self._head, scale, self.out_format))
 
     def __call__(self, inputs):
         shape = parse_image_shape(inputs, self.data_format)
@@ -640,15 +637,18 @@ class Flow(_Weighted):
         self.hip_optflow = bool(hip_optflow)
 
     def __call__(self, inputs):
+        return self.level(inputs).flow
+
+    def level(self, inputs, want_up=False):
+        """The block as a FlowLevel (want_up: see OptFlow.level)."""
         prv, nxt = inputs
         if self.hip_optflow and self.flow.wants_cost84(prv, other_channels=(prv.shape[-1], nxt.shape[-1])):
             cost = _cost84(prv, nxt, self.cost_volume.search_range)
-            return self.flow.from_sources((cost, prv, nxt))
-        cost = self.cost_volume((prv, nxt))
+        else:
+            cost = self.cost_volume((prv, nxt))
         if self.hip_optflow:
-            return self.flow.from_sources((cost, prv, nxt))
-        feat = torch.cat([cost, prv, nxt], dim=self.axis)
-        return self.flow(feat)
+            return self.flow.level((cost, prv, nxt), want_up)
+        return FlowLevel(self.flow(torch.cat([cost, prv, nxt], dim=self.axis)))
 
 
 def _cost84(prv, nxt, search_range, flo=None):
@@ -721,27 +721,29 @@ class UpFlow(_Weighted):
                                (self.fused_forced and fused_kernel_applies(prv, r)))
 
     def __call__(self, inputs):
+        return self.level(inputs).flow
+
+    def level(self, inputs, flo32=None, want_up=False):
+        """The block as a FlowLevel (want_up: see OptFlow.level).  flo32: flo's values as dense fp32 (the level before's
+        FlowLevel.up32): the warp's coordinates are fp32 whatever the storage dtype, and without it flo is cast here."""
         prv, nxt, flo = inputs
         r = self.cost_volume.search_range
         if self.fuses(prv, flo):
-            # coordinates are fp32 whatever the storage dtype (fp16 storage: flow_head_up() wrote them beside the flow)
-            flo32 = getattr(flo, "_qpwc_f32", None) if flo.dtype == torch.float16 else None
             if flo32 is None:
                 flo32 = flo.to(torch.float32).contiguous()
             if self.flow.wants_cost84(prv):
                 cost = _cost84(prv, nxt, r, flo=flo32)
             else:
                 cost = ops.warp_cost_volume(prv.contiguous(), nxt.contiguous(), flo32, r, 0.1)
-            return self.flow.from_sources((cost, prv, flo))
-        nxt_w = self.warp((nxt, flo))
+            return self.flow.level((cost, prv, flo), want_up)
+        nxt_w = self.warp((nxt, flo), flo32=flo32)
         if self.hip_optflow and self.flow.wants_cost84(prv):
-            cost = _cost84(prv, nxt_w, self.cost_volume.search_range)
-            return self.flow.from_sources((cost, prv, flo))
-        cost = self.cost_volume((prv, nxt_w))
+            cost = _cost84(prv, nxt_w, r)
+        else:
+            cost = self.cost_volume((prv, nxt_w))
         if self.hip_optflow:
-            return self.flow.from_sources((cost, prv, flo))
-        feat = torch.cat([cost, prv, flo], dim=self.axis)
-        return self.flow(feat)
+            return self.flow.level((cost, prv, flo), want_up)
+        return FlowLevel(self.flow(torch.cat([cost, prv, flo], dim=self.axis)))
 
 
 class FrameInterpolate(_Weighted):
@@ -799,12 +801,9 @@ class FrameInterpolate(_Weighted):
                 src = [torch.cat([prv_w, nxt_w, small], dim=3)]
             else:
                 src = [prv_w, nxt_w, small]
-            key = self.prefix + "#gemm"
-            mats = self.params.get(key)
-            if mats is None:
-                mats = self.params[key] = (pw.reshape(pw.shape[0], -1).t().contiguous(),
-                                           w2.reshape(w2.shape[0], -1).t().contiguous(),
-                                           ops.pad_pointwise(pw))
+            mats = self.derived("gemm", lambda: (pw.reshape(pw.shape[0], -1).t().contiguous(),
+                                                 w2.reshape(w2.shape[0], -1).t().contiguous(),
+                                                 ops.pad_pointwise(pw)))
             dw9 = self.p32("conv1.depthwise.weight").reshape(-1, 9)
             n_tiles = B * ((H + 7) // 8) * ((W + 15) // 16)
             if prv_w.dtype == torch.float32 and OptFlow._fuse_layer(dw9.shape[0], n_tiles):

@@ -356,8 +356,8 @@ def cost_volume_to_flow(cvol, data_format=CHANNELS_LAST):
     return out if cvol.dim() == 4 else out[0]
 
 
-def _flow_physical(flo, dims, data_format, layout):
-    """fp32 flow, dense over its non-broadcast dims, in the layout the image uses."""
+def _flow_physical(flo, dims, data_format, layout, flo32=None):
+    """fp32 flow (flo32 where warp() was given it, else cast), dense over its non-broadcast dims, in the image's layout."""
     B, H, W, _ = dims
     if flo.dim() != 4:
         raise ValueError("flo must be rank 4, got shape {}".format(tuple(flo.shape)))
@@ -375,9 +375,7 @@ def _flow_physical(flo, dims, data_format, layout):
             raise ValueError("flo shape {} is not broadcastable to the image".format(
                 tuple(flo.shape)))
         mask |= bit
-    f = getattr(flo, "_qpwc_f32", None) if flo.dtype == torch.float16 else None   # written beside it by flow_head_up()
-    if f is None:
-        f = flo.to(torch.float32)
+    f = flo.to(torch.float32) if flo32 is None else flo32
     if data_format == CHANNELS_FIRST and layout == _hip.NHWC:
         f = f.permute(0, 2, 3, 1)  # image is physically NHWC: give the flow the same layout
     return f.contiguous(), mask
@@ -444,9 +442,9 @@ def _grad_flow(flo, img, data_format):
     else:
         B, H, W = img.shape[0], img.shape[2], img.shape[3]
         full = (B, 2, H, W)
-    # An fp16 flow from flow_head_up() carries an fp32 side copy (_qpwc_f32) that the no-grad path reads; it holds
-    # exactly flo.float() (fp16 -> fp32 is exact), so this cast gives the same forward bits, and unlike the side
-    # copy it stays connected to flo in the autograd graph.
+    # warp()'s flo32 (the fp32 coordinates flow_head_up() returns beside an fp16 flow) is for the no-grad path only: it
+    # holds exactly flo.float() (fp16 -> fp32 is exact), so this cast gives the same forward bits, and unlike a
+    # separate tensor it stays connected to flo in the autograd graph.
     f = flo.to(torch.float32)
     try:
         return f.expand(full)
@@ -454,11 +452,16 @@ def _grad_flow(flo, img, data_format):
         raise ValueError("flo shape {} is not broadcastable to the image".format(tuple(flo.shape)))
 
 
-def warp(img, flo, mode="clamp", data_format=CHANNELS_LAST):
+def warp(img, flo, mode="clamp", data_format=CHANNELS_LAST, flo32=None):
     """Warp (mode 'tfwarp', qpwcnet/core/warp.py:63-153) / WarpV2 (mode 'clamp',
     qpwcnet/core/layers.py:177-186): sample img at (y + flo[...,1], x + flo[...,0]).
-    Differentiable in img and flo: with grad enabled and an input requiring grad the same forward runs inside an
-    autograd Function whose backward is qpwc_warp_bwd."""
+    flo32: flo's values as a dense fp32 tensor of flo's shape, from a caller that has them (flow_head_up()): the
+    coordinates are read from it instead of a cast of flo.  Differentiable in img and flo: with grad enabled and an input
+    requiring grad the same forward runs inside an autograd Function whose backward is qpwc_warp_bwd (flo32 is not read)."""
+    if flo32 is not None and isinstance(flo, torch.Tensor) and not (
+            isinstance(flo32, torch.Tensor) and flo32.dtype == torch.float32 and flo32.shape == flo.shape and
+            flo32.device == flo.device and flo32.is_contiguous()):
+        raise ValueError("flo32 must be a dense fp32 tensor of flo's shape on flo's device")
     if _wants_grad(img, flo):
         _refuse_capture("the warp")
         _check_tensor("img", img)
@@ -475,9 +478,9 @@ def warp(img, flo, mode="clamp", data_format=CHANNELS_LAST):
     B, H, W, C = dims
     if layout == _hip.NCHW and C % 4 == 0 and (H >= 2 and W >= 2 or mode == "tfwarp"):
         # dense (B,C,H,W): the 16-byte gather kernel on a channels-last copy (flow: 2 channels, permuted)
-        out_l = warp(layout_transpose(i, CHANNELS_LAST), flo.permute(0, 2, 3, 1), mode, CHANNELS_LAST)
+        out_l = warp(layout_transpose(i, CHANNELS_LAST), (flo if flo32 is None else flo32).permute(0, 2, 3, 1), mode, CHANNELS_LAST)
         return layout_transpose(out_l, CHANNELS_FIRST)
-    f, mask = _flow_physical(flo, dims, data_format, layout)
+    f, mask = _flow_physical(flo, dims, data_format, layout, flo32)
     buf, out = _empty_like_layout(i, dims, C, layout, as_view)
     with torch.cuda.device(i.device), _timed("warp_" + mode, dims):
         rc = _hip.lib().qpwc_warp_fwd(
@@ -773,8 +776,9 @@ def pointwise_bias(y, pw_padded, bias):
 
 def flow_head_up(z, params, scale, up_scale=2.0):
     """flow_head() (channels-last) and the Upsample(x2, * up_scale) that follows it in the flow chain (pwcnet.py:55,60) in one
-    launch (qpwc_flow_head_up_fwd) -> (flow (B,H,W,2), up_scale * bilinear x2 of it (B,2H,2W,2)); the second equals
-    upsample2x_flow(flow, up_scale) bit for bit."""
+    launch (qpwc_flow_head_up_fwd) -> (flow (B,H,W,2), up = up_scale * bilinear x2 of it (B,2H,2W,2), up32); up equals
+    upsample2x_flow(flow, up_scale) bit for bit.  up32: fp16 storage: up.float(), written by the same launch (the next
+    level's WarpV2 takes fp32 coordinates, warp(flo32=...), and the cast was a launch per level); fp32 storage: None."""
     _check_tensor("z", z)
     if z.shape[3] != 16 or not z.is_contiguous():
         raise ValueError("z must be a dense (B,H,W,16) tensor")
@@ -786,17 +790,13 @@ def flow_head_up(z, params, scale, up_scale=2.0):
     B, H, W, _ = z.shape
     out = torch.empty((B, H, W, 2), dtype=z.dtype, device=z.device)
     up = torch.empty((B, 2 * H, 2 * W, 2), dtype=z.dtype, device=z.device)
-    # fp16 storage: the upsampled flow once more as fp32, written by the same launch (== up.float(); found by its consumers
-    # as up._qpwc_f32: the next level's WarpV2 takes fp32 coordinates, and the cast was a launch of its own per level)
     up32 = torch.empty((B, 2 * H, 2 * W, 2), dtype=torch.float32, device=z.device) if z.dtype == torch.float16 else None
     with torch.cuda.device(z.device), _timed("flow_head", (B, H, W, 16)):
         rc = L.qpwc_flow_head_up_fwd(z.data_ptr(), params.data_ptr(), out.data_ptr(), up.data_ptr(),
                                      up32.data_ptr() if up32 is not None else None, B, H, W,
                                      float(scale), float(up_scale), _DTYPES[z.dtype], _stream(z))
     _hip.check(rc)
-    if up32 is not None:
-        up._qpwc_f32 = up32
-    return out, up
+    return out, up, up32
 
 
 def optflow_tail(z2, dw3, pw3, b3, dw4, pw4, b4, head_params, scale, mish_on_load=False, out_format=CHANNELS_LAST):

@@ -112,7 +112,6 @@ class QpwcNet:
         # of a two-branch graph for its whole length (tools/step_time.py prefill_skips=True).  Off.
         self.prefill_skips = False
         self.skip_copy_first = ()    # see _forward_two_streams: (3, 2) 1.140-1.145, (3,) 1.138-1.140, (3, 2, 1, 0) 1.142-1.145 vs () 1.130-1.133 ms/step
-        self._prefilled = {}
         # launches per decoder level on the side stream (slices of the 2B stacked frames), see _forward_two_streams
         # round 3 (tools/step_time.py "dec_chunks=...", three interleaved runs each in one call, ms/step): (2,4,4,4)
         # 1.2147, (2,4,4,2) 1.1996, (2,4,4,1) 1.1991, (2,4,2,2) 1.2005, (2,2,4,1) 1.2031, (2,4,8,8) 1.296: the finest
@@ -189,17 +188,18 @@ class QpwcNet:
         for blk in [self.flow] + self.upflows:
             blk.flow.matmul = v
 
-    def _up(self, flo, last=False):
-        """Upsample(scale=2.0) between levels (pwcnet.py:55,60).  A channels_first model on the
-        channels-last kernels: the flow comes in the declared layout (flow_head wrote it so), the
-        next level wants it channels-last, the last one is an output again."""
-        up = getattr(flo, "_qpwc_up2", None)
-        if up is not None and self._df == self.data_format == CHANNELS_LAST:
-            return up       # written by the flow head's own launch (OptFlow.fuse_upsample, qpwc_flow_head_up_fwd)
+    def _up(self, lvl, last=False):
+        """Upsample(scale=2.0) between levels (pwcnet.py:55,60) of a FlowLevel -> (upsampled flow, its fp32 coordinates
+        where the level's own launch wrote them, else None).  A channels_first model on the channels-last kernels: the flow
+        comes in the declared layout (flow_head wrote it so), the next level wants it channels-last, the last one is an
+        output again."""
+        if lvl.up is not None:
+            return lvl.up, lvl.up32     # written by the flow head's own launch (OptFlow.fuse_upsample, qpwc_flow_head_up_fwd)
+        flo = lvl.flow
         if self._df != self.data_format and flo.is_cuda and flo.shape[1] == 2:
             return ops.upsample2x_flow(flo, 2.0, in_format=self.data_format,
-                                       out_format=self.data_format if last else self._df)
-        return Upsample(scale=2.0, data_format=self.data_format)(flo)
+                                       out_format=self.data_format if last else self._df), None
+        return Upsample(scale=2.0, data_format=self.data_format)(flo), None
 
     def __call__(self, inputs):
         exp = (self.input_shape + (6,)) if self.data_format == CHANNELS_LAST \
@@ -209,12 +209,9 @@ class QpwcNet:
         if self.batch_frames:
             nb = inputs.shape[0]
             overlap = self.overlap_streams and inputs.is_cuda
-            self._prefilled = {}
-            encs = self._encode_stacked(inputs, prefill=overlap and self.prefill_skips)
-            try:
-                return self._forward_stacked(encs, nb, overlap)
-            finally:
-                self._prefilled = {}
+            prefilled = {}      # {decoder level: its concat buffer with the skip half in place}, this forward's
+            encs = self._encode_stacked(inputs, prefilled if overlap and self.prefill_skips else None)
+            return self._forward_stacked(encs, nb, overlap, prefilled)
         img_prv, img_nxt = self.split(inputs)
         encs_prv, encs_nxt = encoder(self.enc, img_prv, img_nxt, True)
         decs_prv, decs_nxt = decoder(self.dec, encs_prv, encs_nxt, self.axis, True)
@@ -222,8 +219,8 @@ class QpwcNet:
                       self.data_format, output_multiscale=self.train)
         return outs if self.train else outs[0]
 
-    def _prefill(self, li, f):
-        """Encoder level li (li < 4) is the skip of decoder level 3 - li: allocate that level's concat buffer and copy the
+    def _prefill(self, li, f, prefilled):
+        """Encoder level li (li < 4) is the skip of decoder level 3 - li: allocate that level's concat buffer (-> prefilled) and copy the
         skip half NOW, on the decoder's side stream, under the encoder's remaining levels (whose kernels leave the memory
         system idle) instead of beside the coarse flow levels, where both queues are full (round 4: the four copies are
         41 us of the second queue's ~310 us in that phase).  The side stream only ever waits for the caller's stream here."""
@@ -244,11 +241,11 @@ class QpwcNet:
             buf = self.dec[i].prefill_skip(f, c_in)
         if buf is not None:
             f.record_stream(side)
-            self._prefilled[i] = buf
+            prefilled[i] = buf
 
-    def _encode_stacked(self, inputs, prefill=False):
+    def _encode_stacked(self, inputs, prefilled=None):
         """The encoder/decoder weights are shared by both frames (pwcnet.py:145-162, 179-206): run
-        the encoder once on the 2B stacked frames [prv; nxt] -> [frames, enc_0 .. enc_4]."""
+        the encoder once on the 2B stacked frames [prv; nxt] -> [frames, enc_0 .. enc_4].  prefilled: see _prefill."""
         h, w = self.input_shape
         first = self.enc[0].first_layer(inputs, self.data_format)
         split_axis = self.axis
@@ -271,28 +268,29 @@ class QpwcNet:
             f, padded = l.forward_padded(f, padded, want_padded=li + 1 < len(self.enc),
                                          after_a=first if li == 0 else None)
             encs.append(f)
-            if prefill and li + 1 < len(self.enc):
-                self._prefill(li, f)
+            if prefilled is not None and li + 1 < len(self.enc):
+                self._prefill(li, f, prefilled)
         return encs
 
-    def _forward_stacked(self, encs, nb, overlap):
+    def _forward_stacked(self, encs, nb, overlap, prefilled=None):
         """Decoder + flow chain on the stacked encoder outputs.  overlap: the two-stream form."""
         if overlap:
-            return self._forward_two_streams(encs, nb)
+            return self._forward_two_streams(encs, nb, prefilled)
         f, decs, i = encs[-1], [], -2
         for l in self.dec:
             f = l.cat_skip(f, encs[i])
             i -= 1
             decs.append(f)
-        flo = self.flow((encs[-1][:nb], encs[-1][nb:]))
-        flos = [flo]
+        lvl = self.flow.level((encs[-1][:nb], encs[-1][nb:]), want_up=True)
+        flos = [lvl.flow]
         for i, upflow in enumerate(self.upflows):
-            flo = upflow((decs[i][:nb], decs[i][nb:], self._up(flo)))
-            flos.append(flo)
-        flos.append(self._up(flo, last=True))
+            flo_u, flo32 = self._up(lvl)
+            lvl = upflow.level((decs[i][:nb], decs[i][nb:], flo_u), flo32, want_up=True)
+            flos.append(lvl.flow)
+        flos.append(self._up(lvl, last=True)[0])
         return flos if self.train else flos[-1]
 
-    def _forward_two_streams(self, encs, nb):
+    def _forward_two_streams(self, encs, nb, prefilled=None):
         """Decoder chain on a side stream, flow chain on the caller's stream: the coarse
         levels' launches are far too small to fill 256 CUs one at a time, and the decoder
         of level i+1 does not depend on the flow of level i (pwcnet.py:179-206 vs 39-57).
@@ -313,6 +311,7 @@ class QpwcNet:
         while len(self._sides) < n_side:
             self._sides.append(self._side if not self._sides else torch.cuda.Stream(device=encs[-1].device))
         sides = self._sides[:n_side]
+        prefilled = {} if prefilled is None else prefilled
         for sd in sides:
             sd.wait_stream(main)            # encoder outputs are ready
         # One library launch over the 2B stacked frames fills the chip with long-lived workgroups and the small
@@ -349,7 +348,7 @@ class QpwcNet:
         # convolution, beside flow levels 2 and 3 where both queues are full (skip_copy_first: decoder levels, in this order).
         # Measured slower in every order tried (the decoder's first level is then late for flow level 1): off.
         for i in self.skip_copy_first:
-            if i in self._prefilled or not 0 <= i < len(self.dec) or ("D%d" % i) not in order:
+            if i in prefilled or not 0 <= i < len(self.dec) or ("D%d" % i) not in order:
                 continue
             side = sides[self.dec_stream_of[i]]
             if side is not sides[0]:
@@ -358,10 +357,10 @@ class QpwcNet:
             with torch.cuda.stream(side):
                 buf = self.dec[i].prefill_skip(encs[-2 - i], c_in)
             if buf is not None:
-                self._prefilled[i] = buf
+                prefilled[i] = buf
         ready, decs, flos, ran_on, flow_done = {}, {}, [], {}, {}
         waited_on_main = set()      # decoder levels whose `ready` event the caller's stream has waited for
-        f, k, flo = encs[-1], -2, None
+        f, k, lvl = encs[-1], -2, None
         for tok in order:
             i = int(tok[1:])
             if tok[0] in "DM":
@@ -380,7 +379,7 @@ class QpwcNet:
                 with torch.cuda.stream(side):
                     hip_chunks = (self.dec_chunks[i] if small else 1) if tok[0] == "D" else 1
                     f = self.dec[i].cat_skip(f, encs[k], batch_chunks=chunks if tok[0] == "D" else 1, hip_chunks=hip_chunks,
-                                             buf=self._prefilled.get(i) if side is sides[0] else None)
+                                             buf=prefilled.get(i) if side is sides[0] else None)
                     k -= 1
                     # allocated on `side`, read by UpFlow on `main`: tell the caching allocator, so that the block
                     # is not handed to a later side-stream allocation while main may still be reading it (the
@@ -393,19 +392,19 @@ class QpwcNet:
                     ready[i].record(side)
                     ran_on[i] = side
             elif i == 0:
-                flo = self.flow((encs[-1][:nb], encs[-1][nb:]))
-                flos.append(flo)
+                lvl = self.flow.level((encs[-1][:nb], encs[-1][nb:]), want_up=True)
+                flos.append(lvl.flow)
             else:
-                flo_u = self._up(flo)
+                flo_u, flo32 = self._up(lvl)
                 if ran_on[i - 1] is not main:
                     main.wait_event(ready[i - 1])
                     waited_on_main.add(i - 1)
-                flo = self.upflows[i - 1]((decs[i - 1][:nb], decs[i - 1][nb:], flo_u))
-                flos.append(flo)
+                lvl = self.upflows[i - 1].level((decs[i - 1][:nb], decs[i - 1][nb:], flo_u), flo32, want_up=True)
+                flos.append(lvl.flow)
             if tok[0] == "F" and i in self.dec_after_flow.values():
                 flow_done[i] = torch.cuda.Event()
                 flow_done[i].record(main)
-        flos.append(self._up(flo, last=True))
+        flos.append(self._up(lvl, last=True)[0])
         # Join before anything is freed or returned.  A side stream whose LAST operation main has already waited for
         # (ready[i] of the last decoder level it ran, consumed by flow level i + 1) is joined already: another wait on
         # it would be one more cross-queue barrier in front of whatever the caller launches next (5-6 us in front of

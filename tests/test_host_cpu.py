@@ -495,3 +495,42 @@ def test_bf16x3_split_error_budget_on_the_cpu():
     six = sum(x.double() * y.double() for x, y in ((a2, b2), (a3, b1), (a1, b3), (a2, b1), (a1, b2), (a1, b1)))
     exact = a.double() * b.double()
     assert float(((six - exact).abs() / exact.abs()).max()) < 2.0 ** -24
+
+
+def test_flow_chain_state_is_passed_not_attached():
+    """Flow-level results and per-call state travel as arguments and return values: no module of the package hangs a
+    result on a tensor (`_qpwc_*`) or probes an OptFlow for an attribute its constructor sets."""
+    import glob
+    import os
+    files = sorted(glob.glob(os.path.join(os.path.dirname(qpwcnet_amd.__file__), "**", "*.py"), recursive=True))
+    assert len(files) > 5
+    for path in files:
+        with open(path) as fh:
+            text = fh.read()
+        for needle in ("_qpwc_", 'getattr(self, "out_format"', 'getattr(self, "_hip_ready"', "_prefilled"):
+            assert needle not in text, "{} contains {!r}".format(path, needle)
+    for fmt in ("channels_last", "channels_first"):
+        of = non_layers.OptFlow({}, "flow.", data_format=fmt)
+        assert of.out_format == of.data_format == fmt and of._hip_ready is False
+    assert non_layers.FlowLevel(1) == (1, None, None) and non_layers.FlowLevel._fields == ("flow", "up", "up32")
+
+
+def test_derived_weights_are_made_once_and_shared_through_the_params_dict():
+    """_Weighted.derived: one maker call per key, stored as `<prefix>#<name>` in the shared dict, so a second functor on
+    the same dict and prefix gets the same object; p32 keeps its `<prefix><name>#f32` key."""
+    params = {"blk.w": torch.arange(6.0).reshape(2, 3).half()}
+    a, b = non_layers._Weighted(params, "blk."), non_layers._Weighted(params, "blk.")
+    other = non_layers._Weighted(params, "other.")
+    made = []
+
+    def make():
+        made.append(1)
+        return params["blk.w"].float() * 2
+    t = a.derived("double", make)
+    assert a.derived("double", make) is t and b.derived("double", make) is t and len(made) == 1
+    assert params["blk.#double"] is t and torch.equal(t, torch.arange(6.0).reshape(2, 3) * 2)
+    assert other.derived("double", make) is not t and len(made) == 2 and "other.#double" in params
+    assert a.derived("pair", lambda: (t, t)) == (t, t) and b.derived("pair", make)[0] is t and len(made) == 2
+    w32 = a.p32("w")
+    assert w32.dtype == torch.float32 and b.p32("w") is w32 and params["blk.w#f32"] is w32
+    assert sorted(params) == ["blk.#double", "blk.#pair", "blk.w", "blk.w#f32", "other.#double"]
