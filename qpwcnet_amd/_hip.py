@@ -16,6 +16,8 @@ F32, F16, U8 = 0, 1, 2
 AUGMENT_COLOR, AUGMENT_RAW = 1, 2
 TRIPLET_RAW = 1
 VIS_MAX_TILE, VIS_TILE = 2048, 1024     # csrc/vis.hip: source pixels per partial maximum, output pixels per workgroup
+QUALITY_TILE = (16, 32)                 # csrc/quality.hip: SSIM positions (rows, columns) per workgroup
+QUALITY_CLIP, QUALITY_U8 = 1, 2
 WARP_CLAMP, WARP_TFWARP = 0, 1
 BCAST_B, BCAST_H, BCAST_W = 1, 2, 4
 LOSS_FLOW_MSE_V2, LOSS_FLOW_MSE, LOSS_FLOW_FINETUNE, LOSS_AUTORESIZE_MSE = 0, 1, 2, 3
@@ -138,6 +140,14 @@ VIS_PROTOTYPES = {
     "qpwc_flow_to_image_fwd_kernel": (_str, [_ci, _ci, _pi, _pi, _ci, _ci, _pvp]),
 }
 
+# The interpolator's image quality (MSE, PSNR, SSIM), declared in include/qpwc_quality.h: a table of its own under the
+# same rules, held to its header by tests/test_quality_cpu.py.
+QUALITY_PROTOTYPES = {
+    "qpwc_image_quality_workspace_floats": (_i64, [_ci, _ci, _ci, _ci]),
+    "qpwc_image_quality_fwd": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cf, _cf, _ci, _cf, _vp, _vp, _vp, _vp]),
+    "qpwc_image_quality_fwd_kernel": (_str, [_ci, _ci, _ci, _ci]),
+}
+
 _lib = None
 
 
@@ -169,7 +179,7 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
-    later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES)
+    later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES, **QUALITY_PROTOTYPES)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
         if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)

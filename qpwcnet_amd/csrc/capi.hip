@@ -7,6 +7,7 @@
 #include <initializer_list>
 
 #include "../../include/qpwc_optim.h"
+#include "../../include/qpwc_quality.h"
 #include "../../include/qpwc_triplet.h"
 #include "../../include/qpwc_vis.h"
 #include "launch.h"
@@ -148,6 +149,17 @@ static int vis_check_shapes(int n, int B, const int* h, const int* w, const int*
     }
     if (!flow_to_image_shape_ok(n, B, h, w, oh, ow))
         return fail(QPWC_E_SHAPE, "B=%d: an element count or a launch grid overflows 32 bits", B);
+    return QPWC_OK;
+}
+
+// the shape rules of the image quality, shared by qpwc_image_quality_workspace_floats / _fwd / _fwd_kernel
+static int quality_check_shapes(int B, int H, int W, int C) {
+    if (B < 1) return fail(QPWC_E_SHAPE, "non-positive extent B=%d", B);
+    if (C < 1 || C > 4) return fail(QPWC_E_SHAPE, "C=%d outside 1..4", C);
+    // tf.image.ssim refuses it the same way: the 11 x 11 window has no position
+    if (H < 11 || W < 11) return fail(QPWC_E_SHAPE, "H=%d W=%d: both must be at least 11, the filter size", H, W);
+    if (!image_quality_shape_ok(B, H, W, C))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d C=%d: the element count or a launch grid overflows 32 bits", B, H, W, C);
     return QPWC_OK;
 }
 
@@ -1502,6 +1514,48 @@ int qpwc_flow_to_image_fwd(const void* const* flows, const int* flow_dtype, cons
     bufs[n] = indexed_buf(ws, (size_t)flow_to_image_workspace_floats(n, B, h, w) * 4, 4, "ws", 0);
     if ((rc = check_bufs(bufs, n, 2 * n + 1)) != QPWC_OK) return rc;
     return flow_to_image_fwd_launch(flows, f16, h, w, n, B, in_layout, outs, oh, ow, u8, out_layout, (float*)ws,
+                                    (hipStream_t)stream);
+}
+
+int64_t qpwc_image_quality_workspace_floats(int B, int H, int W, int C) {
+    const int rc = quality_check_shapes(B, H, W, C);
+    if (rc != QPWC_OK) return rc;
+    return image_quality_workspace_floats(B, H, W, C);
+}
+
+const char* qpwc_image_quality_fwd_kernel(int B, int H, int W, int C) {
+    if (quality_check_shapes(B, H, W, C) != QPWC_OK) return "";
+    return image_quality_fwd_kernel();
+}
+
+int qpwc_image_quality_fwd(const void* truth, int truth_dtype, const void* pred, int pred_dtype, int B, int H, int W,
+                           int C, int layout, float offset_truth, float offset_pred, int flags, float max_val,
+                           void* out, void* state, void* ws, void* stream) {
+    int rc = check_nonnull({{truth, "truth"}, {pred, "pred"}, {out, "out"}, {ws, "ws"}});
+    if (rc != QPWC_OK) return rc;
+    if (truth_dtype != QPWC_F32 && truth_dtype != QPWC_F16) return fail(QPWC_E_DTYPE, "truth: unsupported dtype %d", truth_dtype);
+    if (pred_dtype != QPWC_F32 && pred_dtype != QPWC_F16) return fail(QPWC_E_DTYPE, "pred: unsupported dtype %d", pred_dtype);
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if ((rc = quality_check_shapes(B, H, W, C)) != QPWC_OK) return rc;
+    // written so that a NaN fails each test
+    if (!(max_val > 0.0f && max_val - max_val == 0.0f)) return fail(QPWC_E_RANGE, "max_val=%g must be finite and > 0", max_val);
+    if (!(offset_truth - offset_truth == 0.0f)) return fail(QPWC_E_RANGE, "offset_truth=%g is not finite", offset_truth);
+    if (!(offset_pred - offset_pred == 0.0f)) return fail(QPWC_E_RANGE, "offset_pred=%g is not finite", offset_pred);
+    if ((flags == QPWC_QUALITY_U8 || flags == (QPWC_QUALITY_U8 | QPWC_QUALITY_CLIP)) && max_val != 255.0f)
+        return fail(QPWC_E_RANGE, "QPWC_QUALITY_U8 takes max_val 255, got %g", max_val);
+    if (flags < 0 || flags > 3) return fail(QPWC_E_MODE, "unknown quality flags 0x%x", flags);
+    // the images are only read and may be one buffer; out, the workspace and the state are written
+    const size_t n = (size_t)B * H * W * C;
+    const BufCheck bufs[5] = {
+        {truth, n * esize(truth_dtype), esize(truth_dtype), "truth"},
+        {pred, n * esize(pred_dtype), esize(pred_dtype), "pred"},
+        {out, (size_t)B * 3 * 4, 4, "out"},
+        {ws, (size_t)image_quality_workspace_floats(B, H, W, C) * 4, 4, "ws"},
+        {state, 4 * 8, 8, "state"},
+    };
+    if ((rc = check_bufs(bufs, 2, state ? 5 : 4)) != QPWC_OK) return rc;
+    return image_quality_fwd_launch(truth, truth_dtype == QPWC_F16, pred, pred_dtype == QPWC_F16, B, H, W, C, layout,
+                                    offset_truth, offset_pred, flags, max_val, (float*)out, (double*)state, (float*)ws,
                                     (hipStream_t)stream);
 }
 

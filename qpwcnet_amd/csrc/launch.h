@@ -180,4 +180,12 @@ int flow_to_image_fwd_launch(const void* const* flows, const int* f16, const int
                              int in_layout, void* const* outs, const int* oh, const int* ow, bool u8, int out_layout,
                              float* ws, hipStream_t s);
 
+// quality.hip (include/qpwc_quality.h)
+bool image_quality_shape_ok(int B, int H, int W, int C);
+int64_t image_quality_workspace_floats(int B, int H, int W, int C);
+const char* image_quality_fwd_kernel();
+int image_quality_fwd_launch(const void* truth, bool f16_t, const void* pred, bool f16_p, int B, int H, int W, int C,
+                             int layout, float off_t, float off_p, int flags, float max_val, float* out, double* state,
+                             float* ws, hipStream_t s);
+
 }  // namespace qpwc

@@ -3,12 +3,21 @@
 EPE definition: ``epe_error`` (qpwcnet/app/optical_flow/train.py:247-253);
 per-level ground truth as in ``FlowMseLoss.call`` (qpwcnet/train/loss.py:56-62):
 bilinear resize of the full-resolution flow to (h, w), times h/H.
+
+Image quality of the frame interpolator: ``image_quality`` (per-image MSE, PSNR and SSIM with tf.image.ssim's defaults),
+``psnr`` / ``ssim`` under tf.image's names and ``InterpolationQuality``, the running mean of an evaluation loop
+(qpwcnet/app/pre_train.py:71 feeds ``compiled_metrics``; pre_train_test.py:61-77 is the 8-bit export the defaults
+score).  HIP tensors take two launches (``qpwc_image_quality_fwd``, include/qpwc_quality.h, DESIGN.md section 4.23);
+CPU tensors take ``image_quality_torch``, the same chain from torch operators.
 """
+import collections
+import math
+
 import torch
 import torch.nn.functional as F
 
-from . import ops
-from .backend import CHANNELS_LAST
+from . import _hip, ops
+from .backend import CHANNELS_LAST, get_axis, image_data_format
 
 
 def multiscale_ground_truth(flow_gt, shapes, data_format=CHANNELS_LAST, mode="bilinear"):
@@ -40,3 +49,164 @@ def per_level_epe(flows_true, flows_pred, data_format=CHANNELS_LAST, out=None):
         out.copy_(res)
         return out
     return res
+
+
+ImageQuality = collections.namedtuple("ImageQuality", ["mse", "psnr", "ssim"])
+
+# tf.image.ssim's defaults: the only filter the kernels implement
+SSIM_FILTER = {"filter_size": 11, "filter_sigma": 1.5, "k1": 0.01, "k2": 0.03}
+
+
+def ssim_window():
+    """The 11 taps of tf.image.ssim's default Gaussian (sigma 1.5), normalised in float64 and rounded to float32:
+    the window is their outer product."""
+    k = torch.arange(SSIM_FILTER["filter_size"], dtype=torch.float64) - (SSIM_FILTER["filter_size"] - 1) / 2.0
+    e = torch.exp(-k * k / (2.0 * SSIM_FILTER["filter_sigma"] ** 2))
+    return (e / e.sum()).float()
+
+
+def _quality_value(x, offset, max_val, clip, quantize):
+    v = x.float() + offset
+    if clip:
+        v = v.clamp(0.0, max_val)
+    if quantize:
+        v = torch.trunc(255.0 * v.clamp(0.0, 1.0))
+    return v
+
+
+def image_quality_torch(y_true, y_pred, max_val=1.0, offset=(0.0, 0.0), clip=False, quantize=False,
+                        data_format=CHANNELS_LAST):
+    """``image_quality`` composed from torch operators, on any device: the path CPU tensors take and the baseline the
+    kernels are timed against.  The chain of include/qpwc_quality.h in fp32 -- the value transform, the squared error,
+    ``F.conv2d(groups=C)`` along the rows and then the columns with ``ssim_window``, s -- with the means taken in
+    float64.  Batched (rank 4) inputs, offset = (truth, pred); -> ImageQuality of float32 [B] tensors."""
+    axis = get_axis(data_format)
+    max_val = 255.0 if quantize else float(max_val)
+    with torch.no_grad():
+        vt = _quality_value(y_true.detach(), float(offset[0]), max_val, clip, quantize)
+        vp = _quality_value(y_pred.detach(), float(offset[1]), max_val, clip, quantize)
+        if axis == 3:
+            vt, vp = vt.permute(0, 3, 1, 2), vp.permute(0, 3, 1, 2)
+        C = vt.shape[1]
+        d = vt - vp
+        mse = (d * d).double().mean(dim=(1, 2, 3))
+        psnr = 20.0 * math.log10(max_val) - 10.0 * torch.log10(mse)          # +inf for mse == 0
+        g = ssim_window().to(vt.device)
+        rows, cols = g.view(1, 1, 1, -1).repeat(C, 1, 1, 1), g.view(1, 1, -1, 1).repeat(C, 1, 1, 1)
+        conv = lambda x: F.conv2d(F.conv2d(x.contiguous(), rows, groups=C), cols, groups=C)
+        c1 = float(torch.tensor((SSIM_FILTER["k1"] * max_val) ** 2, dtype=torch.float64).float())
+        c2 = float(torch.tensor((SSIM_FILTER["k2"] * max_val) ** 2, dtype=torch.float64).float())
+        mt, mp = conv(vt), conv(vp)
+        num0, den0 = 2.0 * mt * mp, mt * mt + mp * mp
+        num1, den1 = 2.0 * conv(vt * vp), conv(vt * vt + vp * vp)
+        s = (num0 + c1) / (den0 + c1) * ((num1 - num0 + c2) / (den1 - den0 + c2))
+        ssim_ = s.double().mean(dim=(2, 3)).mean(dim=1)
+        return ImageQuality(mse.float(), psnr.float(), ssim_.float())
+
+
+def _check_images(y_true, y_pred, data_format):
+    for name, t in (("y_true", y_true), ("y_pred", y_pred)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if t.dtype not in (torch.float32, torch.float16):
+            raise ValueError("{}: unsupported dtype {}".format(name, t.dtype))
+    if y_true.shape != y_pred.shape or y_true.device != y_pred.device:
+        raise ValueError("y_true {} on {} and y_pred {} on {} must have one shape and one device".format(
+            tuple(y_true.shape), y_true.device, tuple(y_pred.shape), y_pred.device))
+    if y_true.dim() not in (3, 4):
+        raise ValueError("images must be of rank 3 or 4, got shape {}".format(tuple(y_true.shape)))
+    shape = tuple(y_true.shape[-3:])
+    H, W, C = shape if data_format == CHANNELS_LAST else (shape[1], shape[2], shape[0])
+    if not 1 <= C <= 4:
+        raise ValueError("images must have 1..4 channels, got {} ({}, shape {})".format(C, data_format,
+                                                                                        tuple(y_true.shape)))
+    if H < SSIM_FILTER["filter_size"] or W < SSIM_FILTER["filter_size"]:
+        raise ValueError("images of {}x{} are smaller than the SSIM filter size {}".format(H, W,
+                                                                                           SSIM_FILTER["filter_size"]))
+
+
+def image_quality(y_true, y_pred, max_val=1.0, offset=0.0, clip=False, quantize=False, data_format=None, state=None):
+    """Per-image MSE, PSNR (tf.image.psnr) and SSIM (tf.image.ssim with its defaults: filter_size 11, filter_sigma 1.5,
+    k1 0.01, k2 0.03) of ``y_pred`` against ``y_true``: (B,H,W,C) / (B,C,H,W) by ``data_format`` (default
+    ``backend.image_data_format()``) or one image of rank 3, one shape, each fp32 or fp16, 1..4 channels, H, W >= 11.
+    ``offset`` (a number, or a (truth, pred) pair) is added first; ``clip`` then clamps to [0, max_val]; ``quantize``
+    scores the 8-bit pictures ``trunc(255 * clip(x + offset, 0, 1))`` of pre_train_test.py's export with max_val = 255.
+    -> ImageQuality(mse, psnr, ssim) of float32 [B] tensors on the inputs' device (scalars for one image); psnr is
+    +inf where the images are equal.  ``state``: a float64 tensor of 4 elements on the same device, to which the call
+    adds its sums of mse, psnr, ssim and its image count (``InterpolationQuality`` holds one).  No gradient flows.
+    HIP tensors: two launches, no host synchronisation."""
+    if data_format is None:
+        data_format = image_data_format()
+    get_axis(data_format)
+    _check_images(y_true, y_pred, data_format)
+    off_t, off_p = (offset if isinstance(offset, (tuple, list)) else (offset, offset))
+    off_t, off_p = float(off_t), float(off_p)
+    max_val = 255.0 if quantize else float(max_val)
+    if not (math.isfinite(max_val) and max_val > 0.0 and math.isfinite(off_t) and math.isfinite(off_p)):
+        raise ValueError("max_val must be finite and > 0 and the offsets finite, got {} and {}".format(
+            max_val, (off_t, off_p)))
+    if state is not None and not (isinstance(state, torch.Tensor) and state.dtype == torch.float64
+                                  and state.numel() == 4 and state.device == y_true.device):
+        raise ValueError("state must be a float64 tensor of 4 elements on {}".format(y_true.device))
+    single = y_true.dim() == 3
+    with torch.no_grad():
+        t, p = y_true.detach(), y_pred.detach()
+        if single:
+            t, p = t[None], p[None]
+        if t.is_cuda:
+            flags = (_hip.QUALITY_CLIP if clip else 0) | (_hip.QUALITY_U8 if quantize else 0)
+            res = ImageQuality(*ops.image_quality(t, p, data_format, (off_t, off_p), flags, max_val, state))
+        else:
+            res = image_quality_torch(t, p, max_val, (off_t, off_p), clip, quantize, data_format)
+            if state is not None:
+                # image by image, in float64, as the fold kernel adds them
+                flat = state.view(-1)
+                for i, v in enumerate(res):
+                    flat[i] = torch.cumsum(torch.cat([flat[i:i + 1], v.double()]), 0)[-1]
+                flat[3] += float(t.shape[0])
+    return ImageQuality(*(v[0] for v in res)) if single else res
+
+
+def psnr(a, b, max_val, data_format=None):
+    """tf.image.psnr(a, b, max_val): float32 [B] (a scalar for rank 3), +inf where the images are equal."""
+    return image_quality(a, b, max_val=max_val, data_format=data_format).psnr
+
+
+def ssim(a, b, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, data_format=None):
+    """tf.image.ssim(a, b, max_val) with its default filter, the only one implemented: any other filter_size,
+    filter_sigma, k1 or k2 raises ValueError."""
+    given = {"filter_size": filter_size, "filter_sigma": filter_sigma, "k1": k1, "k2": k2}
+    if given != SSIM_FILTER:
+        raise ValueError("ssim supports only tf.image.ssim's defaults {}, got {}".format(
+            SSIM_FILTER, {k: v for k, v in given.items() if v != SSIM_FILTER[k]}))
+    return image_quality(a, b, max_val=max_val, data_format=data_format).ssim
+
+
+class InterpolationQuality:
+    """Running MSE, PSNR and SSIM of an evaluation loop -- the metric ``pre_train.py`` hands to ``compile``.  The
+    defaults score ``model(img_pair)[-1]`` against ``img1`` as ``pre_train.preprocess`` leaves them, both in
+    [-0.5, 0.5], as the 8-bit pictures of pre_train_test.py's export (offset 0.5, quantize).  The four float64 sums
+    live on the inputs' device and ``update_state`` reads nothing back: ``result()`` does the one host read."""
+
+    def __init__(self, offset=0.5, quantize=True, data_format=None):
+        self.offset, self.quantize, self.data_format = offset, quantize, data_format
+        self.state = None
+
+    def update_state(self, y_true, y_pred):
+        if self.state is None or self.state.device != y_true.device:
+            if self.state is not None and float(self.state[3]) != 0.0:
+                raise ValueError("InterpolationQuality holds sums on {}; got images on {}".format(self.state.device,
+                                                                                                  y_true.device))
+            self.state = torch.zeros(4, dtype=torch.float64, device=y_true.device)
+        return image_quality(y_true, y_pred, offset=self.offset, quantize=self.quantize, data_format=self.data_format,
+                             state=self.state)
+
+    def result(self):
+        """{'mse', 'psnr', 'ssim'}: the means over every image seen since the last reset (0.0 before the first)."""
+        sums = [0.0] * 4 if self.state is None else self.state.cpu().tolist()
+        n = sums[3]
+        return {k: (v / n if n else 0.0) for k, v in zip(ImageQuality._fields, sums)}
+
+    def reset_state(self):
+        if self.state is not None:
+            self.state.zero_()

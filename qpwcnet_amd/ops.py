@@ -1360,6 +1360,61 @@ def flow_to_image(flows, sizes=None, in_layout=CHANNELS_LAST, out_dtype=torch.fl
     return outs
 
 
+def image_quality_kernel(B, H, W, C):
+    """Form of ``qpwc_image_quality_fwd``'s tile kernel for this shape ('quality_tile_kernel': it has one; host only).
+    '' for arguments the entry point refuses."""
+    name = _hip.lib().qpwc_image_quality_fwd_kernel(int(B), int(H), int(W), int(C))
+    return name.decode() if name else ""
+
+
+def image_quality(truth, pred, data_format=CHANNELS_LAST, offsets=(0.0, 0.0), flags=0, max_val=1.0, state=None):
+    """Per-image MSE, PSNR and SSIM (tf.image.ssim's defaults) of ``pred`` against ``truth`` in two launches
+    (qpwc_image_quality_fwd, include/qpwc_quality.h).  truth, pred: (B,H,W,C) / (B,C,H,W) by data_format, one shape, each
+    fp32 or fp16, on one HIP device, H, W >= 11, C in 1..4; offsets = (truth, pred), added before ``flags``
+    (_hip.QUALITY_CLIP, _hip.QUALITY_U8) apply; state: None or a float64 tensor of 4 elements on the same device, to
+    which the call adds its sums of mse, psnr, ssim and its image count.  -> (mse, psnr, ssim), three float32 [B] views
+    of one tensor.  The workspace comes from torch's allocator on the current stream.  Enqueues and returns: no host
+    synchronisation."""
+    get_axis(data_format)
+    nhwc = data_format == CHANNELS_LAST
+    for name, t in (("truth", truth), ("pred", pred)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if not t.is_cuda:
+            raise RuntimeError("qpwcnet_amd: {} is on '{}'; ops.image_quality runs on a HIP device only (metrics.* has "
+                               "the CPU path)".format(name, t.device))
+        if t.dtype not in _DTYPES:
+            raise ValueError("{}: unsupported dtype {}".format(name, t.dtype))
+        if t.dim() != 4:
+            raise ValueError("{} must be rank 4 (batched), got shape {}".format(name, tuple(t.shape)))
+    if truth.shape != pred.shape or truth.device != pred.device:
+        raise ValueError("truth {} on {} and pred {} on {} must have one shape and one device".format(
+            tuple(truth.shape), truth.device, tuple(pred.shape), pred.device))
+    B, H, W, C = (int(v) for v in (truth.shape if nhwc else (truth.shape[0],) + tuple(truth.shape[2:]) + (truth.shape[1],)))
+    if H < 11 or W < 11:
+        raise ValueError("image_quality: H={} W={} must both be at least 11, the SSIM filter size".format(H, W))
+    dev = truth.device
+    if state is not None:
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.float64 and state.numel() == 4
+                and state.is_contiguous() and state.device == dev):
+            raise ValueError("state must be a contiguous float64 tensor of 4 elements on {}".format(dev))
+    truth, pred = truth.contiguous(), pred.contiguous()
+    off_t, off_p = (float(v) for v in offsets)
+    L = _hip.lib()
+    nws = L.qpwc_image_quality_workspace_floats(B, H, W, C)
+    _hip.check(min(int(nws), 0))
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+        out = torch.empty((3, B), dtype=torch.float32, device=dev)
+        with _timed("image_quality", (B, H, W, C)):
+            rc = L.qpwc_image_quality_fwd(
+                truth.data_ptr(), _DTYPES[truth.dtype], pred.data_ptr(), _DTYPES[pred.dtype], B, H, W, C,
+                _hip.NHWC if nhwc else _hip.NCHW, off_t, off_p, int(flags), float(max_val), out.data_ptr(),
+                None if state is None else state.data_ptr(), ws.data_ptr(), _stream(truth))
+    _hip.check(rc)
+    return out[0], out[1], out[2]
+
+
 def _loss_layout(y_true, preds, data_format):
     """-> (y_true, preds, layout code, nhwc_view): 'channels_first' operands that are all physically NHWC (torch
     channels_last memory) are read through their permuted views; everything else dense in its declared layout."""
