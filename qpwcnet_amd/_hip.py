@@ -16,6 +16,7 @@ F32, F16, U8 = 0, 1, 2
 AUGMENT_COLOR, AUGMENT_RAW = 1, 2
 TRIPLET_RAW = 1
 VIS_MAX_TILE, VIS_TILE = 2048, 1024     # csrc/vis.hip: source pixels per partial maximum, output pixels per workgroup
+REVIEW_TILE = 256                       # csrc/review.hip: pixels per workgroup of the panel launch
 QUALITY_TILE = (16, 32)                 # csrc/quality.hip: SSIM positions (rows, columns) per workgroup
 QUALITY_CLIP, QUALITY_U8 = 1, 2
 WARP_CLAMP, WARP_TFWARP = 0, 1
@@ -148,6 +149,16 @@ QUALITY_PROTOTYPES = {
     "qpwc_image_quality_fwd_kernel": (_str, [_ci, _ci, _ci, _ci]),
 }
 
+# The inference review panels of both test scripts, declared in include/qpwc_review.h: a table of its own under the same
+# rules, held to its header by tests/test_review_cpu.py.
+REVIEW_PROTOTYPES = {
+    "qpwc_review_workspace_floats": (_i64, [_ci, _ci, _ci, _ci]),
+    "qpwc_inference_panels_fwd": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _pvp, _ci, _ci, _ci, _vp, _vp]),
+    "qpwc_interpolation_panels_fwd": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _pvp, _ci, _ci, _ci,
+                                            _vp, _vp]),
+    "qpwc_review_panels_fwd_kernel": (_str, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci]),
+}
+
 _lib = None
 
 
@@ -179,7 +190,8 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
-    later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES, **QUALITY_PROTOTYPES)
+    later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES, **QUALITY_PROTOTYPES,
+                 **REVIEW_PROTOTYPES)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
         if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)

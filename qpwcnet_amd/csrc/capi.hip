@@ -8,6 +8,7 @@
 
 #include "../../include/qpwc_optim.h"
 #include "../../include/qpwc_quality.h"
+#include "../../include/qpwc_review.h"
 #include "../../include/qpwc_triplet.h"
 #include "../../include/qpwc_vis.h"
 #include "launch.h"
@@ -163,6 +164,20 @@ static int quality_check_shapes(int B, int H, int W, int C) {
     return QPWC_OK;
 }
 
+// the shape rules of the review panels, shared by qpwc_review_workspace_floats / qpwc_review_panels_fwd_kernel and both
+// entry points; n_flows = 2: the pictures of test_infer.py (h x w is H x W), 1: those of pre_train_test.py
+static int review_check_shapes(int n_flows, int B, int H, int W, int h, int w) {
+    if (n_flows != 1 && n_flows != 2) return fail(QPWC_E_SHAPE, "n_flows %d outside [1,2]", n_flows);
+    if (B <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0)
+        return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d h=%d w=%d", B, H, W, h, w);
+    const int s = H / h;
+    if (s < 1 || H != s * h || (int64_t)W != (int64_t)s * w || (n_flows == 2 && s != 1))
+        return fail(QPWC_E_SHAPE, "%dx%d is not one whole multiple of the flow's %dx%d", H, W, h, w);
+    if (!review_shape_ok(n_flows, B, H, W, h, w))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: an element count or a launch grid overflows 32 bits", B, H, W);
+    return QPWC_OK;
+}
+
 // the first null pointer of a {pointer, name} list fails, by name
 struct PtrName {
     const void* p;
@@ -194,6 +209,42 @@ static int check_bufs(const BufCheck* b, int n_in, int n_all) {
         for (int k = 0; k < o; ++k)
             if (overlaps(b[o].p, b[o].n, b[k].p, b[k].n)) return fail(QPWC_E_ALIAS, "%s overlaps %s", b[o].name, b[k].name);
     return QPWC_OK;
+}
+
+// Every check of the review panels' two entry points after the null pointers, in the order include/qpwc_review.h
+// states; imgs: the n_img images with their channel counts, flows: the n_flows flows of h x w, outs: n_out pictures of
+// H x W but for outs[flow_pic] (-1: none), which has the flow's size.  The store form follows from the shape and decides
+// the alignment the outputs must have: the kernel does not look at the pointers.
+static int review_check(const void* const* imgs, const int* img_c, int n_img, int img_dtype, const void* const* flows,
+                        int n_flows, int B, int H, int W, int h, int w, int in_layout, void* const* outs, int n_out,
+                        int flow_pic, int out_dtype, int out_layout, int grid, const void* ws) {
+    if (img_dtype != QPWC_F32 && img_dtype != QPWC_F16) return fail(QPWC_E_DTYPE, "images: unsupported dtype %d", img_dtype);
+    if (out_dtype != QPWC_F32 && out_dtype != QPWC_U8) return fail(QPWC_E_DTYPE, "unsupported output dtype %d", out_dtype);
+    if (in_layout != QPWC_NHWC && in_layout != QPWC_NCHW)
+        return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", in_layout);
+    if (out_layout != QPWC_NHWC && out_layout != QPWC_NCHW)
+        return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", out_layout);
+    int rc = review_check_shapes(n_flows, B, H, W, h, w);
+    if (rc != QPWC_OK) return rc;
+    if (grid < 0) return fail(QPWC_E_SHAPE, "grid %d is negative", grid);
+    const bool u8 = out_dtype == QPWC_U8;
+    const size_t oalign = review_panels_vec(n_flows, H, W, h, w) ? (u8 ? 4 : 16) : (u8 ? 1 : 4);
+    BufCheck bufs[3 + 2 + 1 + 10];
+    int k = 0;
+    static const char* const img_names[2][3] = {{"img_pair", "img1", "pred"}, {"ims", "", ""}};
+    static const char* const flow_names[2][2] = {{"flow", ""}, {"flo", "flo_pred"}};
+    for (int i = 0; i < n_img; ++i)
+        bufs[k++] = indexed_buf(imgs[i], (size_t)B * H * W * img_c[i] * esize(img_dtype), esize(img_dtype),
+                                img_names[n_flows - 1][i], 0);
+    for (int i = 0; i < n_flows; ++i)
+        bufs[k++] = indexed_buf(flows[i], (size_t)B * h * w * 2 * 4, 4, flow_names[n_flows - 1][i], 0);
+    const int n_in = k;
+    bufs[k++] = indexed_buf(ws, (size_t)review_workspace_floats(n_flows, B, h, w) * 4, 4, "ws", 0);
+    for (int i = 0; i < n_out; ++i) {
+        const size_t px = i == flow_pic ? (size_t)h * w : (size_t)H * W;
+        bufs[k++] = indexed_buf(outs[i], (size_t)B * px * 3 * (u8 ? 1 : 4), oalign, "outs[%d]", i);
+    }
+    return check_bufs(bufs, n_in, k);
 }
 
 static int flow_head_train_check_shape(int B, int H, int W) {
@@ -1557,6 +1608,56 @@ int qpwc_image_quality_fwd(const void* truth, int truth_dtype, const void* pred,
     return image_quality_fwd_launch(truth, truth_dtype == QPWC_F16, pred, pred_dtype == QPWC_F16, B, H, W, C, layout,
                                     offset_truth, offset_pred, flags, max_val, (float*)out, (double*)state, (float*)ws,
                                     (hipStream_t)stream);
+}
+
+int64_t qpwc_review_workspace_floats(int n_flows, int B, int h, int w) {
+    const int rc = review_check_shapes(n_flows, B, h, w, h, w);
+    if (rc != QPWC_OK) return rc;
+    return review_workspace_floats(n_flows, B, h, w);
+}
+
+const char* qpwc_review_panels_fwd_kernel(int n_flows, int B, int H, int W, int h, int w, int out_dtype, int out_layout) {
+    if (out_dtype != QPWC_F32 && out_dtype != QPWC_U8) return "";
+    if (out_layout != QPWC_NHWC && out_layout != QPWC_NCHW) return "";
+    if (review_check_shapes(n_flows, B, H, W, h, w) != QPWC_OK) return "";
+    return review_panels_fwd_kernel(n_flows, H, W, h, w);
+}
+
+int qpwc_inference_panels_fwd(const void* ims, int ims_dtype, const void* flo, const void* flo_pred, int B, int H, int W,
+                              int in_layout, void* const* outs, int out_dtype, int out_layout, int grid, void* ws,
+                              void* stream) {
+    int rc = check_nonnull({{ims, "ims"}, {flo, "flo"}, {flo_pred, "flo_pred"}, {outs, "outs"}, {ws, "ws"}});
+    if (rc != QPWC_OK) return rc;
+    for (int i = 0; i < 10; ++i)
+        if (!outs[i]) return fail(QPWC_E_NULL, "outs[%d] is null", i);
+    const void* const imgs[1] = {ims};
+    const int img_c[1] = {6};
+    const void* const flows[2] = {flo, flo_pred};
+    if ((rc = review_check(imgs, img_c, 1, ims_dtype, flows, 2, B, H, W, H, W, in_layout, outs, 10, -1, out_dtype,
+                           out_layout, grid, ws)) != QPWC_OK)
+        return rc;
+    return inference_panels_launch(ims, ims_dtype == QPWC_F16, (const float*)flo, (const float*)flo_pred, B, H, W,
+                                   in_layout, outs, out_dtype == QPWC_U8, out_layout, grid, (float*)ws,
+                                   (hipStream_t)stream);
+}
+
+int qpwc_interpolation_panels_fwd(const void* img_pair, const void* img1, const void* pred, int img_dtype,
+                                  const void* flow, int B, int H, int W, int h, int w, int in_layout, void* const* outs,
+                                  int out_dtype, int out_layout, int grid, void* ws, void* stream) {
+    int rc = check_nonnull({{img_pair, "img_pair"}, {img1, "img1"}, {pred, "pred"}, {flow, "flow"}, {outs, "outs"},
+                            {ws, "ws"}});
+    if (rc != QPWC_OK) return rc;
+    for (int i = 0; i < 7; ++i)
+        if (!outs[i]) return fail(QPWC_E_NULL, "outs[%d] is null", i);
+    const void* const imgs[3] = {img_pair, img1, pred};
+    const int img_c[3] = {6, 3, 3};
+    const void* const flows[1] = {flow};
+    if ((rc = review_check(imgs, img_c, 3, img_dtype, flows, 1, B, H, W, h, w, in_layout, outs, 7, 5, out_dtype,
+                           out_layout, grid, ws)) != QPWC_OK)
+        return rc;
+    return interpolation_panels_launch(img_pair, img1, pred, img_dtype == QPWC_F16, (const float*)flow, B, H, W, h, w,
+                                       in_layout, outs, out_dtype == QPWC_U8, out_layout, grid, (float*)ws,
+                                       (hipStream_t)stream);
 }
 
 }  // extern "C"

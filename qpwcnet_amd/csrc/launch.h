@@ -188,4 +188,16 @@ int image_quality_fwd_launch(const void* truth, bool f16_t, const void* pred, bo
                              int layout, float off_t, float off_p, int flags, float max_val, float* out, double* state,
                              float* ws, hipStream_t s);
 
+// review.hip (include/qpwc_review.h)
+bool review_shape_ok(int n_flows, int B, int H, int W, int h, int w);
+int64_t review_workspace_floats(int n_flows, int B, int h, int w);
+bool review_panels_vec(int n_flows, int H, int W, int h, int w);
+const char* review_panels_fwd_kernel(int n_flows, int H, int W, int h, int w);
+int inference_panels_launch(const void* ims, bool f16, const float* flo, const float* flo_pred, int B, int H, int W,
+                            int in_layout, void* const* outs, bool u8, int out_layout, int grid, float* ws,
+                            hipStream_t s);
+int interpolation_panels_launch(const void* img_pair, const void* img1, const void* pred, bool f16, const float* flow,
+                                int B, int H, int W, int h, int w, int in_layout, void* const* outs, bool u8,
+                                int out_layout, int grid, float* ws, hipStream_t s);
+
 }  // namespace qpwc

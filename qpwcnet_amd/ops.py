@@ -1360,6 +1360,108 @@ def flow_to_image(flows, sizes=None, in_layout=CHANNELS_LAST, out_dtype=torch.fl
     return outs
 
 
+def review_panels_kernel(n_flows, B, H, W, h=None, w=None, out_dtype=torch.float32, out_layout=CHANNELS_LAST):
+    """Store form of the panel launch of ``qpwc_inference_panels_fwd`` (n_flows = 2) / ``qpwc_interpolation_panels_fwd``
+    (n_flows = 1, flow of h x w) for these shapes: 'review_panels_kernel<vec4>' / 'review_panels_kernel<scalar>' (host
+    only).  '' for arguments the entry points refuse."""
+    h, w = H if h is None else h, W if w is None else w
+    name = _hip.lib().qpwc_review_panels_fwd_kernel(
+        int(n_flows), int(B), int(H), int(W), int(h), int(w),
+        {torch.uint8: _hip.U8, torch.float32: _hip.F32}.get(out_dtype, -1),
+        {CHANNELS_LAST: _hip.NHWC, CHANNELS_FIRST: _hip.NCHW}.get(out_layout, -1))
+    return name.decode() if name else ""
+
+
+def _review_image(name, t, C, nhwc, like=None):
+    """A dense (B,H,W,C) / (B,C,H,W) image of the review panels -> (tensor, (B, H, W))."""
+    _check_tensor(name, t)
+    if t.shape[3 if nhwc else 1] != C:
+        raise ValueError("{} must be {}, got shape {}".format(name, "(B,H,W,%d)" % C if nhwc else "(B,%d,H,W)" % C,
+                                                              tuple(t.shape)))
+    if like is not None and (t.device != like.device or t.dtype != like.dtype):
+        raise ValueError("{} must have {}'s device and dtype".format(name, "the first image"))
+    B, H, W = (t.shape[0], t.shape[1], t.shape[2]) if nhwc else (t.shape[0], t.shape[2], t.shape[3])
+    return t.contiguous(), (int(B), int(H), int(W))
+
+
+def _review_flow(name, t, nhwc, like):
+    t, dims = _review_image(name, t, 2, nhwc)
+    if t.dtype != torch.float32:
+        raise ValueError("{} must be float32 (vis.* widens fp16 flows), got {}".format(name, t.dtype))
+    if t.device != like.device:
+        raise ValueError("{} must be on the images' device".format(name))
+    return t, dims
+
+
+def _review_call(entry, n_flows, n_out, flow_pic, B, H, W, h, w, out_dtype, nhwc_out, grid, like, call):
+    """Allocates the pictures and the workspace of one review-panel call and runs `call(outs_array, ws_ptr)`."""
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError("out_dtype must be torch.float32 or torch.uint8, got {}".format(out_dtype))
+    if int(grid) < 0:
+        raise ValueError("grid must be 0 (off) or a positive period, got {}".format(grid))
+    if min(B, H, W, h, w) <= 0:
+        raise ValueError("empty tensor: B={} H={} W={} h={} w={}".format(B, H, W, h, w))
+    L = _hip.lib()
+    nws = L.qpwc_review_workspace_floats(n_flows, B, h, w)
+    _hip.check(min(int(nws), 0))
+    dev = like.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+        size = lambda i: (h, w) if i == flow_pic else (H, W)
+        outs = [torch.empty((B,) + size(i) + (3,) if nhwc_out else (B, 3) + size(i), dtype=out_dtype, device=dev)
+                for i in range(n_out)]
+        with _timed(entry, (B, H, W, n_out)):
+            rc = call(L, (ctypes.c_void_p * n_out)(*[o.data_ptr() for o in outs]), ws.data_ptr())
+    _hip.check(rc)
+    return outs
+
+
+def inference_panels(ims, flo, flo_pred, in_layout=CHANNELS_LAST, out_dtype=torch.float32, out_layout=CHANNELS_LAST,
+                     grid=0):
+    """The ten pictures of qpwcnet/app/optical_flow/test_infer.py:104-154 in two launches (qpwc_inference_panels_fwd,
+    include/qpwc_review.h).  ims (B,H,W,6) / (B,6,H,W) by in_layout, fp32 or fp16, preprocessed; flo, flo_pred
+    (B,H,W,2) / (B,2,H,W) float32; all dense on one HIP device.  -> a list of ten (B,H,W,3) / (B,3,H,W) tensors by
+    out_layout, float32 or uint8 by out_dtype, in the header's order.  The workspace comes from torch's allocator on the
+    current stream.  Enqueues and returns: no host synchronisation."""
+    nhwc, nhwc_out = get_axis(in_layout) == 3, get_axis(out_layout) == 3
+    ims, (B, H, W) = _review_image("ims", ims, 6, nhwc)
+    flo, d0 = _review_flow("flo", flo, nhwc, ims)
+    flo_pred, d1 = _review_flow("flo_pred", flo_pred, nhwc, ims)
+    if d0 != (B, H, W) or d1 != (B, H, W):
+        raise ValueError("flo {} and flo_pred {} must have ims' batch and size {}".format(d0, d1, (B, H, W)))
+    return _review_call(
+        "inference_panels", 2, 10, -1, B, H, W, H, W, out_dtype, nhwc_out, grid, ims,
+        lambda L, outs, ws: L.qpwc_inference_panels_fwd(
+            ims.data_ptr(), _DTYPES[ims.dtype], flo.data_ptr(), flo_pred.data_ptr(), B, H, W,
+            _hip.NHWC if nhwc else _hip.NCHW, outs, _hip.U8 if out_dtype == torch.uint8 else _hip.F32,
+            _hip.NHWC if nhwc_out else _hip.NCHW, int(grid), ws, _stream(ims)))
+
+
+def interpolation_panels(img_pair, img1, pred, flow, in_layout=CHANNELS_LAST, out_dtype=torch.float32,
+                         out_layout=CHANNELS_LAST, grid=32):
+    """The seven pictures of qpwcnet/app/frame_interpolation/pre_train_test.py:45-79, 121-163 in two launches
+    (qpwc_interpolation_panels_fwd, include/qpwc_review.h).  img_pair (B,H,W,6) / (B,6,H,W), img1 and pred (B,H,W,3) /
+    (B,3,H,W) of one dtype, fp32 or fp16; flow (B,h,w,2) / (B,2,h,w) float32 with H = s * h, W = s * w; all dense on one
+    HIP device.  -> a list of seven tensors in the header's order, all (B,H,W,3) / (B,3,H,W) but '5-flow', which has the
+    flow's size.  The workspace comes from torch's allocator on the current stream.  Enqueues and returns."""
+    nhwc, nhwc_out = get_axis(in_layout) == 3, get_axis(out_layout) == 3
+    img_pair, (B, H, W) = _review_image("img_pair", img_pair, 6, nhwc)
+    img1, d1 = _review_image("img1", img1, 3, nhwc, img_pair)
+    pred, d2 = _review_image("pred", pred, 3, nhwc, img_pair)
+    flow, (Bf, h, w) = _review_flow("flow", flow, nhwc, img_pair)
+    if d1 != (B, H, W) or d2 != (B, H, W) or Bf != B:
+        raise ValueError("img1 {}, pred {} and flow's batch {} must match img_pair's {}".format(d1, d2, Bf, (B, H, W)))
+    s = H // h if h > 0 else 0
+    if s < 1 or H != s * h or W != s * w:
+        raise ValueError("the images' {}x{} must be one whole multiple of the flow's {}x{}".format(H, W, h, w))
+    return _review_call(
+        "interpolation_panels", 1, 7, 5, B, H, W, h, w, out_dtype, nhwc_out, grid, img_pair,
+        lambda L, outs, ws: L.qpwc_interpolation_panels_fwd(
+            img_pair.data_ptr(), img1.data_ptr(), pred.data_ptr(), _DTYPES[img_pair.dtype], flow.data_ptr(), B, H, W,
+            h, w, _hip.NHWC if nhwc else _hip.NCHW, outs, _hip.U8 if out_dtype == torch.uint8 else _hip.F32,
+            _hip.NHWC if nhwc_out else _hip.NCHW, int(grid), ws, _stream(img_pair)))
+
+
 def image_quality_kernel(B, H, W, C):
     """Form of ``qpwc_image_quality_fwd``'s tile kernel for this shape ('quality_tile_kernel': it has one; host only).
     '' for arguments the entry point refuses."""
