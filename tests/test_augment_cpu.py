@@ -49,8 +49,9 @@ def ref_hsv_to_rgb(hh, s, v):
     return ((d - 1) * s[..., None] + 1) * v[..., None]
 
 
-def ref_colours(x, brightness, saturation, hue, contrast, per_frame_means=False):
-    """image_augment_colors on one sample (h,w,6): brightness, saturation, hue, contrast on both frames."""
+def ref_colours(x, brightness, saturation, hue, contrast, per_frame_means=False, mean_over_first=None):
+    """image_augment_colors on one sample (h,w,6): brightness, saturation, hue, contrast on both frames.
+    mean_over_first = N (WRONG on purpose): the contrast mean over the first N pixels, row-major, of both frames."""
     h, w, _ = x.shape
     x = x.reshape(h, w, 2, 3) + brightness
     hh, s, v = ref_rgb_to_hsv(x)
@@ -59,14 +60,17 @@ def ref_colours(x, brightness, saturation, hue, contrast, per_frame_means=False)
     x = ref_hsv_to_rgb(np.mod(hh + hue, 1.0), s, v)
     # 'h w (k c) -> h (w k) c': adjust_contrast's mean runs over the pixels of both frames
     mean = x.mean(axis=(0, 1), keepdims=True) if per_frame_means else x.mean(axis=(0, 1, 2), keepdims=True)
+    if mean_over_first is not None:
+        mean = x.reshape(h * w, 2, 3)[:mean_over_first].mean(axis=(0, 1)).reshape(1, 1, 1, 3)
     x = (x - mean) * contrast + mean
     return x.reshape(h, w, 6)
 
 
 def ref_augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, data_format="channels_last",
-                per_frame_means=False, flow_by_shape_ratio=False):
+                per_frame_means=False, flow_by_shape_ratio=False, mean_over_first=None):
     """float64 outputs for numpy inputs ims (B,H,W,6) uint8 / float, flo (B,H,W,2), iparams (B,6), fparams (B,6).
-    per_frame_means / flow_by_shape_ratio build the two WRONG outputs the GPU suite's negative controls need."""
+    per_frame_means / flow_by_shape_ratio build the two WRONG outputs the GPU suite's negative controls need;
+    mean_over_first = N a third: the contrast mean of a fold that stops after the first N output pixels."""
     ims, flo = np.asarray(ims), np.asarray(flo)
     iparams, fparams = np.asarray(iparams), np.asarray(fparams, np.float32)
     B, H, W, _ = ims.shape
@@ -99,7 +103,9 @@ def ref_augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True,
         if flow_by_shape_ratio:
             mu, mv = np.sign(mu) * rw / W, np.sign(mv) * rh / H
         o_flo[b] = val[..., 6:] * np.array([mu, mv])
-        o_ims[b] = ref_colours(val[..., :6], bri, sat, hue, con, per_frame_means) if colour else val[..., :6]
+        o_ims[b] = val[..., :6]
+        if colour:
+            o_ims[b] = ref_colours(val[..., :6], bri, sat, hue, con, per_frame_means, mean_over_first)
     if finish:
         o_ims = o_ims - 0.5
         o_ims = np.where(np.isnan(o_ims), 0.0, o_ims)

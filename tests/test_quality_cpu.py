@@ -77,18 +77,20 @@ def ref_quality(truth, pred, max_val=1.0, offset=(0.0, 0.0), clip=False, quantiz
 
 
 # ---- the inputs -----------------------------------------------------------------------------------------------------
-def make_images(seed, hw, C, amplitude=0.35):
-    """(truth, pred), float32 (B,H,W,C) in about [0, 1]: a smooth sinusoid plus N(0, 0.05^2) texture; the prediction is
-    the truth plus N(0, 0.04^2) in image 0 and N(0, 0.08^2) in image 1, and the two images differ in content."""
+def make_images(seed, hw, C, amplitude=0.35, batch=B, sigmas=(0.04, 0.08)):
+    """(truth, pred), float32 (batch,H,W,C) in about [0, 1]: a smooth sinusoid plus N(0, 0.05^2) texture; the prediction
+    is the truth plus N(0, sigmas[n]^2) in image n (0.04 in image 0 and 0.08 in image 1), and the images differ in
+    content."""
+    assert len(sigmas) == batch
     rng = np.random.default_rng(seed)
     H, W = hw
     y, x = np.meshgrid(np.arange(H) / H, np.arange(W) / W, indexing="ij")
-    truth = np.empty((B, H, W, C))
-    for n in range(B):
+    truth = np.empty((batch, H, W, C))
+    for n in range(batch):
         for c in range(C):
             truth[n, :, :, c] = 0.5 + amplitude * np.sin(2 * math.pi * ((1.0 + n) * y + (1.5 - 0.5 * n) * x) + 0.7 * c + n)
     truth += 0.05 * rng.standard_normal(truth.shape)
-    pred = truth + rng.standard_normal(truth.shape) * np.asarray([0.04, 0.08]).reshape(B, 1, 1, 1)
+    pred = truth + rng.standard_normal(truth.shape) * np.asarray(sigmas).reshape(batch, 1, 1, 1)
     return truth.astype(np.float32), pred.astype(np.float32)
 
 

@@ -132,19 +132,46 @@ def outside_share(flow, s=1):
     return float(np.mean(sides[0] | sides[1] | sides[2] | sides[3]))
 
 
-def checked_flow(seed, shape, s=1, plant=True, scale=3.0):
+def nudge_to_margin(flow, s=1):
+    """The flow with 4e-3 added to every component whose sample coordinate (any of the s x s it is repeated to) lies
+    within 1.5e-3 of -1, W-1 or H-1 without being that value, again until margin_ok holds: as
+    test_quality_cpu.away_from_steps moves elements off the 8-bit steps.  For fixtures too large to re-seed: among half
+    a million samples some always lie that close.  The condition itself is margin_ok's, unchanged."""
+    flow = flow.copy()
+    n, h, w, _ = flow.shape
+    for _ in range(50):
+        if margin_ok(flow, s):
+            return flow
+        x, y = sample_coordinates(flow, s)
+        H, W = x.shape[1:3]
+        for c, (coord, edges) in enumerate(((x, (-1.0, W - 1.0)), (y, (-1.0, H - 1.0)))):
+            near = np.zeros(coord.shape, bool)
+            for e in edges:
+                d = np.abs(coord - e)
+                near |= (d < 1.5 * MARGIN) & (d != 0.0)
+            flow[..., c][near.reshape(n, h, s, w, s).any(axis=(2, 4))] += np.float32(4e-3)
+    raise AssertionError("could not move every sample away from tf_warp's steps")
+
+
+def checked_flow(seed, shape, s=1, plant=True, scale=3.0, min_outside=0.05, nudge=False):
     """(B,h,w,2) float32 N(0, scale^2) meeting the fixture condition (module docstring).  plant: image 0's largest
     vector at its last pixel (the last, partial max-tile where h * w > _hip.VIS_MAX_TILE) and image 1's at pixel 3
-    (the first), whole numbers far above the rest, as test_gpu_vis.make_levels does."""
+    (the first), whole numbers far above the rest, as test_gpu_vis.make_levels does; or a sequence of
+    (image, pixel, (fx, fy)) to plant other vectors, pixel counted row-major.  min_outside: the share of the samples
+    that must leave the image (None: only that every side is left by some sample, which outside_share asserts).
+    nudge: meet the condition by nudge_to_margin, not by re-seeding."""
     for k in range(1000):
         flow = (np.random.default_rng(seed + 1000 * k).standard_normal(shape + (2,)) * scale).astype(np.float32)
         if plant:
             assert float(np.abs(flow).max()) < 20.0
-            flow[0, -1, -1] = (30.0, -40.0)
-            flow[1, 0, 3] = (-21.0, 20.0)
+            spots = ((0, -1, (30.0, -40.0)), (1, 3, (-21.0, 20.0))) if plant is True else plant
+            for n, pixel, vector in spots:
+                flow[n].reshape(-1, 2)[pixel] = vector
+        if nudge:
+            flow = nudge_to_margin(flow, s)
         if margin_ok(flow, s):
             share = outside_share(flow, s)
-            assert share > 0.05, share
+            assert min_outside is None or share > min_outside, share
             flow.setflags(write=False)
             return flow
     raise AssertionError("no seed meets the margin")
