@@ -191,7 +191,8 @@ int64_t qpwc_loss_workspace_floats(int kind, int B, int H, int W, int C, const i
  * level l's resampled, flow-scaled ground truth.  y_pred[l] may be NULL where gt_out[l] is not (the prediction is
  * then taken as zero).  Outputs and workspace (qpwc_loss_workspace_floats()) must not overlap the inputs or each
  * other.  Errors: QPWC_E_MODE kind, QPWC_E_LAYOUT layout, QPWC_E_DTYPE pred_dtype, QPWC_E_SHAPE n_levels outside
- * 1..8 / extents / C != 2 for a flow loss / an area factor that does not divide, QPWC_E_RANGE delta < 0,
+ * 1..8 / extents / C != 2 for a flow loss / an area factor that does not divide / more than 2^31 - 1 pixels in an
+ * image of y_true or of a level, or 32x32 tiles in y_true (both are counted in 32 bits), QPWC_E_RANGE delta < 0,
  * QPWC_E_NULL, QPWC_E_ALIGN, QPWC_E_ALIAS. */
 int qpwc_loss_fwd(int kind, float p0, float p1, const void* y_true, int B, int H, int W, int C, int layout,
                   const void* const* y_pred, const int* h, const int* w, const int* pred_dtype, int n_levels,

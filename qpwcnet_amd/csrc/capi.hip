@@ -116,8 +116,16 @@ static int loss_check_shapes(int kind, int B, int H, int W, int C, const int* h,
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0)
         return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d C=%d", B, H, W, C);
     if (kind != QPWC_LOSS_AUTORESIZE_MSE && C != 2) return fail(QPWC_E_SHAPE, "flow losses take 2 channels, got %d", C);
+    // loss_pixel_kernel decodes a pixel inside its image in 32 bits
+    if ((int64_t)H * W > INT32_MAX)
+        return fail(QPWC_E_SHAPE, "H=%d W=%d: more than 2^31 - 1 pixels per image", H, W);
+    // loss_area_tile_kernel, which only FlowMseLossV2 can take, counts the ground truth's 32 x 32 tiles in 32 bits
+    if (kind == QPWC_LOSS_FLOW_MSE_V2 && (int64_t)B * (((int64_t)H + 31) / 32) * (((int64_t)W + 31) / 32) > INT32_MAX)
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: more than 2^31 - 1 tiles of 32 x 32 pixels", B, H, W);
     for (int i = 0; i < n_levels; ++i) {
         if (h[i] <= 0 || w[i] <= 0) return fail(QPWC_E_SHAPE, "level %d: non-positive extent %dx%d", i, h[i], w[i]);
+        if ((int64_t)h[i] * w[i] > INT32_MAX)
+            return fail(QPWC_E_SHAPE, "level %d: %dx%d is more than 2^31 - 1 pixels per image", i, h[i], w[i]);
         // einops.reduce('(h sh) (w sw)') in the reference fails the same way
         if (kind == QPWC_LOSS_FLOW_MSE_V2 && (H % h[i] || W % w[i]))
             return fail(QPWC_E_SHAPE, "level %d: %dx%d is not a whole-block area reduction of %dx%d", i, h[i], w[i], H, W);

@@ -1,0 +1,1227 @@
+"""GPU suite of the training kernels where element offsets pass 2^29, 2^30 and 2^31 (byte offsets 2^31 and 2^32, and the
+`int` index limit): one entry of CASES per kernel family, each B = 3 with ragged H x W so that the three boundaries of
+its main operand fall into three different images (tests/test_large_offsets_cpu.py proves that for every entry, and
+that the validators admit the shape).
+
+No whole-array float64 reference exists at 8 GB per operand.  The oracles are
+
+  (a) bit equality on the device, per image: the kernels accumulate a pixel row independently of the rest of the
+      batch (csrc/conv_bwd.hip: "grad_x of an image does not depend on the rest of the batch"), so out[n] and
+      grad_x[n] of the big launch must be torch.equal to the same op on x[n:n+1] alone, a launch that stays below
+      every boundary and that the small-shape suites hold to float64;
+  (b) float64 autograd on the CPU over crops of CROP x CROP output pixels: one around each boundary pixel of every
+      per-pixel operand, one on the last pixels of the last image ('SAME' border, partial last pixel block).  The crop
+      of x is exactly what the crop's outputs read (zeros where that lies outside the image), grad_out is the dense
+      one, and grad_x is compared where every output that reads the x pixel lies inside the crop -- the crop's
+      artificial border cannot contribute to what is compared.  Bound: the family's 1e-4 * max(1, max|ref|);
+  (c) for the sums over the batch (grad_w, grad_b) a second backward with grad_out zero except WIN x WIN windows at
+      the start of image 0, just behind each boundary and in the bottom-right corner of the last image, x still dense
+      random: the float64 answer needs the windows' crops only.  Without Mish every product and partial sum is exact
+      on these grids (tests/test_gpu_conv_grad.py::test_ragged_without_mish_is_exact; the magnitude precondition is
+      asserted) and torch.equal is required; with Mish the family bound.  Negative controls on the device's own data:
+      leaving out any one window, or reading a window's x crop at its offset wrapped mod 2^31 / 2^32 bytes, moves
+      the answer by at least 100 bounds.
+
+The losses and the EPE are sums over the batch only: the prediction equals the level's ground truth outside planted
+windows (the area loss takes the kernel's own gt_out, itself held to float64 on crops; a full-resolution level takes a
+copy of the ground truth), so value and grad_pred follow from the windows' crops in float64.  Their magnitudes are
+1e-6 and below, so their bound is relative (LOSS_REL, derived at its definition), not the 1e-4 of the layers.
+
+Where a family departs from this: grad_img of the warp is a scatter of float atomics, so it is held to (b) only; the
+cost-volume backward is fed a random saved output (it reads it for the LeakyReLU mask only) and gives its two
+gradients in two launches; the SeparableConv2D case calls the backward op without running the fused forward; the
+cost volume, the warp, the image upsampling and the pyramid have no sums over the batch, hence no (c); the pyramid
+needs H and W to be multiples of 32, so its sizes are unequal but not odd.  Not here: the flow
+head's training path, whose validator caps it at 2^24 pixels where its operands stay under 2^29 elements (DESIGN.md
+4.17; a run at exactly the cap was considered: it would cross no boundary, and the cap's reason, fp32 pixel counts, is
+the small-shape suite's subject).
+
+What catches a 32-bit offset, on paper: with the `(int64_t)` of the stage-X store of conv_bwd_gemm_kernel
+(`dst[(((int64_t)img * g.H + row_y) * g.W + row_x) * g.cin + col]`) changed to `int`, the element index of every pixel
+behind 2^31 elements (image 2 from row 6621 on) wraps to a negative offset: grad_x[2] of the big launch keeps whatever
+the allocation held there, while the launch of image 2 alone (offsets < 2^30) writes it, so (a) fails for image 2, and
+(b) fails on the "x>2^31" crop and on the last-corner crop.  The same change in a load of stage W would read x at a
+wrapped place: the "wrapped" control of (c) shows that this moves grad_w by more than 100 bounds.
+
+Everything full-size is drawn on the device from a seeded generator on the grids of the grad suites (multiples of 1/16
+for x and grad_out, 1/8 for weights and bias); only crops leave the device.  Device memory: the peak of each test is
+asserted within planned bytes + 10 % (a hidden full-size copy in ops.py would show), planned being the larger of the
+two phases big launch (operands, outputs, workspace) and one-image repeats (the workspace is released by then), and
+the peak being counted over what earlier tests of the session still hold.
+
+Measured on an MI355X (peak of torch.cuda.max_memory_allocated, wall time of the test body):
+  case                      peak GiB (planned)   seconds      largest |error| against float64 (bound 1e-4 max(1, max|ref|))
+  conv3x3_same_s1 mish      40.16 (40.16)        0.2 - 2.4    out 9.5e-7, grad_x 7.2e-6, grad_w 3.8e-6, grad_b 4.9e-6
+  conv3x3_same_s1 linear    40.16 (40.16)        0.2 - 1.5    0 (exact), grad_w / grad_b torch.equal
+  conv3x3_same_s2 mish      29.46 (29.45)        0.2 - 1.3    out 1.9e-6, grad_x 5.8e-6, grad_w 5.3e-6, grad_b 3.7e-6
+  conv3x3_same_s2 linear    29.46 (29.45)        0.1 - 1.0    0 (exact)
+  upconv4x4s2               40.16 (40.16)        0.5 - 1.4    out 3.3e-7, grad_x 1.1e-6, grad_w 3.1e-6, grad_b 4.1e-6; mish = 0 exact
+  sepconv3x3 flags 11       40.08 (40.08)        0.2 - 3.0    grad_x 1.7e-6, grad_dw 1.2e-5, grad_pw 1.4e-5, grad_bias 4.0e-6
+  sepconv3x3 flags 00       40.08 (40.08)        0.2          0 (exact)
+  cost_volume_bwd           47.77 (47.10)        0.7 - 2.9    grad_prv 3.9e-8, grad_nxt 4.3e-8
+  warp_bwd clamp + fp16     24.70 (24.68)        0.1 - 0.9    0 (exact on the 2^-6 flow grid)
+  warp_bwd tfwarp           24.70 (24.68)        0.1          0
+  image_head                20.29 (19.62)        0.03 - 1.3   0 (exact)
+  upsample2x_image          24.03 (23.36)        0.03 - 2.9   0 (exact)
+  avgpool_pyramid            8.04 (8.04)         0.01         0 (exact)
+  loss tile path            14.01 (16.02)        0.4          relative: loss 5.8e-8, grad_pred 9.0e-8 (bound 1e-5)
+  loss pixel paths, EPE     32.05 (32.05)        0.1          relative: losses 4.3e-8, grad_pred 1.3e-7, EPE 7.7e-10 (bound 1e-5)
+The whole module: 15 tests, 3 - 16 s (the seconds are test bodies in different runs).  The peaks above the plan are the boolean of torch.equal on one image (0.67 GiB);
+ops.py itself allocates what is planned and nothing else.  The negative controls moved the sums by 1300 - 20500 bounds.
+"""
+import gc
+import os
+import sys
+import time
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import torch_ref
+from qpwcnet_amd import ops
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_gpu_conv_grad import same_pad  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+BOUNDARIES = (1 << 29, 1 << 30, 1 << 31)      # fp32 elements: byte offsets 2^31 and 2^32, the int index limit
+CROP, WIN = 24, 16
+GIB = 1 << 30
+# family -> (B, H, W, ...) of the kernel family's own key
+CASES = {
+    "conv3x3_same_s1": (3, 6701, 6703, 16, 16, 1),       # (B, H, W, C_in, C_out, stride)
+    "conv3x3_same_s2": (3, 6701, 6703, 16, 32, 2),
+    "upconv4x4s2": (3, 3349, 3353, 64, 16),              # (B, H, W, C, F)
+    "sepconv3x3": (3, 4733, 4735, 32, 16, 1),            # (B, H, W, C, F, 1): the 3x3 'same' stride-1 geometry
+    "backward": (3, 3349, 3353, 64),                     # (B, H, W, C) of cost_volume_bwd and warp_bwd
+    "image_head": (3, 3349, 3353),                       # (B, H, W) of 64 features: M > 2^25 pixels
+    "upsample2x_image": (3, 7727, 7729, 3),              # (B, h, w, C): 2.150 G output floats
+    "avgpool_pyramid": (3, 15456, 15488, 3, 5),          # (B, H, W, C, levels): 2.154 G input floats
+    "loss": (3, 18912, 18944, 2),                        # (B, H, W, 2) ground truth, H and W multiples of 32: the tile path
+    "epe": (3, 18931, 18937, 2),                         # (B, H, W, 2) odd: pixel and bilinear losses, both EPE kernels
+}
+
+
+# ---- where the boundaries lie (pure; shared with the CPU companion) ------------------------------------------------
+def crossed(n_elems):
+    """The boundaries that an operand of n_elems floats crosses: its last element lies beyond them."""
+    return [b for b in BOUNDARIES if n_elems - 1 > b]
+
+
+def locate(elem, rows, cols, ch):
+    """Element offset into a dense (B, rows, cols, ch) tensor -> (image, row, column) of its pixel."""
+    p = elem // ch
+    return p // (rows * cols), (p // cols) % rows, p % cols
+
+
+def _span(c, size, n):
+    lo = min(max(c - size // 2, 0), n - size)
+    return lo, lo + size
+
+
+def conv_geo(key):
+    """The geometry of a convolution key: (B, H, W, C_in, C_out, stride) of the 3x3 'same' layer, or (B, H, W, C, F) of
+    the 4x4 stride-2 transposed one (up = True: output pixel o = 2 i - 1 + k, k = 0 .. 3)."""
+    if len(key) == 5:
+        B, H, W, C, F_ = key
+        return dict(B=B, H=H, W=W, ci=C, co=F_, up=True, Ho=2 * H, Wo=2 * W)
+    B, H, W, ci, co, s = key
+    return dict(B=B, H=H, W=W, ci=ci, co=co, s=s, up=False, Ho=-(-H // s), Wo=-(-W // s), pt=same_pad(H, s)[0],
+                pl=same_pad(W, s)[0])
+
+
+def conv_operands(key):
+    """Element counts of the full-size operands of a forward + backward."""
+    g = conv_geo(key)
+    n_in, n_out = g["B"] * g["H"] * g["W"] * g["ci"], g["B"] * g["Ho"] * g["Wo"] * g["co"]
+    return {"x": n_in, "grad_x": n_in, "out": n_out, "grad_out": n_out, "gz": n_out}
+
+
+def conv_boundary_pixels(key):
+    """[(tag, image, output row, output column)]: the output pixel at (or, for x, reading) the pixel that holds each
+    boundary of the output-sized operands and of the input-sized ones; one entry per distinct pixel."""
+    g = conv_geo(key)
+    ops_ = conv_operands(key)
+    seen, out = set(), []
+    for b in crossed(ops_["out"]):
+        n, y, x = locate(b, g["Ho"], g["Wo"], g["co"])
+        if (n, y, x) not in seen:
+            seen.add((n, y, x))
+            out.append(("out>2^%d" % (b.bit_length() - 1), n, y, x))
+    for b in crossed(ops_["x"]):
+        n, y, x = locate(b, g["H"], g["W"], g["ci"])
+        y, x = (2 * y, 2 * x) if g["up"] else (y // g["s"], x // g["s"])
+        if (n, y, x) not in seen:
+            seen.add((n, y, x))
+            out.append(("x>2^%d" % (b.bit_length() - 1), n, y, x))
+    return out
+
+
+def conv_crops(key):
+    """[(tag, n, oy0, oy1, ox0, ox1)] in output pixels: a CROP x CROP region around each boundary pixel, one on the
+    last pixels of the last image."""
+    g = conv_geo(key)
+    regs = [(tag, n) + _span(y, CROP, g["Ho"]) + _span(x, CROP, g["Wo"]) for tag, n, y, x in conv_boundary_pixels(key)]
+    regs.append(("last", g["B"] - 1, g["Ho"] - CROP, g["Ho"], g["Wo"] - CROP, g["Wo"]))
+    return regs
+
+
+def conv_windows(key):
+    """[(tag, n, oy0, oy1, ox0, ox1)]: WIN x WIN windows of grad_out for the batch sums: the start of image 0, the rows
+    just behind each boundary pixel, the bottom-right corner of the last image."""
+    g = conv_geo(key)
+    wins = [("first", 0, 0, WIN, 0, WIN)]
+    for tag, n, y, x in conv_boundary_pixels(key):
+        d = 4 if g["up"] else 2                           # far enough down that what the window reads of x lies behind it too
+        assert y + d + WIN <= g["Ho"], (tag, y)
+        wins.append((tag, n, y + d, y + d + WIN) + _span(x, WIN, g["Wo"]))
+    wins.append(("last", g["B"] - 1, g["Ho"] - WIN, g["Ho"], g["Wo"] - WIN, g["Wo"]))
+    return wins
+
+
+def conv_x_region(key, reg):
+    """What the outputs of a region read: ((iy0, iy1, ix0, ix1) inside the image, (left, right, top, bottom) zeros of
+    the 'SAME' window outside it; transposed: the region's place (left, right, top, bottom) in the output of those
+    inputs)."""
+    g = conv_geo(key)
+    _, _, oy0, oy1, ox0, ox1 = reg
+    if g["up"]:      # output o reads inputs ceil((o - 2) / 2) .. floor((o + 1) / 2)
+        cy0, cy1, cx0, cx1 = max((oy0 - 1) // 2, 0), min(oy1 // 2 + 1, g["H"]), max((ox0 - 1) // 2, 0), min(ox1 // 2 + 1, g["W"])
+        return (cy0, cy1, cx0, cx1), (ox0 - 2 * cx0, ox1 - 2 * cx0, oy0 - 2 * cy0, oy1 - 2 * cy0)
+    iy0, iy1 = oy0 * g["s"] - g["pt"], (oy1 - 1) * g["s"] + 3 - g["pt"]
+    ix0, ix1 = ox0 * g["s"] - g["pl"], (ox1 - 1) * g["s"] + 3 - g["pl"]
+    cy0, cy1, cx0, cx1 = max(iy0, 0), min(iy1, g["H"]), max(ix0, 0), min(ix1, g["W"])
+    return (cy0, cy1, cx0, cx1), (cx0 - ix0, ix1 - cx1, cy0 - iy0, iy1 - cy1)
+
+
+def _axis_valid(i0, i1, o0, o1, n_out, s, p):
+    """Per input coordinate of [i0, i1): every output of [0, n_out) whose 3-wide window holds it (s = None: that the
+    transposed convolution writes from it) lies in [o0, o1)."""
+    ok = []
+    for i in range(i0, i1):
+        if s is None:
+            users = range(max(0, 2 * i - 1), min(n_out - 1, 2 * i + 2) + 1)
+        else:
+            users = range(max(0, (i + p - 2 + s - 1) // s), min(n_out - 1, (i + p) // s) + 1)
+        ok.append(all(o0 <= o < o1 for o in users))
+    return torch.tensor(ok)
+
+
+def conv_gx_valid(key, reg):
+    """Mask over the x region of a crop: grad_x there depends on outputs of the crop only."""
+    g = conv_geo(key)
+    (cy0, cy1, cx0, cx1), _ = conv_x_region(key, reg)
+    _, _, oy0, oy1, ox0, ox1 = reg
+    return _axis_valid(cy0, cy1, oy0, oy1, g["Ho"], g.get("s"), g.get("pt"))[:, None] & \
+        _axis_valid(cx0, cx1, ox0, ox1, g["Wo"], g.get("s"), g.get("pl"))[None, :]
+
+
+def conv_wrapped_regions(key, reg):
+    """The x region of a window as a 32-bit byte offset would find it: its first element's byte offset mod 2^31 and
+    mod 2^32, where that differs -> [(modulus, (n, iy0, iy1, ix0, ix1))] of the same extent, inside the tensor."""
+    g = conv_geo(key)
+    (cy0, cy1, cx0, cx1), _ = conv_x_region(key, reg)
+    first = ((reg[1] * g["H"] + cy0) * g["W"] + cx0) * g["ci"]
+    out = []
+    for mod in (1 << 31, 1 << 32):
+        e = (first * 4 % mod) // 4
+        if e == first:
+            continue
+        n, y, x = locate(e, g["H"], g["W"], g["ci"])
+        y0, x0 = min(y, g["H"] - (cy1 - cy0)), min(x, g["W"] - (cx1 - cx0))
+        out.append((mod, (n, y0, y0 + cy1 - cy0, x0, x0 + cx1 - cx0)))
+    return out
+
+
+def conv_planned_bytes(key, ws_floats, ws_floats_one):
+    """Planned device memory of a test: the larger of the big launch (x, grad_out, out, grad_x, workspace) and the
+    one-image repeats beside the big launch's tensors (out, grad_x and workspace of one image)."""
+    n = conv_operands(key)
+    B = key[0]
+    held = n["x"] + n["grad_out"] + n["out"] + n["grad_x"]
+    return 4 * max(held + ws_floats, held + n["out"] // B + n["grad_x"] // B + ws_floats_one)
+
+
+# ---- the float64 restatement on crops -----------------------------------------------------------------------------
+def _tol(ref):
+    return 1e-4 * max(1.0, float(ref.abs().max()))
+
+
+def conv_region_ref(key, xc, pads, w, b, gc, mish):
+    """Float64 autograd of the layer on a crop: xc (1, h, w, C_in) as conv_x_region() cut it, gc the crop's grad_out
+    -> (out, grad of xc, grad_w, grad_b)."""
+    if isinstance(w, (tuple, list)):
+        # SeparableConv2D: w = (dw (C,1,3,3), pw (F,C)), mish = (on load, on store); grad_w = grad_dw | grad_pw, flat
+        leaves = [t.double().clone().requires_grad_() for t in (xc, w[0], w[1], b)]
+        xp = F.pad(leaves[0], (0, 0, pads[0], pads[1], pads[2], pads[3]))        # Mish(0) = 0: the padding stays zero
+        d = torch_ref.depthwise3x3([xp], leaves[1], mish[0])[:, 1:-1, 1:-1]
+        z = d @ leaves[2].t() + leaves[3]
+        out = torch_ref.mish(z) if mish[1] else z
+        assert out.shape == gc.shape, (out.shape, gc.shape)
+        out.backward(gc.double())
+        return out.detach(), leaves[0].grad, torch.cat([leaves[1].grad.flatten(), leaves[2].grad.flatten()]), leaves[3].grad
+    leaves = [t.double().clone().requires_grad_() for t in (xc, w, b)]
+    if len(key) == 5:
+        z = F.conv_transpose2d(leaves[0].permute(0, 3, 1, 2), leaves[1], leaves[2], stride=2, padding=1)
+        z = z.permute(0, 2, 3, 1)[:, pads[2]:pads[3], pads[0]:pads[1]]
+    else:
+        z = F.conv2d(F.pad(leaves[0].permute(0, 3, 1, 2), pads), leaves[1], leaves[2], stride=key[5]).permute(0, 2, 3, 1)
+    out = torch_ref.mish(z) if mish else z
+    assert out.shape == gc.shape, (out.shape, gc.shape)
+    out.backward(gc.double())
+    return out.detach(), leaves[0].grad, leaves[1].grad, leaves[2].grad
+
+
+def conv_window_sums(key, crops, w, b, mish):
+    """grad_w, grad_b in float64 of a grad_out that is zero outside the windows: crops = [(xc, pads, gc)]."""
+    gw, gb = 0.0, 0.0
+    for xc, pads, gc in crops:
+        _, _, w_, b_ = conv_region_ref(key, xc, pads, w, b, gc, mish)
+        gw, gb = gw + w_, gb + b_
+    return gw, gb
+
+
+def conv_controls(key, crops, moved, w, b, mish):
+    """The negative controls of the window sums -> [(what, max|change| of grad_w / its bound)]: every window left out
+    in turn, and every moved = [(what, window index, x crop read elsewhere)] put in its window's place."""
+    ref = conv_window_sums(key, crops, w, b, mish)[0]
+    out = []
+    for k in range(len(crops)):
+        alt = conv_window_sums(key, crops[:k] + crops[k + 1:], w, b, mish)[0]
+        out.append(("without window %d" % k, float((alt - ref).abs().max()) / _tol(ref)))
+    for what, k, xc in moved:
+        alt = conv_window_sums(key, crops[:k] + [(xc,) + crops[k][1:]] + crops[k + 1:], w, b, mish)[0]
+        out.append((what, float((alt - ref).abs().max()) / _tol(ref)))
+    return out
+
+
+def exactness_precondition(key, crops, w, b, unit=2 ** 8):
+    """sum|terms| * unit < 2^24 for every sum of the linear layer on these grids, 1 / unit the product of the grids'
+    steps (2^-8 with 1/8 weights, 2^-10 with 1/64 weights) -> the largest sum."""
+    ab = [(xc.abs(), pads, gc.abs()) for xc, pads, gc in crops]
+    biggest = 0.0
+    linear = (False, False) if isinstance(w, (tuple, list)) else False
+    w = tuple(t.abs() for t in w) if isinstance(w, (tuple, list)) else w.abs()
+    for xc, pads, gc in ab:
+        biggest = max(biggest, max(float(t.max()) for t in conv_region_ref(key, xc, pads, w, b.abs(), gc, linear)[:2]))
+    biggest = max(biggest, max(float(t.max()) for t in conv_window_sums(key, ab, w, b.abs(), linear)))
+    assert biggest * unit < 2 ** 24, biggest
+    return biggest
+
+
+# ---- the device side -------------------------------------------------------------------------------------------------
+def _dgrid(gen, shape, step, lim=1.0):
+    n = int(round(lim / step))
+    return torch.randint(-n, n + 1, shape, generator=gen, device=DEV, dtype=torch.float32).mul_(step)
+
+
+def _check(got, ref, what):
+    got = got.detach().double().cpu()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert bool(torch.isfinite(got).all()), what
+    d = float((got - ref).abs().max())
+    print("{}: max|d| = {:.3e}, bound {:.3e}".format(what, d, _tol(ref)))
+    assert d <= _tol(ref), "{}: max|d| = {:.3e} > {:.3e}".format(what, d, _tol(ref))
+    return d
+
+
+@pytest.fixture
+def arena():
+    """Holds a case's device tensors; frees them and the allocator's cache when the test is over."""
+    if torch.cuda.get_device_properties(0).total_memory < 96 * GIB:
+        pytest.skip("needs a device with at least 96 GiB")
+    gc.collect()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    held = {"_base": torch.cuda.memory_allocated()}      # what earlier tests of the session still hold
+    yield held
+    held.clear()
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def _cut(t, n, y0, y1, x0, x1):
+    return t.detach()[n:n + 1, y0:y1, x0:x1, :].cpu()
+
+
+@pytest.mark.parametrize("mish", [True, False], ids=["mish", "linear"])
+@pytest.mark.parametrize("name", ["conv3x3_same_s1", "conv3x3_same_s2"])
+def test_conv3x3_same(name, mish, arena):
+    """Conv2D 3x3 'same' forward and stages Z, X, W, R of its backward at x of 2.156 G floats.  The forward runs
+    conv3x3_mish_kernel (stride 1 with Mish) or conv_bwd_gemm_kernel mode 0.  Measured: peak 40.16 GiB (stride 1) / 29.46 GiB (stride 2), 0.1 - 2.4 s a case."""
+    key = CASES[name]
+    B, H, W, ci, co, s = key
+    g_ = conv_geo(key)
+    Ho, Wo = g_["Ho"], g_["Wo"]
+    L = ops._hip.lib()
+    planned = conv_planned_bytes(key, L.qpwc_conv3x3_same_bwd_workspace_floats(B, H, W, ci, co, s),
+                                 L.qpwc_conv3x3_same_bwd_workspace_floats(1, H, W, ci, co, s))
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    a = arena
+    a["x"] = _dgrid(gen, (B, H, W, ci), 1 / 16).requires_grad_()
+    a["w"] = _dgrid(gen, (co, ci, 3, 3), 1 / 8).requires_grad_()
+    a["b"] = _dgrid(gen, (co,), 1 / 8).requires_grad_()
+    a["g"] = _dgrid(gen, (B, Ho, Wo, co), 1 / 16)
+    x, w, b, g = a["x"], a["w"], a["b"], a["g"]
+    assert x.numel() > 1 << 31
+
+    # the big launch, through autograd
+    a["out"] = ops.conv3x3_same(x, w, b, stride=s, mish=mish)
+    a["out"].backward(g)
+    out, gx = a["out"].detach(), x.grad
+    assert tuple(out.shape) == (B, Ho, Wo, co) and tuple(gx.shape) == (B, H, W, ci)
+    assert w.grad is not None and b.grad is not None and bool(torch.isfinite(w.grad).all())
+    wd, bd = w.detach(), b.detach()
+
+    # (a) every image alone
+    for n in range(B):
+        x1 = x.detach()[n:n + 1].requires_grad_()
+        assert x1.is_contiguous() and x1.data_ptr() == x.data_ptr() + 4 * n * H * W * ci
+        o1 = ops.conv3x3_same(x1, wd, bd, stride=s, mish=mish)
+        o1.backward(g[n:n + 1])
+        assert torch.equal(o1.detach(), out[n:n + 1]), "out of image %d" % n
+        assert torch.equal(x1.grad, gx[n:n + 1]), "grad_x of image %d" % n
+        del x1, o1
+
+    # (b) float64 on crops
+    wc, bc = wd.cpu(), bd.cpu()
+    worst = {"out": 0.0, "grad_x": 0.0}
+    for reg in conv_crops(key):
+        (cy0, cy1, cx0, cx1), pads = conv_x_region(key, reg)
+        tag, n = reg[0], reg[1]
+        ro, rx, _, _ = conv_region_ref(key, _cut(x, n, cy0, cy1, cx0, cx1), pads, wc, bc, _cut(g, *reg[1:]), mish)
+        worst["out"] = max(worst["out"], _check(_cut(out, *reg[1:]), ro, "%s %s out" % (name, tag)))
+        ok = conv_gx_valid(key, reg)
+        assert int(ok.sum()) >= (CROP - 2) ** 2, (tag, int(ok.sum()))
+        got = _cut(gx, n, cy0, cy1, cx0, cx1)[0][ok]
+        worst["grad_x"] = max(worst["grad_x"], _check(got, rx[0][ok], "%s %s grad_x" % (name, tag)))
+
+    # (c) the sums over the batch: grad_out zero outside the windows
+    wins = conv_windows(key)
+    g.zero_()
+    crops, moved = [], []
+    for k, reg in enumerate(wins):
+        n, oy0, oy1, ox0, ox1 = reg[1:]
+        g[n, oy0:oy1, ox0:ox1, :] = _dgrid(gen, (oy1 - oy0, ox1 - ox0, co), 1 / 16)
+        (cy0, cy1, cx0, cx1), pads = conv_x_region(key, reg)
+        crops.append((_cut(x, n, cy0, cy1, cx0, cx1), pads, _cut(g, *reg[1:])))
+        for mod, at in conv_wrapped_regions(key, reg):
+            moved.append(("window %d (%s) x read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k, _cut(x, *at)))
+    assert 0 < sum(int(torch.count_nonzero(g[n])) for n in range(B)) <= len(wins) * WIN * WIN * co
+    _, gt, gb = ops.conv3x3_same_bwd(x.detach(), ops.conv3x3_same_taps(wd), bd, g, s, mish, need=(False, True, True))
+    gw = gt[..., :ci].reshape(3, 3, co, ci).permute(2, 3, 0, 1)
+    rw, rb = conv_window_sums(key, crops, wc, bc, mish)
+    if mish:
+        worst["grad_w"], worst["grad_b"] = _check(gw, rw, name + " grad_w"), _check(gb, rb, name + " grad_b")
+    else:
+        exactness_precondition(key, crops, wc, bc)
+        assert torch.equal(gw.double().cpu(), rw), float((gw.double().cpu() - rw).abs().max())
+        assert torch.equal(gb.double().cpu(), rb), float((gb.double().cpu() - rb).abs().max())
+    controls = conv_controls(key, crops, moved, wc, bc, mish)
+    assert len(controls) >= len(wins) + 2, controls
+    for what, ratio in controls:
+        assert ratio >= 100.0, (what, ratio)
+    print("{}: controls move grad_w by {:.0f} .. {:.0f} bounds".format(name, min(r for _, r in controls),
+                                                                         max(r for _, r in controls)))
+
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("{} mish={}: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}".format(
+        name, mish, peak / GIB, planned / GIB, secs, worst))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+def test_upconv4x4s2(arena):
+    """Transposed conv 4x4 stride 2: the layer's forward (upconv4x4s2_mish_kernel) and stages Z, X, W, R of its backward
+    at x and out of 2.156 G floats each.  The layer always applies Mish; the batch sums are also taken with mish = 0
+    through ops.upconv4x4s2_bwd, where they are exact.  Measured: peak 40.16 GiB, 0.5 - 1.4 s."""
+    name = "upconv4x4s2"
+    key = CASES[name]
+    B, H, W, C, F_ = key
+    L = ops._hip.lib()
+    planned = conv_planned_bytes(key, L.qpwc_upconv4x4s2_bwd_workspace_floats(B, H, W, C, F_),
+                                 L.qpwc_upconv4x4s2_bwd_workspace_floats(1, H, W, C, F_))
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(1)
+    a = arena
+    a["x"] = _dgrid(gen, (B, H, W, C), 1 / 16).requires_grad_()
+    a["w"] = _dgrid(gen, (C, F_, 4, 4), 1 / 64, 1 / 8).requires_grad_()
+    a["b"] = _dgrid(gen, (F_,), 1 / 8).requires_grad_()
+    a["g"] = _dgrid(gen, (B, 2 * H, 2 * W, F_), 1 / 16)
+    x, w, b, g = a["x"], a["w"], a["b"], a["g"]
+    assert x.numel() > 1 << 31 and g.numel() > 1 << 31
+
+    a["out"] = ops.upconv4x4s2(x, w, b)
+    a["out"].backward(g)
+    out, gx = a["out"].detach(), x.grad
+    assert tuple(out.shape) == (B, 2 * H, 2 * W, F_) and tuple(gx.shape) == (B, H, W, C)
+    assert w.grad is not None and b.grad is not None and bool(torch.isfinite(w.grad).all())
+    wd, bd = w.detach(), b.detach()
+
+    # (a) every image alone
+    for n in range(B):
+        x1 = x.detach()[n:n + 1].requires_grad_()
+        o1 = ops.upconv4x4s2(x1, wd, bd)
+        o1.backward(g[n:n + 1])
+        assert torch.equal(o1.detach(), out[n:n + 1]), "out of image %d" % n
+        assert torch.equal(x1.grad, gx[n:n + 1]), "grad_x of image %d" % n
+        del x1, o1
+
+    # (b) float64 on crops
+    wc, bc = wd.cpu(), bd.cpu()
+    worst = {"out": 0.0, "grad_x": 0.0}
+    for reg in conv_crops(key):
+        (cy0, cy1, cx0, cx1), place = conv_x_region(key, reg)
+        tag, n = reg[0], reg[1]
+        ro, rx, _, _ = conv_region_ref(key, _cut(x, n, cy0, cy1, cx0, cx1), place, wc, bc, _cut(g, *reg[1:]), True)
+        worst["out"] = max(worst["out"], _check(_cut(out, *reg[1:]), ro, "%s %s out" % (name, tag)))
+        ok = conv_gx_valid(key, reg)
+        assert int(ok.sum()) >= (CROP // 2 - 2) ** 2, (tag, int(ok.sum()))
+        got = _cut(gx, n, cy0, cy1, cx0, cx1)[0][ok]
+        worst["grad_x"] = max(worst["grad_x"], _check(got, rx[0][ok], "%s %s grad_x" % (name, tag)))
+
+    # (c) the sums over the batch: grad_out zero outside the windows
+    wins = conv_windows(key)
+    g.zero_()
+    crops, moved = [], []
+    for k, reg in enumerate(wins):
+        n, oy0, oy1, ox0, ox1 = reg[1:]
+        g[n, oy0:oy1, ox0:ox1, :] = _dgrid(gen, (oy1 - oy0, ox1 - ox0, F_), 1 / 16)
+        (cy0, cy1, cx0, cx1), place = conv_x_region(key, reg)
+        crops.append((_cut(x, n, cy0, cy1, cx0, cx1), place, _cut(g, *reg[1:])))
+        for mod, at in conv_wrapped_regions(key, reg):
+            moved.append(("window %d (%s) x read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k, _cut(x, *at)))
+    assert 0 < sum(int(torch.count_nonzero(g[n])) for n in range(B)) <= len(wins) * WIN * WIN * F_
+    taps = ops.upconv_taps(wd)
+    for mish in (True, False):
+        _, gt, gb = ops.upconv4x4s2_bwd(x.detach(), taps, bd, g, mish, need=(False, True, True))
+        gw = gt.reshape(4, 4, F_, C).permute(3, 2, 0, 1)
+        rw, rb = conv_window_sums(key, crops, wc, bc, mish)
+        if mish:
+            worst["grad_w"], worst["grad_b"] = _check(gw, rw, name + " grad_w"), _check(gb, rb, name + " grad_b")
+        else:
+            exactness_precondition(key, crops, wc, bc, unit=2 ** 10)
+            assert torch.equal(gw.double().cpu(), rw), float((gw.double().cpu() - rw).abs().max())
+            assert torch.equal(gb.double().cpu(), rb), float((gb.double().cpu() - rb).abs().max())
+        controls = conv_controls(key, crops, moved, wc, bc, mish)
+        assert len(controls) >= len(wins) + 2, controls
+        for what, ratio in controls:
+            assert ratio >= 100.0, (what, ratio)
+        print("{} mish={}: controls move grad_w by {:.0f} .. {:.0f} bounds".format(
+            name, mish, min(r for _, r in controls), max(r for _, r in controls)))
+        del gt, gb, gw
+
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("{}: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}".format(name, peak / GIB, planned / GIB, secs, worst))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+def sepconv_operands(key):
+    """Element counts of the SeparableConv2D backward's full-size operands and workspace regions (Cpad = C here)."""
+    B, H, W, C, F_ = key[:5]
+    assert C % 32 == 0
+    M = B * H * W
+    return {"x": M * C, "grad_x": M * C, "grad_out": M * F_, "d": M * C, "gd": M * C, "gz": M * F_}
+
+
+def sepconv_planned_bytes(key, ws_floats, ws_floats_one):
+    """x, grad_out, grad_x and the workspace of the big launch, or beside them grad_x and workspace of one image."""
+    n = sepconv_operands(key)
+    held = n["x"] + n["grad_out"] + n["grad_x"]
+    return 4 * max(held + ws_floats, held + n["grad_x"] // key[0] + ws_floats_one)
+
+
+@pytest.mark.parametrize("flags", [(True, True), (False, False)], ids=["11", "00"])
+def test_sepconv3x3_bwd(flags, arena):
+    """SeparableConv2D backward, stages A to D, one source of 2.151 G floats, through ops.sepconv3x3_bwd (what the
+    autograd Function's backward calls; the forward is not run: the backward recomputes d and z).  The workspace
+    regions d | gd | gz start at 0, 2.15 G and 4.30 G floats: gd lies behind 2^31 elements, gz behind 2^32.  grad_x is
+    held to oracles (a) and (b); grad_dw, grad_pw and grad_bias to (c), exact with both flags off.  Measured: peak 40.08 GiB, 0.2 - 3.0 s."""
+    name = "sepconv3x3"
+    key = CASES[name]
+    B, H, W, C, F_ = key[:5]
+    L = ops._hip.lib()
+    planned = sepconv_planned_bytes(key, L.qpwc_sepconv3x3_bwd_workspace_floats(B, H, W, C, F_),
+                                    L.qpwc_sepconv3x3_bwd_workspace_floats(1, H, W, C, F_))
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(2)
+    a = arena
+    a["x"] = _dgrid(gen, (B, H, W, C), 1 / 16)
+    dw, pw, b = _dgrid(gen, (C, 1, 3, 3), 1 / 8), _dgrid(gen, (F_, C), 1 / 8), _dgrid(gen, (F_,), 1 / 8)
+    a["g"] = _dgrid(gen, (B, H, W, F_), 1 / 16)
+    x, g = a["x"], a["g"]
+    pwp = ops.pad_pointwise(pw)
+    assert x.numel() > 1 << 31 and tuple(pwp.shape) == (F_, C)
+
+    gs, gdw, gpw, gb = ops.sepconv3x3_bwd([x], dw, pwp, b, g, *flags)
+    a["gx"] = gx = gs[0]
+    assert tuple(gx.shape) == (B, H, W, C) and all(bool(torch.isfinite(t).all()) for t in (gdw, gpw, gb))
+    del gs, gdw, gpw, gb
+
+    # (a) every image alone
+    for n in range(B):
+        one = ops.sepconv3x3_bwd([x[n:n + 1]], dw, pwp, b, g[n:n + 1], *flags, need=(True, False, False, False))[0][0]
+        assert torch.equal(one, gx[n:n + 1]), "grad_x of image %d" % n
+        del one
+
+    # (b) float64 on crops
+    wc, bc = (dw.cpu(), pw.cpu()), b.cpu()
+    worst = {"grad_x": 0.0}
+    for reg in conv_crops(key):
+        (cy0, cy1, cx0, cx1), pads = conv_x_region(key, reg)
+        tag, n = reg[0], reg[1]
+        _, rx, _, _ = conv_region_ref(key, _cut(x, n, cy0, cy1, cx0, cx1), pads, wc, bc, _cut(g, *reg[1:]), flags)
+        ok = conv_gx_valid(key, reg)
+        assert int(ok.sum()) >= (CROP - 2) ** 2, (tag, int(ok.sum()))
+        got = _cut(gx, n, cy0, cy1, cx0, cx1)[0][ok]
+        worst["grad_x"] = max(worst["grad_x"], _check(got, rx[0][ok], "%s %s grad_x" % (name, tag)))
+
+    # (c) the sums over the batch: grad_out zero outside the windows
+    wins = conv_windows(key)
+    g.zero_()
+    crops, moved = [], []
+    for k, reg in enumerate(wins):
+        n, oy0, oy1, ox0, ox1 = reg[1:]
+        g[n, oy0:oy1, ox0:ox1, :] = _dgrid(gen, (oy1 - oy0, ox1 - ox0, F_), 1 / 16)
+        (cy0, cy1, cx0, cx1), pads = conv_x_region(key, reg)
+        crops.append((_cut(x, n, cy0, cy1, cx0, cx1), pads, _cut(g, *reg[1:])))
+        for mod, at in conv_wrapped_regions(key, reg):
+            moved.append(("window %d (%s) x read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k, _cut(x, *at)))
+    assert 0 < sum(int(torch.count_nonzero(g[n])) for n in range(B)) <= len(wins) * WIN * WIN * F_
+    _, gdw, gpw, gb = ops.sepconv3x3_bwd([x], dw, pwp, b, g, *flags, need=(False, True, True, True))
+    rw, rb = conv_window_sums(key, crops, wc, bc, flags)
+    rdw, rpw = rw[:C * 9].reshape(C, 1, 3, 3), rw[C * 9:].reshape(F_, C)
+    if flags == (False, False):
+        exactness_precondition(key, crops, wc, bc, unit=2 ** 11)
+        for got, ref, what in ((gdw.reshape(C, 1, 3, 3), rdw, "grad_dw"), (gpw, rpw, "grad_pw"), (gb, rb, "grad_bias")):
+            assert torch.equal(got.double().cpu(), ref), (what, float((got.double().cpu() - ref).abs().max()))
+    else:
+        worst["grad_dw"] = _check(gdw.reshape(C, 1, 3, 3), rdw, name + " grad_dw")
+        worst["grad_pw"] = _check(gpw, rpw, name + " grad_pw")
+        worst["grad_bias"] = _check(gb, rb, name + " grad_bias")
+    controls = conv_controls(key, crops, moved, wc, bc, flags)
+    assert len(controls) >= len(wins) + 2, controls
+    for what, ratio in controls:
+        assert ratio >= 100.0, (what, ratio)
+    print("{} {}: controls move grad_dw | grad_pw by {:.0f} .. {:.0f} bounds".format(
+        name, flags, min(r for _, r in controls), max(r for _, r in controls)))
+
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("{} {}: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}".format(name, flags, peak / GIB, planned / GIB,
+                                                                                 secs, worst))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- cost volume and warp backward: per-pixel outputs only ---------------------------------------------------------
+F16_EPS = 2.0 ** -11
+SEARCH = 4           # the cost volume's search range: grad_prv / grad_nxt of a pixel depend on pixels within +-4
+REACH = 3            # |flow| <= 3 pixels: a warp sample's corners lie within 4 pixels
+
+
+def pixel_crops(B, H, W, C, margin):
+    """[(tag, n, y0, y1, x0, x1, (ey0, ey1, ex0, ex1))]: CROP x CROP pixels around the pixel that holds each boundary of
+    a dense (B,H,W,C) operand and on the last pixels of the last image, each with the region `margin` pixels wider
+    (clipped to the image) that the reference is computed on."""
+    regs = []
+    for b in crossed(B * H * W * C):
+        n, y, x = locate(b, H, W, C)
+        regs.append((">2^%d" % (b.bit_length() - 1), n) + _span(y, CROP, H) + _span(x, CROP, W))
+    regs.append(("last", B - 1, H - CROP, H, W - CROP, W))
+    return [r + ((max(r[2] - margin, 0), min(r[3] + margin, H), max(r[4] - margin, 0), min(r[5] + margin, W)),)
+            for r in regs]
+
+
+def cost_volume_bwd_ref(prv, nxt, out, g, r=SEARCH, slope=0.1):
+    """The formulas of csrc/backward.hip in float64 on a (1,h,w,C) region whose outside counts as zero: g' = g where the
+    saved output is > 0, else slope g; grad_prv = (1/C) sum_ij g'[.., ij] nxt[+(i-r, j-r)]; grad_nxt likewise from the
+    pixels whose window holds it."""
+    prv, nxt, out, g = [t.double() for t in (prv, nxt, out, g)]
+    _, h, w, C = prv.shape
+    d = 2 * r + 1
+    gq = torch.where(out > 0, g, slope * g)
+    pad = lambda t: F.pad(t, (0, 0, r, r, r, r))
+    nxt_p = pad(nxt)
+    gp, gn_p = torch.zeros_like(prv), torch.zeros_like(nxt_p)
+    for i in range(d):
+        for j in range(d):
+            gij = gq[..., i * d + j].unsqueeze(-1)
+            gp += gij * nxt_p[:, i:i + h, j:j + w]
+            gn_p[:, i:i + h, j:j + w] += gij * prv
+    return gp / C, gn_p[:, r:r + h, r:r + w] / C
+
+
+def warp_bwd_ref(img, flo, g, mode):
+    """Float64 autograd of oracle.torch_ref.warp_v2 / tf_warp on a region -> (grad_img, grad_flo)."""
+    a, f = img.double().clone().requires_grad_(), flo.double().clone().requires_grad_()
+    (torch_ref.warp_v2 if mode == "clamp" else torch_ref.tf_warp)(a, f).backward(g.double())
+    return a.grad, f.grad
+
+
+def _dflow(gen, B, H, W, reach=REACH):
+    """Multiples of 2^-6 within +-reach pixels; every 5th pixel an exact integer, every 7th zero."""
+    f = torch.randint(-reach * 64, reach * 64 + 1, (B, H, W, 2), generator=gen, device=DEV, dtype=torch.float32).div_(64)
+    flat = f.view(-1, 2)
+    flat[::5] = flat[::5].round()
+    flat[::7] = 0
+    return f
+
+
+def _inner(t, reg):
+    """The CROP x CROP part of a tensor cut on the wider region of a pixel_crops() entry."""
+    _, _, y0, y1, x0, x1, (ey0, _, ex0, _) = reg
+    return t[:, y0 - ey0:y1 - ey0, x0 - ex0:x1 - ex0]
+
+
+def cost_volume_planned_bytes(key):
+    """prv, nxt, the saved output and grad_out, one gradient at a time, and that gradient of one image."""
+    B, H, W, C = key
+    n_in, n_cv = B * H * W * C, B * H * W * (2 * SEARCH + 1) ** 2
+    return 4 * (2 * n_in + 2 * n_cv + n_in + n_in // B)
+
+
+def warp_planned_bytes(key):
+    """img, grad_out, grad_img; the flow and grad_flo; grad_flo of one image."""
+    B, H, W, C = key
+    return 4 * (3 * B * H * W * C + 2 * B * H * W * 2 + H * W * 2)
+
+
+def test_cost_volume_bwd(arena):
+    """cost_volume_bwd_kernel at prv / nxt of 2.156 G floats and a saved output / grad_out of 2.729 G (81 per pixel),
+    through ops.cost_volume_bwd.  The saved output is drawn at random, zeros included: the backward reads it for the
+    LeakyReLU mask only, and the forward cost volume at this size is not part of this suite.  grad_prv and grad_nxt are
+    asked for in two launches (one pointer NULL each), which keeps the planned memory under 48 GiB.  Oracles (a) and
+    (b); there is no sum over the batch.  Measured: peak 47.77 GiB, 0.7 - 2.9 s."""
+    B, H, W, C = CASES["backward"]
+    D = (2 * SEARCH + 1) ** 2
+    n_in, n_cv = B * H * W * C, B * H * W * D
+    planned = cost_volume_planned_bytes(CASES["backward"])
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(3)
+    a = arena
+    a["prv"], a["nxt"] = _dgrid(gen, (B, H, W, C), 1 / 16), _dgrid(gen, (B, H, W, C), 1 / 16)
+    a["out"], a["g"] = _dgrid(gen, (B, H, W, D), 1 / 16), _dgrid(gen, (B, H, W, D), 1 / 16)
+    prv, nxt, out, g = a["prv"], a["nxt"], a["out"], a["g"]
+    assert prv.numel() > 1 << 31 and out.numel() > 1 << 31
+    worst = {}
+    for k, what in enumerate(("grad_prv", "grad_nxt")):
+        need = (k == 0, k == 1)
+        both = ops.cost_volume_bwd(prv, nxt, out, g, SEARCH, 0.1, *need)
+        assert both[1 - k] is None
+        a["grad"] = big = both[k]
+        del both
+        for n in range(B):
+            one = ops.cost_volume_bwd(prv[n:n + 1], nxt[n:n + 1], out[n:n + 1], g[n:n + 1], SEARCH, 0.1, *need)[k]
+            assert torch.equal(one, big[n:n + 1]), "%s of image %d" % (what, n)
+            del one
+        worst[what] = 0.0
+        for reg in pixel_crops(B, H, W, C, SEARCH) + [r for r in pixel_crops(B, H, W, D, SEARCH) if r[0] != "last"]:
+            n, e = reg[1], reg[6]
+            ref = cost_volume_bwd_ref(*[_cut(t, n, *e) for t in (prv, nxt, out, g)])[k]
+            worst[what] = max(worst[what], _check(_inner(_cut(big, n, *e), reg), _inner(ref, reg),
+                                                  "cost volume %s %s" % (reg[0], what)))
+        del big
+        a.pop("grad")
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("cost_volume_bwd: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}".format(peak / GIB, planned / GIB,
+                                                                                             secs, worst))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+@pytest.mark.parametrize("mode", ["clamp", "tfwarp"])
+def test_warp_bwd(mode, arena):
+    """warp_bwd_kernel and fill_zero_kernel at img and grad_out of 2.156 G floats, through ops.warp_bwd.  grad_flo is a
+    gather: oracles (a) and (b).  grad_img is a scatter of float atomics whose bits may vary with their order, so no
+    bit equality is asked of it: oracle (b) only.  In clamp mode the fp16 path follows, whose grad_img is accumulated
+    in the fp32 workspace and cast by f32_to_f16_kernel (bound of tests/test_gpu_autograd.py's fp16 case).
+    Measured: peak 24.70 GiB, 0.1 - 0.9 s."""
+    B, H, W, C = CASES["backward"]
+    n_in = B * H * W * C
+    planned = warp_planned_bytes(CASES["backward"])
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(4)
+    a = arena
+    a["img"], a["flo"], a["g"] = _dgrid(gen, (B, H, W, C), 1 / 16), _dflow(gen, B, H, W), _dgrid(gen, (B, H, W, C), 1 / 16)
+    img, flo, g = a["img"], a["flo"], a["g"]
+    assert img.numel() > 1 << 31
+    a["gi"], a["gf"] = gi, gf = ops.warp_bwd(img, flo, g, mode)
+    for n in range(B):
+        one = ops.warp_bwd(img[n:n + 1], flo[n:n + 1], g[n:n + 1], mode, need_img=False)[1]
+        assert torch.equal(one, gf[n:n + 1]), "grad_flo of image %d" % n
+        del one
+    worst = {"grad_img": 0.0, "grad_flo": 0.0}
+    crops = pixel_crops(B, H, W, C, REACH + 2)
+    refs = []
+    for reg in crops:
+        n, e = reg[1], reg[6]
+        ri, rf = warp_bwd_ref(_cut(img, n, *e), _cut(flo, n, *e), _cut(g, n, *e), mode)
+        refs.append(_inner(ri, reg))
+        worst["grad_img"] = max(worst["grad_img"], _check(_inner(_cut(gi, n, *e), reg), refs[-1], "warp %s grad_img" % reg[0]))
+        worst["grad_flo"] = max(worst["grad_flo"], _check(_inner(_cut(gf, n, *e), reg), _inner(rf, reg), "warp %s grad_flo" % reg[0]))
+    if mode == "clamp":          # fp16 storage: values on the 1/16 grid are exact in fp16
+        del gi, gf
+        a.pop("gi"), a.pop("gf")
+        a["img"], a["g"] = img, g = img.half(), g.half()
+        gi16, gf16 = ops.warp_bwd(img, flo, g, mode)
+        assert gi16.dtype == torch.float16
+        for reg, ref in zip(crops, refs):
+            got = _inner(_cut(gi16, reg[1], *reg[6]), reg).double()
+            bound = F16_EPS * ref.abs() + 1e-6 * float(ref.abs().max()) + 2.0 ** -24
+            assert bool(((got - ref).abs() <= bound).all()), ("fp16 grad_img", reg[0], float((got - ref).abs().max()))
+        del gi16, gf16
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("warp_bwd {}: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}".format(mode, peak / GIB, planned / GIB,
+                                                                                         secs, worst))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- the interpolator's pieces ---------------------------------------------------------------------------------------
+def pixel_windows(B, H, W, C):
+    """[(tag, n, y0, y1, x0, x1)]: WIN x WIN pixels at the start of image 0, in the rows just behind the pixel that holds
+    each boundary of a dense (B,H,W,C) operand, and in the bottom-right corner of the last image."""
+    wins = [("first", 0, 0, WIN, 0, WIN)]
+    for b in crossed(B * H * W * C):
+        n, y, x = locate(b, H, W, C)
+        assert y + 1 + WIN <= H, (b, y)
+        wins.append((">2^%d" % (b.bit_length() - 1), n, y + 1, y + 1 + WIN) + _span(x, WIN, W))
+    wins.append(("last", B - 1, H - WIN, H, W - WIN, W))
+    return wins
+
+
+def wrapped_pixel_regions(B, H, W, C, reg):
+    """conv_wrapped_regions for an operand that is read pixel by pixel: the window itself at its first element's byte
+    offset mod 2^31 and mod 2^32, where that differs."""
+    _, n, y0, y1, x0, x1 = reg
+    first = ((n * H + y0) * W + x0) * C
+    out = []
+    for mod in (1 << 31, 1 << 32):
+        e = (first * 4 % mod) // 4
+        if e != first:
+            m, y, x = locate(e, H, W, C)
+            y, x = min(y, H - (y1 - y0)), min(x, W - (x1 - x0))
+            out.append((mod, (m, y, y + y1 - y0, x, x + x1 - x0)))
+    return out
+
+
+def head_window_sums(crops, w2):
+    """grad_w2 (3,64) and grad_b2 (3) in float64 of a grad_out that is zero outside the windows: crops = [(z, g)]."""
+    gw = sum(g.double().reshape(-1, 3).t() @ z.double().reshape(-1, 64) for z, g in crops)
+    return gw, sum(g.double().reshape(-1, 3).sum(0) for _, g in crops)
+
+
+def head_controls(crops, moved):
+    ref = head_window_sums(crops, None)[0]
+    out = [("without window %d" % k, float((head_window_sums(crops[:k] + crops[k + 1:], None)[0] - ref).abs().max()) / _tol(ref))
+           for k in range(len(crops))]
+    for what, k, z in moved:
+        alt = head_window_sums(crops[:k] + [(z, crops[k][1])] + crops[k + 1:], None)[0]
+        out.append((what, float((alt - ref).abs().max()) / _tol(ref)))
+    return out
+
+
+def image_head_planned_bytes(key, ws_floats):
+    """z and grad_z, out and grad_out, the workspace; out and grad_z of one image."""
+    B, H, W = key
+    M = B * H * W
+    return 4 * (2 * M * 64 + 2 * M * 3 + ws_floats + H * W * 67)
+
+
+def upsample_planned_bytes(key):
+    """in and grad_in, out and grad_out; out and grad_in of one image."""
+    B, h, w, C = key
+    n_in = B * h * w * C
+    return 4 * (2 * n_in + 8 * n_in + (4 * n_in + n_in) // B)
+
+
+def pyramid_planned_bytes(key):
+    """x, the output, the output of the one-image repeats."""
+    B, H, W, C, levels = key
+    return 4 * (B * H * W * C + 2 * B * H * W * C // (1 << 2 * levels))
+
+
+def test_image_head(arena):
+    """Image head forward and backward at M = 33.7 M pixels (> 2^25) of 64 features, z and grad_z of 2.156 G floats,
+    through autograd.  out and grad_z: oracles (a) and (b) (the op is pixel-wise: a crop needs no halo).  grad_w2 and
+    grad_b2: oracle (c); the layer is linear, so they are exact on the grids (precondition asserted).
+    Measured: peak 20.29 GiB, 0.03 - 1.3 s."""
+    B, H, W = CASES["image_head"]
+    M = B * H * W
+    L = ops._hip.lib()
+    planned = image_head_planned_bytes(CASES["image_head"], L.qpwc_image_head_bwd_workspace_floats(M))
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(5)
+    a = arena
+    a["z"] = _dgrid(gen, (B, H, W, 64), 1 / 16).requires_grad_()
+    w2 = _dgrid(gen, (3, 64, 1, 1), 1 / 64, 1 / 8).requires_grad_()
+    b2 = _dgrid(gen, (3,), 1 / 8).requires_grad_()
+    a["g"] = _dgrid(gen, (B, H, W, 3), 1 / 16)
+    z, g = a["z"], a["g"]
+    assert z.numel() > 1 << 31 and M > 1 << 25
+    a["out"] = ops.image_head(z, w2, b2)
+    a["out"].backward(g)
+    out, gz = a["out"].detach(), z.grad
+    wd, bd = w2.detach(), b2.detach()
+    for n in range(B):
+        z1 = z.detach()[n:n + 1].requires_grad_()
+        o1 = ops.image_head(z1, wd, bd)
+        o1.backward(g[n:n + 1])
+        assert torch.equal(o1.detach(), out[n:n + 1]) and torch.equal(z1.grad, gz[n:n + 1]), "image %d" % n
+        del z1, o1
+    wc, bc = wd.double().cpu().reshape(3, 64), bd.double().cpu()
+    worst = {"out": 0.0, "grad_z": 0.0}
+    for reg in pixel_crops(B, H, W, 64, 0):
+        zc, gc = _cut(z, *reg[1:6]).double(), _cut(g, *reg[1:6]).double()
+        worst["out"] = max(worst["out"], _check(_cut(out, *reg[1:6]), zc @ wc.t() + bc, "image head %s out" % reg[0]))
+        worst["grad_z"] = max(worst["grad_z"], _check(_cut(gz, *reg[1:6]), gc @ wc, "image head %s grad_z" % reg[0]))
+    wins = pixel_windows(B, H, W, 64)
+    g.zero_()
+    crops, moved = [], []
+    for k, reg in enumerate(wins):
+        n, y0, y1, x0, x1 = reg[1:]
+        g[n, y0:y1, x0:x1, :] = _dgrid(gen, (y1 - y0, x1 - x0, 3), 1 / 16)
+        crops.append((_cut(z, *reg[1:]), _cut(g, *reg[1:])))
+        for mod, at in wrapped_pixel_regions(B, H, W, 64, reg):
+            moved.append(("window %d (%s) z read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k, _cut(z, *at)))
+    _, gw, gb = ops.image_head_bwd(z.detach(), wd, g, need=(False, True, True))
+    rw, rb = head_window_sums(crops, None)
+    assert float(head_window_sums([(zc.abs(), gc.abs()) for zc, gc in crops], None)[0].max()) * 2 ** 8 < 2 ** 24
+    assert torch.equal(gw.double().cpu(), rw), float((gw.double().cpu() - rw).abs().max())
+    assert torch.equal(gb.double().cpu(), rb), float((gb.double().cpu() - rb).abs().max())
+    controls = head_controls(crops, moved)
+    assert len(controls) >= len(wins) + 2 and min(r for _, r in controls) >= 100.0, controls
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("image_head: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
+        peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+def upsample_regions(reg, h, w):
+    """An output region (.., oy0, oy1, ox0, ox1) of the x2 upsampling -> (the input region one pixel wider than what it
+    reads, clipped to the image; the region's place (y0, y1, x0, x1) in the upsampled input region)."""
+    _, _, oy0, oy1, ox0, ox1 = reg[:6]
+    iy0, iy1 = max((oy0 - 1) // 2 - 1, 0), min(oy1 // 2 + 2, h)
+    ix0, ix1 = max((ox0 - 1) // 2 - 1, 0), min(ox1 // 2 + 2, w)
+    return (iy0, iy1, ix0, ix1), (oy0 - 2 * iy0, oy1 - 2 * iy0, ox0 - 2 * ix0, ox1 - 2 * ix0)
+
+
+def upsample_valid(reg, h, w):
+    """Mask over the input region: the four output rows / columns that an input pixel's gradient reads (2i - 1 .. 2i + 2,
+    clamped to the image) all lie in the output region."""
+    (iy0, iy1, ix0, ix1), _ = upsample_regions(reg, h, w)
+    _, _, oy0, oy1, ox0, ox1 = reg[:6]
+    ok = lambda i, o0, o1, n: all(o0 <= min(max(t, 0), 2 * n - 1) < o1 for t in (2 * i - 1, 2 * i, 2 * i + 1, 2 * i + 2))
+    return torch.tensor([ok(i, oy0, oy1, h) for i in range(iy0, iy1)])[:, None] & \
+        torch.tensor([ok(j, ox0, ox1, w) for j in range(ix0, ix1)])[None, :]
+
+
+def upsample_region_ref(xc, place, gc, scale):
+    """Float64 autograd of F.interpolate(x2, bilinear) on an input region -> (the output region, grad of the input)."""
+    leaf = xc.double().clone().requires_grad_()
+    up = F.interpolate(leaf.permute(0, 3, 1, 2), scale_factor=2, mode="bilinear", align_corners=False).permute(0, 2, 3, 1) * scale
+    out = up[:, place[0]:place[1], place[2]:place[3]]
+    out.backward(gc.double())
+    return out.detach(), leaf.grad
+
+
+def test_upsample2x_image(arena):
+    """upsample2x_image forward and backward at C = 3 with 2.150 G output floats (and 0.537 G input floats, past 2^29),
+    through autograd, scale 2.  Per-pixel outputs only: oracles (a) and (b).  Measured: peak 24.03 GiB, 0.03 - 2.9 s."""
+    B, h, w, C = CASES["upsample2x_image"]
+    n_in = B * h * w * C
+    planned = upsample_planned_bytes(CASES["upsample2x_image"])
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(6)
+    a = arena
+    a["x"] = _dgrid(gen, (B, h, w, C), 1 / 16).requires_grad_()
+    a["g"] = _dgrid(gen, (B, 2 * h, 2 * w, C), 1 / 16)
+    x, g = a["x"], a["g"]
+    assert g.numel() > 1 << 31 and x.numel() > 1 << 29
+    a["out"] = ops.upsample2x_image(x, 2.0)
+    a["out"].backward(g)
+    out, gx = a["out"].detach(), x.grad
+    for n in range(B):
+        x1 = x.detach()[n:n + 1].requires_grad_()
+        o1 = ops.upsample2x_image(x1, 2.0)
+        o1.backward(g[n:n + 1])
+        assert torch.equal(o1.detach(), out[n:n + 1]) and torch.equal(x1.grad, gx[n:n + 1]), "image %d" % n
+        del x1, o1
+    worst = {"out": 0.0, "grad_in": 0.0}
+    regs = pixel_crops(B, 2 * h, 2 * w, C, 0)
+    for b in crossed(n_in):                      # and around the input pixel that holds the input's own boundary
+        n, y, x_ = locate(b, h, w, C)
+        regs.append(("in>2^%d" % (b.bit_length() - 1), n) + _span(2 * y, CROP, 2 * h) + _span(2 * x_, CROP, 2 * w))
+    for reg in regs:
+        n = reg[1]
+        (iy0, iy1, ix0, ix1), place = upsample_regions(reg, h, w)
+        ro, rx = upsample_region_ref(_cut(x, n, iy0, iy1, ix0, ix1), place, _cut(g, *reg[1:6]), 2.0)
+        worst["out"] = max(worst["out"], _check(_cut(out, *reg[1:6]), ro, "upsample %s out" % reg[0]))
+        ok = upsample_valid(reg, h, w)
+        assert int(ok.sum()) >= (CROP // 2 - 2) ** 2, (reg[0], int(ok.sum()))
+        worst["grad_in"] = max(worst["grad_in"], _check(_cut(gx, n, iy0, iy1, ix0, ix1)[0][ok], rx[0][ok],
+                                                        "upsample %s grad_in" % reg[0]))
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("upsample2x_image: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}".format(peak / GIB, planned / GIB,
+                                                                                             secs, worst))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+def pyramid_ref(x, levels):
+    """`levels` 2 x 2 means in float64, each (((a + b) + c) + d) / 4 in row-major order like a chain of AvgPool2D."""
+    x = x.double()
+    for _ in range(levels):
+        x = (((x[:, 0::2, 0::2] + x[:, 0::2, 1::2]) + x[:, 1::2, 0::2]) + x[:, 1::2, 1::2]) * 0.25
+    return x
+
+
+def test_avgpool_pyramid(arena):
+    """avgpool_pyramid at levels = 5 on 2.154 G input floats (C = 3).  Oracle (a) per image, and (b) on the 4 x 4 output
+    pixels around the one whose 32 x 32 inputs hold each boundary, and on the last ones.  Measured: peak 8.04 GiB, 0.01 s."""
+    B, H, W, C, levels = CASES["avgpool_pyramid"]
+    S = 1 << levels
+    n_in = B * H * W * C
+    planned = pyramid_planned_bytes(CASES["avgpool_pyramid"])
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(7)
+    arena["x"] = x = _dgrid(gen, (B, H, W, C), 1 / 16)
+    assert x.numel() > 1 << 31
+    out = ops.avgpool_pyramid(x, levels)
+    assert tuple(out.shape) == (B, H // S, W // S, C)
+    for n in range(B):
+        assert torch.equal(ops.avgpool_pyramid(x[n:n + 1], levels), out[n:n + 1]), "image %d" % n
+    worst = 0.0
+    regs = [(">2^%d" % (b.bit_length() - 1),) + locate(b, H, W, C) for b in crossed(n_in)]
+    regs = [(t, n) + _span(y // S, 4, H // S) + _span(x_ // S, 4, W // S) for t, n, y, x_ in regs]
+    regs.append(("last", B - 1, H // S - 4, H // S, W // S - 4, W // S))
+    for tag, n, y0, y1, x0, x1 in regs:
+        ref = pyramid_ref(_cut(x, n, y0 * S, y1 * S, x0 * S, x1 * S), levels)
+        worst = max(worst, _check(_cut(out, n, y0, y1, x0, x1), ref, "pyramid %s" % tag))
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("avgpool_pyramid: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {:.3e}".format(peak / GIB, planned / GIB,
+                                                                                              secs, worst))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- losses and EPE: sums over the batch, planted windows ------------------------------------------------------------
+LOSS_DELTA = 0.1                 # FlowMseLossV2's Huber delta, the reference's
+# a loss value or an EPE is a sum of fp32 terms that are exactly zero outside the windows: a thread adds a few window
+# terms, then 6 wave steps, 2 block steps, and the fold of at most 2048 partials in 256 lanes + 8 steps; with the few
+# roundings of a term itself fewer than 64 roundings of 2^-24 lie on any path, 3.8e-6 relative.  Asserted: 1e-5.
+LOSS_REL = 1e-5
+
+
+def loss_planned_bytes(key, level, with_gt_out):
+    """gt, and per prediction level: the prediction, dpred saved by the forward, grad_pred (and gt_out where the
+    prediction is made from it)."""
+    B, H, W, C = key
+    return 4 * (B * H * W * C + (4 if with_gt_out else 3) * B * level[0] * level[1] * C)
+
+
+def loss_window_ref(kind, crops, n_pix, hw, scale=1.0):
+    """Float64 value and gradients of a loss whose prediction equals the level's ground truth outside the windows:
+    crops = [(gl, p)], gl the level's resampled, flow-scaled ground truth on a window, p the prediction there; n_pix the
+    pixels of the whole level.  kind "v2": FlowMseLossV2 (Keras Huber of s * pred - s * gt, s = 2 / (w + h), mean over
+    elements); "norm": FlowMseLoss and the EPE (mean over pixels of the 2-norm, gradient 0 at a zero residual).
+    -> (scale * loss, [d / d p])."""
+    leaves = [p.double().clone().requires_grad_() for _, p in crops]
+    total = torch.zeros((), dtype=torch.float64)
+    for (gl, _), p in zip(crops, leaves):
+        if kind == "v2":
+            s = 2.0 / (hw[0] + hw[1])
+            e = s * p - s * gl.double()
+            a = e.abs()
+            total = total + torch.where(a <= LOSS_DELTA, 0.5 * e * e, LOSS_DELTA * a - 0.5 * LOSS_DELTA ** 2).sum() / (2 * n_pix)
+        else:
+            sq = (gl.double() - p).pow(2).sum(-1)
+            total = total + (torch.where(sq > 0, sq, torch.ones_like(sq)).sqrt() * (sq > 0)).sum() / n_pix
+    total = total * scale
+    total.backward()
+    return total.detach(), [t.grad for t in leaves]
+
+
+def loss_controls(kind, crops, moved, n_pix, hw):
+    """[(what, |change of the loss| / its bound)]: every window left out in turn; every moved = (what, window index,
+    the level's ground truth as a wrapped offset finds it) in its window's place."""
+    ref = float(loss_window_ref(kind, crops, n_pix, hw)[0])
+    out = []
+    for k in range(len(crops)):
+        alt = float(loss_window_ref(kind, crops[:k] + crops[k + 1:], n_pix, hw)[0])
+        out.append(("without window %d" % k, abs(alt - ref) / (LOSS_REL * abs(ref))))
+    for what, k, gl in moved:
+        alt = float(loss_window_ref(kind, crops[:k] + [(gl, crops[k][1])] + crops[k + 1:], n_pix, hw)[0])
+        out.append((what, abs(alt - ref) / (LOSS_REL * abs(ref))))
+    return out
+
+
+def area_level_ref(gt_crop, sh, sw, fscale):
+    """FlowMseLossV2's level ground truth of a crop in float64: the mean over sh x sw blocks times the flow scale."""
+    _, hh, ww, c = gt_crop.shape
+    return gt_crop.double().reshape(1, hh // sh, sh, ww // sw, sw, c).mean((2, 4)) * fscale
+
+
+def loss_tile_windows(key):
+    """Windows of the half-resolution prediction of the tile case: pixel_windows of the prediction itself, and behind
+    the prediction pixel under each boundary pixel of the ground truth; one entry per distinct place."""
+    B, H, W, C = key
+    h, w = H // 2, W // 2
+    wins = pixel_windows(B, h, w, C)
+    seen = {x[1:] for x in wins}
+    for b in crossed(B * H * W * C):
+        n, y, x = locate(b, H, W, C)
+        assert y // 2 + 2 + WIN <= h
+        reg = (n, y // 2 + 2, y // 2 + 2 + WIN) + _span(x // 2, WIN, w)
+        if reg not in seen:
+            seen.add(reg)
+            wins.insert(-1, ("gt>2^%d" % (b.bit_length() - 1),) + reg)
+    return wins
+
+
+def _rel_check(got, ref, what):
+    got = got.detach().double().cpu()
+    scale = float(ref.abs().max())
+    d = float((got - ref).abs().max())
+    print("{}: max|d| = {:.3e} of {:.3e}, bound {:.1e} relative".format(what, d, scale, LOSS_REL))
+    assert scale > 0 and bool(torch.isfinite(got).all()) and d <= LOSS_REL * scale, (what, d, scale)
+    return d / scale
+
+
+def _count_above(t, thr, rows=1024):
+    """Elements of a (B,H,W,C) tensor with |value| > thr, counted a block of rows at a time (small temporaries)."""
+    return sum(int(torch.count_nonzero(t[n, y:y + rows].abs() > thr)) for n in range(t.shape[0])
+               for y in range(0, t.shape[1], rows))
+
+
+def _loss_run(kind_id, gt, pred, scale):
+    """ops.loss through autograd -> (loss value on the device, grad of pred)."""
+    p = pred.detach().requires_grad_()
+    losses = ops.loss(kind_id, gt, [p], p0=LOSS_DELTA)
+    (losses * scale).sum().backward()
+    return losses.detach()[0], p.grad
+
+
+def test_loss_tile_path(arena):
+    """FlowMseLossV2 on loss_area_tile_kernel and loss_bwd_kernel's float4 path at a ground truth of 1.075 G pixels
+    (2.150 G floats) and one half-resolution level.  The prediction is the kernel's own gt_out, held on crops to the
+    float64 area mean bit for bit (oracle (b)), plus planted windows; the loss value and grad_pred against float64
+    from the windows' crops (oracle (c), LOSS_REL).  Outside the windows the kernel's Huber error s * pred - s * gt is the
+    rounding of its own fused multiply-add, not zero: grad_pred there must stay below LOSS_REL of the windows' largest
+    gradient, which is asserted over the whole tensor.  Measured: peak 14.01 GiB (planned 16.02), 0.4 s."""
+    key = CASES["loss"]
+    B, H, W, C = key
+    h, w = H // 2, W // 2
+    hip = ops._hip
+    planned = loss_planned_bytes(key, (h, w), True)
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(8)
+    a = arena
+    a["gt"] = gt = _dgrid(gen, (B, H, W, C), 1 / 16)
+    assert B * H * W > 1 << 30 and gt.numel() > 1 << 31 and gt.data_ptr() % 16 == 0
+    I = ops.ctypes.c_int
+    assert hip.lib().qpwc_loss_fwd_kernel(hip.LOSS_FLOW_MSE_V2, gt.data_ptr(), B, H, W, C, (I * 1)(h), (I * 1)(w),
+                                          1).decode() == "loss_area_tile_kernel"
+    a["gl"] = gl = ops.area_ground_truth(gt, [(h, w)])[0]
+    regs = [r[:6] for r in pixel_crops(B, h, w, C, 0)]
+    regs += [("gt" + t, n, y0 // 2, y0 // 2 + CROP // 2, x0 // 2, x0 // 2 + CROP // 2)     # the level pixels under a boundary
+             for t, n, y0, _, x0, _, _ in pixel_crops(B, H, W, C, 0) if t != "last"]       # pixel of the ground truth
+    for tag, n, y0, y1, x0, x1 in regs:
+        ref = area_level_ref(_cut(gt, n, 2 * y0, 2 * y1, 2 * x0, 2 * x1), 2, 2, h / H)
+        assert torch.equal(_cut(gl, n, y0, y1, x0, x1).double(), ref), "gt_out " + tag
+    a["pred"] = pred = gl.clone()
+    wins = loss_tile_windows(key)
+    crops, moved = [], []
+    for k, reg in enumerate(wins):
+        n, y0, y1, x0, x1 = reg[1:]
+        pred[n, y0:y1, x0:x1, :] += _dgrid(gen, (y1 - y0, x1 - x0, C), 1 / 16)
+        crops.append((area_level_ref(_cut(gt, n, 2 * y0, 2 * y1, 2 * x0, 2 * x1), 2, 2, h / H), _cut(pred, *reg[1:])))
+        for mod, at in wrapped_pixel_regions(B, H, W, C, (reg[0], n, 2 * y0, 2 * y1, 2 * x0, 2 * x1)):
+            moved.append(("window %d (%s) gt read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k,
+                          area_level_ref(_cut(gt, *at), 2, 2, h / H)))
+    del gl
+    a.pop("gl")
+    value, grad = _loss_run(hip.LOSS_FLOW_MSE_V2, gt, pred, 7.0)
+    a["grad"] = grad
+    rv, rg = loss_window_ref("v2", crops, B * h * w, (h, w), 7.0)
+    worst = {"loss": _rel_check(value * 7.0, rv, "tile loss")}
+    worst["grad_pred"] = max(_rel_check(_cut(grad, *reg[1:]), g, "tile grad_pred %s" % reg[0]) for reg, g in zip(wins, rg))
+    big = max(float(g.abs().max()) for g in rg)
+    assert 0 < _count_above(grad, LOSS_REL * big) <= len(wins) * WIN * WIN * C       # nothing of weight outside the windows
+    assert grad.numel() % 4 == 0                                       # loss_bwd_kernel's float4 path
+    controls = loss_controls("v2", crops, moved, B * h * w, (h, w))
+    assert len(controls) >= len(wins) + 2 and min(r for _, r in controls) >= 100.0, controls
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("loss tile: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
+        peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+def test_loss_pixel_paths_and_epe(arena):
+    """On an odd-sized ground truth of 1.075 G pixels with one full-resolution level (the resampling is the identity,
+    so the prediction is a copy of the ground truth plus planted windows): FlowMseLossV2 on loss_pixel_kernel (area
+    1 x 1), FlowMseLoss on its bilinear branch, loss_bwd_kernel's scalar path (the element count is no multiple of 4),
+    epe_partial_kernel and epe_multi_partial_kernel (float4 loop with the odd last pixel).  Values and grad_pred
+    against float64 from the windows' crops (oracle (c), LOSS_REL), grad_pred below LOSS_REL of the windows' largest
+    gradient everywhere else (asserted over the whole tensor); prediction and
+    grad_pred cross all three boundaries like the ground truth.  Measured: peak 32.05 GiB (planned 32.05), 0.1 s."""
+    key = CASES["epe"]
+    B, H, W, C = key
+    hip = ops._hip
+    planned = loss_planned_bytes(key, (H, W), False)
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(9)
+    a = arena
+    a["gt"] = gt = _dgrid(gen, (B, H, W, C), 1 / 16)
+    assert B * H * W > 1 << 30 and gt.numel() > 1 << 31 and gt.numel() % 4 and (B * H * W) % 2
+    I = ops.ctypes.c_int
+    for kind in (hip.LOSS_FLOW_MSE_V2, hip.LOSS_FLOW_MSE):
+        assert hip.lib().qpwc_loss_fwd_kernel(kind, gt.data_ptr(), B, H, W, C, (I * 1)(H), (I * 1)(W),
+                                              1).decode() == "loss_pixel_kernel"
+    a["pred"] = pred = gt.clone()
+    wins = pixel_windows(B, H, W, C)
+    crops, moved = [], []
+    for k, reg in enumerate(wins):
+        n, y0, y1, x0, x1 = reg[1:]
+        pred[n, y0:y1, x0:x1, :] += _dgrid(gen, (y1 - y0, x1 - x0, C), 1 / 16)
+        crops.append((_cut(gt, *reg[1:]).double(), _cut(pred, *reg[1:])))
+        for mod, at in wrapped_pixel_regions(B, H, W, C, reg):
+            moved.append(("window %d (%s) gt read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k,
+                          _cut(gt, *at).double()))
+    worst = {}
+    for name, kind_id, kind in (("v2 pixel", hip.LOSS_FLOW_MSE_V2, "v2"), ("bilinear", hip.LOSS_FLOW_MSE, "norm")):
+        value, grad = _loss_run(kind_id, gt, pred, 7.0)
+        rv, rg = loss_window_ref(kind, crops, B * H * W, (H, W), 7.0)
+        worst[name] = _rel_check(value * 7.0, rv, name + " loss")
+        worst[name + " grad"] = max(_rel_check(_cut(grad, *reg[1:]), g, "%s grad_pred %s" % (name, reg[0]))
+                                    for reg, g in zip(wins, rg))
+        big = max(float(g.abs().max()) for g in rg)
+        assert 0 < _count_above(grad, LOSS_REL * big) <= len(wins) * WIN * WIN * C
+        del grad
+        controls = loss_controls(kind, crops, moved, B * H * W, (H, W))
+        assert len(controls) >= len(wins) + 2 and min(r for _, r in controls) >= 100.0, controls
+    rv = loss_window_ref("norm", crops, B * H * W, (H, W))[0]
+    worst["epe"] = _rel_check(ops.epe(gt, pred), rv, "epe")
+    worst["epe_multi"] = _rel_check(ops.epe_multi([gt], [pred])[0], rv, "epe_multi")
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("loss pixel / epe: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
+        peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)

@@ -1,0 +1,883 @@
+"""CPU companion of tests/test_gpu_large_offsets.py: every shape of its CASES crosses the boundaries it claims (2^29,
+2^30 and 2^31 fp32 elements: byte offsets 2^31 and 2^32, the `int` index limit), with each boundary in the image the
+GPU test relies on, and is still admitted by the validators; the workspace regions cross what DESIGN.md 4.17 says
+they cross; the planned device memory stays under 48 GiB; the float64 restatement on crops and windows agrees with
+the fp32 torch composition within the bounds the GPU test uses; the negative controls move the window sums by at
+least 100 bounds; and the ctypes table carries every size that can pass 2^31 as a 64-bit integer.
+
+The plans are restated from the constants read out of the kernel sources (tests/test_conv_grad_cpu.py::_plan) and
+compared with the library's own host functions, so a changed plan constant that pulls a region back under a boundary
+fails here."""
+import ctypes
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import test_gpu_large_offsets as lo  # noqa: E402
+from test_capi_prototypes_cpu import parse_header  # noqa: E402
+from test_conv_grad_cpu import CB, CSRC, _plan  # noqa: E402
+from test_gpu_autograd import _flow, _oracle_warp  # noqa: E402
+from test_gpu_conv_grad import _grid, composite  # noqa: E402
+from test_gpu_flow_head_grad import upsample_composite  # noqa: E402
+from test_gpu_interp_grad import head_composite, pyramid_composite  # noqa: E402
+from test_training_scale_cpu import _backward_cap  # noqa: E402
+from test_gpu_upconv_grad import composite as up_composite  # noqa: E402
+from test_gpu_sepconv_grad import composite as sep_composite  # noqa: E402
+from test_sepconv_grad_cpu import KC, SCB, _workspace as _sep_workspace  # noqa: E402
+from test_upconv_grad_cpu import UB, _plan as _up_plan  # noqa: E402
+
+P29, P30, P31 = lo.BOUNDARIES
+CONV = ("conv3x3_same_s1", "conv3x3_same_s2")
+UP = "upconv4x4s2"
+SEP = "sepconv3x3"
+
+
+def test_boundaries_are_the_byte_and_index_limits():
+    assert (P29 * 4, P30 * 4, P31) == (1 << 31, 1 << 32, 1 << 31)
+    assert lo.crossed(P31 + 2) == [P29, P30, P31] and lo.crossed(P31 + 1) == [P29, P30] and lo.crossed(P29) == []
+
+
+# ---- Conv2D 3x3 'same' -----------------------------------------------------------------------------------------------
+def conv_plan(key):
+    """cb_plan() + cg_split() restated: the workspace regions gz | part_w | part_b as (first, end) in floats."""
+    B, H, W, ci, co, s = key
+    n_pb, nsplit, total = _plan(*key)
+    M, cp = B * -(-H // s) * -(-W // s), -(-ci // 4) * 4
+    off_pw = M * co
+    off_pb = off_pw + nsplit * 9 * co * cp
+    assert total == off_pb + -(-nsplit * co // 4) * 4
+    return {"gz": (0, off_pw), "part_w": (off_pw, off_pb), "part_b": (off_pb, total)}, n_pb, nsplit
+
+
+def test_conv_cases_cross_what_they_claim():
+    claims = {"conv3x3_same_s1": {"x": [P29, P30, P31], "out": [P29, P30, P31]},
+              "conv3x3_same_s2": {"x": [P29, P30, P31], "out": [P29, P30]}}
+    images = {"conv3x3_same_s1": {"x": [0, 1, 2], "out": [0, 1, 2]}, "conv3x3_same_s2": {"x": [0, 1, 2], "out": [1, 2]}}
+    for name in CONV:
+        key = lo.CASES[name]
+        B, H, W, ci, co, s = key
+        g = lo.conv_geo(key)
+        n = lo.conv_operands(key)
+        assert B == 3 and H % 2 and W % 2 and H != W                                    # ragged
+        assert n["x"] == n["grad_x"] == B * H * W * ci > P31
+        assert n["out"] == n["grad_out"] == n["gz"] == B * g["Ho"] * g["Wo"] * co
+        assert lo.crossed(n["x"]) == claims[name]["x"] and lo.crossed(n["out"]) == claims[name]["out"]
+        # each boundary in another image, none in a first or last row or column: both terms of the offset count
+        at = [lo.locate(b, H, W, ci) for b in lo.crossed(n["x"])]
+        assert [a[0] for a in at] == images[name]["x"]
+        at_o = [lo.locate(b, g["Ho"], g["Wo"], co) for b in lo.crossed(n["out"])]
+        assert [a[0] for a in at_o] == images[name]["out"]
+        for rows, cols, where in ((H, W, at), (g["Ho"], g["Wo"], at_o)):
+            assert all(0 < y < rows - 2 - lo.WIN and 0 < x < cols - 1 for _, y, x in where), where
+        # the last pixel block is partial, so the crop on the last pixels holds it
+        assert (B * g["Ho"] * g["Wo"]) % CB["kCbPx"]
+
+
+def test_conv_workspace_regions(hip_lib):
+    """Stage Z's gz in the workspace crosses what grad_out crosses; the partials lie behind all of it, so their
+    offsets (off_pw, off_pb of cg_split) are beyond 2^31 elements at stride 1 and beyond 2^30 at stride 2."""
+    want = {"conv3x3_same_s1": [P29, P30, P31], "conv3x3_same_s2": [P29, P30]}
+    for name in CONV:
+        key = lo.CASES[name]
+        regions, n_pb, nsplit = conv_plan(key)
+        assert hip_lib.qpwc_conv3x3_same_bwd_workspace_floats(*key) == regions["part_b"][1]
+        assert lo.crossed(regions["gz"][1]) == want[name]
+        assert regions["part_w"][0] > want[name][-1] and regions["part_b"][0] > regions["part_w"][0]
+        assert n_pb > (1 << 19) and nsplit == CB["kCbWBlocks"] // 9          # stage W walks > 2^12 blocks a workgroup
+        # one image alone stays below every boundary but the first: what oracle (a) compares with
+        one = (1,) + key[1:]
+        assert lo.crossed(lo.conv_operands(one)["x"]) == [P29]
+        assert hip_lib.qpwc_conv3x3_same_bwd_workspace_floats(*one) < P30
+
+
+def test_conv_cases_are_admitted(hip_lib):
+    from qpwcnet_amd import _hip
+    text = open(os.path.join(CSRC, "conv_bwd.hip")).read()
+    m = re.search(r"bool conv3x3_same_shape_ok\(.*?\{(.*?)\n\}", text, re.S)
+    body = m.group(1)
+    # the rule, each expression exactly once: pixel blocks of the input within INT32_MAX, B within 2^24
+    assert body.count("(p.M_in + kCbPx - 1) / kCbPx <= INT32_MAX") == 1 and body.count("B <= (1 << 24)") == 1
+    assert body.count("return") == 1
+    assert text.count("p.M_in = (int64_t)B * H * W;") == 1 and text.count("p.M_out = (int64_t)B * g.Ho * g.Wo;") == 1
+    for name in CONV:
+        B, H, W, ci, co, s = lo.CASES[name]
+        assert -(-B * H * W // CB["kCbPx"]) <= 2 ** 31 - 1 and B <= 1 << 24
+        assert max(B, H, W, ci, co) < 2 ** 31                      # every size argument of the entry points fits an int
+        assert hip_lib.qpwc_conv3x3_same_bwd_workspace_floats(B, H, W, ci, co, s) > 0
+    # the cap is far off (2^37 pixels): no case sits at it, the refusal is by name all the same
+    assert hip_lib.qpwc_conv3x3_same_bwd_workspace_floats(1 << 16, 1 << 15, 1 << 7, 16, 16, 1) == _hip.E_SHAPE
+    assert b"too large for the launch grids" in hip_lib.qpwc_last_error()
+    assert hip_lib.qpwc_conv3x3_same_bwd_workspace_floats((1 << 16) - 1, 1 << 15, 1 << 6, 16, 16, 1) > P31
+
+
+def test_conv_planned_memory(hip_lib):
+    ws = hip_lib.qpwc_conv3x3_same_bwd_workspace_floats
+    for name in CONV:
+        key = lo.CASES[name]
+        planned = lo.conv_planned_bytes(key, ws(*key), ws(1, *key[1:]))
+        n = lo.conv_operands(key)
+        assert planned >= 4 * (n["x"] + n["grad_x"] + n["out"] + n["grad_out"] + n["gz"])
+        assert planned <= 48 * lo.GIB, planned / lo.GIB
+        assert 1.10 * planned <= 64 * lo.GIB
+
+
+def test_conv_crops_and_windows_lie_where_the_offsets_wrap():
+    for name in CONV + (UP, SEP):
+        key = lo.CASES[name]
+        g = lo.conv_geo(key)
+        g.setdefault("s", 1)                    # transposed: the windows' x rows lie within 3 input rows of the boundary
+        n_el = lo.conv_operands(key)
+        crops, wins = lo.conv_crops(key), lo.conv_windows(key)
+        tags = [c[0] for c in crops]
+        assert tags[-1] == "last" and len(set(tags)) == len(tags)
+        assert {t for t in tags if t.startswith("x>")} | {t for t in tags if t.startswith("out>")} == set(tags[:-1])
+        for b in lo.crossed(n_el["out"]):              # the pixel before and the pixel at the boundary are compared
+            n, y, x = lo.locate(b, g["Ho"], g["Wo"], g["co"])
+            assert any(c[1] == n and c[2] <= y < c[3] and c[4] <= x - 1 and x < c[5] for c in crops), (name, b)
+        for b in lo.crossed(n_el["x"]):
+            n, y, x = lo.locate(b, g["H"], g["W"], g["ci"])
+            hit = False
+            for c in crops:
+                (cy0, cy1, cx0, cx1), _ = lo.conv_x_region(key, c)
+                if c[1] == n and cy0 <= y < cy1 and cx0 <= x - 1 and x < cx1:
+                    ok = lo.conv_gx_valid(key, c)
+                    hit |= bool(ok[y - cy0, x - cx0]) and bool(ok[y - cy0, x - 1 - cx0])
+            assert hit, (name, b)
+        last = crops[-1]
+        (cy0, cy1, cx0, cx1), pads = lo.conv_x_region(key, last)
+        assert (cy1, cx1) == (g["H"], g["W"]) and (g["up"] or pads[1] + pads[3] >= 1)    # the 'SAME' border is in it
+        assert bool(lo.conv_gx_valid(key, last)[-1, -1])                            # and the very last x pixel
+        # windows: disjoint, the first at offset 0, one wholly behind every boundary, the last in the corner
+        assert wins[0][1:] == (0, 0, lo.WIN, 0, lo.WIN) and wins[-1][1] == g["B"] - 1 and wins[-1][3] == g["Ho"]
+        for i, a in enumerate(wins):
+            for b_ in wins[i + 1:]:
+                assert a[1] != b_[1] or a[3] <= b_[2] or b_[3] <= a[2] or a[5] <= b_[4] or b_[5] <= a[4], (a, b_)
+        for b in lo.crossed(n_el["out"]):
+            assert any(((w[1] * g["Ho"] + w[2]) * g["Wo"] + w[4]) * g["co"] > b and
+                       ((w[1] * g["Ho"] + w[2] - 1) * g["Wo"] + w[4]) * g["co"] < b + 5 * g["Wo"] * g["co"]
+                       for w in wins[1:-1]), (name, b)
+        for b in lo.crossed(n_el["x"]):
+            firsts = []
+            for w in wins[1:-1]:
+                (cy0, _, cx0, _), _ = lo.conv_x_region(key, w)
+                firsts.append(((w[1] * g["H"] + cy0) * g["W"] + cx0) * g["ci"])
+            assert any(b < f < b + (2 * g["s"] + 2) * g["W"] * g["ci"] for f in firsts), (name, b)
+        # a 32-bit byte offset finds every window behind a boundary somewhere else, inside the tensor
+        moved = [lo.conv_wrapped_regions(key, w) for w in wins]
+        assert moved[0] == [] and all(len(m) >= 1 for m in moved[1:])
+        assert {mod for m in moved for mod, _ in m} == {1 << 31, 1 << 32}
+        for m, w in zip(moved, wins):
+            (cy0, cy1, cx0, cx1), _ = lo.conv_x_region(key, w)
+            for _, (n, y0, y1, x0, x1) in m:
+                assert 0 <= n < g["B"] and 0 <= y0 < y1 <= g["H"] and 0 <= x0 < x1 <= g["W"]
+                assert (y1 - y0, x1 - x0) == (cy1 - cy0, cx1 - cx0) and (n, y0, x0) != (w[1], cy0, cx0)
+
+
+def _axis_users_brute(i, n_out, s, p):
+    return [o for o in range(n_out) if 0 <= i - (o * s - p) <= 2]
+
+
+def test_gx_valid_mask_against_brute_force():
+    for key in ((1, 9, 11, 16, 16, 1), (1, 9, 11, 16, 32, 2), (1, 8, 12, 16, 32, 2)):
+        g = lo.conv_geo(key)
+        for o0, o1 in ((0, 3), (1, 4), (g["Ho"] - 3, g["Ho"])):
+            reg = ("t", 0, o0, o1, 0, g["Wo"])
+            (cy0, cy1, _, _), _ = lo.conv_x_region(key, reg)
+            want = [all(o0 <= o < o1 for o in _axis_users_brute(i, g["Ho"], g["s"], g["pt"])) for i in range(cy0, cy1)]
+            assert lo.conv_gx_valid(key, reg)[:, 0].tolist() == want, (key, o0)
+
+
+@pytest.mark.parametrize("stride,hw", [(1, (40, 45)), (2, (81, 87)), (2, (80, 86))], ids=["s1", "s2odd", "s2even"])
+@pytest.mark.parametrize("mish", [True, False], ids=["mish", "linear"])
+def test_crop_restatement_is_the_layer(stride, hw, mish):
+    """conv_region_ref on a crop against the float64 composite of the whole (small) tensor, wherever the crop lies:
+    the outputs everywhere in the crop, grad_x where conv_gx_valid says so; and the window sums against the composite
+    fed a grad_out that is zero outside the windows."""
+    key = (2,) + hw + (16, 32 if stride == 2 else 16, stride)
+    gen = torch.Generator().manual_seed(5)
+    g_ = lo.conv_geo(key)
+    x, w, b = _grid(gen, (2,) + hw + (16,), 1 / 16), _grid(gen, (key[4], 16, 3, 3), 1 / 8), _grid(gen, (key[4],), 1 / 8)
+    go = _grid(gen, (2, g_["Ho"], g_["Wo"], key[4]), 1 / 16)
+    leaves = [t.clone().requires_grad_() for t in (x, w, b)]
+    out = composite(*leaves, stride, mish)
+    out.backward(go)
+    C = lo.CROP
+    regs = [("tl", 0, 0, C, 0, C), ("mid", 1, 5, 5 + C, 7, 7 + C), ("br", 1, g_["Ho"] - C, g_["Ho"], g_["Wo"] - C, g_["Wo"])]
+    for reg in regs:
+        (cy0, cy1, cx0, cx1), pads = lo.conv_x_region(key, reg)
+        n = reg[1]
+        ro, rx, _, _ = lo.conv_region_ref(key, x[n:n + 1, cy0:cy1, cx0:cx1], pads, w, b,
+                                          go[n:n + 1, reg[2]:reg[3], reg[4]:reg[5]], mish)
+        assert float((ro - out.detach()[n:n + 1, reg[2]:reg[3], reg[4]:reg[5]]).abs().max()) < 1e-12
+        ok = lo.conv_gx_valid(key, reg)
+        assert int(ok.sum()) >= (C - 2) ** 2
+        assert float((rx[0][ok] - leaves[0].grad[n, cy0:cy1, cx0:cx1][ok]).abs().max()) < 1e-12
+        assert float((rx[0][~ok] - leaves[0].grad[n, cy0:cy1, cx0:cx1][~ok]).abs().max()) > 1e-3      # the mask is needed
+    wins = [("a", 0, 0, 16, 0, 16), ("b", 1, 3, 19, 9, 25), ("c", 1, g_["Ho"] - 16, g_["Ho"], g_["Wo"] - 16, g_["Wo"])]
+    sparse = torch.zeros_like(go)
+    crops = []
+    for reg in wins:
+        sparse[reg[1], reg[2]:reg[3], reg[4]:reg[5]] = go[reg[1], reg[2]:reg[3], reg[4]:reg[5]]
+        (cy0, cy1, cx0, cx1), pads = lo.conv_x_region(key, reg)
+        crops.append((x[reg[1]:reg[1] + 1, cy0:cy1, cx0:cx1], pads, go[reg[1]:reg[1] + 1, reg[2]:reg[3], reg[4]:reg[5]]))
+    leaves = [t.clone().requires_grad_() for t in (x, w, b)]
+    composite(*leaves, stride, mish).backward(sparse)
+    rw, rb = lo.conv_window_sums(key, crops, w, b, mish)
+    assert float((rw - leaves[1].grad).abs().max()) < 1e-11 and float((rb - leaves[2].grad).abs().max()) < 1e-11
+
+
+def _cpu_windows(key, seed):
+    """The windows of a case with crops drawn on the CPU from the grids the GPU test draws from on the device."""
+    gen = torch.Generator().manual_seed(seed)
+    ci, co = key[3], key[4]
+    w, b = _grid(gen, (co, ci, 3, 3), 1 / 8), _grid(gen, (co,), 1 / 8)
+    crops, moved = [], []
+    for k, reg in enumerate(lo.conv_windows(key)):
+        (cy0, cy1, cx0, cx1), pads = lo.conv_x_region(key, reg)
+        crops.append((_grid(gen, (1, cy1 - cy0, cx1 - cx0, ci), 1 / 16), pads,
+                      _grid(gen, (1, reg[3] - reg[2], reg[5] - reg[4], co), 1 / 16)))
+        for mod, _ in lo.conv_wrapped_regions(key, reg):        # dense random data read elsewhere: another draw
+            moved.append(("window %d mod %d" % (k, mod), k, _grid(gen, (1, cy1 - cy0, cx1 - cx0, ci), 1 / 16)))
+    return crops, moved, w, b
+
+
+@pytest.mark.parametrize("name", CONV)
+@pytest.mark.parametrize("mish", [True, False], ids=["mish", "linear"])
+def test_conv_window_sums_bounds_and_negative_controls(name, mish):
+    """On the CPU: the fp32 composition of the window sums stays within the bound the GPU test uses (1e-4 max(1,
+    max|ref|)) of the float64 restatement -- exactly on it without Mish, under the asserted magnitude precondition --
+    and every negative control moves grad_w by at least 100 bounds."""
+    key = lo.CASES[name]
+    crops, moved, w, b = _cpu_windows(key, 11)
+    rw, rb = lo.conv_window_sums(key, crops, w, b, mish)
+    gw32, gb32 = 0.0, 0.0
+    for xc, pads, gc in crops:
+        lv = [t.float().clone().requires_grad_() for t in (xc, w, b)]
+        z = torch.nn.functional.conv2d(torch.nn.functional.pad(lv[0].permute(0, 3, 1, 2), pads), lv[1], lv[2],
+                                       stride=key[5]).permute(0, 2, 3, 1)
+        (lo.torch_ref.mish(z) if mish else z).backward(gc.float())
+        gw32, gb32 = gw32 + lv[1].grad, gb32 + lv[2].grad
+    if mish:
+        assert float((gw32.double() - rw).abs().max()) <= 0.1 * lo._tol(rw)
+        assert float((gb32.double() - rb).abs().max()) <= 0.1 * lo._tol(rb)
+    else:
+        assert lo.exactness_precondition(key, crops, w, b) * 2 ** 8 < 2 ** 24
+        assert torch.equal(gw32.double(), rw) and torch.equal(gb32.double(), rb)
+    controls = lo.conv_controls(key, crops, moved, w, b, mish)
+    assert len(controls) == len(crops) + len(moved) and len(moved) >= 2
+    assert min(r for _, r in controls) >= 100.0, controls
+
+
+def test_size_arguments_of_the_entry_points_used():
+    """The entry points the GPU test reaches are in the table that tests/test_capi_prototypes_cpu.py compares with
+    the header; what can pass 2^31 there -- the workspace size -- is 64-bit on both sides, and every `int` parameter
+    carries an extent that the cases keep far below 2^31."""
+    from qpwcnet_amd import _hip
+    protos = {name: (ret, params) for name, ret, params in parse_header()}
+    for name in ("qpwc_conv3x3_same_fwd", "qpwc_conv3x3_same_bwd", "qpwc_conv3x3_mish_fwd"):
+        assert name in protos and name in _hip.PROTOTYPES
+        assert protos[name][0] == "int" and set(protos[name][1]) <= {"const void*", "void*", "int"}
+    ret, params = protos["qpwc_conv3x3_same_bwd_workspace_floats"]
+    assert ret == "int64_t" and params == ["int"] * 6
+    restype, argtypes = _hip.PROTOTYPES["qpwc_conv3x3_same_bwd_workspace_floats"]
+    assert ctypes.sizeof(restype) == 8 and all(t is ctypes.c_int for t in argtypes)
+
+
+# ---- transposed conv 4x4 stride 2 ------------------------------------------------------------------------------------
+def test_upconv_case_crosses_what_it_claims(hip_lib):
+    from qpwcnet_amd import _hip
+    key = lo.CASES[UP]
+    B, H, W, C, F_ = key
+    n = lo.conv_operands(key)
+    assert B == 3 and H % 2 and W % 2 and H != W
+    assert n["x"] == B * H * W * C and n["out"] == n["gz"] == B * 2 * H * 2 * W * F_ == n["x"]
+    assert lo.crossed(n["x"]) == lo.crossed(n["out"]) == [P29, P30, P31]
+    assert [lo.locate(b, H, W, C)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert [lo.locate(b, 2 * H, 2 * W, F_)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    for rows, cols, ch in ((H, W, C), (2 * H, 2 * W, F_)):
+        assert all(0 < y < rows - 4 - lo.WIN and 0 < x < cols - 1 for _, y, x in (lo.locate(b, rows, cols, ch) for b in lo.BOUNDARIES))
+    assert (B * H * W) % UB["kUbPx"]                                              # a partial last pixel block
+    # ub_plan() restated: gz | part_w | part_b; gz crosses all three, the partials lie behind 2^31 elements
+    n_pb, nsplit, total = _up_plan(*key)
+    off_pw = 4 * B * H * W * F_
+    off_pb = off_pw + nsplit * 16 * F_ * C
+    assert total == off_pb + -(-nsplit * F_ // 4) * 4 == hip_lib.qpwc_upconv4x4s2_bwd_workspace_floats(*key)
+    assert lo.crossed(off_pw) == [P29, P30, P31] and off_pb > off_pw > P31 and nsplit == UB["kUbWBlocks"] // 16
+    one = (1,) + key[1:]
+    assert lo.crossed(lo.conv_operands(one)["x"]) == [P29] and hip_lib.qpwc_upconv4x4s2_bwd_workspace_floats(*one) < P30
+    # admitted: upconv4x4s2_bwd_shape_ok, each expression once
+    text = open(os.path.join(CSRC, "upconv_bwd.hip")).read()
+    body = re.search(r"bool upconv4x4s2_bwd_shape_ok\(.*?\{(.*?)\n\}", text, re.S).group(1)
+    for expr in ("p.n_pb <= INT32_MAX", "B <= (1 << 24)", "H <= (1 << 29)", "W <= (1 << 29)"):
+        assert body.count(expr) == 1, expr
+    assert body.count("return") == 1 and text.count("p.M_in = (int64_t)B * H * W;") == 1
+    assert n_pb <= 2 ** 31 - 1 and B <= 1 << 24 and max(H, W) <= 1 << 29
+    ws = hip_lib.qpwc_upconv4x4s2_bwd_workspace_floats
+    assert ws(1, (1 << 29) + 1, 1, 64, 16) == _hip.E_SHAPE and b"too large for the launch grids" in hip_lib.qpwc_last_error()
+    assert ws(1 << 16, 1 << 15, 1 << 7, 64, 16) == _hip.E_SHAPE
+    planned = lo.conv_planned_bytes(key, ws(*key), ws(*one))
+    assert 4 * 5 * n["x"] <= planned <= 48 * lo.GIB and 1.10 * planned <= 64 * lo.GIB
+
+
+@pytest.mark.parametrize("mish", [True, False], ids=["mish", "linear"])
+def test_upconv_crop_restatement_is_the_layer(mish):
+    key = (2, 20, 23, 64, 16)
+    gen = torch.Generator().manual_seed(6)
+    x, w, b = _grid(gen, (2, 20, 23, 64), 1 / 16), _grid(gen, (64, 16, 4, 4), 1 / 64, 1 / 8), _grid(gen, (16,), 1 / 8)
+    go = _grid(gen, (2, 40, 46, 16), 1 / 16)
+    leaves = [t.clone().requires_grad_() for t in (x, w, b)]
+    out = up_composite(*leaves, mish)
+    out.backward(go)
+    C = lo.CROP
+    for reg in (("tl", 0, 0, C, 0, C), ("mid", 1, 5, 5 + C, 7, 7 + C), ("mid2", 1, 6, 6 + C, 8, 8 + C), ("br", 1, 40 - C, 40, 46 - C, 46)):
+        (cy0, cy1, cx0, cx1), place = lo.conv_x_region(key, reg)
+        n = reg[1]
+        ro, rx, _, _ = lo.conv_region_ref(key, x[n:n + 1, cy0:cy1, cx0:cx1], place, w, b,
+                                          go[n:n + 1, reg[2]:reg[3], reg[4]:reg[5]], mish)
+        assert float((ro - out.detach()[n:n + 1, reg[2]:reg[3], reg[4]:reg[5]]).abs().max()) < 1e-12
+        ok = lo.conv_gx_valid(key, reg)
+        assert int(ok.sum()) >= (C // 2 - 2) ** 2
+        assert float((rx[0][ok] - leaves[0].grad[n, cy0:cy1, cx0:cx1][ok]).abs().max()) < 1e-12
+        assert float((rx[0][~ok] - leaves[0].grad[n, cy0:cy1, cx0:cx1][~ok]).abs().max()) > 1e-3
+    wins = [("a", 0, 0, 16, 0, 16), ("b", 1, 3, 19, 9, 25), ("c", 1, 24, 40, 30, 46)]
+    sparse = torch.zeros_like(go)
+    crops = []
+    for reg in wins:
+        sparse[reg[1], reg[2]:reg[3], reg[4]:reg[5]] = go[reg[1], reg[2]:reg[3], reg[4]:reg[5]]
+        (cy0, cy1, cx0, cx1), place = lo.conv_x_region(key, reg)
+        crops.append((x[reg[1]:reg[1] + 1, cy0:cy1, cx0:cx1], place, go[reg[1]:reg[1] + 1, reg[2]:reg[3], reg[4]:reg[5]]))
+    leaves = [t.clone().requires_grad_() for t in (x, w, b)]
+    up_composite(*leaves, mish).backward(sparse)
+    rw, rb = lo.conv_window_sums(key, crops, w, b, mish)
+    assert float((rw - leaves[1].grad).abs().max()) < 1e-11 and float((rb - leaves[2].grad).abs().max()) < 1e-11
+
+
+@pytest.mark.parametrize("mish", [True, False], ids=["mish", "linear"])
+def test_upconv_window_sums_bounds_and_negative_controls(mish):
+    key = lo.CASES[UP]
+    gen = torch.Generator().manual_seed(12)
+    C, F_ = key[3], key[4]
+    w, b = _grid(gen, (C, F_, 4, 4), 1 / 64, 1 / 8), _grid(gen, (F_,), 1 / 8)
+    crops, moved = [], []
+    for k, reg in enumerate(lo.conv_windows(key)):
+        (cy0, cy1, cx0, cx1), place = lo.conv_x_region(key, reg)
+        crops.append((_grid(gen, (1, cy1 - cy0, cx1 - cx0, C), 1 / 16), place,
+                      _grid(gen, (1, reg[3] - reg[2], reg[5] - reg[4], F_), 1 / 16)))
+        for mod, _ in lo.conv_wrapped_regions(key, reg):
+            moved.append(("window %d mod %d" % (k, mod), k, _grid(gen, (1, cy1 - cy0, cx1 - cx0, C), 1 / 16)))
+    rw, rb = lo.conv_window_sums(key, crops, w, b, mish)
+    gw32, gb32 = 0.0, 0.0
+    for xc, place, gc in crops:
+        lv = [t.float().clone().requires_grad_() for t in (xc, w, b)]
+        z = torch.nn.functional.conv_transpose2d(lv[0].permute(0, 3, 1, 2), lv[1], lv[2], stride=2, padding=1)
+        z = z.permute(0, 2, 3, 1)[:, place[2]:place[3], place[0]:place[1]]
+        (lo.torch_ref.mish(z) if mish else z).backward(gc.float())
+        gw32, gb32 = gw32 + lv[1].grad, gb32 + lv[2].grad
+    if mish:
+        assert float((gw32.double() - rw).abs().max()) <= 0.1 * lo._tol(rw)
+        assert float((gb32.double() - rb).abs().max()) <= 0.1 * lo._tol(rb)
+    else:
+        assert lo.exactness_precondition(key, crops, w, b, unit=2 ** 10) * 2 ** 10 < 2 ** 24
+        assert torch.equal(gw32.double(), rw) and torch.equal(gb32.double(), rb)
+    controls = lo.conv_controls(key, crops, moved, w, b, mish)
+    assert len(controls) == len(crops) + len(moved) and len(moved) >= 2
+    assert min(r for _, r in controls) >= 100.0, controls
+
+
+def test_size_arguments_of_the_upconv_entry_points():
+    from qpwcnet_amd import _hip
+    protos = {name: (ret, params) for name, ret, params in parse_header()}
+    ret, params = protos["qpwc_upconv4x4s2_bwd"]
+    # grad_out's pixel stride is the one size there that is 64-bit; every extent is an int the case keeps small
+    assert ret == "int" and params.count("int64_t") == 1 and set(params) <= {"const void*", "void*", "int", "int64_t"}
+    assert [ctypes.sizeof(t) for t in _hip.PROTOTYPES["qpwc_upconv4x4s2_bwd"][1]].count(8) >= 1
+    ret, params = protos["qpwc_upconv4x4s2_bwd_workspace_floats"]
+    assert ret == "int64_t" and params == ["int"] * 5
+    assert ctypes.sizeof(_hip.PROTOTYPES["qpwc_upconv4x4s2_bwd_workspace_floats"][0]) == 8
+    assert "qpwc_upconv4x4s2_mish_fwd" in protos and "qpwc_upconv4x4s2_mish_fwd" in _hip.PROTOTYPES
+
+
+# ---- SeparableConv2D backward ---------------------------------------------------------------------------------------
+def sep_plan(key):
+    """scb_plan() restated: the workspace regions d | gd | gz | part_pw | part_b | part_dw as (first, end) in floats."""
+    B, H, W, C, F_ = key[:5]
+    M, cpad = B * H * W, -(-C // KC) * KC
+    chunks = cpad // KC
+    up4 = lambda n: -(-n // 4) * 4
+    pw_x = min(-(-M // SCB["kScbPx"]), max(1, SCB["kScbPwBlocks"] // chunks))
+    groups = -(-(B * H * -(-W // SCB["kScbStrip"])) // SCB["kScbDwSlots"])
+    dw_x = min(groups, max(1, SCB["kScbDwBlocks"] // chunks))
+    sizes = (("d", M * cpad), ("gd", M * cpad), ("gz", up4(M * F_)), ("part_pw", pw_x * F_ * cpad),
+             ("part_b", up4(pw_x * F_)), ("part_dw", up4(dw_x * C * 9)))
+    regions, at = {}, 0
+    for name, n in sizes:
+        regions[name] = (at, at + n)
+        at += n
+    assert at == _sep_workspace(B, H, W, C, F_)
+    return regions
+
+
+def test_sepconv_case_crosses_what_it_claims(hip_lib):
+    from qpwcnet_amd import _hip
+    key = lo.CASES[SEP]
+    B, H, W, C, F_, one_ = key
+    assert one_ == 1 and B == 3 and H % 2 and W % 2 and H != W and C == KC           # Cpad = C: d and gd are x-sized
+    n = lo.sepconv_operands(key)
+    assert n["x"] == lo.conv_operands(key)["x"] == B * H * W * C and n["grad_out"] == lo.conv_operands(key)["out"]
+    assert lo.crossed(n["x"]) == [P29, P30, P31] and lo.crossed(n["grad_out"]) == [P29, P30]
+    assert [lo.locate(b, H, W, C)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert [lo.locate(b, H, W, F_)[0] for b in (P29, P30)] == [1, 2]
+    assert all(0 < y < H - 2 - lo.WIN and 0 < x < W - 1 for _, y, x in (lo.locate(b, H, W, C) for b in lo.BOUNDARIES))
+    assert (B * H * W) % SCB["kScbPx"] and W % SCB["kScbStrip"]                        # partial last block, partial strips
+    # the workspace: gd starts behind 2^31 elements, gz and the partials behind 2^32; d itself crosses all three
+    r = sep_plan(key)
+    ws = hip_lib.qpwc_sepconv3x3_bwd_workspace_floats
+    assert ws(B, H, W, C, F_) == r["part_dw"][1]
+    assert lo.crossed(r["d"][1]) == [P29, P30, P31]
+    assert r["gd"][0] > P31 and r["gz"][0] > 1 << 32 and r["part_pw"][0] > r["gz"][0] and r["part_dw"][0] > r["part_b"][0]
+    assert r["gz"][1] * 4 > 1 << 34                                                     # byte offsets past 2^34
+    assert lo.crossed(lo.sepconv_operands((1,) + key[1:])["x"]) == [P29] and ws(1, H, W, C, F_) < P31
+    # admitted: sepconv3x3_bwd_shape_ok, each expression once; C <= 2^20 in the C boundary
+    text = open(os.path.join(CSRC, "sepconv_bwd.hip")).read()
+    body = re.search(r"bool sepconv3x3_bwd_shape_ok\(.*?\{(.*?)\n\}", text, re.S).group(1)
+    for expr in ("p.chunks <= 65535", "(p.n_strips * p.cpad + 255) / 256 <= INT32_MAX", "p.n_pb <= INT32_MAX",
+                 "(int64_t)F * p.cpad <= INT32_MAX / 2", "(int64_t)C * 9 <= INT32_MAX / 2"):
+        assert body.count(expr) == 1, expr
+    assert body.count("return") == 1
+    strips = B * H * -(-W // SCB["kScbStrip"])
+    assert -(-strips * C // 256) <= 2 ** 31 - 1 and -(-B * H * W // SCB["kScbPx"]) <= 2 ** 31 - 1
+    # the rule bounds grids, not bytes: one step past the stage-A grid is refused by name
+    assert ws(1 << 14, 1 << 14, 1 << 13, 32, 16) == _hip.E_SHAPE
+    assert b"too large for the backward's launch grids" in hip_lib.qpwc_last_error()
+    planned = lo.sepconv_planned_bytes(key, ws(B, H, W, C, F_), ws(1, H, W, C, F_))
+    assert 4 * (n["x"] + n["grad_x"] + n["grad_out"] + n["d"] + n["gd"] + n["gz"]) <= planned <= 48 * lo.GIB
+    assert 1.10 * planned <= 64 * lo.GIB
+
+
+@pytest.mark.parametrize("flags", [(True, True), (False, False)], ids=["11", "00"])
+def test_sepconv_crop_restatement_is_the_layer(flags):
+    key = (2, 40, 45, 32, 16, 1)
+    gen = torch.Generator().manual_seed(7)
+    x, dw, pw, b = (_grid(gen, (2, 40, 45, 32), 1 / 16), _grid(gen, (32, 1, 3, 3), 1 / 8), _grid(gen, (16, 32), 1 / 8),
+                    _grid(gen, (16,), 1 / 8))
+    go = _grid(gen, (2, 40, 45, 16), 1 / 16)
+    leaves = [t.clone().requires_grad_() for t in (x, dw, pw, b)]
+    out = sep_composite([leaves[0]], leaves[1], leaves[2], leaves[3], *flags)
+    out.backward(go)
+    C = lo.CROP
+    for reg in (("tl", 0, 0, C, 0, C), ("mid", 1, 5, 5 + C, 7, 7 + C), ("br", 1, 40 - C, 40, 45 - C, 45)):
+        (cy0, cy1, cx0, cx1), pads = lo.conv_x_region(key, reg)
+        n = reg[1]
+        ro, rx, _, _ = lo.conv_region_ref(key, x[n:n + 1, cy0:cy1, cx0:cx1], pads, (dw, pw), b,
+                                          go[n:n + 1, reg[2]:reg[3], reg[4]:reg[5]], flags)
+        assert float((ro - out.detach()[n:n + 1, reg[2]:reg[3], reg[4]:reg[5]]).abs().max()) < 1e-12
+        ok = lo.conv_gx_valid(key, reg)
+        assert int(ok.sum()) >= (C - 2) ** 2
+        assert float((rx[0][ok] - leaves[0].grad[n, cy0:cy1, cx0:cx1][ok]).abs().max()) < 1e-12
+        assert float((rx[0][~ok] - leaves[0].grad[n, cy0:cy1, cx0:cx1][~ok]).abs().max()) > 1e-3
+    wins = [("a", 0, 0, 16, 0, 16), ("b", 1, 3, 19, 9, 25), ("c", 1, 24, 40, 29, 45)]
+    sparse = torch.zeros_like(go)
+    crops = []
+    for reg in wins:
+        sparse[reg[1], reg[2]:reg[3], reg[4]:reg[5]] = go[reg[1], reg[2]:reg[3], reg[4]:reg[5]]
+        (cy0, cy1, cx0, cx1), pads = lo.conv_x_region(key, reg)
+        crops.append((x[reg[1]:reg[1] + 1, cy0:cy1, cx0:cx1], pads, go[reg[1]:reg[1] + 1, reg[2]:reg[3], reg[4]:reg[5]]))
+    leaves = [t.clone().requires_grad_() for t in (x, dw, pw, b)]
+    sep_composite([leaves[0]], leaves[1], leaves[2], leaves[3], *flags).backward(sparse)
+    rw, rb = lo.conv_window_sums(key, crops, (dw, pw), b, flags)
+    want = torch.cat([leaves[1].grad.flatten(), leaves[2].grad.flatten()])
+    assert float((rw - want).abs().max()) < 1e-11 and float((rb - leaves[3].grad).abs().max()) < 1e-11
+
+
+@pytest.mark.parametrize("flags", [(True, True), (False, False)], ids=["11", "00"])
+def test_sepconv_window_sums_bounds_and_negative_controls(flags):
+    key = lo.CASES[SEP]
+    gen = torch.Generator().manual_seed(13)
+    C, F_ = key[3], key[4]
+    dw, pw, b = _grid(gen, (C, 1, 3, 3), 1 / 8), _grid(gen, (F_, C), 1 / 8), _grid(gen, (F_,), 1 / 8)
+    crops, moved = [], []
+    for k, reg in enumerate(lo.conv_windows(key)):
+        (cy0, cy1, cx0, cx1), pads = lo.conv_x_region(key, reg)
+        crops.append((_grid(gen, (1, cy1 - cy0, cx1 - cx0, C), 1 / 16), pads,
+                      _grid(gen, (1, reg[3] - reg[2], reg[5] - reg[4], F_), 1 / 16)))
+        for mod, _ in lo.conv_wrapped_regions(key, reg):
+            moved.append(("window %d mod %d" % (k, mod), k, _grid(gen, (1, cy1 - cy0, cx1 - cx0, C), 1 / 16)))
+    rw, rb = lo.conv_window_sums(key, crops, (dw, pw), b, flags)
+    gw32, gb32 = 0.0, 0.0
+    for xc, pads, gc in crops:
+        lv = [t.float().clone().requires_grad_() for t in (xc, dw, pw, b)]
+        xp = torch.nn.functional.pad(lv[0], (0, 0) + tuple(pads))
+        d = lo.torch_ref.depthwise3x3([xp], lv[1], flags[0])[:, 1:-1, 1:-1]
+        z = d @ lv[2].t() + lv[3]
+        (lo.torch_ref.mish(z) if flags[1] else z).backward(gc.float())
+        gw32, gb32 = gw32 + torch.cat([lv[1].grad.flatten(), lv[2].grad.flatten()]), gb32 + lv[3].grad
+    rdw, rpw = rw[:C * 9], rw[C * 9:]
+    if flags == (False, False):
+        assert lo.exactness_precondition(key, crops, (dw, pw), b, unit=2 ** 11) * 2 ** 11 < 2 ** 24
+        assert torch.equal(gw32.double(), rw) and torch.equal(gb32.double(), rb)
+    else:
+        assert float((gw32.double()[:C * 9] - rdw).abs().max()) <= 0.1 * lo._tol(rdw)
+        assert float((gw32.double()[C * 9:] - rpw).abs().max()) <= 0.1 * lo._tol(rpw)
+        assert float((gb32.double() - rb).abs().max()) <= 0.1 * lo._tol(rb)
+    controls = lo.conv_controls(key, crops, moved, (dw, pw), b, flags)
+    assert len(controls) == len(crops) + len(moved) and len(moved) >= 2
+    assert min(r for _, r in controls) >= 100.0, controls
+
+
+def test_size_arguments_of_the_sepconv_entry_points():
+    from qpwcnet_amd import _hip
+    protos = {name: (ret, params) for name, ret, params in parse_header()}
+    ret, params = protos["qpwc_sepconv3x3_bwd"]
+    # the pixel strides are the sizes there that can be large: an int64_t array on both sides
+    assert ret == "int" and params.count("const int64_t*") == 1
+    assert _hip.PROTOTYPES["qpwc_sepconv3x3_bwd"][1][2]._type_ is ctypes.c_int64
+    ret, params = protos["qpwc_sepconv3x3_bwd_workspace_floats"]
+    assert ret == "int64_t" and params == ["int"] * 5
+    assert ctypes.sizeof(_hip.PROTOTYPES["qpwc_sepconv3x3_bwd_workspace_floats"][0]) == 8
+
+
+# ---- cost volume and warp backward ------------------------------------------------------------------------------------
+def test_backward_case_crosses_what_it_claims(hip_lib):
+    B, H, W, C = lo.CASES["backward"]
+    D = (2 * lo.SEARCH + 1) ** 2
+    assert B == 3 and H % 2 and W % 2 and H != W
+    assert lo.crossed(B * H * W * C) == lo.crossed(B * H * W * D) == [P29, P30, P31]
+    assert [lo.locate(b, H, W, C)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert [lo.locate(b, H, W, D)[0] for b in lo.BOUNDARIES] == [0, 1, 2]        # 81 floats a pixel
+    assert lo.crossed(B * H * W * 2) == []                                            # the flow stays small
+    assert lo.crossed(H * W * C) == [P29] and lo.crossed(H * W * D) == [P29]          # one image alone
+    # the kernels walk pixel groups in grid-stride order past the grid cap; the last trip is uneven
+    threads = _backward_cap() * 256
+    assert B * H * W * 64 > 4 * threads and (B * H * W * 64) % threads
+    # admitted: check_common asks for positive extents only; the fp16 workspace of the warp is the image's size
+    from qpwcnet_amd import _hip
+    assert hip_lib.qpwc_warp_bwd_workspace_floats(B, H, W, C, _hip.F16) == B * H * W * C > P31
+    assert hip_lib.qpwc_warp_bwd_workspace_floats(B, H, W, C, _hip.F32) == 0
+    # planned memory of the two tests, as they state it
+    n_in, n_cv = B * H * W * C, B * H * W * D
+    assert 4 * (2 * n_in + 2 * n_cv + n_in) <= lo.cost_volume_planned_bytes(lo.CASES["backward"]) <= 48 * lo.GIB
+    assert 4 * 3 * n_in <= lo.warp_planned_bytes(lo.CASES["backward"]) <= 48 * lo.GIB
+    # the crops hold the pixel before and the pixel at every boundary, `margin` inside the region of the reference
+    for ch, margin in ((C, lo.SEARCH), (D, lo.SEARCH), (C, lo.REACH + 2)):
+        crops = lo.pixel_crops(B, H, W, ch, margin)
+        assert [c[0] for c in crops] == [">2^29", ">2^30", ">2^31", "last"]
+        for b, c in zip(lo.BOUNDARIES, crops):
+            n, y, x = lo.locate(b, H, W, ch)
+            assert c[1] == n and c[2] <= y < c[3] and c[4] <= x - 1 and x < c[5]
+            assert c[6] == (c[2] - margin, c[3] + margin, c[4] - margin, c[5] + margin)
+        assert crops[-1][1:6] == (B - 1, H - lo.CROP, H, W - lo.CROP, W) and crops[-1][6][1::2] == (H, W)
+
+
+def test_cost_volume_bwd_restatement_is_the_derivative():
+    """cost_volume_bwd_ref against float64 autograd of oracle.torch_ref.cost_volume fed its own output, whole and on a
+    region with the reference's margin; a random saved output changes the result (the mask is really read)."""
+    from oracle import torch_ref
+    gen = torch.Generator().manual_seed(8)
+    prv, nxt, g = _grid(gen, (1, 20, 23, 8), 1 / 16), _grid(gen, (1, 20, 23, 8), 1 / 16), _grid(gen, (1, 20, 23, 81), 1 / 16)
+    a, b = prv.clone().requires_grad_(), nxt.clone().requires_grad_()
+    out = torch_ref.cost_volume(a, b, 4)
+    out.backward(g)
+    out = out.detach()
+    gp, gn = lo.cost_volume_bwd_ref(prv, nxt, out, g)
+    assert float((gp - a.grad).abs().max()) < 1e-14 and float((gn - b.grad).abs().max()) < 1e-14
+    m = lo.SEARCH
+    cut = lambda t: t[:, 2:18, 3:20]
+    gp2, gn2 = lo.cost_volume_bwd_ref(cut(prv), cut(nxt), cut(out), cut(g))
+    assert float((gp2[:, m:-m, m:-m] - cut(a.grad)[:, m:-m, m:-m]).abs().max()) < 1e-14
+    assert float((gn2[:, m:-m, m:-m] - cut(b.grad)[:, m:-m, m:-m]).abs().max()) < 1e-14
+    assert float((gn2 - cut(b.grad)).abs().max()) > 1e-3                               # the margin is needed
+    other = lo.cost_volume_bwd_ref(prv, nxt, _grid(gen, (1, 20, 23, 81), 1 / 16), g)[0]
+    assert float((other - gp).abs().max()) > 100 * lo._tol(gp)
+
+
+@pytest.mark.parametrize("mode", ["clamp", "tfwarp"])
+def test_warp_bwd_reference_on_a_region(mode):
+    """warp_bwd_ref on a region REACH + 2 wider than what is compared equals the gradient of the whole image there,
+    also where the region ends at the image's last row and column; and the fp32 composition stays within the bound."""
+    gen = torch.Generator().manual_seed(9)
+    img, flo, g = _grid(gen, (1, 60, 64, 4), 1 / 16), _flow(gen, 1, 60, 64, lo.REACH), _grid(gen, (1, 60, 64, 4), 1 / 16)
+    _, gi, gf = _oracle_warp(img, flo, g, mode)
+    m = lo.REACH + 2
+    for y0, y1, x0, x1 in ((10, 10 + lo.CROP + 2 * m, 12, 12 + lo.CROP + 2 * m), (60 - lo.CROP - m, 60, 64 - lo.CROP - m, 64)):
+        cut = lambda t: t[:, y0:y1, x0:x1]
+        ri, rf = lo.warp_bwd_ref(cut(img), cut(flo), cut(g), mode)
+        ys = slice(m, m + lo.CROP)
+        assert float((ri[:, ys, ys] - cut(gi)[:, ys, ys]).abs().max()) < 1e-13
+        assert float((rf[:, ys, ys] - cut(gf)[:, ys, ys]).abs().max()) < 1e-13
+        r32 = lo.warp_bwd_ref(cut(img).float(), cut(flo).float(), cut(g).float(), mode)
+        a32, f32 = cut(img).float().requires_grad_(), cut(flo).float().requires_grad_()
+        (lo.torch_ref.warp_v2 if mode == "clamp" else lo.torch_ref.tf_warp)(a32, f32).backward(cut(g).float())
+        assert float((a32.grad.double() - r32[0]).abs().max()) <= 0.1 * lo._tol(r32[0])
+        assert float((f32.grad.double() - r32[1]).abs().max()) <= 0.1 * lo._tol(r32[1])
+
+
+def test_size_arguments_of_the_backward_entry_points():
+    from qpwcnet_amd import _hip
+    protos = {name: (ret, params) for name, ret, params in parse_header()}
+    for name in ("qpwc_cost_volume_bwd", "qpwc_warp_bwd"):
+        assert name in _hip.PROTOTYPES and protos[name][0] == "int"
+        assert set(protos[name][1]) <= {"const void*", "void*", "int", "float"}          # extents only, each small
+    ret, params = protos["qpwc_warp_bwd_workspace_floats"]
+    assert ret == "int64_t" and ctypes.sizeof(_hip.PROTOTYPES["qpwc_warp_bwd_workspace_floats"][0]) == 8
+
+
+# ---- losses: what Step 0 of the audit found ---------------------------------------------------------------------------
+def test_loss_validator_refuses_what_the_kernels_decode_in_32_bits(hip_lib):
+    """loss_pixel_kernel decodes a pixel inside its image as `(int)(i - b * plane)` and loss_area_tile_kernel counts the
+    ground truth's tiles in an `int`: an image, or a level, of 2^31 pixels and a ground truth of 2^31 tiles are refused
+    by name, one step below they are admitted."""
+    from qpwcnet_amd import _hip
+    text = open(os.path.join(CSRC, "loss.hip")).read()
+    assert text.count("const int r = (int)(i - b * plane);") == 1 and text.count("const int ntiles = B * tiles_y * tiles_x;") == 1
+    I = ctypes.c_int
+
+    def ws(kind, B, H, W, h, w):
+        return hip_lib.qpwc_loss_workspace_floats(kind, B, H, W, 2, (I * 1)(h), (I * 1)(w), 1)
+
+    v2, mse = _hip.LOSS_FLOW_MSE_V2, _hip.LOSS_FLOW_MSE
+    assert ws(v2, 3, 1 << 15, 1 << 15, 1 << 14, 1 << 14) > 0                        # 2^30 pixels an image, 3 images
+    assert ws(v2, 1, 1 << 16, (1 << 15) - 1, 1 << 15, (1 << 15) - 1) > 0             # 2^31 - 2^16 pixels
+    assert ws(v2, 1, 1 << 16, 1 << 15, 1 << 15, 1 << 14) == _hip.E_SHAPE
+    assert b"pixels per image" in hip_lib.qpwc_last_error()
+    assert ws(v2, 2047, 1 << 15, 1 << 15, 1 << 14, 1 << 14) > 0                      # 2047 * 2^20 tiles
+    assert ws(v2, 2048, 1 << 15, 1 << 15, 1 << 14, 1 << 14) == _hip.E_SHAPE
+    assert b"tiles of 32 x 32" in hip_lib.qpwc_last_error()
+    assert ws(mse, 2048, 1 << 15, 1 << 15, 1 << 14, 1 << 14) > 0                     # no tile path, no tile count
+    assert ws(mse, 1, 8, 8, 1 << 16, (1 << 15) - 1) > 0                              # a bilinear level may be larger
+    assert ws(mse, 1, 8, 8, 1 << 16, 1 << 15) == _hip.E_SHAPE
+    assert b"level 0" in hip_lib.qpwc_last_error()
+
+
+# ---- the interpolator's pieces ----------------------------------------------------------------------------------------
+IH = {k: int(re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % k, open(os.path.join(CSRC, "interp.hip")).read())[0])
+      for k in ("kIhC", "kIhK", "kIhPx", "kIhBlocks", "kUiBlocks", "kUiBwdBlocks", "kApTilePx", "kApMaxLevels")}
+
+
+def test_interp_cases_cross_what_they_claim(hip_lib):
+    from qpwcnet_amd import _hip
+    # image head: M > 2^25 pixels of 64 features; ih_plan() restated; M is 64-bit on both sides, the cap 2^40
+    B, H, W = lo.CASES["image_head"]
+    M = B * H * W
+    assert B == 3 and H % 2 and W % 2 and M > 1 << 25 and M % IH["kIhPx"]
+    assert lo.crossed(M * IH["kIhC"]) == [P29, P30, P31] and lo.crossed(M * IH["kIhK"]) == []
+    assert [lo.locate(b, H, W, 64)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    blocks = min(-(-M // IH["kIhPx"]), IH["kIhBlocks"])
+    ws = hip_lib.qpwc_image_head_bwd_workspace_floats
+    assert ws(M) == blocks * IH["kIhK"] * IH["kIhC"] + -(-blocks * IH["kIhK"] // 4) * 4 and blocks == IH["kIhBlocks"]
+    assert ws(1 << 40) > 0 and ws((1 << 40) + 1) == _hip.E_SHAPE and b"2^40" in hip_lib.qpwc_last_error()
+    protos = {name: (ret, params) for name, ret, params in parse_header()}
+    for name in ("qpwc_image_head_fwd", "qpwc_image_head_bwd", "qpwc_image_head_bwd_workspace_floats"):
+        assert protos[name][1][-2 if name != "qpwc_image_head_bwd_workspace_floats" else -1] == "int64_t", name
+        args = _hip.PROTOTYPES[name][1]
+        assert ctypes.sizeof(args[-2] if name != "qpwc_image_head_bwd_workspace_floats" else args[-1]) == 8
+    assert 4 * 2 * M * 64 <= lo.image_head_planned_bytes(lo.CASES["image_head"], ws(M)) <= 48 * lo.GIB
+    wins = lo.pixel_windows(B, H, W, 64)
+    assert [w[0] for w in wins] == ["first", ">2^29", ">2^30", ">2^31", "last"]
+    moved = [lo.wrapped_pixel_regions(B, H, W, 64, w) for w in wins]
+    assert moved[0] == [] and all(m for m in moved[1:]) and {mod for m in moved for mod, _ in m} == {1 << 31, 1 << 32}
+    for b, w in zip(lo.BOUNDARIES, wins[1:4]):
+        assert b < ((w[1] * H + w[2]) * W + w[4]) * 64 < b + 2 * W * 64
+    # image upsampling: C = 3, more than 2^31 output elements, the input itself past 2^29
+    B, h, w, C = lo.CASES["upsample2x_image"]
+    assert B == 3 and h % 2 and w % 2 and C == 3
+    assert lo.crossed(4 * B * h * w * C) == [P29, P30, P31] and lo.crossed(B * h * w * C) == [P29]
+    assert [lo.locate(b, 2 * h, 2 * w, C)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert max(h, w) <= 1 << 29 and 4 * B * h * w > 4 * IH["kUiBlocks"] * 256 and B * h * w > 4 * IH["kUiBwdBlocks"] * 256
+    assert 4 * 10 * B * h * w * C <= lo.upsample_planned_bytes(lo.CASES["upsample2x_image"]) <= 48 * lo.GIB
+    # the pyramid: levels = 5, more than 2^31 input elements, H and W multiples of 32
+    B, H, W, C, levels = lo.CASES["avgpool_pyramid"]
+    S = 1 << levels
+    assert B == 3 and levels == 5 <= IH["kApMaxLevels"] and H % S == 0 and W % S == 0 and H != W
+    assert lo.crossed(B * H * W * C) == [P29, P30, P31] and [lo.locate(b, H, W, C)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert 4 * B * H * W * C <= lo.pyramid_planned_bytes(lo.CASES["avgpool_pyramid"]) <= 48 * lo.GIB
+    TW = min(max(IH["kApTilePx"] // S, S), W)
+    assert B * (H // S) * -(-W // TW) <= 2 ** 31 - 1 and (H * W * C) % 2 == 0        # tiles fit; an image alone is 8-byte aligned
+
+
+def test_interp_references_are_the_layers():
+    gen = torch.Generator().manual_seed(14)
+    x, g = _grid(gen, (1, 20, 23, 3), 1 / 16), _grid(gen, (1, 40, 46, 3), 1 / 16)
+    leaf = x.clone().requires_grad_()
+    up = upsample_composite(leaf, 2.0)
+    up.backward(g)
+    C = lo.CROP
+    for reg in (("a", 0, 0, C, 0, C), ("b", 0, 7, 7 + C, 9, 9 + C), ("c", 0, 8, 8 + C, 10, 10 + C), ("d", 0, 40 - C, 40, 46 - C, 46)):
+        (iy0, iy1, ix0, ix1), place = lo.upsample_regions(reg, 20, 23)
+        ro, rx = lo.upsample_region_ref(x[:, iy0:iy1, ix0:ix1], place, g[:, reg[2]:reg[3], reg[4]:reg[5]], 2.0)
+        ok = lo.upsample_valid(reg, 20, 23)
+        assert torch.equal(ro, up.detach()[:, reg[2]:reg[3], reg[4]:reg[5]]) and int(ok.sum()) >= (C // 2 - 2) ** 2
+        assert torch.equal(rx[0][ok], leaf.grad[0, iy0:iy1, ix0:ix1][ok])
+        assert float((rx[0][~ok] - leaf.grad[0, iy0:iy1, ix0:ix1][~ok]).abs().max()) > 1e-3
+    xx = _grid(gen, (1, 64, 96, 3), 1 / 16)
+    assert torch.equal(lo.pyramid_ref(xx, 5), pyramid_composite(xx, 5))
+    # the image head's window sums are those of the composite fed a grad_out that is zero outside the windows
+    z, w2, b2, go = _grid(gen, (1, 20, 23, 64), 1 / 16), _grid(gen, (3, 64), 1 / 64, 1 / 8), _grid(gen, (3,), 1 / 8), _grid(gen, (1, 20, 23, 3), 1 / 16)
+    sparse = torch.zeros_like(go)
+    crops = []
+    for y0, x0 in ((0, 0), (12, 15)):
+        sparse[:, y0:y0 + 8, x0:x0 + 8] = go[:, y0:y0 + 8, x0:x0 + 8]
+        crops.append((z[:, y0:y0 + 8, x0:x0 + 8], go[:, y0:y0 + 8, x0:x0 + 8]))
+    leaves = [t.clone().requires_grad_() for t in (z, w2, b2)]
+    head_composite(*leaves).backward(sparse)
+    gw, gb = lo.head_window_sums(crops, None)
+    assert torch.equal(gw, leaves[1].grad) and torch.equal(gb, leaves[2].grad)
+
+
+def test_image_head_window_controls():
+    B, H, W = lo.CASES["image_head"]
+    gen = torch.Generator().manual_seed(15)
+    crops, moved = [], []
+    for k, reg in enumerate(lo.pixel_windows(B, H, W, 64)):
+        crops.append((_grid(gen, (1, 16, 16, 64), 1 / 16), _grid(gen, (1, 16, 16, 3), 1 / 16)))
+        for mod, _ in lo.wrapped_pixel_regions(B, H, W, 64, reg):
+            moved.append(("window %d mod %d" % (k, mod), k, _grid(gen, (1, 16, 16, 64), 1 / 16)))
+    assert float(lo.head_window_sums([(z.abs(), g.abs()) for z, g in crops], None)[0].max()) * 2 ** 8 < 2 ** 24
+    gw32 = sum(g.float().reshape(-1, 3).t() @ z.float().reshape(-1, 64) for z, g in crops)
+    assert torch.equal(gw32.double(), lo.head_window_sums(crops, None)[0])              # exact in fp32 on the grids
+    controls = lo.head_controls(crops, moved)
+    assert len(controls) == len(crops) + len(moved) and len(moved) >= 2 and min(r for _, r in controls) >= 100.0, controls
+
+
+def test_flow_head_cap_keeps_its_operands_under_every_boundary(hip_lib):
+    """flow_head_train_check_shape caps the training flow head at 2^24 pixels (its pixel counts are fp32): there z has
+    2^28 elements and the upsampled gradient 2^27, below 2^29, so no GPU case exists for it; one pixel more is refused
+    by name."""
+    from qpwcnet_amd import _hip
+    text = open(os.path.join(CSRC, "capi.hip")).read()
+    body = re.search(r"static int flow_head_train_check_shape\(.*?\{(.*?)\n\}", text, re.S).group(1)
+    assert body.count("(int64_t)B * H * W > (1 << 24)") == 1
+    cap = 1 << 24
+    assert lo.crossed(cap * 16) == [] and lo.crossed(4 * cap * 2) == []
+    for fn in (hip_lib.qpwc_flow_head_bwd_workspace_floats, hip_lib.qpwc_flow_head_stats_workspace_floats):
+        assert fn(1, 4096, 4096) > 0
+        assert fn(1, 4097, 4096) == _hip.E_SHAPE and b"2^24" in hip_lib.qpwc_last_error()
+        assert fn(1, cap + 1, 1) == _hip.E_SHAPE and b"more than 2^24 pixels" in hip_lib.qpwc_last_error()
+
+
+# ---- losses and EPE: the GPU cases --------------------------------------------------------------------------------------
+def test_loss_and_epe_cases_cross_what_they_claim(hip_lib):
+    from qpwcnet_amd import _hip
+    from test_training_scale_cpu import EPE, LOSS
+    I = ctypes.c_int
+    aligned = 1 << 20
+
+    def pick(kind, B, H, W, h, w):
+        return hip_lib.qpwc_loss_fwd_kernel(kind, aligned, B, H, W, 2, (I * 1)(h), (I * 1)(w), 1).decode()
+
+    def ws(kind, B, H, W, h, w):
+        return hip_lib.qpwc_loss_workspace_floats(kind, B, H, W, 2, (I * 1)(h), (I * 1)(w), 1)
+
+    for name in ("loss", "epe"):
+        B, H, W, C = lo.CASES[name]
+        assert B == 3 and C == 2 and H != W and B * H * W > 1 << 30                  # more than 2^30 ground-truth pixels
+        assert lo.crossed(B * H * W * C) == [P29, P30, P31]
+        at = [lo.locate(b, H, W, C) for b in lo.BOUNDARIES]
+        assert [a[0] for a in at] == [0, 1, 2] and all(0 < y < H - 2 - lo.WIN and 0 < x < W - 1 for _, y, x in at)
+        assert H * W <= 2 ** 31 - 1 and B * -(-H // 32) * -(-W // 32) <= 2 ** 31 - 1  # what loss_check_shapes asks
+    # the tile case: H, W multiples of the tile, one half-resolution level -> loss_area_tile_kernel, float4 backward
+    key = lo.CASES["loss"]
+    B, H, W, C = key
+    h, w = H // 2, W // 2
+    assert H % LOSS["kLossTile"] == 0 and W % LOSS["kLossTile"] == 0
+    assert pick(_hip.LOSS_FLOW_MSE_V2, B, H, W, h, w) == "loss_area_tile_kernel"
+    assert ws(_hip.LOSS_FLOW_MSE_V2, B, H, W, h, w) == LOSS["kLossTileBlocks"]
+    tiles = B * (H // LOSS["kLossTile"]) * (W // LOSS["kLossTile"])
+    assert tiles > 256 * LOSS["kLossTileBlocks"] and tiles % LOSS["kLossTileBlocks"]   # every workgroup walks > 256 tiles
+    assert lo.crossed(B * h * w * C) == [P29] and (B * h * w * C) % 4 == 0
+    assert B * h * w * C // 4 > LOSS["kLossBwdBlocks"] * LOSS["kLossThreads"]
+    assert 4 * (B * H * W * C + 4 * B * h * w * C) == lo.loss_planned_bytes(key, (h, w), True) <= 48 * lo.GIB
+    wins = lo.loss_tile_windows(key)
+    assert [x[0] for x in wins] == ["first", ">2^29", "gt>2^29", "gt>2^30", "gt>2^31", "last"]
+    for i, a in enumerate(wins):
+        for b_ in wins[i + 1:]:
+            assert a[1] != b_[1] or a[3] <= b_[2] or b_[3] <= a[2] or a[5] <= b_[4] or b_[5] <= a[4], (a, b_)
+    for b, x in zip(lo.BOUNDARIES, wins[2:5]):                       # the ground truth under a window lies behind its boundary
+        assert b < ((x[1] * H + 2 * x[2]) * W + 2 * x[4]) * C < b + 6 * W * C
+    assert P29 < ((wins[1][1] * h + wins[1][2]) * w + wins[1][4]) * C < P29 + 2 * w * C
+    moved = [lo.wrapped_pixel_regions(B, H, W, C, (x[0], x[1], 2 * x[2], 2 * x[3], 2 * x[4], 2 * x[5])) for x in wins]
+    assert moved[0] == [] and all(m for m in moved[1:]) and {mod for m in moved for mod, _ in m} == {1 << 31, 1 << 32}
+    # the odd case: a full-resolution level -> loss_pixel_kernel for the area loss (1 x 1) and the bilinear one, the
+    # scalar backward (no multiple of 4), the EPE kernels' float4 loop with the odd last pixel
+    key = lo.CASES["epe"]
+    B, H, W, C = key
+    assert H % 2 and W % 2 and (B * H * W) % 2 and (B * H * W * C) % 4
+    for kind in (_hip.LOSS_FLOW_MSE_V2, _hip.LOSS_FLOW_MSE):
+        assert pick(kind, B, H, W, H, W) == "loss_pixel_kernel" and ws(kind, B, H, W, H, W) > 0
+    assert B * H * W > LOSS["kLossPixBlocks"] * LOSS["kLossThreads"] and B * H * W * C > LOSS["kLossBwdBlocks"] * LOSS["kLossThreads"]
+    assert B * H * W // 2 > 3 * EPE["kEpeMultiBlocks"] * EPE["kEpeThreads"] and B * H * W > EPE["kEpeBlocks"] * EPE["kEpeThreads"]
+    assert 4 * 4 * B * H * W * C == lo.loss_planned_bytes(key, (H, W), False) <= 48 * lo.GIB
+    wins = lo.pixel_windows(B, H, W, C)
+    assert [x[0] for x in wins] == ["first", ">2^29", ">2^30", ">2^31", "last"]
+    for b, x in zip(lo.BOUNDARIES, wins[1:4]):
+        assert b < ((x[1] * H + x[2]) * W + x[4]) * C < b + 2 * W * C
+    moved = [lo.wrapped_pixel_regions(B, H, W, C, x) for x in wins]
+    assert moved[0] == [] and all(m for m in moved[1:]) and {mod for m in moved for mod, _ in m} == {1 << 31, 1 << 32}
+    # the ctypes widths: element and pixel counts are 64-bit arrays on both sides; the extents are ints the cases keep small
+    protos = {name: (ret, params) for name, ret, params in parse_header()}
+    assert protos["qpwc_loss_bwd"][1].count("const int64_t*") == 1
+    assert _hip.PROTOTYPES["qpwc_loss_bwd"][1][3]._type_ is ctypes.c_int64
+    for name in ("qpwc_epe_multi_fwd", "qpwc_epe_multi_mixed_fwd"):
+        assert protos[name][1].count("const int64_t*") == 2
+        assert [t._type_ for t in _hip.PROTOTYPES[name][1][2:4]] == [ctypes.c_int64, ctypes.c_int64]
+    for name in ("qpwc_loss_fwd", "qpwc_epe_fwd", "qpwc_loss_workspace_floats"):
+        assert "int64_t" not in protos[name][1] and max(B, H, W) < 2 ** 31
+    assert protos["qpwc_loss_workspace_floats"][0] == "int64_t"
+
+
+@pytest.mark.parametrize("kind", ["v2", "norm"])
+def test_loss_window_reference_is_the_loss(kind):
+    """loss_window_ref on the windows alone is the loss of the whole tensors when the prediction equals the level's
+    ground truth elsewhere, and that loss is Keras' Huber mean / the mean end-point error; area_level_ref is the area
+    mean times the flow scale; the fp32 composition stays within a tenth of the GPU test's bound."""
+    from oracle import torch_ref
+    gen = torch.Generator().manual_seed(16)
+    gt = _grid(gen, (2, 40, 48, 2), 1 / 16)
+    gl = lo.area_level_ref(gt[:1], 2, 2, 0.5)
+    want = torch.nn.functional.avg_pool2d(gt[:1].permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1) * 0.5
+    assert torch.equal(gl, want)
+    gl = torch.cat([gl, lo.area_level_ref(gt[1:], 2, 2, 0.5)])
+    pred = gl.clone()
+    wins = [(0, 0, 8, 0, 8), (1, 5, 13, 9, 17), (1, 12, 20, 0, 8)]
+    crops = []
+    for n, y0, y1, x0, x1 in wins:
+        pred[n, y0:y1, x0:x1] += _grid(gen, (y1 - y0, x1 - x0, 2), 1 / 16)
+        crops.append((gl[n:n + 1, y0:y1, x0:x1], pred[n:n + 1, y0:y1, x0:x1]))
+    hw, n_pix = (20, 24), 2 * 20 * 24
+    value, grads = lo.loss_window_ref(kind, crops, n_pix, hw, 7.0)
+    whole, gw = lo.loss_window_ref(kind, [(gl, pred)], n_pix, hw, 7.0)
+    assert abs(float(value - whole)) <= 1e-15 * abs(float(whole)) + 1e-300
+    for (n, y0, y1, x0, x1), g in zip(wins, grads):
+        assert torch.equal(g[0], gw[0][n, y0:y1, x0:x1])
+    if kind == "v2":
+        s = 2.0 / (hw[0] + hw[1])
+        other = 7.0 * torch.nn.functional.huber_loss(s * pred, s * gl, delta=lo.LOSS_DELTA)
+    else:
+        other = 7.0 * torch_ref.epe_error(gl, pred)
+    assert abs(float(other - whole)) <= 1e-12 * abs(float(whole))
+    v32 = lo.loss_window_ref(kind, [(a.float(), b.float().double()) for a, b in crops], n_pix, hw, 7.0)[0]
+    assert abs(float(v32 - value)) <= 0.1 * lo.LOSS_REL * abs(float(value))
+
+
+@pytest.mark.parametrize("name,kind", [("loss", "v2"), ("epe", "v2"), ("epe", "norm")])
+def test_loss_negative_controls(name, kind):
+    key = lo.CASES[name]
+    B, H, W, C = key
+    tile = name == "loss"
+    h, w = (H // 2, W // 2) if tile else (H, W)
+    gen = torch.Generator().manual_seed(17)
+    crops, moved = [], []
+    for k, reg in enumerate(lo.loss_tile_windows(key) if tile else lo.pixel_windows(B, H, W, C)):
+        level = (lambda: lo.area_level_ref(_grid(gen, (1, 32, 32, 2), 1 / 16), 2, 2, 0.5)) if tile else \
+            (lambda: _grid(gen, (1, 16, 16, 2), 1 / 16))
+        gl = level()
+        crops.append((gl, gl + _grid(gen, (1, 16, 16, 2), 1 / 16)))
+        gt_reg = (reg[0], reg[1], 2 * reg[2], 2 * reg[3], 2 * reg[4], 2 * reg[5]) if tile else reg
+        for mod, _ in lo.wrapped_pixel_regions(B, H, W, C, gt_reg):
+            moved.append(("window %d mod %d" % (k, mod), k, level()))
+    controls = lo.loss_controls(kind, crops, moved, B * h * w, (h, w))
+    assert len(controls) == len(crops) + len(moved) and len(moved) >= 2
+    assert min(r for _, r in controls) >= 100.0, controls
