@@ -26,7 +26,7 @@
  *                 255.5 rule of qpwc_flow_to_image_fwd.  The grid is drawn before it.
  *   Non-finite values are outside the contract: the result is unspecified, no access leaves a buffer.
  *   Two launches, no atomics, no value read back and no state kept between calls (a captured graph replays them
- *   unchanged; two runs are bit-identical): review_mag_max_kernel writes one partial maximum per (flow, image, tile of
+ *   unchanged; two runs are bit-identical): flow_mag_max_kernel writes one partial maximum per (flow, image, tile of
  *   2048 flow pixels) to `ws`; review_panels_kernel folds the partials of its image and writes every picture of a tile
  *   of 256 pixels.  `ws` holds qpwc_review_workspace_floats floats and needs no initialisation.
  *   Store form, chosen from the shape alone: "review_panels_kernel<vec4>" when every picture's pixel count per image

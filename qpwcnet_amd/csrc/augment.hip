@@ -13,6 +13,7 @@
 // order as 16-byte stores.  No atomics: two runs are bit-identical.
 #include "augment_common.h"
 #include "launch.h"
+#include "pixel_io.h"
 
 namespace qpwc {
 
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* 
                                                                    int nblk, int flags, float* __restrict__ out_ims,
                                                                    float* __restrict__ out_flo,
                                                                    float* __restrict__ partial) {
-    __shared__ aug_f32x4 stage4[kAugThreads * 8 / 4];   // <vec4>: the chunk in output order, image then flow (8 KB)
+    __shared__ pix_f32x4 stage4[kAugThreads * 8 / 4];   // <vec4>: the chunk in output order, image then flow (8 KB)
     __shared__ float red[3][kAugThreads / 64];
     const int tid = threadIdx.x;
     const int b = blockIdx.x / nblk, chunk = blockIdx.x - b * nblk;
@@ -146,57 +147,23 @@ __global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* 
         if (tid < 3) partial[((int64_t)b * 3 + tid) * nblk + chunk] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
     }
 
+    // the image, then the flow: element by element, or <vec4> through LDS (pixel_io.h)
+    using Ims = TileStore<VEC, LAYOUT, 6, kAugThreads, kAugThreads, float>;
+    using Flo = TileStore<VEC, LAYOUT, 2, kAugThreads, kAugThreads, float>;
     const int64_t obase = (int64_t)b * hw;
-    if (!VEC) {
-        if (!valid) return;
-        if (LAYOUT == QPWC_NHWC) {
+    float* sims = reinterpret_cast<float*>(stage4);
+    float* sflo = sims + Ims::kElems;
+    if (VEC || valid) {
 #pragma unroll
-            for (int c = 0; c < 6; ++c) out_ims[(obase + pix) * 6 + c] = v[c];
-            out_flo[(obase + pix) * 2] = v[6];
-            out_flo[(obase + pix) * 2 + 1] = v[7];
-        } else {
+        for (int c = 0; c < 6; ++c) Ims::put(sims, out_ims, obase, hw, base, tid, c, v[c]);
 #pragma unroll
-            for (int c = 0; c < 6; ++c) out_ims[(obase * 6 + (int64_t)c * hw) + pix] = v[c];
-            out_flo[obase * 2 + pix] = v[6];
-            out_flo[obase * 2 + hw + pix] = v[7];
-        }
-        return;
+        for (int c = 0; c < 2; ++c) Flo::put(sflo, out_flo, obase, hw, base, tid, c, v[6 + c]);
     }
-    // <vec4>: hw % 4 == 0, so the chunk holds n = a multiple of 4 valid pixels and every 16-byte piece is whole
-    float* stage = reinterpret_cast<float*>(stage4);
-    float* sflo = stage + kAugThreads * 6;
-    const int n = min(kAugThreads, hw - base);
-    if (LAYOUT == QPWC_NHWC) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) stage[tid * 6 + c] = v[c];
-        sflo[tid * 2] = v[6];
-        sflo[tid * 2 + 1] = v[7];
-    } else {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) stage[c * kAugThreads + tid] = v[c];
-        sflo[tid] = v[6];
-        sflo[kAugThreads + tid] = v[7];
-    }
+    if (!VEC) return;
     __syncthreads();
-    aug_f32x4* o4 = reinterpret_cast<aug_f32x4*>(out_ims);
-    aug_f32x4* of4 = reinterpret_cast<aug_f32x4*>(out_flo);
-    const aug_f32x4* sflo4 = stage4 + kAugThreads * 6 / 4;
-    if (LAYOUT == QPWC_NHWC) {
-        const int64_t g = (obase + base) * 6 / 4;
-        for (int i = tid; i < n * 6 / 4; i += kAugThreads) o4[g + i] = stage4[i];
-        const int64_t gf = (obase + base) * 2 / 4;
-        if (tid < n * 2 / 4) of4[gf + tid] = sflo4[tid];
-    } else {
-        const int q = kAugThreads / 4;   // 16-byte pieces of one plane of the chunk
-        for (int i = tid; i < 6 * q; i += kAugThreads) {
-            const int c = i / q, j = i - c * q;
-            if (4 * j < n) o4[(obase * 6 + (int64_t)c * hw + base) / 4 + j] = stage4[i];
-        }
-        if (tid < 2 * q) {
-            const int c = tid / q, j = tid - c * q;
-            if (4 * j < n) of4[(obase * 2 + (int64_t)c * hw + base) / 4 + j] = sflo4[tid];
-        }
-    }
+    const int n = min(kAugThreads, hw - base);
+    Ims::flush(sims, out_ims, obase, hw, base, n);
+    Flo::flush(sflo, out_flo, obase, hw, base, n);
 }
 
 // blockIdx.x = sample * nblk2 + chunk of kAugPass2Pixels pixels: adjust_contrast with the mean of each colour channel
@@ -234,9 +201,9 @@ __global__ __launch_bounds__(kAugThreads) void augment_contrast_kernel(float* __
     const int64_t e0 = (int64_t)chunk * kAugPass2Pixels * 6;
     const int64_t e1 = min(e0 + (int64_t)kAugPass2Pixels * 6, (int64_t)hw * 6);
     if (VEC) {
-        aug_f32x4* p4 = reinterpret_cast<aug_f32x4*>(img);
+        pix_f32x4* p4 = reinterpret_cast<pix_f32x4*>(img);
         for (int64_t i = e0 / 4 + tid; i < e1 / 4; i += kAugThreads) {
-            aug_f32x4 x = p4[i];
+            pix_f32x4 x = p4[i];
             if (LAYOUT == QPWC_NHWC) {
                 const int c = (int)((4 * i) % 6);   // 0, 4 or 2
                 x.x = fin(x.x, c % 3);
@@ -262,7 +229,7 @@ __global__ __launch_bounds__(kAugThreads) void augment_contrast_kernel(float* __
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static int64_t aug_nblk(int h, int w) { return ((int64_t)h * w + kAugThreads - 1) / kAugThreads; }
+static int64_t aug_nblk(int h, int w) { return ceil_div((int64_t)h * w, kAugThreads); }
 
 // 3 partial sums per pass-1 workgroup
 int64_t augment_workspace_floats(int B, int h, int w) { return 3 * (int64_t)B * aug_nblk(h, w); }
@@ -287,34 +254,24 @@ int augment_fwd_launch(const void* ims, bool u8, const float* flo, int B, int H,
     const int nblk = (int)aug_nblk(h, w);
     const bool vec = aug_vec(h, w, out_ims, out_flo);
     const dim3 grid((unsigned)(B * nblk)), block(kAugThreads);
-#define QPWC_AUG_PIX(U, L, V)                                                                                          \
-    hipLaunchKernelGGL((augment_pixel_kernel<U, L, V>), grid, block, 0, s, ims, flo, H, W, iparams, fparams, h, w, nblk, \
-                       flags, out_ims, out_flo, ws)
-#define QPWC_AUG_PIX_LV(U)                                                                                             \
-    do {                                                                                                               \
-        if (layout == QPWC_NHWC) {                                                                                     \
-            if (vec) QPWC_AUG_PIX(U, QPWC_NHWC, true); else QPWC_AUG_PIX(U, QPWC_NHWC, false);                         \
-        } else {                                                                                                       \
-            if (vec) QPWC_AUG_PIX(U, QPWC_NCHW, true); else QPWC_AUG_PIX(U, QPWC_NCHW, false);                         \
-        }                                                                                                              \
-    } while (0)
-    if (u8) QPWC_AUG_PIX_LV(true);
-    else QPWC_AUG_PIX_LV(false);
-#undef QPWC_AUG_PIX_LV
-#undef QPWC_AUG_PIX
+    dispatch_bool(u8, [&](auto U) {
+        dispatch_layout(layout, [&](auto L) {
+            dispatch_bool(vec, [&](auto V) {
+                hipLaunchKernelGGL((augment_pixel_kernel<decltype(U)::value, decltype(L)::value, decltype(V)::value>), grid,
+                                   block, 0, s, ims, flo, H, W, iparams, fparams, h, w, nblk, flags, out_ims, out_flo, ws);
+            });
+        });
+    });
     int rc = check_launch("augment_pixel_kernel");
     if (rc != QPWC_OK || !(flags & QPWC_AUGMENT_COLOR)) return rc;
-    const int nblk2 = (int)(((int64_t)h * w + kAugPass2Pixels - 1) / kAugPass2Pixels);
+    const int nblk2 = (int)ceil_div((int64_t)h * w, kAugPass2Pixels);
     const dim3 grid2((unsigned)(B * nblk2));
-#define QPWC_AUG_CON(L, V)                                                                                             \
-    hipLaunchKernelGGL((augment_contrast_kernel<L, V>), grid2, block, 0, s, out_ims, ws, fparams, h, w, nblk, nblk2,    \
-                       flags & QPWC_AUGMENT_RAW)
-    if (layout == QPWC_NHWC) {
-        if (vec) QPWC_AUG_CON(QPWC_NHWC, true); else QPWC_AUG_CON(QPWC_NHWC, false);
-    } else {
-        if (vec) QPWC_AUG_CON(QPWC_NCHW, true); else QPWC_AUG_CON(QPWC_NCHW, false);
-    }
-#undef QPWC_AUG_CON
+    dispatch_layout(layout, [&](auto L) {
+        dispatch_bool(vec, [&](auto V) {
+            hipLaunchKernelGGL((augment_contrast_kernel<decltype(L)::value, decltype(V)::value>), grid2, block, 0, s,
+                               out_ims, ws, fparams, h, w, nblk, nblk2, flags & QPWC_AUGMENT_RAW);
+        });
+    });
     return check_launch("augment_contrast_kernel");
 }
 

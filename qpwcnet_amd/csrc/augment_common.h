@@ -10,8 +10,6 @@ namespace qpwc {
 
 constexpr int kAugThreads = 256;
 
-typedef float aug_f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 // index of floor / ceil of a source coordinate, clamped into the image whatever the parameters hold (NaN -> 0)

@@ -179,6 +179,8 @@ const char* flow_to_image_fwd_kernel(int n, const int* oh, const int* ow, const 
 int flow_to_image_fwd_launch(const void* const* flows, const int* f16, const int* h, const int* w, int n, int B,
                              int in_layout, void* const* outs, const int* oh, const int* ow, bool u8, int out_layout,
                              float* ws, hipStream_t s);
+struct VisMaxLevels;   // vis_common.h
+int flow_mag_max_launch(const VisMaxLevels& m, int blocks, int in_layout, float* ws, hipStream_t s);
 
 // quality.hip (include/qpwc_quality.h)
 bool image_quality_shape_ok(int B, int H, int W, int C);

@@ -1,8 +1,8 @@
 // The inference review panels (include/qpwc_review.h): every picture qpwcnet/app/optical_flow/test_infer.py:104-154
 // (set 1, ten pictures) and qpwcnet/app/frame_interpolation/pre_train_test.py:45-79, 121-163 (set 2, seven pictures, the
 // alignment grid and the 8-bit export) show for a batch, in two launches:
-//   review_mag_max_kernel  one workgroup per (flow, image, tile of 2048 flow pixels) writes the tile's largest magnitude
-//                          to the workspace;
+//   flow_mag_max_kernel    vis.hip's, with the one or two flows as its levels: one workgroup per (flow, image, tile of
+//                          2048 flow pixels) writes the tile's largest magnitude to the workspace;
 //   review_panels_kernel   one workgroup per (image, tile of 256 pixels), one lane per pixel: the lane reads its image
 //                          values and flows, gathers the corners of its tf_warp samples (2 x 4 x 3 values in set 1,
 //                          4 x 3 in set 2), folds the partials of its image and writes its pixel of every picture: 30
@@ -12,12 +12,14 @@
 // (channels-last pictures have 12-byte pixels): 16-byte stores for fp32, packed dwords for uint8.  The form follows from
 // the shape alone (every picture's pixel count a multiple of 4); the boundary demands the alignment it needs, so no
 // pointer's low bits are looked at here.  No atomics and no state between calls: two runs are bit-identical and a
-// captured graph replays both launches unchanged.  The sampling rule is common.h's taps_tfwarp / blend, the colouring
-// vis_common.h's vis_colour: the code of qpwc_warp_fwd and qpwc_flow_to_image_fwd, not a copy of it.
+// captured graph replays both launches unchanged.  The sampling rule is common.h's taps_tfwarp / blend, the flow load,
+// the fold and the colouring vis_common.h's, the tile store pixel_io.h's: the code of qpwc_warp_fwd and
+// qpwc_flow_to_image_fwd, not a copy of it.
 #include <limits.h>
 
 #include "../../include/qpwc_review.h"
 #include "launch.h"
+#include "pixel_io.h"
 #include "vis_common.h"
 
 // every product and sum of include/qpwc_review.h is rounded separately
@@ -26,9 +28,6 @@
 namespace qpwc {
 
 constexpr int kRevTile = kVisThreads;    // pixels per workgroup of the panel launch, one per lane
-constexpr int kRevQuads = kRevTile * 3 / 4;   // 16-byte pieces (fp32) / dwords (uint8) of one picture's tile: 192
-
-typedef float rev_f32x4 __attribute__((ext_vector_type(4)));
 
 struct RevArgs {
     const void* img[3];      // set 1: ims; set 2: img_pair, img1, pred
@@ -46,24 +45,6 @@ namespace {
 
 __device__ __forceinline__ float rev_ld(const void* img, int f16, int64_t at) {
     return f16 ? __half2float(reinterpret_cast<const __half*>(img)[at]) : reinterpret_cast<const float*>(img)[at];
-}
-
-// (fx, fy) of pixel `pix` of image n of a (B,h,w,2) / (B,2,h,w) fp32 flow with hw pixels per image
-__device__ __forceinline__ float2 rev_flow(const float* flow, int nhwc, int64_t n, int pix, int hw) {
-    if (nhwc) {
-        const float* p = flow + (n * hw + pix) * 2;
-        return make_float2(p[0], p[1]);
-    }
-    const float* p = flow + n * 2 * hw + pix;
-    return make_float2(p[0], p[hw]);
-}
-
-// the maximum of image n's magnitudes of flow k: its mtiles partials, written by the launch before this one
-__device__ __forceinline__ float rev_fold(const float* ws, int k, int n, int B, int mt, float* red) {
-    const float* part = ws + ((int64_t)k * B + n) * mt;
-    float m = 0.0f;
-    for (int i = threadIdx.x; i < mt; i += kVisThreads) m = fmaxf(m, part[i]);
-    return vis_block_max(m, red);
 }
 
 // _show's export: (255 * np.clip(x, 0, 1)).astype(np.uint8)
@@ -85,11 +66,12 @@ __device__ __forceinline__ void rev_warp3(const void* img, int f16, int64_t ib, 
 // stores.  outs[p]: (B,oh,ow,3) / (B,3,oh,ow).  Every lane of the workgroup calls it (<vec4> has a barrier).
 template <int OUT_LAYOUT, bool U8, bool VEC, int NP>
 __device__ __forceinline__ void rev_emit(const float (&v)[NP][3], void* const* outs, int n, int base, int ohw, int ow,
-                                         int grid, rev_f32x4* stage4) {
+                                         int grid, pix_f32x4* stage4) {
+    using T = std::conditional_t<U8, uint8_t, float>;
+    using Tile = TileStore<VEC, OUT_LAYOUT, 3, kRevTile, kVisThreads, T>;   // pixel_io.h; a picture's tile
     const int tid = threadIdx.x, pix = base + tid;
     const int64_t obase = (int64_t)n * ohw;   // first pixel of the image
-    float* stage = reinterpret_cast<float*>(stage4);
-    uint8_t* stage_b = reinterpret_cast<uint8_t*>(stage4);
+    T* stage = reinterpret_cast<T*>(stage4);
     if (pix < ohw) {
         bool line = false;
         if (grid > 0) {
@@ -101,73 +83,29 @@ __device__ __forceinline__ void rev_emit(const float (&v)[NP][3], void* const* o
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float x = line ? 1.0f : v[p][c];
-                if (VEC) {
-                    const int at = p * (kRevTile * 3) + (OUT_LAYOUT == QPWC_NHWC ? tid * 3 + c : c * kRevTile + tid);
-                    if (U8) stage_b[at] = rev_u8(x);
-                    else stage[at] = x;
-                } else {
-                    const int64_t at = OUT_LAYOUT == QPWC_NHWC ? (obase + pix) * 3 + c : (obase * 3 + (int64_t)c * ohw) + pix;
-                    if (U8) reinterpret_cast<uint8_t*>(outs[p])[at] = rev_u8(x);
-                    else reinterpret_cast<float*>(outs[p])[at] = x;
-                }
+                Tile::put(stage + p * Tile::kElems, reinterpret_cast<T*>(outs[p]), obase, ohw, base, tid, c,
+                          U8 ? (T)rev_u8(x) : (T)x);
             }
         }
     }
     if (!VEC) return;
-    // <vec4>: ohw % 4 == 0, so the tile holds cnt = a multiple of 4 pixels: whole 16-byte pieces of fp32 in either
-    // layout, whole dwords of uint8; every output and with it every image, plane and tile starts 16-byte (fp32) / 4-byte
-    // (uint8) aligned (the boundary refuses any other).  A picture's tile is kRevQuads pieces in its own order.
+    // the pictures' alignment is the boundary's demand: it refuses an output off the piece's grid
     __syncthreads();
     const int cnt = min(kRevTile, ohw - base);
-    if (tid >= kRevQuads) return;
-    int64_t g;    // the lane's piece of the picture
-    bool ok;
-    if (OUT_LAYOUT == QPWC_NHWC) {
-        g = (obase + base) * 3 / 4 + tid;
-        ok = tid < cnt * 3 / 4;
-    } else {
-        const int c = tid / (kRevTile / 4), i = tid - c * (kRevTile / 4);
-        g = (obase * 3 + (int64_t)c * ohw + base) / 4 + i;
-        ok = 4 * i < cnt;
-    }
-    if (!ok) return;
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        if (U8) reinterpret_cast<uint32_t*>(outs[p])[g] = reinterpret_cast<const uint32_t*>(stage4)[p * kRevQuads + tid];
-        else reinterpret_cast<rev_f32x4*>(outs[p])[g] = stage4[p * kRevQuads + tid];
-    }
+    for (int p = 0; p < NP; ++p) Tile::flush(stage + p * Tile::kElems, reinterpret_cast<T*>(outs[p]), obase, ohw, base, cnt);
 }
 
 }  // namespace
 
-// blockIdx.x = (flow * B + image) * mtiles + tile; ws[blockIdx.x] = the tile's largest magnitude
-__global__ __launch_bounds__(kVisThreads) void review_mag_max_kernel(const float* __restrict__ f0,
-                                                                     const float* __restrict__ f1, int B, int hw, int mt,
-                                                                     int nhwc, float* __restrict__ ws) {
-    __shared__ float red[kVisThreads / 64];
-    const int bid = blockIdx.x;
-    const int per = B * mt;
-    const int k = bid / per, rel = bid - k * per;
-    const int n = rel / mt, tile = rel - n * mt;
-    const float* flow = k ? f1 : f0;
-    float m2 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVisMaxPix; ++j) {
-        const int64_t pix = (int64_t)tile * kVisMaxTile + j * kVisThreads + (int)threadIdx.x;
-        if (pix < hw) m2 = fmaxf(m2, vis_mag2(rev_flow(flow, nhwc, n, (int)pix, hw)));
-    }
-    m2 = vis_block_max(m2, red);
-    // the square root is monotone: the root of the largest square is the largest magnitude, bit for bit
-    if (threadIdx.x == 0) ws[bid] = sqrtf(m2);
-}
-
+// The partials of flow k lie from ws[k * B * mtiles] on (the max launch: flow_mag_max_kernel, vis.hip).
 // blockIdx.x = image * tiles + tile for the H x W pictures; SET 2: from B * tiles on, image * ftiles + tile of 5-flow.
 // Lane t owns pixel tile * 256 + t (row-major).
 template <int SET, int OUT_LAYOUT, bool U8, bool VEC>
 __global__ __launch_bounds__(kVisThreads) void review_panels_kernel(RevArgs a, const float* __restrict__ ws) {
     constexpr int NP = SET == 1 ? 10 : 6;
     __shared__ float red[2][kVisThreads / 64];
-    __shared__ rev_f32x4 stage4[VEC ? NP * kRevTile * 3 / (U8 ? 16 : 4) : 1];   // <vec4>: the tiles in output order
+    __shared__ pix_f32x4 stage4[VEC ? NP * kRevTile * 3 / (U8 ? 16 : 4) : 1];   // <vec4>: the tiles in output order
     const int tid = threadIdx.x;
     const int bid = blockIdx.x;
     const int H = a.H, W = a.W, HW = H * W;
@@ -177,9 +115,9 @@ __global__ __launch_bounds__(kVisThreads) void review_panels_kernel(RevArgs a, c
         const int rel = bid - a.B * a.tiles;
         const int n = rel / a.ftiles, tile = rel - n * a.ftiles;
         const int hw = a.h * a.w, base = tile * kRevTile, pix = base + tid;
-        const float denom = rev_fold(ws, 0, n, a.B, a.mtiles, red[0]) + 1e-6f;
+        const float denom = vis_fold_max(ws, 0, n, a.mtiles, red[0]) + 1e-6f;
         float v[1][3] = {{0.0f, 0.0f, 0.0f}};
-        if (pix < hw) vis_colour(rev_flow(a.flow[0], nhwc, n, pix, hw), denom, v[0]);
+        if (pix < hw) vis_colour(vis_load(a.flow[0], nhwc, 0, 0, n, pix, hw), denom, v[0]);
         rev_emit<OUT_LAYOUT, U8, VEC, 1>(v, a.out + 6, n, base, hw, a.w, a.grid, stage4);
         return;
     }
@@ -193,12 +131,13 @@ __global__ __launch_bounds__(kVisThreads) void review_panels_kernel(RevArgs a, c
     float v[NP][3] = {};
 
     if (SET == 1) {
-        const float denom0 = rev_fold(ws, 0, n, a.B, a.mtiles, red[0]) + 1e-6f;
-        const float denom1 = rev_fold(ws, 1, n, a.B, a.mtiles, red[1]) + 1e-6f;
+        const float denom0 = vis_fold_max(ws, 0, n, a.mtiles, red[0]) + 1e-6f;
+        const float denom1 = vis_fold_max(ws, a.B * a.mtiles, n, a.mtiles, red[1]) + 1e-6f;
         if (live) {
             const void* ims = a.img[0];
             const int64_t ib = (int64_t)n * 6 * HW, at = ib + (int64_t)pix * ps6;
-            const float2 flo = rev_flow(a.flow[0], nhwc, n, pix, HW), flo_pred = rev_flow(a.flow[1], nhwc, n, pix, HW);
+            const float2 flo = vis_load(a.flow[0], nhwc, 0, 0, n, pix, HW);
+            const float2 flo_pred = vis_load(a.flow[1], nhwc, 0, 0, n, pix, HW);
             float w_pred[3], w_gt[3];
             rev_warp3(ims, f16, ib + 3 * cs, ps6, cs, Y, X, flo_pred, H, W, w_pred);
             rev_warp3(ims, f16, ib + 3 * cs, ps6, cs, Y, X, flo, H, W, w_gt);
@@ -223,7 +162,7 @@ __global__ __launch_bounds__(kVisThreads) void review_panels_kernel(RevArgs a, c
         const int64_t ib6 = (int64_t)n * 6 * HW, ib3 = (int64_t)n * 3 * HW;
         const int64_t at6 = ib6 + (int64_t)pix * ps6, at3 = ib3 + (int64_t)pix * ps3;
         const int s = a.s;
-        const float2 f = rev_flow(a.flow[0], nhwc, n, (Y / s) * a.w + X / s, a.h * a.w);
+        const float2 f = vis_load(a.flow[0], nhwc, 0, 0, n, (Y / s) * a.w + X / s, a.h * a.w);
         const float2 up = make_float2((float)s * f.x, (float)s * f.y);
         rev_warp3(img1, f16, ib3, ps3, cs, Y, X, up, H, W, v[5]);
 #pragma unroll
@@ -241,17 +180,18 @@ __global__ __launch_bounds__(kVisThreads) void review_panels_kernel(RevArgs a, c
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static int64_t rev_tiles(int a, int b, int tile) { return ((int64_t)a * b + tile - 1) / tile; }
-
 // every count the launches index with fits 32 bits: 6 * B * H * W (the largest tensor) and the workgroups of both launches
 bool review_shape_ok(int n_flows, int B, int H, int W, int h, int w) {
     if (6 * (int64_t)B * H * W > INT32_MAX || 2 * (int64_t)B * h * w > INT32_MAX) return false;
-    const int64_t mblk = (int64_t)n_flows * B * rev_tiles(h, w, kVisMaxTile);
-    const int64_t pblk = B * (rev_tiles(H, W, kRevTile) + (n_flows == 1 ? rev_tiles(h, w, kRevTile) : 0));
-    return mblk <= INT32_MAX && pblk <= INT32_MAX;
+    const int64_t HW = (int64_t)H * W, hw = (int64_t)h * w;
+    const int64_t pblk = B * (ceil_div(HW, kRevTile) + (n_flows == 1 ? ceil_div(hw, kRevTile) : 0));
+    return review_workspace_floats(n_flows, B, h, w) <= INT32_MAX && pblk <= INT32_MAX;
 }
 
-int64_t review_workspace_floats(int n_flows, int B, int h, int w) { return (int64_t)n_flows * B * rev_tiles(h, w, kVisMaxTile); }
+// one partial per workgroup of the max launch
+int64_t review_workspace_floats(int n_flows, int B, int h, int w) {
+    return (int64_t)n_flows * B * ceil_div((int64_t)h * w, kVisMaxTile);
+}
 
 bool review_panels_vec(int n_flows, int H, int W, int h, int w) {
     return ((int64_t)H * W) % 4 == 0 && (n_flows == 2 || ((int64_t)h * w) % 4 == 0);
@@ -264,30 +204,32 @@ const char* review_panels_fwd_kernel(int n_flows, int H, int W, int h, int w) {
 template <int SET>
 static int review_launch(RevArgs a, bool u8, int out_layout, float* ws, hipStream_t s) {
     const int n_flows = SET == 1 ? 2 : 1;
-    a.mtiles = (int)rev_tiles(a.h, a.w, kVisMaxTile);
-    a.tiles = (int)rev_tiles(a.H, a.W, kRevTile);
-    a.ftiles = SET == 2 ? (int)rev_tiles(a.h, a.w, kRevTile) : 0;
-    const dim3 block(kVisThreads);
-    hipLaunchKernelGGL(review_mag_max_kernel, dim3((unsigned)(n_flows * a.B * a.mtiles)), block, 0, s, a.flow[0],
-                       a.flow[SET == 1 ? 1 : 0], a.B, a.h * a.w, a.mtiles, a.nhwc, ws);
-    int rc = check_launch("review_mag_max_kernel");
+    a.mtiles = (int)ceil_div((int64_t)a.h * a.w, kVisMaxTile);
+    a.tiles = (int)ceil_div((int64_t)a.H * a.W, kRevTile);
+    a.ftiles = SET == 2 ? (int)ceil_div((int64_t)a.h * a.w, kRevTile) : 0;
+    // the max launch: the fp32 flows as levels of one size, each read element by element
+    VisMaxLevels m = {};
+    for (int k = 0; k < kVisMaxLevels; ++k) {
+        m.mblk0[k] = INT_MAX;
+        if (k >= n_flows) continue;
+        m.flow[k] = a.flow[k];
+        m.hw[k] = a.h * a.w;
+        m.mtiles[k] = a.mtiles;
+        m.mblk0[k] = k * a.B * a.mtiles;
+    }
+    const int rc = flow_mag_max_launch(m, n_flows * a.B * a.mtiles, a.nhwc ? QPWC_NHWC : QPWC_NCHW, ws, s);
     if (rc != QPWC_OK) return rc;
 
     const bool vec = review_panels_vec(n_flows, a.H, a.W, a.h, a.w);
-    const dim3 grid((unsigned)(a.B * (a.tiles + a.ftiles)));
-#define QPWC_REV(O, U, V) hipLaunchKernelGGL((review_panels_kernel<SET, O, U, V>), grid, block, 0, s, a, (const float*)ws)
-#define QPWC_REV_UV(O)                                                    \
-    do {                                                                  \
-        if (u8) {                                                         \
-            if (vec) QPWC_REV(O, true, true); else QPWC_REV(O, true, false);   \
-        } else {                                                          \
-            if (vec) QPWC_REV(O, false, true); else QPWC_REV(O, false, false); \
-        }                                                                 \
-    } while (0)
-    if (out_layout == QPWC_NHWC) QPWC_REV_UV(QPWC_NHWC);
-    else QPWC_REV_UV(QPWC_NCHW);
-#undef QPWC_REV_UV
-#undef QPWC_REV
+    dispatch_layout(out_layout, [&](auto O) {
+        dispatch_bool(u8, [&](auto U) {
+            dispatch_bool(vec, [&](auto V) {
+                hipLaunchKernelGGL((review_panels_kernel<SET, decltype(O)::value, decltype(U)::value, decltype(V)::value>),
+                                   dim3((unsigned)(a.B * (a.tiles + a.ftiles))), dim3(kVisThreads), 0, s, a,
+                                   (const float*)ws);
+            });
+        });
+    });
     return check_launch("review_panels_kernel");
 }
 

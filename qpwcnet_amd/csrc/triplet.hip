@@ -11,6 +11,7 @@
 #include "../../include/qpwc_triplet.h"
 #include "augment_common.h"
 #include "launch.h"
+#include "pixel_io.h"
 
 namespace qpwc {
 
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(kAugThreads) void triplet_pixel_kernel(const void* 
                                                                    const float* __restrict__ fparams, int h, int w,
                                                                    int nblk, int flags, float* __restrict__ out_pair,
                                                                    float* __restrict__ out_mid) {
-    __shared__ aug_f32x4 stage4[kAugThreads * 9 / 4];   // <vec4>: the chunk in output order, pair then middle (9 KB)
+    __shared__ pix_f32x4 stage4[kAugThreads * 9 / 4];   // <vec4>: the chunk in output order, pair then middle (9 KB)
     const int tid = threadIdx.x;
     const int b = blockIdx.x / nblk, chunk = blockIdx.x - b * nblk;
     const int hw = h * w;
@@ -111,57 +112,23 @@ __global__ __launch_bounds__(kAugThreads) void triplet_pixel_kernel(const void* 
         }
     }
 
+    // the pair, then the middle frame: element by element, or <vec4> through LDS (pixel_io.h)
+    using Pair = TileStore<VEC, LAYOUT, 6, kAugThreads, kAugThreads, float>;
+    using Mid = TileStore<VEC, LAYOUT, 3, kAugThreads, kAugThreads, float>;
     const int64_t obase = (int64_t)b * hw;
-    if (!VEC) {
-        if (!valid) return;
-        if (LAYOUT == QPWC_NHWC) {
+    float* spair = reinterpret_cast<float*>(stage4);
+    float* smid = spair + Pair::kElems;
+    if (VEC || valid) {
 #pragma unroll
-            for (int c = 0; c < 6; ++c) out_pair[(obase + pix) * 6 + c] = v[c];
+        for (int c = 0; c < 6; ++c) Pair::put(spair, out_pair, obase, hw, base, tid, c, v[c]);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) out_mid[(obase + pix) * 3 + c] = v[6 + c];
-        } else {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) out_pair[(obase * 6 + (int64_t)c * hw) + pix] = v[c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) out_mid[(obase * 3 + (int64_t)c * hw) + pix] = v[6 + c];
-        }
-        return;
+        for (int c = 0; c < 3; ++c) Mid::put(smid, out_mid, obase, hw, base, tid, c, v[6 + c]);
     }
-    // <vec4>: hw % 4 == 0, so the chunk holds n = a multiple of 4 valid pixels and every 16-byte piece is whole
-    float* stage = reinterpret_cast<float*>(stage4);
-    float* smid = stage + kAugThreads * 6;
-    const int n = min(kAugThreads, hw - base);
-    if (LAYOUT == QPWC_NHWC) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) stage[tid * 6 + c] = v[c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) smid[tid * 3 + c] = v[6 + c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) stage[c * kAugThreads + tid] = v[c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) smid[c * kAugThreads + tid] = v[6 + c];
-    }
+    if (!VEC) return;
     __syncthreads();
-    aug_f32x4* o4 = reinterpret_cast<aug_f32x4*>(out_pair);
-    aug_f32x4* om4 = reinterpret_cast<aug_f32x4*>(out_mid);
-    const aug_f32x4* smid4 = stage4 + kAugThreads * 6 / 4;
-    if (LAYOUT == QPWC_NHWC) {
-        const int64_t g = (obase + base) * 6 / 4;
-        for (int i = tid; i < n * 6 / 4; i += kAugThreads) o4[g + i] = stage4[i];
-        const int64_t gm = (obase + base) * 3 / 4;
-        if (tid < n * 3 / 4) om4[gm + tid] = smid4[tid];
-    } else {
-        const int q = kAugThreads / 4;   // 16-byte pieces of one plane of the chunk
-        for (int i = tid; i < 6 * q; i += kAugThreads) {
-            const int c = i / q, j = i - c * q;
-            if (4 * j < n) o4[(obase * 6 + (int64_t)c * hw + base) / 4 + j] = stage4[i];
-        }
-        if (tid < 3 * q) {
-            const int c = tid / q, j = tid - c * q;
-            if (4 * j < n) om4[(obase * 3 + (int64_t)c * hw + base) / 4 + j] = smid4[tid];
-        }
-    }
+    const int n = min(kAugThreads, hw - base);
+    Pair::flush(spair, out_pair, obase, hw, base, n);
+    Mid::flush(smid, out_mid, obase, hw, base, n);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -177,24 +144,17 @@ const char* augment_triplet_fwd_kernel(int h, int w, const void* out_pair, const
 int augment_triplet_fwd_launch(const void* a, const void* b, const void* c, bool u8, int B, int H, int W,
                                const int* iparams, const float* fparams, int h, int w, int flags, int layout,
                                float* out_pair, float* out_mid, hipStream_t s) {
-    const int nblk = (int)(((int64_t)h * w + kAugThreads - 1) / kAugThreads);
+    const int nblk = (int)ceil_div((int64_t)h * w, kAugThreads);
     const bool vec = tri_vec(h, w, out_pair, out_mid);
     const dim3 grid((unsigned)(B * nblk)), block(kAugThreads);
-#define QPWC_TRI_PIX(U, L, V)                                                                                          \
-    hipLaunchKernelGGL((triplet_pixel_kernel<U, L, V>), grid, block, 0, s, a, b, c, H, W, iparams, fparams, h, w, nblk, \
-                       flags, out_pair, out_mid)
-#define QPWC_TRI_PIX_LV(U)                                                                                             \
-    do {                                                                                                               \
-        if (layout == QPWC_NHWC) {                                                                                     \
-            if (vec) QPWC_TRI_PIX(U, QPWC_NHWC, true); else QPWC_TRI_PIX(U, QPWC_NHWC, false);                         \
-        } else {                                                                                                       \
-            if (vec) QPWC_TRI_PIX(U, QPWC_NCHW, true); else QPWC_TRI_PIX(U, QPWC_NCHW, false);                         \
-        }                                                                                                              \
-    } while (0)
-    if (u8) QPWC_TRI_PIX_LV(true);
-    else QPWC_TRI_PIX_LV(false);
-#undef QPWC_TRI_PIX_LV
-#undef QPWC_TRI_PIX
+    dispatch_bool(u8, [&](auto U) {
+        dispatch_layout(layout, [&](auto L) {
+            dispatch_bool(vec, [&](auto V) {
+                hipLaunchKernelGGL((triplet_pixel_kernel<decltype(U)::value, decltype(L)::value, decltype(V)::value>), grid,
+                                   block, 0, s, a, b, c, H, W, iparams, fparams, h, w, nblk, flags, out_pair, out_mid);
+            });
+        });
+    });
     return check_launch("triplet_pixel_kernel");
 }
 

@@ -14,6 +14,7 @@
 
 #include "../../include/qpwc_vis.h"
 #include "launch.h"
+#include "pixel_io.h"
 #include "vis_common.h"
 
 // (1 - s) + s * d and the hue are separately rounded products and sums, as include/qpwc_vis.h states them
@@ -21,24 +22,16 @@
 
 namespace qpwc {
 
-constexpr int kVisMaxLevels = 8;
-
-typedef float vis_f32x4 __attribute__((ext_vector_type(4)));
-
 struct VisLevels {
-    const void* flow[kVisMaxLevels];
+    VisMaxLevels m;                              // the flows and their partials
     void* out[kVisMaxLevels];
     int h[kVisMaxLevels], w[kVisMaxLevels];      // the flow's own size
     int oh[kVisMaxLevels], ow[kVisMaxLevels];    // the picture's size
-    int f16[kVisMaxLevels];
-    int pair[kVisMaxLevels];                     // NHWC and the flow aligned to a whole pixel: one load per pixel
     float ry[kVisMaxLevels], rx[kVisMaxLevels];  // (float)h / oh, (float)w / ow
     int step_y[kVisMaxLevels], step_x[kVisMaxLevels];   // 256 output pixels further: 256 / ow rows and 256 % ow columns
-    int mtiles[kVisMaxLevels];                   // max-tiles per image
     int ctiles[kVisMaxLevels];                   // colour tiles per image
-    int mblk0[kVisMaxLevels];                    // the level's first workgroup of the max launch = its first partial
     int cblk0[kVisMaxLevels];                    // the level's first workgroup of the colour launch
-};                                               // unused levels: mblk0 = cblk0 = INT_MAX
+};                                               // unused levels: m.mblk0 = cblk0 = INT_MAX
 
 namespace {
 
@@ -48,29 +41,6 @@ __device__ __forceinline__ int vis_level(const int* blk0, int bid) {
 #pragma unroll
     for (int k = 1; k < kVisMaxLevels; ++k) l += bid >= blk0[k] ? 1 : 0;
     return l;
-}
-
-// (fx, fy) of pixel `pix` of image n of a (B,h,w,2) / (B,2,h,w) flow with hw pixels per image
-template <int IN_LAYOUT>
-__device__ __forceinline__ float2 vis_load(const void* flow, int f16, int pair, int64_t n, int pix, int hw) {
-    if (IN_LAYOUT == QPWC_NHWC) {
-        const int64_t o = (n * hw + pix) * 2;
-        if (f16) {
-            const __half* p = reinterpret_cast<const __half*>(flow) + o;
-            if (pair) return __half22float2(*reinterpret_cast<const __half2*>(p));
-            return make_float2(__half2float(p[0]), __half2float(p[1]));
-        }
-        const float* p = reinterpret_cast<const float*>(flow) + o;
-        if (pair) return *reinterpret_cast<const float2*>(p);
-        return make_float2(p[0], p[1]);
-    }
-    const int64_t o = n * 2 * hw + pix;
-    if (f16) {
-        const __half* p = reinterpret_cast<const __half*>(flow) + o;
-        return make_float2(__half2float(p[0]), __half2float(p[hw]));
-    }
-    const float* p = reinterpret_cast<const float*>(flow) + o;
-    return make_float2(p[0], p[hw]);
 }
 
 // tf.image.convert_image_dtype(uint8, saturate=True)
@@ -83,20 +53,20 @@ constexpr int kVisTile = kVisThreads * kVisPix;          // 1024
 
 // blockIdx.x = mblk0[level] + image * mtiles[level] + tile; ws[blockIdx.x] = the tile's largest magnitude
 template <int IN_LAYOUT>
-__global__ __launch_bounds__(kVisThreads) void flow_mag_max_kernel(VisLevels lv, float* __restrict__ ws) {
+__global__ __launch_bounds__(kVisThreads) void flow_mag_max_kernel(VisMaxLevels lv, float* __restrict__ ws) {
     __shared__ float red[kVisThreads / 64];
     const int bid = blockIdx.x;
     const int l = vis_level(lv.mblk0, bid);
     const int rel = bid - lv.mblk0[l], mt = lv.mtiles[l];
     const int n = rel / mt, tile = rel - n * mt;
-    const int hw = lv.h[l] * lv.w[l];
+    const int hw = lv.hw[l];
     const void* flow = lv.flow[l];
     const int f16 = lv.f16[l], pair = lv.pair[l];
     float m2 = 0.0f;
 #pragma unroll
     for (int k = 0; k < kVisMaxPix; ++k) {
         const int pix = tile * kVisMaxTile + k * kVisThreads + (int)threadIdx.x;
-        if (pix < hw) m2 = fmaxf(m2, vis_mag2(vis_load<IN_LAYOUT>(flow, f16, pair, n, pix, hw)));
+        if (pix < hw) m2 = fmaxf(m2, vis_mag2(vis_load(flow, IN_LAYOUT == QPWC_NHWC, f16, pair, n, pix, hw)));
     }
     m2 = vis_block_max(m2, red);
     // the square root is monotone: the root of the largest square is the largest magnitude, bit for bit
@@ -108,7 +78,9 @@ __global__ __launch_bounds__(kVisThreads) void flow_mag_max_kernel(VisLevels lv,
 template <int IN_LAYOUT, int OUT_LAYOUT, bool U8, bool VEC>
 __global__ __launch_bounds__(kVisThreads) void flow_to_image_kernel(VisLevels lv, const float* __restrict__ ws) {
     __shared__ float red[kVisThreads / 64];
-    __shared__ vis_f32x4 stage4[VEC ? kVisTile * 3 / (U8 ? 16 : 4) : 1];   // <vec4>: the tile in output order
+    using T = std::conditional_t<U8, uint8_t, float>;
+    using Tile = TileStore<VEC, OUT_LAYOUT, 3, kVisTile, kVisThreads, T>;   // pixel_io.h
+    __shared__ pix_f32x4 stage4[VEC ? kVisTile * 3 / (U8 ? 16 : 4) : 1];   // <vec4>: the tile in output order
     const int tid = threadIdx.x;
     const int bid = blockIdx.x;
     const int l = vis_level(lv.cblk0, bid);
@@ -118,23 +90,14 @@ __global__ __launch_bounds__(kVisThreads) void flow_to_image_kernel(VisLevels lv
     const int hw = h * w, ohw = oh * ow;
     const float ry = lv.ry[l], rx = lv.rx[l];
     const int step_y = lv.step_y[l], step_x = lv.step_x[l];
-    const void* flow = lv.flow[l];
-    const int f16 = lv.f16[l], pair = lv.pair[l];
-
-    // the image's maximum: its mtiles partials, written by the launch before this one
-    const int mt = lv.mtiles[l];
-    const float* part = ws + lv.mblk0[l] + (int64_t)n * mt;
-    float smax = 0.0f;
-    for (int i = tid; i < mt; i += kVisThreads) smax = fmaxf(smax, part[i]);
-    smax = vis_block_max(smax, red);
-    const float denom = smax + 1e-6f;
+    const void* flow = lv.m.flow[l];
+    const int f16 = lv.m.f16[l], pair = lv.m.pair[l];
+    const float denom = vis_fold_max(ws, lv.m.mblk0[l], n, lv.m.mtiles[l], red) + 1e-6f;
 
     const int base = tile * kVisTile;       // first pixel of the tile
     const int64_t obase = (int64_t)n * ohw;  // first pixel of the image
-    float* stage = reinterpret_cast<float*>(stage4);
-    uint8_t* stage_b = reinterpret_cast<uint8_t*>(stage4);
-    float* outf = reinterpret_cast<float*>(lv.out[l]);
-    uint8_t* outb = reinterpret_cast<uint8_t*>(lv.out[l]);
+    T* stage = reinterpret_cast<T*>(stage4);
+    T* out = reinterpret_cast<T*>(lv.out[l]);
 
     // one division per lane: its further pixels lie 256 = step_y * ow + step_x pixels on
     int Y = (base + tid) / ow, X = (base + tid) - Y * ow;
@@ -149,60 +112,24 @@ __global__ __launch_bounds__(kVisThreads) void flow_to_image_kernel(VisLevels lv
         const int sy = min((int)floorf(((float)Y + 0.5f) * ry), h - 1);
         const int sx = min((int)floorf(((float)X + 0.5f) * rx), w - 1);
         float rgb[3];
-        vis_colour(vis_load<IN_LAYOUT>(flow, f16, pair, n, sy * w + sx, hw), denom, rgb);
-        if (VEC) {
+        vis_colour(vis_load(flow, IN_LAYOUT == QPWC_NHWC, f16, pair, n, sy * w + sx, hw), denom, rgb);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int at = OUT_LAYOUT == QPWC_NHWC ? t * 3 + c : c * kVisTile + t;
-                if (U8) stage_b[at] = vis_u8(rgb[c]);
-                else stage[at] = rgb[c];
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int64_t at = OUT_LAYOUT == QPWC_NHWC ? (obase + pix) * 3 + c : (obase * 3 + (int64_t)c * ohw) + pix;
-                if (U8) outb[at] = vis_u8(rgb[c]);
-                else outf[at] = rgb[c];
-            }
-        }
+        for (int c = 0; c < 3; ++c)
+            Tile::put(stage, out, obase, ohw, base, t, c, U8 ? (T)vis_u8(rgb[c]) : (T)rgb[c]);
     }
     if (!VEC) return;
-    // <vec4>: ohw % 4 == 0, so the tile holds cnt = a multiple of 4 pixels: whole 16-byte pieces of fp32 in either
-    // layout, whole dwords of uint8; the output and with it every image, plane and tile start 16-byte (fp32) / 4-byte
-    // (uint8) aligned
     __syncthreads();
-    const int cnt = min(kVisTile, ohw - base);
-    if (!U8) {
-        vis_f32x4* o4 = reinterpret_cast<vis_f32x4*>(outf);
-        if (OUT_LAYOUT == QPWC_NHWC) {
-            const int64_t g = (obase + base) * 3 / 4;
-            for (int i = tid; i < cnt * 3 / 4; i += kVisThreads) o4[g + i] = stage4[i];
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int64_t g = (obase * 3 + (int64_t)c * ohw + base) / 4;
-                if (4 * tid < cnt) o4[g + tid] = stage4[c * (kVisTile / 4) + tid];
-            }
-        }
-    } else {
-        uint32_t* o1 = reinterpret_cast<uint32_t*>(outb);
-        const uint32_t* stage1 = reinterpret_cast<const uint32_t*>(stage4);
-        if (OUT_LAYOUT == QPWC_NHWC) {
-            const int64_t g = (obase + base) * 3 / 4;
-            for (int i = tid; i < cnt * 3 / 4; i += kVisThreads) o1[g + i] = stage1[i];
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int64_t g = (obase * 3 + (int64_t)c * ohw + base) / 4;
-                if (4 * tid < cnt) o1[g + tid] = stage1[c * (kVisTile / 4) + tid];
-            }
-        }
-    }
+    Tile::flush(stage, out, obase, ohw, base, min(kVisTile, ohw - base));
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static int64_t vis_tiles(int a, int b, int tile) { return ((int64_t)a * b + tile - 1) / tile; }
+int flow_mag_max_launch(const VisMaxLevels& m, int blocks, int in_layout, float* ws, hipStream_t s) {
+    dispatch_layout(in_layout, [&](auto I) {
+        hipLaunchKernelGGL((flow_mag_max_kernel<decltype(I)::value>), dim3((unsigned)blocks), dim3(kVisThreads), 0, s, m, ws);
+    });
+    return check_launch("flow_mag_max_kernel");
+}
 
 // every count the launches index with fits 32 bits: 2 * B * h * w and 3 * B * oh * ow of each level (oh, ow may be
 // NULL: the workspace query) and the workgroups of both launches
@@ -210,10 +137,10 @@ bool flow_to_image_shape_ok(int n, int B, const int* h, const int* w, const int*
     int64_t mblk = 0, cblk = 0;
     for (int l = 0; l < n; ++l) {
         if (2 * (int64_t)B * h[l] * w[l] > INT32_MAX) return false;
-        mblk += B * vis_tiles(h[l], w[l], kVisMaxTile);
+        mblk += B * ceil_div((int64_t)h[l] * w[l], kVisMaxTile);
         if (oh) {
             if (3 * (int64_t)B * oh[l] * ow[l] > INT32_MAX) return false;
-            cblk += B * vis_tiles(oh[l], ow[l], kVisTile);
+            cblk += B * ceil_div((int64_t)oh[l] * ow[l], kVisTile);
         }
     }
     return mblk <= INT32_MAX && cblk <= INT32_MAX;
@@ -221,7 +148,7 @@ bool flow_to_image_shape_ok(int n, int B, const int* h, const int* w, const int*
 
 int64_t flow_to_image_workspace_floats(int n, int B, const int* h, const int* w) {
     int64_t f = 0;
-    for (int l = 0; l < n; ++l) f += B * vis_tiles(h[l], w[l], kVisMaxTile);
+    for (int l = 0; l < n; ++l) f += B * ceil_div((int64_t)h[l] * w[l], kVisMaxTile);
     return f;
 }
 
@@ -241,56 +168,43 @@ int flow_to_image_fwd_launch(const void* const* flows, const int* f16, const int
     VisLevels lv = {};
     int mblk = 0, cblk = 0;
     for (int l = 0; l < kVisMaxLevels; ++l) {
-        lv.mblk0[l] = lv.cblk0[l] = INT_MAX;
+        lv.m.mblk0[l] = lv.cblk0[l] = INT_MAX;
         if (l >= n) continue;
-        lv.flow[l] = flows[l];
+        lv.m.flow[l] = flows[l];
         lv.out[l] = outs[l];
         lv.h[l] = h[l];
         lv.w[l] = w[l];
         lv.oh[l] = oh[l];
         lv.ow[l] = ow[l];
-        lv.f16[l] = f16[l];
-        lv.pair[l] = in_layout == QPWC_NHWC && (uintptr_t)flows[l] % (f16[l] ? 4 : 8) == 0;
+        lv.m.f16[l] = f16[l];
+        lv.m.pair[l] = in_layout == QPWC_NHWC && (uintptr_t)flows[l] % (f16[l] ? 4 : 8) == 0;
+        lv.m.hw[l] = h[l] * w[l];
         lv.ry[l] = (float)h[l] / (float)oh[l];
         lv.rx[l] = (float)w[l] / (float)ow[l];
         lv.step_y[l] = kVisThreads / ow[l];
         lv.step_x[l] = kVisThreads % ow[l];
-        lv.mtiles[l] = (int)vis_tiles(h[l], w[l], kVisMaxTile);
-        lv.ctiles[l] = (int)vis_tiles(oh[l], ow[l], kVisTile);
-        lv.mblk0[l] = mblk;
+        lv.m.mtiles[l] = (int)ceil_div((int64_t)h[l] * w[l], kVisMaxTile);
+        lv.ctiles[l] = (int)ceil_div((int64_t)oh[l] * ow[l], kVisTile);
+        lv.m.mblk0[l] = mblk;
         lv.cblk0[l] = cblk;
-        mblk += B * lv.mtiles[l];
+        mblk += B * lv.m.mtiles[l];
         cblk += B * lv.ctiles[l];
     }
-    const dim3 block(kVisThreads);
-    if (in_layout == QPWC_NHWC)
-        hipLaunchKernelGGL((flow_mag_max_kernel<QPWC_NHWC>), dim3((unsigned)mblk), block, 0, s, lv, ws);
-    else
-        hipLaunchKernelGGL((flow_mag_max_kernel<QPWC_NCHW>), dim3((unsigned)mblk), block, 0, s, lv, ws);
-    int rc = check_launch("flow_mag_max_kernel");
+    const int rc = flow_mag_max_launch(lv.m, mblk, in_layout, ws, s);
     if (rc != QPWC_OK) return rc;
 
     const bool vec = vis_vec(n, oh, ow, outs);
-    const dim3 grid((unsigned)cblk);
-#define QPWC_VIS(I, O, U, V) \
-    hipLaunchKernelGGL((flow_to_image_kernel<I, O, U, V>), grid, block, 0, s, lv, (const float*)ws)
-#define QPWC_VIS_UV(I, O)                                                          \
-    do {                                                                           \
-        if (u8) {                                                                  \
-            if (vec) QPWC_VIS(I, O, true, true); else QPWC_VIS(I, O, true, false); \
-        } else {                                                                   \
-            if (vec) QPWC_VIS(I, O, false, true); else QPWC_VIS(I, O, false, false); \
-        }                                                                          \
-    } while (0)
-    if (in_layout == QPWC_NHWC) {
-        if (out_layout == QPWC_NHWC) QPWC_VIS_UV(QPWC_NHWC, QPWC_NHWC);
-        else QPWC_VIS_UV(QPWC_NHWC, QPWC_NCHW);
-    } else {
-        if (out_layout == QPWC_NHWC) QPWC_VIS_UV(QPWC_NCHW, QPWC_NHWC);
-        else QPWC_VIS_UV(QPWC_NCHW, QPWC_NCHW);
-    }
-#undef QPWC_VIS_UV
-#undef QPWC_VIS
+    dispatch_layout(in_layout, [&](auto I) {
+        dispatch_layout(out_layout, [&](auto O) {
+            dispatch_bool(u8, [&](auto U) {
+                dispatch_bool(vec, [&](auto V) {
+                    hipLaunchKernelGGL((flow_to_image_kernel<decltype(I)::value, decltype(O)::value, decltype(U)::value,
+                                                             decltype(V)::value>),
+                                       dim3((unsigned)cblk), dim3(kVisThreads), 0, s, lv, (const float*)ws);
+                });
+            });
+        });
+    });
     return check_launch("flow_to_image_kernel");
 }
 

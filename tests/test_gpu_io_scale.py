@@ -59,7 +59,7 @@ CASES = {
                       ((0, 17, (12.0, -16.0)), (1, 34, (-15.0, 8.0)))]},
     # review_panels_kernel: set 1 at 725 x 725 (525,625 pixels, odd: <scalar>), set 2 at 724 x 726 with s = 1 (525,624:
     # <vec4>), 257 max-tiles each.  flo and set 2's flow: image 0's maximum at its last pixel, image 1's at pixel 3;
-    # flo_pred: image 1's inside the last max-tile, image 0's in the first -- each rev_fold call needs its second trip.
+    # flo_pred: image 1's inside the last max-tile, image 0's in the first -- each vis_fold_max call needs its second trip.
     "review": {1: {"size": (725, 725), "grid": 0,
                    "plant": {"flo": ((0, 725 * 725 - 1, (30.0, -40.0)), (1, 3, (-21.0, 20.0))),
                              "flo_pred": ((0, 7, (-28.0, 45.0)), (1, 256 * 2048 + 1000, (36.0, 27.0)))}},

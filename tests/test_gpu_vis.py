@@ -8,8 +8,10 @@ LEVELS, one call: three flows of different sizes, B = 2.  Level 0 (33 x 70 = 231
 one max-tile (_hip.VIS_MAX_TILE) and no multiple of it, its largest vector in the last, partial tile of image 0 and
 in the first tile of image 1; level 1 (5 x 7) is smaller than a wave; level 2 (15 x 25) is odd in both extents.
 Pictures: the flows' own sizes and (37, 70) take the <scalar> stores (2310, 35, 375 and 2590 pixels: no multiple of 4),
-(64, 128) takes <vec4> with 8 colour tiles (_hip.VIS_TILE) per image; both resized forms have non-integer ratios without
-ties (ref_nearest_index asserts it).  Measured on an MI355X: see the docstrings of the tests."""
+(64, 128) takes <vec4> with 8 colour tiles (_hip.VIS_TILE) per image and (36, 70) takes it with two whole tiles and one
+of 472 pixels (2520 = 2 * 1024 + 472, a multiple of 4: the partial tile of either layout, fp32 and uint8); the resized
+forms have non-integer ratios without ties (ref_nearest_index asserts it).  Measured on an MI355X: see the docstrings
+of the tests."""
 import os
 import sys
 
@@ -29,7 +31,7 @@ DEV = "cuda:0"
 dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 B = 2
 SHAPES = [(33, 70), (5, 7), (15, 25)]
-SIZES = {"native": None, "scalar": (37, 70), "vec4": (64, 128)}
+SIZES = {"native": None, "scalar": (37, 70), "vec4": (64, 128), "vec4_tail": (36, 70)}
 U8_SEED = 20                      # N(0, 3^2) flows: the share of elements near a uint8 step is asserted below
 
 
@@ -76,13 +78,13 @@ def picture_sizes(size):
 @pytest.mark.parametrize("in_format", FORMATS)
 def test_kernels_match_the_float64_restatement(in_format, out_format, form, half):
     """Every element of the three pictures.  Measured on an MI355X: max |err| 4.8e-7 (fp32 flows) and 5.1e-7 (fp16)
-    over the 24 cases; the torch composition on the CPU is at 4.6e-7."""
+    over the 32 cases; the torch composition on the CPU is at 4.6e-7."""
     size = SIZES[form]
     flows = LEVELS_F16 if half else LEVELS
     outs, got = run(flows, size, in_format, out_format, torch.float32)
     want = reference("f16" if half else "f32", [f.astype(np.float32) for f in flows], size)
     name = ops.flow_to_image_kernel(B, picture_sizes(size), torch.float32, out_format, outs)
-    assert name == "flow_to_image_kernel<{}>".format("vec4" if form == "vec4" else "scalar")
+    assert name == "flow_to_image_kernel<{}>".format("vec4" if form.startswith("vec4") else "scalar")
     for l, (g, r) in enumerate(zip(got, want)):
         assert g.shape == r.shape and g.dtype == np.float32 and np.isfinite(g).all()
         e = float(np.abs(g - r).max())                          # over EVERY element
@@ -109,14 +111,14 @@ def test_negative_control():
 @pytest.mark.parametrize("in_format", FORMATS)
 def test_uint8_pictures(in_format, out_format, form):
     """uint8 against float64: at most one level off, and only where the float64 value times 255.5 lies within 1e-3 of a
-    whole number; those elements may be at most 1 % (0.15 % of these pictures at the flows' own sizes, 0.42 %
-    resized: a property of the restatement; on an MI355X no element is off anywhere else)."""
+    whole number; those elements may be at most 1 % (0.15 % of these pictures at the flows' own sizes, 0.41 % to
+    0.44 % resized: a property of the restatement; on an MI355X no element is off anywhere else)."""
     size = SIZES[form]
     flows = [random_flow(U8_SEED + i, (B,) + s) for i, s in enumerate(SHAPES)]
     outs, got = run(flows, size, in_format, out_format, torch.uint8)
     want = reference("u8", flows, size)
     name = ops.flow_to_image_kernel(B, picture_sizes(size), torch.uint8, out_format, outs)
-    assert name == "flow_to_image_kernel<{}>".format("vec4" if form == "vec4" else "scalar")
+    assert name == "flow_to_image_kernel<{}>".format("vec4" if form.startswith("vec4") else "scalar")
     near = total = 0
     for g, r in zip(got, want):
         assert g.dtype == np.uint8 and g.shape == r.shape

@@ -58,8 +58,7 @@ WAVE = 64
 
 # the loops the cases are built for, as their files spell them
 LOOPS = [("augment.hip", "for (int i = tid; i < nblk; i += kAugThreads) s += p[i];"),
-         ("vis.hip", "for (int i = tid; i < mt; i += kVisThreads) smax = fmaxf(smax, part[i]);"),
-         ("review.hip", "for (int i = threadIdx.x; i < mt; i += kVisThreads) m = fmaxf(m, part[i]);"),
+         ("vis_common.h", "for (int i = threadIdx.x; i < mt; i += kVisThreads) m = fmaxf(m, part[i]);"),
          ("quality.hip", "for (int n0 = 0; n0 < B; n0 += kQualFoldThreads / 64) {"),
          ("quality.hip", "for (int t = lane; t < tiles; t += 64) {")]
 
@@ -76,20 +75,26 @@ def test_each_loop_header_occurs_once(name, header):
 
 def test_review_folds_both_flows_of_set_1_and_the_flow_of_set_2():
     text = _text("review.hip")
-    assert text.count("rev_fold(ws, 0, n, a.B, a.mtiles, red[0])") == 2        # set 1's flo and set 2's flow
-    assert text.count("rev_fold(ws, 1, n, a.B, a.mtiles, red[1])") == 1        # set 1's flo_pred
-    assert len(re.findall(r"\brev_fold\(", text)) == 4                          # and the definition
-    assert "static int64_t rev_tiles(int a, int b, int tile)" in text
-    assert text.count("a.mtiles = (int)rev_tiles(a.h, a.w, kVisMaxTile);") == 1
-    assert _text("vis.hip").count("lv.mtiles[l] = (int)vis_tiles(h[l], w[l], kVisMaxTile);") == 1
-    assert _text("vis_common.h").count("constexpr int kVisMaxTile = kVisThreads * kVisMaxPix;") == 1
+    assert text.count("vis_fold_max(ws, 0, n, a.mtiles, red[0])") == 2          # set 1's flo and set 2's flow
+    assert text.count("vis_fold_max(ws, a.B * a.mtiles, n, a.mtiles, red[1])") == 1   # set 1's flo_pred, behind flo's
+    assert len(re.findall(r"\bvis_fold_max\(", text)) == 3                      # the definition is vis_common.h's
+    assert text.count("m.mblk0[k] = k * a.B * a.mtiles;") == 1                  # where the max launch leaves flow k's
+    common = _text("vis_common.h")
+    assert len(re.findall(r"\bvis_fold_max\(", common)) == 1
+    assert "const float* part = ws + blk0 + (int64_t)n * mt;" in common
+    assert len(re.findall(r"\bvis_fold_max\(", _text("vis.hip"))) == 1
+    assert "inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }" in _text("pixel_io.h")
+    assert text.count("a.mtiles = (int)ceil_div((int64_t)a.h * a.w, kVisMaxTile);") == 1
+    assert _text("vis.hip").count("lv.m.mtiles[l] = (int)ceil_div((int64_t)h[l] * w[l], kVisMaxTile);") == 1
+    assert common.count("constexpr int kVisMaxTile = kVisThreads * kVisMaxPix;") == 1
 
 
 def test_augment_cases_fold_more_partials_than_lanes():
     threads, chunk = AUG["kAugThreads"], AUG["kAugPass2Pixels"]
     text = _text("augment.hip")
-    assert "return ((int64_t)h * w + kAugThreads - 1) / kAugThreads; }" in text                   # nblk
-    assert "const int nblk2 = (int)(((int64_t)h * w + kAugPass2Pixels - 1) / kAugPass2Pixels);" in text
+    assert "inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }" in _text("pixel_io.h")
+    assert "return ceil_div((int64_t)h * w, kAugThreads); }" in text                              # nblk
+    assert "const int nblk2 = (int)ceil_div((int64_t)h * w, kAugPass2Pixels);" in text
     forms = CASES["augment"]
     for form in ("vec4", "scalar"):
         h, w = forms[form]
@@ -119,7 +124,7 @@ def test_vis_and_review_cases_fold_more_max_tiles_than_lanes():
         assert max(tiles.values()) >= threads and min(tiles.values()) == 0, (key, tiles)
     flo, flo_pred = (CASES["review"][1]["plant"][k] for k in ("flo", "flo_pred"))
     late = lambda spots: [n for n, pixel, _ in spots if pixel // VIS_MAX_TILE >= threads]
-    assert late(flo) == [0] and late(flo_pred) == [1]                          # each rev_fold call needs its own
+    assert late(flo) == [0] and late(flo_pred) == [1]                          # each vis_fold_max call needs its own
     # level 1 reads its partials behind level 0's: ws + mblk0[1] = B * mtiles[0]
     fh, fw = CASES["vis"]["levels"][0]
     assert len(CASES["vis"]["levels"]) == 2 and B * _ceil(fh * fw, VIS_MAX_TILE) >= 2 * threads

@@ -48,7 +48,7 @@ def calls(hip_lib):
 def test_a_valid_call_reaches_the_launch(calls):
     for call in calls:
         rc, text = call()
-        assert rc == _hip.E_LAUNCH and text.startswith("review_mag_max_kernel: "), (rc, text)
+        assert rc == _hip.E_LAUNCH and text.startswith("flow_mag_max_kernel: "), (rc, text)
         for ok in (dict(out_dtype=_hip.U8), dict(in_layout=_hip.NCHW), dict(out_layout=_hip.NCHW), dict(grid=1),
                    dict(grid=0), dict(H=7, W=5) if call is calls[0] else dict(H=9, W=15, h=3, w=5)):
             assert call(**ok)[0] == _hip.E_LAUNCH, ok
