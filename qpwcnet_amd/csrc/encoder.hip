@@ -18,22 +18,9 @@
 // then all compute).  Resident workgroups walking the tiles with the next halo prefetched into registers
 // and a double-buffered LDS image need 144 / 196 registers (loop-invariant addresses stay live): 34.7 us
 // at C = 16, 34.8 (from 31.8) at C = 32 -- not kept.
-#include "common.h"
-#include "launch.h"
+#include "conv_fwd_common.h"
 
 namespace qpwc {
-
-// (same fast form as optflow.hip's mishf)
-__device__ __forceinline__ float enc_mishf(float x) {
-    // v_exp_f32 / v_rcp_f32 directly: hipcc lowers __expf with denormal range handling and __fdividef to
-    // the full IEEE division sequence (div_scale / div_fmas / div_fixup), ~28 instructions per value
-    const float e = __builtin_amdgcn_exp2f(fminf(x, 20.0f) * 1.4426950408889634f);
-    const float t = e * (e + 2.0f);
-    const float m = x * (t * __builtin_amdgcn_rcpf(t + 2.0f));
-    return m;   // x > 20: e is clamped, t / (t + 2) rounds to 1 +- 1 ulp, m = x to 2 ulp -- no compare + select per value
-}
-
-typedef float f32x4e __attribute__((ext_vector_type(4)));
 
 // two consecutive elements as fp32 / four fp32 values stored as four elements (one 8- or 16-byte access)
 __device__ __forceinline__ float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); }
@@ -49,6 +36,7 @@ __device__ __forceinline__ void st4q(__half* p, float4 v) {
 
 constexpr int kEcTH = 8, kEcTW = 16;
 constexpr int kEcHW = kEcTW + 2, kEcNH = (kEcTH + 2) * kEcHW;   // 180 halo pixels
+static_assert(kEcTW == kCfTW && kEcHW == kCfHW, "the shared staging, border and tile-plan code works on this tile width");
 
 // weight: [9 taps][C out][C in] fp32; out: (B, H + pad_h, W + pad_w, C), border zero
 // 16-byte chunk q of halo pixel hp sits at chunk ec_slot(q, hp) of the pixel's row: the matrix operand
@@ -104,9 +92,7 @@ __device__ __forceinline__ int ec_slot(int q, int hp) {
 #ifndef QPWC_W_NEXT_ALWAYS
 #define QPWC_W_NEXT_ALWAYS 1
 #endif
-#ifndef QPWC_W_NEXT_ALWAYS_F16
-#define QPWC_W_NEXT_ALWAYS_F16 0   // the fp16 kernels (16-cycle matrix instructions, two waves per SIMD) lose with it: config 5 1.627-1.629 vs 1.604-1.611 ms
-#endif
+// (the fp16 kernels -- 16-cycle matrix instructions, two waves per SIMD -- lose with it and keep the conditional request: DESIGN.md 7.0a)
 #if QPWC_W_NEXT_ALWAYS
 #define QPWC_LOAD_W_NEXT(END) load_w(wn, kb + 1 < (END) ? kb + 1 : kb)
 #else
@@ -239,27 +225,10 @@ __global__ __launch_bounds__(256, 4) void conv3x3_mish_kernel(const float* __res
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const int gy = Y0 + 2 * wave + m, gx = X0 + n;
-                if (gy < H && gx < W)
-                    *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * C + 16 * ft + 4 * g) =
-                        make_float4(enc_mishf(acc[m][0] + bq.x), enc_mishf(acc[m][1] + bq.y),
-                                    enc_mishf(acc[m][2] + bq.z), enc_mishf(acc[m][3] + bq.w));
+                if (gy < H && gx < W) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * C + 16 * ft + 4 * g, acc[m], bq);
             }
         }
-        // ---- zero border of the padded output (columns W.., rows H..), written by the edge tiles ----
-        if (pad_w > 0 && X0 + kEcTW >= W) {
-            for (int i = tid; i < kEcTH * pad_w * NQ; i += 256) {
-                const int q = i % NQ, r = i / NQ, col = r % pad_w, row = r / pad_w;
-                const int gy = Y0 + row;
-                if (gy < H) *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + W + col) * C + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-        if (pad_h > 0 && Y0 + kEcTH >= H) {
-            const int x_end = (X0 + kEcTW >= W) ? Wo : X0 + kEcTW;   // the corner belongs to the last tile
-            for (int i = tid; i < pad_h * (x_end - X0) * NQ; i += 256) {
-                const int q = i % NQ, r = i / NQ, col = r % (x_end - X0), row = r / (x_end - X0);
-                *reinterpret_cast<float4*>(ob + ((int64_t)(H + row) * Wo + X0 + col) * C + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
+        zero_border<float, kEcTH, NQ>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 0);
         ENC_CENSUS(4);
         if (more) {
             // buffer (t + 1) & 1 was last read by tile t - 1, whose waves all passed the previous barrier
@@ -452,77 +421,44 @@ __global__ __launch_bounds__(256, (2 * EwShape<C, TH>::LDS <= 160 * 1024) ? 2 : 
 #pragma unroll
     for (int m = 0; m < TH; ++m) {
         const int gy = Y0 + m, gx = X0 + n;
-        if (gy < H && gx < W)
-            *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * C + fo + 4 * g) =
-                make_float4(enc_mishf(acc[m][0] + bq.x), enc_mishf(acc[m][1] + bq.y),
-                            enc_mishf(acc[m][2] + bq.z), enc_mishf(acc[m][3] + bq.w));
+        if (gy < H && gx < W) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * C + fo + 4 * g, acc[m], bq);
     }
-    // ---- zero border of the padded output, this slice's 64 channels, written by the edge tiles ----
-    if (pad_w > 0 && X0 + kEcTW >= W) {
-        for (int i = tid; i < TH * pad_w * 16; i += 256) {
-            const int q = i & 15, r = i >> 4, col = r % pad_w, row = r / pad_w;
-            const int gy = Y0 + row;
-            if (gy < H) *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + W + col) * C + 64 * slice + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    if (pad_h > 0 && Y0 + TH >= H) {
-        const int x_end = (X0 + kEcTW >= W) ? Wo : X0 + kEcTW;   // the corner belongs to the last tile
-        for (int i = tid; i < pad_h * (x_end - X0) * 16; i += 256) {
-            const int q = i & 15, r = i >> 4, col = r % (x_end - X0), row = r / (x_end - X0);
-            *reinterpret_cast<float4*>(ob + ((int64_t)(H + row) * Wo + X0 + col) * C + 64 * slice + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
+    zero_border<float, TH, 16>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 64 * slice);
 }
 
 template <int C, int TH>
 static int conv3x3_mish_ring_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H,
                                     int W, int pad_h, int pad_w, hipStream_t s) {
-    const int tiles_x = (W + kEcTW - 1) / kEcTW, tiles_y = (H + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * (C / 64) > INT32_MAX || (int64_t)H * W * C * 4 > INT32_MAX) {
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, TH, C / 64, "conv3x3_mish") || (int64_t)H * W * C * 4 > INT32_MAX) {
         set_error("conv3x3_mish: too many tiles or a frame of 2 GiB or more");
         return QPWC_E_SHAPE;
     }
-    hipLaunchKernelGGL((conv3x3_mish_ring_kernel<C, TH>), dim3((unsigned)(n_tiles * (C / 64))), dim3(256), 0, s,
+    hipLaunchKernelGGL((conv3x3_mish_ring_kernel<C, TH>), dim3((unsigned)p.n_wgs), dim3(256), 0, s,
                        (const float*)x, (const float*)weight, (const float*)bias, (float*)out, H, W, pad_h, pad_w,
-                       tiles_x, tiles_y, (int)n_tiles);
+                       p.tiles_x, p.tiles_y, (int)p.n_tiles);
     return check_launch("conv3x3_mish_ring_kernel");
 }
 
 // ---------------------------------------------------------------------------
-// fp16-storage twin of the two kernels above (BASELINE configs[4]; the reference itself has no fp16 path):
-// x, weight ([9 taps][C out][C in]) and out fp16, bias fp32; products on v_mfma_f32_16x16x32_f16 with fp32
-// accumulation, bias + Mish in fp32, ONE rounding to fp16 at the store (the library path it replaces rounds the
-// convolution output and the activation).  One matrix instruction per tap and 32-channel block where fp32 needs
-// eight, so the layer is bound by its activations' bytes; the structure is kept simple: 8 x 16 (TH x 16) pixel tile,
-// the whole halo tile of all input channels in LDS (pixels of CP = max(C, 32) halves, 16-byte chunk q of halo pixel p
-// at slot f16_slot(q, p)), a workgroup = 4 waves = TH / 4 tile rows each x min(C, 64) outputs (grid = tiles x C / 64),
-// the weights streamed from L1 / L2 (16 bytes per lane, tap and output block).  C = 16: the upper half of every
-// 32-channel pixel is zero in LDS and the weight lanes of k >= 16 are zero.
-typedef _Float16 f16x8e __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4e __attribute__((ext_vector_type(4)));
-
-template <int CP>
-__device__ __forceinline__ int f16_slot(int q, int hp) {
-    // pixels of 64 / 128 / 256 / 512 bytes: 16 consecutive pixels x one chunk must spread over the 16 sixteen-byte
-    // slots of the 64 banks
-    return CP == 32 ? (q ^ ((0 - (hp >> 2)) & 3)) : (CP == 64 ? (q ^ ((hp >> 1) & 7)) : (q ^ (hp & 15)));
-}
-
+// fp16-storage twin of the ring kernel above for the wide levels (C = 64 / 128 / 256; BASELINE configs[4]; the
+// reference itself has no fp16 path): x, weight ([9 taps][C out][C in]) and out fp16, bias fp32; products on
+// v_mfma_f32_16x16x32_f16 with fp32 accumulation, bias + Mish in fp32, ONE rounding to fp16 at the store (the library
+// path it replaces rounds the convolution output and the activation).  One matrix instruction per tap and 32-channel
+// block where fp32 needs eight, so the layer is bound by its activations' bytes; the structure is kept simple: TH x 16
+// pixel tile, the whole halo tile of all input channels in LDS (stage_halo_f16), a workgroup = 4 waves x 16 = 64
+// outputs (grid = tiles x C / 64).  A wave owns ONE block of 16 outputs for all TH tile rows and keeps that block's
+// weights for 32 input channels in registers (9 taps x 16 bytes, the next block's requested before this block's matrix
+// work) -- no weight is fetched twice by a workgroup, every B operand read feeds one matrix instruction.
 template <int C, int TH>
 __global__ __launch_bounds__(256) void conv3x3_mish_f16_kernel(const __half* __restrict__ x,
                                                               const __half* __restrict__ weight,
                                                               const float* __restrict__ bias,
                                                               __half* __restrict__ out, int H, int W, int pad_h,
                                                               int pad_w, int tiles_x, int tiles_y, int n_tiles) {
-    constexpr int CP = C < 32 ? 32 : C;            // halves per pixel in LDS
-    constexpr int NQ = CP / 8, NQG = C / 8;        // 16-byte chunks per pixel: LDS / global
-    constexpr int HH = TH + 2, NH = HH * kEcHW;
-    constexpr int NKB = CP / 32;
-    constexpr int FW = C < 64 ? C : 64, NFT = FW / 16, NSL = C / FW;   // outputs per workgroup, blocks, slices
-    constexpr int RW = TH / 4;                     // tile rows per wave
-    constexpr int NST = (NH * NQ + 255) / 256;
-    __shared__ __attribute__((aligned(16))) __half in_s[NH * CP];
+    static_assert(C % 64 == 0, "the narrow levels run on conv3x3_mish_f16_narrow_kernel");
+    constexpr int NH = (TH + 2) * kEcHW, NKB = C / 32;
+    __shared__ __attribute__((aligned(16))) __half in_s[NH * C];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63, n = lane & 15, g = lane >> 4;
@@ -530,199 +466,76 @@ __global__ __launch_bounds__(256) void conv3x3_mish_f16_kernel(const __half* __r
     const int tile = xcd_swizzle(blockIdx.x % n_tiles, n_tiles);
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
     const int X0 = tx * kEcTW, Y0 = ty * TH;
-    const int f0 = FW * slice;
-    const __half* xb = x + (int64_t)b * H * W * C;
-    {
-        uint4 st[NST];
-#pragma unroll
-        for (int it = 0; it < NST; ++it) {
-            const int idx = tid + 256 * it;
-            const int hp = idx / NQ, q = idx - hp * NQ;
-            const int hy = hp / kEcHW, hx = hp - hy * kEcHW;
-            const int gy = Y0 - 1 + hy, gx = X0 - 1 + hx;
-            st[it] = (idx < NH * NQ && q < NQG && gy >= 0 && gy < H && gx >= 0 && gx < W)
-                         ? *reinterpret_cast<const uint4*>(xb + ((int64_t)gy * W + gx) * C + 8 * q)
-                         : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int it = 0; it < NST; ++it) {
-            const int idx = tid + 256 * it;
-            const int hp = idx / NQ, q = idx - hp * NQ;
-            if (idx < NH * NQ) *reinterpret_cast<uint4*>(in_s + hp * CP + 8 * f16_slot<CP>(q, hp)) = st[it];
-        }
-    }
+    const int fo = 64 * slice + 16 * wave;
+    stage_halo_f16<C, TH>(x + (int64_t)b * H * W * C, in_s, tid, Y0, X0, H, W);
     const int Ho = H + pad_h, Wo = W + pad_w;
     __half* ob = out + (int64_t)b * Ho * Wo * C;
-    if (C >= 64) {
-        // wide levels: a wave owns ONE block of 16 outputs for all TH tile rows and keeps that block's weights for 32
-        // input channels in registers (9 taps x 16 bytes, the next block's requested before this block's matrix work)
-        // -- no weight is fetched twice by a workgroup, every B operand read feeds one matrix instruction
-        const int fo = f0 + 16 * wave;
-        f32x4e acw[TH];
+    f32x4e acw[TH];
 #pragma unroll
-        for (int r = 0; r < TH; ++r) acw[r] = f32x4e{0.f, 0.f, 0.f, 0.f};
-        f16x8e wv[9], wn[9];
-        auto load_w = [&](f16x8e (&w)[9], int kb) {
+    for (int r = 0; r < TH; ++r) acw[r] = f32x4e{0.f, 0.f, 0.f, 0.f};
+    f16x8e wv[9], wn[9];
+    auto load_w = [&](f16x8e (&w)[9], int kb) {
 #pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
-                w[tap] = *reinterpret_cast<const f16x8e*>(weight + ((int64_t)tap * C + fo + n) * C + 32 * kb + 8 * g);
-        };
-        load_w(wv, 0);
-        __syncthreads();
-        // one 32-channel block with the weights in `wv`; the two register sets alternate (QPWC_W_NEXT_ALWAYS)
-        auto block = [&](f16x8e (&wv)[9], int kb) __attribute__((always_inline)) {
-            // one step = one tap: TH ds_read_b128 feed TH matrix instructions of 16 cycles each; the reads of tap
-            // t + 1 go out before the matrix instructions of tap t (round 3: as the compiler placed them every matrix
-            // instruction waited for its own read -- 33 us for a layer whose bytes and products are 4 us each)
-            f16x8e bb[2][TH];
-            auto read_b = [&](f16x8e (&bv)[TH], int tap) __attribute__((always_inline)) {
-                const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-                for (int r = 0; r < TH; ++r) {
-                    const int hp = (r + ky) * kEcHW + n + kx;
-                    bv[r] = *reinterpret_cast<const f16x8e*>(in_s + hp * CP + 8 * f16_slot<CP>(4 * kb + g, hp));
-                }
-            };
-            read_b(bb[0], 0);
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                if (tap + 1 < 9) read_b(bb[(tap + 1) & 1], tap + 1);
-#pragma unroll
-                for (int r = 0; r < TH; ++r)
-                    acw[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[tap], bb[tap & 1][r], acw[r], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-#if QPWC_W_NEXT_ALWAYS_F16
-        {
-            int kb = 0;
-#pragma unroll 1
-            for (; kb + 1 < NKB; kb += 2) {
-                load_w(wn, kb + 1);
-                __builtin_amdgcn_sched_barrier(0);   // (unfenced, the scheduler sinks the requests to just in front of their use)
-                block(wv, kb);
-                load_w(wv, kb + 2 < NKB ? kb + 2 : kb);   // (last trip: a harmless re-read)
-                __builtin_amdgcn_sched_barrier(0);
-                block(wn, kb + 1);
-            }
-            if (kb < NKB) block(wv, kb);   // odd number of blocks
-        }
-#else
-#pragma unroll 1
-        for (int kb = 0; kb < NKB; ++kb) {
-            if (kb + 1 < NKB) load_w(wn, kb + 1);
-            block(wv, kb);
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) wv[tap] = wn[tap];
-        }
-#endif
-        const float4 bq = *reinterpret_cast<const float4*>(bias + fo + 4 * g);
-#pragma unroll
-        for (int r = 0; r < TH; ++r) {
-            const int gy = Y0 + r, gx = X0 + n;
-            if (gy < H && gx < W) {
-                f16x4e o;
-                o[0] = (_Float16)enc_mishf(acw[r][0] + bq.x);
-                o[1] = (_Float16)enc_mishf(acw[r][1] + bq.y);
-                o[2] = (_Float16)enc_mishf(acw[r][2] + bq.z);
-                o[3] = (_Float16)enc_mishf(acw[r][3] + bq.w);
-                *reinterpret_cast<f16x4e*>(ob + ((int64_t)gy * Wo + gx) * C + fo + 4 * g) = o;
-            }
-        }
-    } else {
-    f32x4e acc[RW][NFT];
-#pragma unroll
-    for (int r = 0; r < RW; ++r)
-#pragma unroll
-        for (int ft = 0; ft < NFT; ++ft) acc[r][ft] = f32x4e{0.f, 0.f, 0.f, 0.f};
+        for (int tap = 0; tap < 9; ++tap)
+            w[tap] = *reinterpret_cast<const f16x8e*>(weight + ((int64_t)tap * C + fo + n) * C + 32 * kb + 8 * g);
+    };
+    load_w(wv, 0);
     __syncthreads();
-    const bool kvalid = 8 * g < C;   // C = 16: lanes of k >= 16 carry zeros
-#pragma unroll 1
-    for (int kb = 0; kb < NKB; ++kb) {
+    // one 32-channel block with the weights in `wv`
+    auto block = [&](f16x8e (&wv)[9], int kb) __attribute__((always_inline)) {
+        // one step = one tap: TH ds_read_b128 feed TH matrix instructions of 16 cycles each; the reads of tap
+        // t + 1 go out before the matrix instructions of tap t (round 3: as the compiler placed them every matrix
+        // instruction waited for its own read -- 33 us for a layer whose bytes and products are 4 us each)
+        f16x8e bb[2][TH];
+        auto read_b = [&](f16x8e (&bv)[TH], int tap) __attribute__((always_inline)) {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+#pragma unroll
+            for (int r = 0; r < TH; ++r) {
+                const int hp = (r + ky) * kEcHW + n + kx;
+                bv[r] = *reinterpret_cast<const f16x8e*>(in_s + hp * C + 8 * px16_slot<C>(4 * kb + g, hp));
+            }
+        };
+        read_b(bb[0], 0);
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3, kx = tap - 3 * ky;
-            f16x8e wv[NFT];
+            if (tap + 1 < 9) read_b(bb[(tap + 1) & 1], tap + 1);
 #pragma unroll
-            for (int ft = 0; ft < NFT; ++ft) {
-                wv[ft] = f16x8e{0, 0, 0, 0, 0, 0, 0, 0};
-                if (kvalid)
-                    wv[ft] = *reinterpret_cast<const f16x8e*>(weight + ((int64_t)tap * C + f0 + 16 * ft + n) * C + 32 * kb + 8 * g);
-            }
-            f16x8e bv[RW];
-#pragma unroll
-            for (int r = 0; r < RW; ++r) {
-                const int hp = (RW * wave + r + ky) * kEcHW + n + kx;
-                bv[r] = *reinterpret_cast<const f16x8e*>(in_s + hp * CP + 8 * f16_slot<CP>(4 * kb + g, hp));
-            }
-#pragma unroll
-            for (int ft = 0; ft < NFT; ++ft)
-#pragma unroll
-                for (int r = 0; r < RW; ++r)
-                    acc[r][ft] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[ft], bv[r], acc[r][ft], 0, 0, 0);
+            for (int r = 0; r < TH; ++r)
+                acw[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[tap], bb[tap & 1][r], acw[r], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
-    }
-    // ---- bias + Mish, one rounding to fp16: lane = pixel n of tile row RW wave + r, outputs f0 + 16 ft + 4g .. + 3 ----
-    // (all bias values requested before the first store: a load behind stores waits for them too, vmcnt counts both)
-    float4 bqs[NFT];
+    };
+#pragma unroll 1
+    for (int kb = 0; kb < NKB; ++kb) {
+        if (kb + 1 < NKB) load_w(wn, kb + 1);
+        block(wv, kb);
 #pragma unroll
-    for (int ft = 0; ft < NFT; ++ft) bqs[ft] = *reinterpret_cast<const float4*>(bias + f0 + 16 * ft + 4 * g);
+        for (int tap = 0; tap < 9; ++tap) wv[tap] = wn[tap];
+    }
+    const float4 bq = *reinterpret_cast<const float4*>(bias + fo + 4 * g);
 #pragma unroll
-    for (int ft = 0; ft < NFT; ++ft) {
-        const float4 bq = bqs[ft];
-#pragma unroll
-        for (int r = 0; r < RW; ++r) {
-            const int gy = Y0 + RW * wave + r, gx = X0 + n;
-            if (gy < H && gx < W) {
-                f16x4e o;
-                o[0] = (_Float16)enc_mishf(acc[r][ft][0] + bq.x);
-                o[1] = (_Float16)enc_mishf(acc[r][ft][1] + bq.y);
-                o[2] = (_Float16)enc_mishf(acc[r][ft][2] + bq.z);
-                o[3] = (_Float16)enc_mishf(acc[r][ft][3] + bq.w);
-                *reinterpret_cast<f16x4e*>(ob + ((int64_t)gy * Wo + gx) * C + f0 + 16 * ft + 4 * g) = o;
-            }
-        }
+    for (int r = 0; r < TH; ++r) {
+        const int gy = Y0 + r, gx = X0 + n;
+        if (gy < H && gx < W) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * C + fo + 4 * g, acw[r], bq);
     }
-    }
-    // ---- zero border of the padded output, this slice's FW channels (FW / 8 sixteen-byte chunks per pixel) ----
-    constexpr int NQF = FW / 8;
-    if (pad_w > 0 && X0 + kEcTW >= W) {
-        for (int i = tid; i < TH * pad_w * NQF; i += 256) {
-            const int q = i % NQF, r = i / NQF, col = r % pad_w, row = r / pad_w;
-            const int gy = Y0 + row;
-            if (gy < H) *reinterpret_cast<uint4*>(ob + ((int64_t)gy * Wo + W + col) * C + f0 + 8 * q) = make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
-    if (pad_h > 0 && Y0 + TH >= H) {
-        const int x_end = (X0 + kEcTW >= W) ? Wo : X0 + kEcTW;   // the corner belongs to the last tile
-        for (int i = tid; i < pad_h * (x_end - X0) * NQF; i += 256) {
-            const int q = i % NQF, r = i / NQF, col = r % (x_end - X0), row = r / (x_end - X0);
-            *reinterpret_cast<uint4*>(ob + ((int64_t)(H + row) * Wo + X0 + col) * C + f0 + 8 * q) = make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
-    (void)NSL;
+    zero_border<__half, TH, 8>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 64 * slice);
 }
 
 // ---------------------------------------------------------------------------
-// The narrow levels of the fp16 layer (C = 16 / 32), round 3.  The kernel above runs them at 60 / 34 us for 64 frames
-// (config 5) where their bytes allow 17 / 8: half of every C = 16 matrix instruction multiplies zeros, the weights are
-// fetched again for every tap and every matrix instruction waits for its own operand read.  Here (the structure of
+// The narrow levels of the fp16 layer (C = 16 / 32), round 3.  On the kernel above (pixels padded to 32 halves, 8 x 16
+// tile, TH / 4 rows x all outputs per wave) they ran at 60 / 34 us for 64 frames (config 5) where their bytes allow
+// 17 / 8: half of every C = 16 matrix instruction multiplied zeros, the weights were fetched again for every tap and
+// every matrix instruction waited for its own operand read.  Here (the structure of
 // conv3x3_mish_x3_narrow_kernel): 16 x 16 pixel tile, a wave owns four tile rows and ALL outputs, the weights of the
 // whole layer sit in registers (C = 32: 9 taps x 2 output blocks; C = 16: 5 tap PAIRS -- k-slots g = 0, 1 carry tap 2j,
 // g = 2, 3 tap 2j + 1, so no lane multiplies padding except in the tenth half), and a tap's four operand reads go out
 // one tap ahead of its matrix instructions.
 template <int C>
-__device__ __forceinline__ int f16n_slot(int q, int hp) {
-    return C == 16 ? (q ^ ((hp >> 3) & 1)) : (q ^ ((0 - (hp >> 2)) & 3));
-}
-
-template <int C>
 __global__ __launch_bounds__(256, C == 16 ? 4 : 3) void conv3x3_mish_f16_narrow_kernel(
     const __half* __restrict__ x, const __half* __restrict__ weight, const float* __restrict__ bias,
     __half* __restrict__ out, int H, int W, int pad_h, int pad_w, int tiles_x, int tiles_y) {
-    constexpr int TH = 16, RW = 4, HWD = kEcTW + 2;
-    constexpr int NQ = C / 8, NH = (TH + 2) * HWD;
-    constexpr int NST = (NH * NQ + 255) / 256;
+    constexpr int TH = 16, RW = 4;
+    constexpr int NH = (TH + 2) * kEcHW;
     constexpr int NFT = C / 16;
     __shared__ __attribute__((aligned(16))) __half in_s[NH * C];
     const int tid = threadIdx.x;
@@ -734,25 +547,7 @@ __global__ __launch_bounds__(256, C == 16 ? 4 : 3) void conv3x3_mish_f16_narrow_
     const __half* xb = x + (int64_t)b * H * W * C;
     const int Ho = H + pad_h, Wo = W + pad_w;
     __half* ob = out + (int64_t)b * Ho * Wo * C;
-    {
-        uint4 st[NST];
-#pragma unroll
-        for (int it = 0; it < NST; ++it) {
-            const int idx = tid + 256 * it;
-            const int hp = idx / NQ, q = idx - hp * NQ;
-            const int hy = hp / HWD, hx = hp - hy * HWD;
-            const int gy = Y0 - 1 + hy, gx = X0 - 1 + hx;
-            st[it] = (idx < NH * NQ && gy >= 0 && gy < H && gx >= 0 && gx < W)
-                         ? *reinterpret_cast<const uint4*>(xb + ((int64_t)gy * W + gx) * C + 8 * q)
-                         : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int it = 0; it < NST; ++it) {
-            const int idx = tid + 256 * it;
-            const int hp = idx / NQ, q = idx - hp * NQ;
-            if (idx < NH * NQ) *reinterpret_cast<uint4*>(in_s + hp * C + 8 * f16n_slot<C>(q, hp)) = st[it];
-        }
-    }
+    stage_halo_f16<C, TH>(xb, in_s, tid, Y0, X0, H, W);
     // steps: C = 32: the 9 taps (lane's k-slot = channels 8g .. 8g+7); C = 16: 5 tap pairs (tap 2j + (g >> 1), channels
     // 8 (g & 1) .. + 7; the tenth half has zero weights and reads a valid pixel)
     constexpr int NS = C == 16 ? 5 : 9;
@@ -780,8 +575,8 @@ __global__ __launch_bounds__(256, C == 16 ? 4 : 3) void conv3x3_mish_f16_narrow_
         const int ky = tap / 3, kx = tap - 3 * ky;
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
-            const int hp = (RW * wave + r + ky) * HWD + n + kx;
-            bv[r] = *reinterpret_cast<const f16x8e*>(in_s + hp * C + 8 * f16n_slot<C>(gq, hp));
+            const int hp = (RW * wave + r + ky) * kEcHW + n + kx;
+            bv[r] = *reinterpret_cast<const f16x8e*>(in_s + hp * C + 8 * px16_slot<C>(gq, hp));
         }
     };
     read_b(bb[0], 0);
@@ -806,73 +601,38 @@ __global__ __launch_bounds__(256, C == 16 ? 4 : 3) void conv3x3_mish_f16_narrow_
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const int gy = Y0 + RW * wave + r, gx = X0 + n;
-            if (gy < H && gx < W) {
-                f16x4e o;
-                o[0] = (_Float16)enc_mishf(acc[r][ft][0] + bq.x);
-                o[1] = (_Float16)enc_mishf(acc[r][ft][1] + bq.y);
-                o[2] = (_Float16)enc_mishf(acc[r][ft][2] + bq.z);
-                o[3] = (_Float16)enc_mishf(acc[r][ft][3] + bq.w);
-                *reinterpret_cast<f16x4e*>(ob + ((int64_t)gy * Wo + gx) * C + 16 * ft + 4 * g) = o;
-            }
+            if (gy < H && gx < W) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * C + 16 * ft + 4 * g, acc[r][ft], bq);
         }
     }
-    // ---- zero border of the padded output (C / 8 sixteen-byte chunks per pixel) ----
-    if (pad_w > 0 && X0 + kEcTW >= W) {
-        for (int i = tid; i < TH * pad_w * NQ; i += 256) {
-            const int q = i % NQ, r = i / NQ, col = r % pad_w, row = r / pad_w;
-            const int gy = Y0 + row;
-            if (gy < H) *reinterpret_cast<uint4*>(ob + ((int64_t)gy * Wo + W + col) * C + 8 * q) = make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
-    if (pad_h > 0 && Y0 + TH >= H) {
-        const int x_end = (X0 + kEcTW >= W) ? Wo : X0 + kEcTW;   // the corner belongs to the last tile
-        for (int i = tid; i < pad_h * (x_end - X0) * NQ; i += 256) {
-            const int q = i % NQ, r = i / NQ, col = r % (x_end - X0), row = r / (x_end - X0);
-            *reinterpret_cast<uint4*>(ob + ((int64_t)(H + row) * Wo + X0 + col) * C + 8 * q) = make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
+    zero_border<__half, TH, C / 8>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 0);
 }
 
-#ifndef QPWC_ENC16_NARROW
-#define QPWC_ENC16_NARROW 1   // 0: the narrow levels on conv3x3_mish_f16_kernel (A/B)
-#endif
 template <int C>
 static int conv3x3_mish_f16_narrow_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H,
                                           int W, int pad_h, int pad_w, hipStream_t s) {
-    const int tiles_x = (W + kEcTW - 1) / kEcTW, tiles_y = (H + 15) / 16;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles > INT32_MAX) {
-        set_error("conv3x3_mish_f16: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((conv3x3_mish_f16_narrow_kernel<C>), dim3((unsigned)n_tiles), dim3(256), 0, s, (const __half*)x,
-                       (const __half*)weight, (const float*)bias, (__half*)out, H, W, pad_h, pad_w, tiles_x, tiles_y);
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, 16, 1, "conv3x3_mish_f16")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((conv3x3_mish_f16_narrow_kernel<C>), dim3((unsigned)p.n_wgs), dim3(256), 0, s, (const __half*)x,
+                       (const __half*)weight, (const float*)bias, (__half*)out, H, W, pad_h, pad_w, p.tiles_x, p.tiles_y);
     return check_launch("conv3x3_mish_f16_narrow_kernel");
 }
 
 template <int C, int TH>
 static int conv3x3_mish_f16_launch_t(const void* x, const void* weight, const void* bias, void* out, int B, int H,
                                      int W, int pad_h, int pad_w, hipStream_t s) {
-    constexpr int NSL = C < 64 ? 1 : C / 64;
-    const int tiles_x = (W + kEcTW - 1) / kEcTW, tiles_y = (H + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * NSL > INT32_MAX) {
-        set_error("conv3x3_mish_f16: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((conv3x3_mish_f16_kernel<C, TH>), dim3((unsigned)(n_tiles * NSL)), dim3(256), 0, s,
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, TH, C / 64, "conv3x3_mish_f16")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((conv3x3_mish_f16_kernel<C, TH>), dim3((unsigned)p.n_wgs), dim3(256), 0, s,
                        (const __half*)x, (const __half*)weight, (const float*)bias, (__half*)out, H, W, pad_h, pad_w,
-                       tiles_x, tiles_y, (int)n_tiles);
+                       p.tiles_x, p.tiles_y, (int)p.n_tiles);
     return check_launch("conv3x3_mish_f16_kernel");
 }
 
 int conv3x3_mish_f16_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                             int C, int pad_h, int pad_w, hipStream_t s) {
     switch (C) {
-        case 16: return QPWC_ENC16_NARROW ? conv3x3_mish_f16_narrow_launch<16>(x, weight, bias, out, B, H, W, pad_h, pad_w, s)
-                                          : conv3x3_mish_f16_launch_t<16, 8>(x, weight, bias, out, B, H, W, pad_h, pad_w, s);
-        case 32: return QPWC_ENC16_NARROW ? conv3x3_mish_f16_narrow_launch<32>(x, weight, bias, out, B, H, W, pad_h, pad_w, s)
-                                          : conv3x3_mish_f16_launch_t<32, 8>(x, weight, bias, out, B, H, W, pad_h, pad_w, s);
+        case 16: return conv3x3_mish_f16_narrow_launch<16>(x, weight, bias, out, B, H, W, pad_h, pad_w, s);
+        case 32: return conv3x3_mish_f16_narrow_launch<32>(x, weight, bias, out, B, H, W, pad_h, pad_w, s);
         case 64: return conv3x3_mish_f16_launch_t<64, 8>(x, weight, bias, out, B, H, W, pad_h, pad_w, s);
         case 128: return conv3x3_mish_f16_launch_t<128, 8>(x, weight, bias, out, B, H, W, pad_h, pad_w, s);
         case 256: return conv3x3_mish_f16_launch_t<256, 4>(x, weight, bias, out, B, H, W, pad_h, pad_w, s);
@@ -1025,9 +785,7 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_kernel(const float* _
         const int gy = Y0 + m, gx = X0 + n;
         if (gy < H && gx < W) {
             float* op = ob + ((int64_t)(2 * gy + py) * W2 + 2 * gx + px) * out_pixel_stride + fo + 4 * g;
-            *reinterpret_cast<float4*>(op) =
-                make_float4(enc_mishf(acc[m][0] + bq.x), enc_mishf(acc[m][1] + bq.y),
-                            enc_mishf(acc[m][2] + bq.z), enc_mishf(acc[m][3] + bq.w));
+            bias_mish_store4(op, acc[m], bq);
             if (sk != nullptr) *reinterpret_cast<float4*>(op + F) = sv[m];
         }
     }
@@ -1036,21 +794,17 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_kernel(const float* _
 template <int C, int TH>
 static int upconv_launch_t(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W, int F,
                            int out_pixel_stride, hipStream_t s, UpSkip skip) {
-    const int tiles_x = (W + kEcTW - 1) / kEcTW, tiles_y = (H + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * (F / 16) > INT32_MAX) {
-        set_error("upconv4x4s2_mish: too many tiles");
-        return QPWC_E_SHAPE;
-    }
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, TH, F / 16, "upconv4x4s2_mish")) return QPWC_E_SHAPE;
     // QPWC_UPCONV64_LDS_TOTAL (A/B, round 4): pad the workgroup's LDS footprint to this many bytes with dynamic LDS the kernel never
     // touches -- 81 KiB leaves ONE decoder workgroup per CU and room for a 79 KiB SeparableConv2D workgroup of the flow chain
     constexpr size_t kStatic = (size_t)(TH + 2) * kEcHW * C * sizeof(float);
     // (the finest decoder level of a SMALL step only: at config 4's 32 k workgroups one per CU costs +0.7 %)
-    const size_t want = (C == 64 && QPWC_UPCONV64_LDS_TOTAL && n_tiles * (F / 16) <= 2048) ? QPWC_UPCONV64_LDS_TOTAL : 0;
+    const size_t want = (C == 64 && QPWC_UPCONV64_LDS_TOTAL && p.n_wgs <= 2048) ? QPWC_UPCONV64_LDS_TOTAL : 0;
     const size_t extra = want > kStatic ? want - kStatic : 0;
-    hipLaunchKernelGGL((upconv4x4s2_mish_kernel<C, TH>), dim3((unsigned)(n_tiles * (F / 16))), dim3(256), extra, s,
+    hipLaunchKernelGGL((upconv4x4s2_mish_kernel<C, TH>), dim3((unsigned)p.n_wgs), dim3(256), extra, s,
                        (const float*)x, (const float*)weight, (const float*)bias, (float*)out, H, W, F,
-                       out_pixel_stride, tiles_x, tiles_y, (int)n_tiles, skip);
+                       out_pixel_stride, p.tiles_x, p.tiles_y, (int)p.n_tiles, skip);
     return check_launch("upconv4x4s2_mish_kernel");
 }
 
@@ -1077,9 +831,7 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
                                                                       __half* __restrict__ out, int H, int W, int F,
                                                                       int out_pixel_stride, int tiles_x, int tiles_y,
                                                                       int n_tiles, UpSkip skip, int nfb) {
-    constexpr int NQ = C / 8, NKB = C / 32;
-    constexpr int HH = TH + 2, NH = HH * kEcHW;
-    constexpr int NST = (NH * NQ + 255) / 256;
+    constexpr int NH = (TH + 2) * kEcHW, NKB = C / 32;
     __shared__ __attribute__((aligned(16))) __half in_s[NH * C];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1092,26 +844,7 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
     const int X0 = tx * kEcTW, Y0 = ty * TH;
     int fo = 16 * fblk0;
-    const __half* xb = x + (int64_t)b * H * W * C;
-    {
-        uint4 st[NST];
-#pragma unroll
-        for (int it = 0; it < NST; ++it) {
-            const int idx = tid + 256 * it;
-            const int hp = idx / NQ, q = idx - hp * NQ;
-            const int hy = hp / kEcHW, hx = hp - hy * kEcHW;
-            const int gy = Y0 - 1 + hy, gx = X0 - 1 + hx;
-            st[it] = (idx < NH * NQ && gy >= 0 && gy < H && gx >= 0 && gx < W)
-                         ? *reinterpret_cast<const uint4*>(xb + ((int64_t)gy * W + gx) * C + 8 * q)
-                         : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int it = 0; it < NST; ++it) {
-            const int idx = tid + 256 * it;
-            const int hp = idx / NQ, q = idx - hp * NQ;
-            if (idx < NH * NQ) *reinterpret_cast<uint4*>(in_s + hp * C + 8 * f16_slot<C>(q, hp)) = st[it];
-        }
-    }
+    stage_halo_f16<C, TH>(x + (int64_t)b * H * W * C, in_s, tid, Y0, X0, H, W);
     const int dy1 = py ? 1 : -1, dx1 = px ? 1 : -1;
     const int ky0 = py ? 2 : 1, ky1 = py ? 0 : 3, kx0 = px ? 2 : 1, kx1 = px ? 0 : 3;
     const int kpos[4] = {ky0 * 4 + kx0, ky0 * 4 + kx1, ky1 * 4 + kx0, ky1 * 4 + kx1};
@@ -1125,7 +858,7 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
     };
     load_w(wv, 0);
     __syncthreads();
-    // one 32-channel block with the weights in `wv`; the two register sets alternate (QPWC_W_NEXT_ALWAYS)
+    // one 32-channel block with the weights in `wv`
     auto block = [&](f16x8e (&wv)[4], int kb) __attribute__((always_inline)) {
         // (operand reads one tap ahead, as in conv3x3_mish_f16_kernel: config 5's step 1.709 vs 1.706 ms -- as the compiler places them)
 #pragma unroll
@@ -1133,7 +866,7 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
 #pragma unroll
             for (int m = 0; m < TH; ++m) {
                 const int hp = (m + 1 + offy[t]) * kEcHW + n + 1 + offx[t];
-                const f16x8e bv = *reinterpret_cast<const f16x8e*>(in_s + hp * C + 8 * f16_slot<C>(4 * kb + g, hp));
+                const f16x8e bv = *reinterpret_cast<const f16x8e*>(in_s + hp * C + 8 * px16_slot<C>(4 * kb + g, hp));
                 acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[t], bv, acc[m], 0, 0, 0);
             }
     };
@@ -1143,21 +876,6 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
     if (fb > 0) load_w(wv, 0);     // (the first block's weights went out before the barrier)
 #pragma unroll
     for (int m = 0; m < TH; ++m) acc[m] = f32x4e{0.f, 0.f, 0.f, 0.f};
-#if QPWC_W_NEXT_ALWAYS_F16
-    {
-        int kb = 0;
-#pragma unroll 1
-        for (; kb + 1 < NKB; kb += 2) {
-            load_w(wn, kb + 1);
-            __builtin_amdgcn_sched_barrier(0);   // (unfenced, the scheduler sinks the requests to just in front of their use)
-            block(wv, kb);
-            load_w(wv, kb + 2 < NKB ? kb + 2 : kb);   // (last trip: a harmless re-read)
-            __builtin_amdgcn_sched_barrier(0);
-            block(wn, kb + 1);
-        }
-        if (kb < NKB) block(wv, kb);   // odd number of blocks
-    }
-#else
 #pragma unroll 1
     for (int kb = 0; kb < NKB; ++kb) {
         if (kb + 1 < NKB) load_w(wn, kb + 1);
@@ -1165,7 +883,6 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
 #pragma unroll
         for (int t = 0; t < 4; ++t) wv[t] = wn[t];
     }
-#endif
     const int H2 = 2 * H, W2 = 2 * W;
     __half* ob = out + (int64_t)b * H2 * W2 * out_pixel_stride;
     const __half* sk = reinterpret_cast<const __half*>(skip.p);   // (see upconv4x4s2_mish_kernel)
@@ -1185,13 +902,8 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
     for (int m = 0; m < TH; ++m) {
         const int gy = Y0 + m, gx = X0 + n;
         if (gy < H && gx < W) {
-            f16x4e o;
-            o[0] = (_Float16)enc_mishf(acc[m][0] + bq.x);
-            o[1] = (_Float16)enc_mishf(acc[m][1] + bq.y);
-            o[2] = (_Float16)enc_mishf(acc[m][2] + bq.z);
-            o[3] = (_Float16)enc_mishf(acc[m][3] + bq.w);
             __half* op = ob + ((int64_t)(2 * gy + py) * W2 + 2 * gx + px) * out_pixel_stride + fo + 4 * g;
-            *reinterpret_cast<f16x4e*>(op) = o;
+            bias_mish_store4(op, acc[m], bq);
             if (sk != nullptr) *reinterpret_cast<f16x4e*>(op + F) = sv[m];
         }
     }
@@ -1201,18 +913,15 @@ __global__ __launch_bounds__(256, 2) void upconv4x4s2_mish_f16_kernel(const __ha
 template <int C, int TH>
 static int upconv_f16_launch_t(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W, int F,
                                int out_pixel_stride, hipStream_t s, UpSkip skip) {
-    const int tiles_x = (W + kEcTW - 1) / kEcTW, tiles_y = (H + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * (F / 16) > INT32_MAX) {
-        set_error("upconv4x4s2_mish_f16: too many tiles");
-        return QPWC_E_SHAPE;
-    }
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, TH, F / 16, "upconv4x4s2_mish_f16")) return QPWC_E_SHAPE;
+    const int64_t n_tiles = p.n_tiles;
     // output blocks per workgroup: as many as leave the launch QPWC_UPCONV16_NFB_MIN_WGS workgroups (two per CU)
     int nfb = 1;
     while (nfb * 2 <= F / 16 && (F / 16) % (nfb * 2) == 0 && n_tiles * (F / 16) / (nfb * 2) >= QPWC_UPCONV16_NFB_MIN_WGS) nfb *= 2;
-    hipLaunchKernelGGL((upconv4x4s2_mish_f16_kernel<C, TH>), dim3((unsigned)(n_tiles * (F / 16) / nfb)), dim3(256), 0, s,
+    hipLaunchKernelGGL((upconv4x4s2_mish_f16_kernel<C, TH>), dim3((unsigned)(p.n_wgs / nfb)), dim3(256), 0, s,
                        (const __half*)x, (const __half*)weight, (const float*)bias, (__half*)out, H, W, F,
-                       out_pixel_stride, tiles_x, tiles_y, (int)n_tiles, skip, nfb);
+                       out_pixel_stride, p.tiles_x, p.tiles_y, (int)n_tiles, skip, nfb);
     return check_launch("upconv4x4s2_mish_f16_kernel");
 }
 
@@ -1325,27 +1034,21 @@ __global__ __launch_bounds__(256, 4) void first_conv_mish_kernel(const T* __rest
     for (int r = 0; r < kFcTR; ++r) {
         const int gy = Y0 + kFcTR * (wave & 1) + r, gx = X0 + n;
         if (gy < Ho && gx < Wo)
-            st4q(ob + ((int64_t)gy * Wo + gx) * 16 + 4 * g,
-                 make_float4(enc_mishf(acc[r][0] + bq.x), enc_mishf(acc[r][1] + bq.y), enc_mishf(acc[r][2] + bq.z),
-                             enc_mishf(acc[r][3] + bq.w)));
+            st4q(ob + ((int64_t)gy * Wo + gx) * 16 + 4 * g, bias_mish4(acc[r], bq));
     }
 }
 
 int first_conv_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                            int layout, int dtype, hipStream_t s) {
-    const int tiles_x = (W / 2 + kEcTW - 1) / kEcTW, tiles_y = (H / 2 + kFcTH - 1) / kFcTH;
-    const int64_t nblk = (int64_t)tiles_x * tiles_y * B;
-    if (nblk > INT32_MAX) {
-        set_error("first_conv_mish: too many tiles");
-        return QPWC_E_SHAPE;
-    }
+    TilePlan p;
+    if (!tile_plan(p, B, H / 2, W / 2, kFcTH, 1, "first_conv_mish")) return QPWC_E_SHAPE;
     if (dtype == QPWC_F32)
-        hipLaunchKernelGGL(first_conv_mish_kernel<float>, dim3((unsigned)nblk), dim3(256), 0, s, (const float*)x,
-                           (const float*)weight, (const float*)bias, (float*)out, B, H, W, tiles_x, tiles_y,
+        hipLaunchKernelGGL(first_conv_mish_kernel<float>, dim3((unsigned)p.n_wgs), dim3(256), 0, s, (const float*)x,
+                           (const float*)weight, (const float*)bias, (float*)out, B, H, W, p.tiles_x, p.tiles_y,
                            layout == QPWC_NCHW ? 1 : 0);
     else
-        hipLaunchKernelGGL(first_conv_mish_kernel<__half>, dim3((unsigned)nblk), dim3(256), 0, s, (const __half*)x,
-                           (const float*)weight, (const float*)bias, (__half*)out, B, H, W, tiles_x, tiles_y,
+        hipLaunchKernelGGL(first_conv_mish_kernel<__half>, dim3((unsigned)p.n_wgs), dim3(256), 0, s, (const __half*)x,
+                           (const float*)weight, (const float*)bias, (__half*)out, B, H, W, p.tiles_x, p.tiles_y,
                            layout == QPWC_NCHW ? 1 : 0);
     return check_launch("first_conv_mish_kernel");
 }
@@ -1426,10 +1129,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3s2_mish_kernel(const float* __r
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const int gy = Y0 + 2 * wave + m, gx = X0 + n;
-            if (gy < Ho && gx < Wo)
-                *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * CO + 16 * ft + 4 * g) =
-                    make_float4(enc_mishf(acc[m][ft][0] + bq.x), enc_mishf(acc[m][ft][1] + bq.y),
-                                enc_mishf(acc[m][ft][2] + bq.z), enc_mishf(acc[m][ft][3] + bq.w));
+            if (gy < Ho && gx < Wo) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * CO + 16 * ft + 4 * g, acc[m][ft], bq);
         }
     }
 }
@@ -1553,26 +1253,18 @@ __global__ __launch_bounds__(256, (2 * (2 * TH + 1) * (kEcTW + 1) * CI * 4 > 80 
 #pragma unroll
     for (int m = 0; m < TH; ++m) {
         const int gy = Y0 + m, gx = X0 + n;
-        if (gy < Ho && gx < Wo)
-            *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * CO + fo + 4 * g) =
-                make_float4(enc_mishf(acc[m][0] + bq.x), enc_mishf(acc[m][1] + bq.y),
-                            enc_mishf(acc[m][2] + bq.z), enc_mishf(acc[m][3] + bq.w));
+        if (gy < Ho && gx < Wo) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * CO + fo + 4 * g, acc[m], bq);
     }
 }
 
 template <int CI, int TH>
 static int conv3x3s2_mish_wide_launch(const void* x, const void* weight, const void* bias, void* out, int B,
                                       int H, int W, hipStream_t s) {
-    const int tiles_x = (W / 2 + kEcTW - 1) / kEcTW, tiles_y = (H / 2 + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    const int slices = 2 * CI / 64;
-    if (n_tiles * slices > INT32_MAX) {
-        set_error("conv3x3s2_mish: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((conv3x3s2_mish_wide_kernel<CI, TH>), dim3((unsigned)(n_tiles * slices)), dim3(256), 0, s,
-                       (const float*)x, (const float*)weight, (const float*)bias, (float*)out, H, W, tiles_x, tiles_y,
-                       (int)n_tiles);
+    TilePlan p;
+    if (!tile_plan(p, B, H / 2, W / 2, TH, 2 * CI / 64, "conv3x3s2_mish")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((conv3x3s2_mish_wide_kernel<CI, TH>), dim3((unsigned)p.n_wgs), dim3(256), 0, s,
+                       (const float*)x, (const float*)weight, (const float*)bias, (float*)out, H, W, p.tiles_x, p.tiles_y,
+                       (int)p.n_tiles);
     return check_launch("conv3x3s2_mish_wide_kernel");
 }
 
@@ -1582,14 +1274,10 @@ int conv3x3s2_mish_any_launch(const void* x, const void* weight, const void* bia
 
 int conv3x3s2_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                           hipStream_t s) {
-    const int tiles_x = (W / 2 + kEcTW - 1) / kEcTW, tiles_y = (H / 2 + kEcTH - 1) / kEcTH;
-    const int64_t nblk = (int64_t)tiles_x * tiles_y * B;
-    if (nblk > INT32_MAX) {
-        set_error("conv3x3s2_mish: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL(conv3x3s2_mish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const float*)x,
-                       (const float*)weight, (const float*)bias, (float*)out, H, W, tiles_x, tiles_y);
+    TilePlan p;
+    if (!tile_plan(p, B, H / 2, W / 2, kEcTH, 1, "conv3x3s2_mish")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL(conv3x3s2_mish_kernel, dim3((unsigned)p.n_wgs), dim3(256), 0, s, (const float*)x,
+                       (const float*)weight, (const float*)bias, (float*)out, H, W, p.tiles_x, p.tiles_y);
     return check_launch("conv3x3s2_mish_kernel");
 }
 
@@ -1607,8 +1295,8 @@ int conv3x3s2_mish_any_launch(const void* x, const void* weight, const void* bia
 // fp16-storage twin of the stride-2 kernels (conv_a of encoder levels 2..5, BASELINE configs[4]): x_padded
 // (B, H+1, W+1, CI), weight ([9][2 CI][CI]) and out (B, H/2, W/2, 2 CI) fp16, bias fp32.  TH x 16 output pixels per
 // workgroup; the (2 TH + 1) x 33 input patch sits in LDS with even and odd columns in separate planes, so the taps of
-// 16 neighbouring outputs are 16 consecutive pixels of a plane; pixels of max(CI, 32) halves, chunk swizzle as in
-// conv3x3_mish_f16_kernel.  A wave owns one block of 16 outputs (2 CI = 32: two waves per block, half the rows each)
+// 16 neighbouring outputs are 16 consecutive pixels of a plane; pixels of max(CI, 32) halves, chunk swizzle
+// px16_slot.  A wave owns one block of 16 outputs (2 CI = 32: two waves per block, half the rows each)
 // with its weights for 32 input channels in registers; one v_mfma_f32_16x16x32_f16 per tap, row and 32-channel block.
 template <int CI, int TH>
 __global__ __launch_bounds__(256) void conv3x3s2_mish_f16_kernel(const __half* __restrict__ x,
@@ -1653,7 +1341,7 @@ __global__ __launch_bounds__(256) void conv3x3s2_mish_f16_kernel(const __half* _
             const int q = idx % NQ, pc = idx / NQ;
             const int row = pc / (2 * kEcTW + 1), col = pc - row * (2 * kEcTW + 1);
             const int hp = ((col & 1) * IH + row) * PW + (col >> 1);
-            if (idx < NCH) *reinterpret_cast<uint4*>(in_s + hp * CP + 8 * f16_slot<CP>(q, hp)) = st[it];
+            if (idx < NCH) *reinterpret_cast<uint4*>(in_s + hp * CP + 8 * px16_slot<CP>(q, hp)) = st[it];
         }
     }
     const int blk = WB == 4 ? 4 * slice + wave : (wave % WB);
@@ -1673,7 +1361,7 @@ __global__ __launch_bounds__(256) void conv3x3s2_mish_f16_kernel(const __half* _
     };
     load_w(wv, 0);
     __syncthreads();
-    // one 32-channel block with the weights in `wv`; the two register sets alternate (QPWC_W_NEXT_ALWAYS)
+    // one 32-channel block with the weights in `wv`
     auto block = [&](f16x8e (&wv)[9], int kb) __attribute__((always_inline)) {
         // (operand reads two taps ahead of their matrix instructions: config 5's step 1.709 vs 1.706 ms -- as the compiler places them)
 #pragma unroll
@@ -1682,26 +1370,11 @@ __global__ __launch_bounds__(256) void conv3x3s2_mish_f16_kernel(const __half* _
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
                 const int hp = ((kx & 1) * IH + 2 * (r0 + r) + ky) * PW + n + (kx >> 1);
-                const f16x8e bv = *reinterpret_cast<const f16x8e*>(in_s + hp * CP + 8 * f16_slot<CP>(4 * kb + g, hp));
+                const f16x8e bv = *reinterpret_cast<const f16x8e*>(in_s + hp * CP + 8 * px16_slot<CP>(4 * kb + g, hp));
                 acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[tap], bv, acc[r], 0, 0, 0);
             }
         }
     };
-#if QPWC_W_NEXT_ALWAYS_F16
-    {
-        int kb = 0;
-#pragma unroll 1
-        for (; kb + 1 < NKB; kb += 2) {
-            load_w(wn, kb + 1);
-            __builtin_amdgcn_sched_barrier(0);   // (unfenced, the scheduler sinks the requests to just in front of their use)
-            block(wv, kb);
-            load_w(wv, kb + 2 < NKB ? kb + 2 : kb);   // (last trip: a harmless re-read)
-            __builtin_amdgcn_sched_barrier(0);
-            block(wn, kb + 1);
-        }
-        if (kb < NKB) block(wv, kb);   // odd number of blocks
-    }
-#else
 #pragma unroll 1
     for (int kb = 0; kb < NKB; ++kb) {
         if (kb + 1 < NKB) load_w(wn, kb + 1);
@@ -1709,16 +1382,13 @@ __global__ __launch_bounds__(256) void conv3x3s2_mish_f16_kernel(const __half* _
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) wv[tap] = wn[tap];
     }
-#endif
     __half* ob = out + (int64_t)b * Ho * Wo * CO;
     const float4 bq = *reinterpret_cast<const float4*>(bias + fo + 4 * g);
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
         const int gy = Y0 + r0 + r, gx = X0 + n;
         if (gy < Ho && gx < Wo)
-            st4q(ob + ((int64_t)gy * Wo + gx) * CO + fo + 4 * g,
-                 make_float4(enc_mishf(acc[r][0] + bq.x), enc_mishf(acc[r][1] + bq.y), enc_mishf(acc[r][2] + bq.z),
-                             enc_mishf(acc[r][3] + bq.w)));
+            st4q(ob + ((int64_t)gy * Wo + gx) * CO + fo + 4 * g, bias_mish4(acc[r], bq));
     }
 }
 
@@ -1726,15 +1396,11 @@ template <int CI, int TH>
 static int conv3x3s2_mish_f16_launch_t(const void* x, const void* weight, const void* bias, void* out, int B, int H,
                                        int W, hipStream_t s) {
     constexpr int NSL = (2 * CI / 16) < 4 ? 1 : (2 * CI / 16) / 4;
-    const int tiles_x = (W / 2 + kEcTW - 1) / kEcTW, tiles_y = (H / 2 + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * NSL > INT32_MAX) {
-        set_error("conv3x3s2_mish_f16: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((conv3x3s2_mish_f16_kernel<CI, TH>), dim3((unsigned)(n_tiles * NSL)), dim3(256), 0, s,
-                       (const __half*)x, (const __half*)weight, (const float*)bias, (__half*)out, H, W, tiles_x,
-                       tiles_y, (int)n_tiles);
+    TilePlan p;
+    if (!tile_plan(p, B, H / 2, W / 2, TH, NSL, "conv3x3s2_mish_f16")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((conv3x3s2_mish_f16_kernel<CI, TH>), dim3((unsigned)p.n_wgs), dim3(256), 0, s,
+                       (const __half*)x, (const __half*)weight, (const float*)bias, (__half*)out, H, W, p.tiles_x,
+                       p.tiles_y, (int)p.n_tiles);
     return check_launch("conv3x3s2_mish_f16_kernel");
 }
 
@@ -1751,15 +1417,11 @@ int conv3x3s2_mish_f16_launch(const void* x, const void* weight, const void* bia
 
 int conv3x3_mish_launch(const void* x, const void* weight, const void* bias, void* out, int B, int H, int W,
                         int C, int pad_h, int pad_w, hipStream_t s) {
-    const int tiles_x = (W + kEcTW - 1) / kEcTW, tiles_y = (H + kEcTH - 1) / kEcTH;
-    constexpr int NT = QPWC_ENC_NT;
-    const int groups_x = (tiles_x + NT - 1) / NT;
-    const int64_t nblk = (int64_t)groups_x * tiles_y * B;
-    if (nblk > INT32_MAX) {
-        set_error("conv3x3_mish: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    const dim3 grid((unsigned)nblk);
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, kEcTH, 1, "conv3x3_mish")) return QPWC_E_SHAPE;
+    constexpr int NT = QPWC_ENC_NT;   // a workgroup of the narrow kernel walks NT tiles
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y, groups_x = (tiles_x + NT - 1) / NT;
+    const dim3 grid((unsigned)((int64_t)groups_x * tiles_y * B));
     if (C == 16)
         hipLaunchKernelGGL((conv3x3_mish_kernel<16, NT>), grid, dim3(256), 0, s, (const float*)x, (const float*)weight,
                            (const float*)bias, (float*)out, H, W, pad_h, pad_w, tiles_x, tiles_y, groups_x);

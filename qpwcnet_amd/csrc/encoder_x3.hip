@@ -6,90 +6,12 @@
 // staging and its activations' bytes instead.
 //
 // The input tile (with its 3x3 halo) is split ONCE per workgroup while it is staged: LDS holds three bf16 images of
-// the tile (pixels of C halves, 16-byte chunk q of halo pixel p at slot x3_slot(q, p) -- the layout of the fp16
+// the tile (pixels of C halves, 16-byte chunk q of halo pixel p at slot px16_slot(q, p) -- the layout of the fp16
 // kernels); the weights are split once on the host side of the boundary (qpwc_split_bf16x3_fwd) and streamed as
 // 16-byte operands.
-#include "common.h"
-#include "launch.h"
-#include "split_bf16.h"
+#include "conv_fwd_common.h"
 
 namespace qpwc {
-
-namespace {
-
-__device__ __forceinline__ float x3_mishf(float x) {
-    const float e = __builtin_amdgcn_exp2f(fminf(x, 20.0f) * 1.4426950408889634f);
-    const float t = e * (e + 2.0f);
-    const float m = x * (t * __builtin_amdgcn_rcpf(t + 2.0f));
-    return m;   // x > 20: e is clamped, t / (t + 2) rounds to 1 +- 1 ulp, m = x to 2 ulp -- no compare + select per value
-}
-
-constexpr int kX3TW = 16, kX3HW = kX3TW + 2;
-
-// 16-byte chunk q of halo pixel hp within a pixel of C bf16 values (32 / 64 / 128 / 256 / 512 bytes): the sixteen
-// pixels one matrix operand read covers must spread over the 64 banks
-template <int C>
-__device__ __forceinline__ int x3_slot(int q, int hp) {
-    return C == 16 ? (q ^ ((hp >> 3) & 1)) : (C == 32 ? (q ^ ((0 - (hp >> 2)) & 3)) : (C == 64 ? (q ^ ((hp >> 1) & 7)) : (q ^ (hp & 15))));
-}
-
-// Stage the (TH + 2) x 18 halo tile of all C channels as three bf16 images (zero outside the image): all global
-// loads first, then split + LDS writes.  s1 = image 1; images 2 and 3 follow at PL halves each.
-template <int C, int TH>
-__device__ __forceinline__ void x3_stage_tile(const float* __restrict__ xb, unsigned short* s1, int tid, int Y0, int X0,
-                                              int H, int W) {
-    constexpr int NQ = C / 8, NH = (TH + 2) * kX3HW, PL = NH * C;
-    constexpr int NST = (NH * NQ + 255) / 256;
-    float4 st[NST][2];
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-        const int idx = tid + 256 * it;
-        const int hp = idx / NQ, q = idx - hp * NQ;
-        const int hy = hp / kX3HW, hx = hp - hy * kX3HW;
-        const int gy = Y0 - 1 + hy, gx = X0 - 1 + hx;
-        const bool ok = idx < NH * NQ && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const float* p = xb + ((int64_t)gy * W + gx) * C + 8 * q;
-        st[it][0] = ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-        st[it][1] = ok ? *reinterpret_cast<const float4*>(p + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-        const int idx = tid + 256 * it;
-        const int hp = idx / NQ, q = idx - hp * NQ;
-        if (idx < NH * NQ) {
-            uint4 p1, p2, p3;
-            split8_bf16x3(st[it][0], st[it][1], p1, p2, p3);
-            unsigned short* d = s1 + hp * C + 8 * x3_slot<C>(q, hp);
-            *reinterpret_cast<uint4*>(d) = p1;
-            *reinterpret_cast<uint4*>(d + PL) = p2;
-            *reinterpret_cast<uint4*>(d + 2 * PL) = p3;
-        }
-    }
-}
-
-// zero border of the padded output (columns W.., rows H..) for channels [c0, c0 + 4 NQF) -- the 'SAME' padding the
-// following stride-2 convolution reads -- written by the edge tiles
-template <int TH>
-__device__ __forceinline__ void x3_zero_border(float* ob, int tid, int Y0, int X0, int H, int W, int pad_h, int pad_w,
-                                               int C, int c0, int NQF) {
-    const int Wo = W + pad_w;
-    if (pad_w > 0 && X0 + kX3TW >= W) {
-        for (int i = tid; i < TH * pad_w * NQF; i += 256) {
-            const int q = i % NQF, r = i / NQF, col = r % pad_w, row = r / pad_w;
-            const int gy = Y0 + row;
-            if (gy < H) *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + W + col) * C + c0 + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    if (pad_h > 0 && Y0 + TH >= H) {
-        const int x_end = (X0 + kX3TW >= W) ? Wo : X0 + kX3TW;   // the corner belongs to the last tile
-        for (int i = tid; i < pad_h * (x_end - X0) * NQF; i += 256) {
-            const int q = i % NQF, r = i / NQF, col = r % (x_end - X0), row = r / (x_end - X0);
-            *reinterpret_cast<float4*>(ob + ((int64_t)(H + row) * Wo + X0 + col) * C + c0 + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------
 // Wide levels (C = 64 / 128 / 256): a wave owns ONE block of 16 outputs for all TH rows of a TH x 16 pixel tile;
@@ -99,10 +21,10 @@ __device__ __forceinline__ void x3_zero_border(float* ob, int tid, int Y0, int X
 // wave at every level of the 256x512 pyramid.
 // w3: [3 images][9 taps][C out][C in] bf16.
 template <int C, int TH>
-__global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024 || TH >= 8) ? 1 : 2) void conv3x3_mish_x3_wide_kernel(
+__global__ __launch_bounds__(256, (3 * (TH + 2) * kCfHW * C * 2 > 80 * 1024 || TH >= 8) ? 1 : 2) void conv3x3_mish_x3_wide_kernel(
     const float* __restrict__ x, const unsigned short* __restrict__ w3, const float* __restrict__ bias,
     float* __restrict__ out, int H, int W, int pad_h, int pad_w, int tiles_x, int tiles_y, int n_tiles) {
-    constexpr int NH = (TH + 2) * kX3HW, PL = NH * C;
+    constexpr int NH = (TH + 2) * kCfHW, PL = NH * C;
     constexpr int NKB = C / 32;
     __shared__ __attribute__((aligned(16))) unsigned short in_s[3 * PL];
     const int tid = threadIdx.x;
@@ -111,7 +33,7 @@ __global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024 || T
     const int slice = blockIdx.x / n_tiles;                       // 64 outputs
     const int tile = xcd_swizzle(blockIdx.x % n_tiles, n_tiles);
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int X0 = tx * kX3TW, Y0 = ty * TH;
+    const int X0 = tx * kCfTW, Y0 = ty * TH;
     const int fo = 64 * slice + 16 * wave;                        // this wave's output block
     const float* xb = x + (int64_t)b * H * W * C;
 
@@ -142,8 +64,8 @@ __global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024 || T
         uint4 bb[3][3];
         auto read_b = [&](uint4 (&bv)[3], int i) __attribute__((always_inline)) {
             const int tap = i / TH, m = i - tap * TH, ky = tap / 3, kx = tap - 3 * ky;
-            const int hp = (m + ky) * kX3HW + nn + kx;
-            const unsigned short* bp = in_s + hp * C + 8 * x3_slot<C>(4 * kb + gg, hp);
+            const int hp = (m + ky) * kCfHW + nn + kx;
+            const unsigned short* bp = in_s + hp * C + 8 * px16_slot<C>(4 * kb + gg, hp);
             bv[0] = *reinterpret_cast<const uint4*>(bp);
             bv[1] = *reinterpret_cast<const uint4*>(bp + PL);
             bv[2] = *reinterpret_cast<const uint4*>(bp + 2 * PL);
@@ -171,12 +93,9 @@ __global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024 || T
 #pragma unroll
     for (int m = 0; m < TH; ++m) {
         const int gy = Y0 + m, gx = X0 + n;
-        if (gy < H && gx < W)
-            *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * C + fo + 4 * g) =
-                make_float4(x3_mishf(acc[m][0] + bq.x), x3_mishf(acc[m][1] + bq.y), x3_mishf(acc[m][2] + bq.z),
-                            x3_mishf(acc[m][3] + bq.w));
+        if (gy < H && gx < W) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * C + fo + 4 * g, acc[m], bq);
     }
-    x3_zero_border<TH>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 64 * slice, 16);
+    zero_border<float, TH, 16>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 64 * slice);
 }
 
 // ---------------------------------------------------------------------------
@@ -189,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mish_x3_narrow_kernel(
     const float* __restrict__ x, const unsigned short* __restrict__ w3, const float* __restrict__ bias,
     float* __restrict__ out, int H, int W, int pad_h, int pad_w, int tiles_x, int tiles_y) {
     constexpr int TH = 16, RW = 4;
-    constexpr int NH = (TH + 2) * kX3HW, PL = NH * C;
+    constexpr int NH = (TH + 2) * kCfHW, PL = NH * C;
     constexpr int NFT = C / 16;
     __shared__ __attribute__((aligned(16))) unsigned short in_s[3 * PL];
     const int tid = threadIdx.x;
@@ -197,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mish_x3_narrow_kernel(
     const int lane = tid & 63, n = lane & 15, g = lane >> 4;
     const int tile = xcd_swizzle(blockIdx.x, gridDim.x);
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int X0 = tx * kX3TW, Y0 = ty * TH;
+    const int X0 = tx * kCfTW, Y0 = ty * TH;
     const float* xb = x + (int64_t)b * H * W * C;
     const int Wo = W + pad_w;
     float* ob = out + (int64_t)b * (H + pad_h) * Wo * C;
@@ -224,8 +143,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mish_x3_narrow_kernel(
                 const int ky = tap / 3, kx = tap - 3 * ky;
 #pragma unroll
                 for (int r = 0; r < RW; ++r) {
-                    const int hp = (RW * wave + r + ky) * kX3HW + n + kx;
-                    const unsigned short* bp = in_s + hp * C + 8 * x3_slot<C>(g, hp);
+                    const int hp = (RW * wave + r + ky) * kCfHW + n + kx;
+                    const unsigned short* bp = in_s + hp * C + 8 * px16_slot<C>(g, hp);
                     const uint4 b1 = *reinterpret_cast<const uint4*>(bp);
                     const uint4 b2 = *reinterpret_cast<const uint4*>(bp + PL);
                     const uint4 b3 = *reinterpret_cast<const uint4*>(bp + 2 * PL);
@@ -238,10 +157,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mish_x3_narrow_kernel(
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
                 const int gy = Y0 + RW * wave + r, gx = X0 + n;
-                if (gy < H && gx < W)
-                    *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * C + 16 * ft + 4 * g) =
-                        make_float4(x3_mishf(acc[r][0] + bq.x), x3_mishf(acc[r][1] + bq.y),
-                                    x3_mishf(acc[r][2] + bq.z), x3_mishf(acc[r][3] + bq.w));
+                if (gy < H && gx < W) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * C + 16 * ft + 4 * g, acc[r], bq);
             }
         }
     } else {
@@ -267,8 +183,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mish_x3_narrow_kernel(
             const int ky = tap / 3, kx = tap - 3 * ky;
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
-                const int hp = (RW * wave + r + ky) * kX3HW + n + kx;
-                const unsigned short* bp = in_s + hp * C + 8 * x3_slot<C>(gq, hp);
+                const int hp = (RW * wave + r + ky) * kCfHW + n + kx;
+                const unsigned short* bp = in_s + hp * C + 8 * px16_slot<C>(gq, hp);
                 const uint4 b1 = *reinterpret_cast<const uint4*>(bp);
                 const uint4 b2 = *reinterpret_cast<const uint4*>(bp + PL);
                 const uint4 b3 = *reinterpret_cast<const uint4*>(bp + 2 * PL);
@@ -279,41 +195,30 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mish_x3_narrow_kernel(
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const int gy = Y0 + RW * wave + r, gx = X0 + n;
-            if (gy < H && gx < W)
-                *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * C + 4 * g) =
-                    make_float4(x3_mishf(acc[r][0] + bq.x), x3_mishf(acc[r][1] + bq.y), x3_mishf(acc[r][2] + bq.z),
-                                x3_mishf(acc[r][3] + bq.w));
+            if (gy < H && gx < W) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * C + 4 * g, acc[r], bq);
         }
     }
-    x3_zero_border<TH>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 0, C / 4);
+    zero_border<float, TH, C / 4>(ob, tid, Y0, X0, H, W, pad_h, pad_w, C, 0);
 }
 
 template <int C, int TH>
 static int conv3x3_mish_x3_wide_launch(const void* x, const void* w3, const void* bias, void* out, int B, int H, int W,
                                        int pad_h, int pad_w, hipStream_t s) {
-    const int tiles_x = (W + kX3TW - 1) / kX3TW, tiles_y = (H + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * (C / 64) > INT32_MAX) {
-        set_error("conv3x3_mish_x3: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((conv3x3_mish_x3_wide_kernel<C, TH>), dim3((unsigned)(n_tiles * (C / 64))), dim3(256), 0, s,
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, TH, C / 64, "conv3x3_mish_x3")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((conv3x3_mish_x3_wide_kernel<C, TH>), dim3((unsigned)p.n_wgs), dim3(256), 0, s,
                        (const float*)x, (const unsigned short*)w3, (const float*)bias, (float*)out, H, W, pad_h, pad_w,
-                       tiles_x, tiles_y, (int)n_tiles);
+                       p.tiles_x, p.tiles_y, (int)p.n_tiles);
     return check_launch("conv3x3_mish_x3_wide_kernel");
 }
 
 template <int C>
 static int conv3x3_mish_x3_narrow_launch(const void* x, const void* w3, const void* bias, void* out, int B, int H, int W,
                                          int pad_h, int pad_w, hipStream_t s) {
-    const int tiles_x = (W + kX3TW - 1) / kX3TW, tiles_y = (H + 15) / 16;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles > INT32_MAX) {
-        set_error("conv3x3_mish_x3: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((conv3x3_mish_x3_narrow_kernel<C>), dim3((unsigned)n_tiles), dim3(256), 0, s, (const float*)x,
-                       (const unsigned short*)w3, (const float*)bias, (float*)out, H, W, pad_h, pad_w, tiles_x, tiles_y);
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, 16, 1, "conv3x3_mish_x3")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((conv3x3_mish_x3_narrow_kernel<C>), dim3((unsigned)p.n_wgs), dim3(256), 0, s, (const float*)x,
+                       (const unsigned short*)w3, (const float*)bias, (float*)out, H, W, pad_h, pad_w, p.tiles_x, p.tiles_y);
     return check_launch("conv3x3_mish_x3_narrow_kernel");
 }
 
@@ -342,11 +247,11 @@ int conv3x3_mish_x3_launch(const void* x, const void* w3, const void* bias, void
 // grid = tiles x 2 C_in / 64; weights (3, 9, 2 C_in, C_in) bf16 streamed through a ring of nine steps as in the
 // stride-1 kernel.
 template <int CI, int TH>
-__global__ __launch_bounds__(256, (3 * 2 * (2 * TH + 1) * (kX3TW + 1) * CI * 2 > 80 * 1024) ? 1 : 2) void conv3x3s2_mish_x3_kernel(
+__global__ __launch_bounds__(256, (3 * 2 * (2 * TH + 1) * (kCfTW + 1) * CI * 2 > 80 * 1024) ? 1 : 2) void conv3x3s2_mish_x3_kernel(
     const float* __restrict__ x, const unsigned short* __restrict__ w3, const float* __restrict__ bias,
     float* __restrict__ out, int H, int W, int tiles_x, int tiles_y, int n_tiles) {
     constexpr int CO = 2 * CI, NQ = CI / 8, NKB = CI / 32;
-    constexpr int IH = 2 * TH + 1, PW = kX3TW + 1;
+    constexpr int IH = 2 * TH + 1, PW = kCfTW + 1;
     constexpr int NPX = IH * 33, PL = 2 * IH * PW * CI;      // staged pixels; halves per image
     constexpr int NST = (NPX * NQ + 255) / 256;
     __shared__ __attribute__((aligned(16))) unsigned short in_s[3 * PL];
@@ -356,7 +261,7 @@ __global__ __launch_bounds__(256, (3 * 2 * (2 * TH + 1) * (kX3TW + 1) * CI * 2 >
     const int slice = blockIdx.x / n_tiles;
     const int tile = xcd_swizzle(blockIdx.x % n_tiles, n_tiles);
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int X0 = tx * kX3TW, Y0 = ty * TH;               // output coordinates
+    const int X0 = tx * kCfTW, Y0 = ty * TH;               // output coordinates
     const int Hp = H + 1, Wp = W + 1, Ho = H / 2, Wo = W / 2;
     const int fo = 64 * slice + 16 * wave;
     const float* xb = x + (int64_t)b * Hp * Wp * CI;
@@ -392,7 +297,7 @@ __global__ __launch_bounds__(256, (3 * 2 * (2 * TH + 1) * (kX3TW + 1) * CI * 2 >
             if (idx < NPX * NQ) {
                 uint4 p1, p2, p3;
                 split8_bf16x3(st[it][0], st[it][1], p1, p2, p3);
-                unsigned short* d = in_s + pix * CI + 8 * x3_slot<CI>(q, pix);
+                unsigned short* d = in_s + pix * CI + 8 * px16_slot<CI>(q, pix);
                 *reinterpret_cast<uint4*>(d) = p1;
                 *reinterpret_cast<uint4*>(d + PL) = p2;
                 *reinterpret_cast<uint4*>(d + 2 * PL) = p3;
@@ -411,7 +316,7 @@ __global__ __launch_bounds__(256, (3 * 2 * (2 * TH + 1) * (kX3TW + 1) * CI * 2 >
         auto read_b = [&](uint4 (&bv)[3], int i) __attribute__((always_inline)) {
             const int tap = i / TH, m = i - tap * TH, ky = tap / 3, kx = tap - 3 * ky;
             const int pix = ((kx & 1) * IH + 2 * m + ky) * PW + nn + (kx >> 1);
-            const unsigned short* bp = in_s + pix * CI + 8 * x3_slot<CI>(4 * kb + gg, pix);
+            const unsigned short* bp = in_s + pix * CI + 8 * px16_slot<CI>(4 * kb + gg, pix);
             bv[0] = *reinterpret_cast<const uint4*>(bp);
             bv[1] = *reinterpret_cast<const uint4*>(bp + PL);
             bv[2] = *reinterpret_cast<const uint4*>(bp + 2 * PL);
@@ -437,26 +342,18 @@ __global__ __launch_bounds__(256, (3 * 2 * (2 * TH + 1) * (kX3TW + 1) * CI * 2 >
 #pragma unroll
     for (int m = 0; m < TH; ++m) {
         const int gy = Y0 + m, gx = X0 + n;
-        if (gy < Ho && gx < Wo)
-            *reinterpret_cast<float4*>(ob + ((int64_t)gy * Wo + gx) * CO + fo + 4 * g) =
-                make_float4(x3_mishf(acc[m][0] + bq.x), x3_mishf(acc[m][1] + bq.y), x3_mishf(acc[m][2] + bq.z),
-                            x3_mishf(acc[m][3] + bq.w));
+        if (gy < Ho && gx < Wo) bias_mish_store4(ob + ((int64_t)gy * Wo + gx) * CO + fo + 4 * g, acc[m], bq);
     }
 }
 
 template <int CI, int TH>
 static int conv3x3s2_mish_x3_launch_t(const void* x, const void* w3, const void* bias, void* out, int B, int H, int W,
                                       hipStream_t s) {
-    const int Ho = H / 2, Wo = W / 2;
-    const int tiles_x = (Wo + kX3TW - 1) / kX3TW, tiles_y = (Ho + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * (2 * CI / 64) > INT32_MAX) {
-        set_error("conv3x3s2_mish_x3: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((conv3x3s2_mish_x3_kernel<CI, TH>), dim3((unsigned)(n_tiles * (2 * CI / 64))), dim3(256), 0, s,
-                       (const float*)x, (const unsigned short*)w3, (const float*)bias, (float*)out, H, W, tiles_x, tiles_y,
-                       (int)n_tiles);
+    TilePlan p;
+    if (!tile_plan(p, B, H / 2, W / 2, TH, 2 * CI / 64, "conv3x3s2_mish_x3")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((conv3x3s2_mish_x3_kernel<CI, TH>), dim3((unsigned)p.n_wgs), dim3(256), 0, s,
+                       (const float*)x, (const unsigned short*)w3, (const float*)bias, (float*)out, H, W, p.tiles_x,
+                       p.tiles_y, (int)p.n_tiles);
     return check_launch("conv3x3s2_mish_x3_kernel");
 }
 
@@ -478,10 +375,10 @@ int conv3x3s2_mish_x3_launch(const void* x, const void* w3, const void* bias, vo
 // taps x 32 channels of split weights in 48 registers, the next 32-channel block's prefetched.
 // w3: (3, 16 taps, F, C) bf16.
 template <int C, int TH>
-__global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024) ? 1 : 2) void upconv4x4s2_mish_x3_kernel(
+__global__ __launch_bounds__(256, (3 * (TH + 2) * kCfHW * C * 2 > 80 * 1024) ? 1 : 2) void upconv4x4s2_mish_x3_kernel(
     const float* __restrict__ x, const unsigned short* __restrict__ w3, const float* __restrict__ bias,
     float* __restrict__ out, int H, int W, int F, int out_pixel_stride, int tiles_x, int tiles_y, int n_tiles) {
-    constexpr int NH = (TH + 2) * kX3HW, PL = NH * C, NKB = C / 32;
+    constexpr int NH = (TH + 2) * kCfHW, PL = NH * C, NKB = C / 32;
     __shared__ __attribute__((aligned(16))) unsigned short in_s[3 * PL];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -490,7 +387,7 @@ __global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024) ? 1
     const int fblk = blockIdx.x / n_tiles;
     const int tile = xcd_swizzle(blockIdx.x % n_tiles, n_tiles);
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int X0 = tx * kX3TW, Y0 = ty * TH;
+    const int X0 = tx * kCfTW, Y0 = ty * TH;
     const int fo = 16 * fblk;
     const float* xb = x + (int64_t)b * H * W * C;
     // the 2 x 2 taps of this wave's parity: input offset (dy, dx), kernel position (ky, kx)
@@ -521,8 +418,8 @@ __global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024) ? 1
         uint4 bb[3][3];
         auto read_b = [&](uint4 (&bv)[3], int i) __attribute__((always_inline)) {
             const int t = i / TH, m = i - t * TH;
-            const int hp = (m + 1 + offy[t]) * kX3HW + nn + 1 + offx[t];
-            const unsigned short* bp = in_s + hp * C + 8 * x3_slot<C>(4 * kb + gg, hp);
+            const int hp = (m + 1 + offy[t]) * kCfHW + nn + 1 + offx[t];
+            const unsigned short* bp = in_s + hp * C + 8 * px16_slot<C>(4 * kb + gg, hp);
             bv[0] = *reinterpret_cast<const uint4*>(bp);
             bv[1] = *reinterpret_cast<const uint4*>(bp + PL);
             bv[2] = *reinterpret_cast<const uint4*>(bp + 2 * PL);
@@ -549,24 +446,18 @@ __global__ __launch_bounds__(256, (3 * (TH + 2) * kX3HW * C * 2 > 80 * 1024) ? 1
     for (int m = 0; m < TH; ++m) {
         const int gy = Y0 + m, gx = X0 + n;
         if (gy < H && gx < W)
-            *reinterpret_cast<float4*>(ob + ((int64_t)(2 * gy + py) * W2 + 2 * gx + px) * out_pixel_stride + fo + 4 * g) =
-                make_float4(x3_mishf(acc[m][0] + bq.x), x3_mishf(acc[m][1] + bq.y), x3_mishf(acc[m][2] + bq.z),
-                            x3_mishf(acc[m][3] + bq.w));
+            bias_mish_store4(ob + ((int64_t)(2 * gy + py) * W2 + 2 * gx + px) * out_pixel_stride + fo + 4 * g, acc[m], bq);
     }
 }
 
 template <int C, int TH>
 static int upconv_x3_launch_t(const void* x, const void* w3, const void* bias, void* out, int B, int H, int W, int F,
                               int out_pixel_stride, hipStream_t s) {
-    const int tiles_x = (W + kX3TW - 1) / kX3TW, tiles_y = (H + TH - 1) / TH;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    if (n_tiles * (F / 16) > INT32_MAX) {
-        set_error("upconv4x4s2_mish_x3: too many tiles");
-        return QPWC_E_SHAPE;
-    }
-    hipLaunchKernelGGL((upconv4x4s2_mish_x3_kernel<C, TH>), dim3((unsigned)(n_tiles * (F / 16))), dim3(256), 0, s,
+    TilePlan p;
+    if (!tile_plan(p, B, H, W, TH, F / 16, "upconv4x4s2_mish_x3")) return QPWC_E_SHAPE;
+    hipLaunchKernelGGL((upconv4x4s2_mish_x3_kernel<C, TH>), dim3((unsigned)p.n_wgs), dim3(256), 0, s,
                        (const float*)x, (const unsigned short*)w3, (const float*)bias, (float*)out, H, W, F,
-                       out_pixel_stride, tiles_x, tiles_y, (int)n_tiles);
+                       out_pixel_stride, p.tiles_x, p.tiles_y, (int)p.n_tiles);
     return check_launch("upconv4x4s2_mish_x3_kernel");
 }
 

@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import net_ref, torch_ref
-from qpwcnet_amd import non_layers, ops, synth
+from qpwcnet_amd import _hip, non_layers, ops, synth
 from qpwcnet_amd.pwcnet import build_flower
 
 pytestmark = pytest.mark.gpu
@@ -558,6 +558,56 @@ def test_conv3x3_mish_encoder_kernel_fp16_storage(C, hw, pad):
     assert float((err - (2.0 ** -11) * ref.abs()).max()) <= 2e-5
     if pad:
         assert float(out[:, H:].abs().max()) == 0.0 and float(out[:, :, W:].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("pad_h,pad_w", [(1, 1), (1, 0), (0, 1)])
+@pytest.mark.parametrize("hw", [(16, 32), (9, 17)])
+@pytest.mark.parametrize("C", [16, 32, 64, 128, 256])
+def test_conv3x3_mish_border_on_poisoned_output(C, hw, pad_h, pad_w):
+    """The zero border of the padded output is WRITTEN by the three stride-1 kernels (fp32, fp16 storage, bf16x3): the
+    C entry points run on buffers filled with 7.0, so a border element nobody stored stays 7.0 where fresh memory
+    would often read as zero.  (16, 32) is a whole number of tiles for every tile height in use (2, 4, 8, 16): one
+    tile owns the corner; (9, 17) has ragged edge tiles; with one pad at 0 each border loop runs alone.  The interior
+    meets the bounds of test_conv3x3_mish_encoder_kernel, its fp16 twin and test_gpu_x3's float64 comparison."""
+    rng = np.random.default_rng(C + hw[0] + 3 * pad_h + pad_w)
+    H, W = hw
+    B = 2
+    x = _rand(rng, B, H, W, C)
+    w = _rand(rng, C, C, 3, 3) / np.sqrt(9 * C)
+    b = _rand(rng, C)
+    L = _hip.lib()
+
+    def run(fn, xd, taps, dtype):
+        out = torch.full((B, H + pad_h, W + pad_w, C), 7.0, dtype=dtype, device=DEV)
+        bd = b.to(DEV)
+        with torch.cuda.device(out.device):
+            _hip.check(fn(xd.data_ptr(), taps.data_ptr(), bd.data_ptr(), out.data_ptr(), B, H, W, C, pad_h, pad_w,
+                          torch.cuda.current_stream(out.device).cuda_stream))
+        out = out.cpu()
+        assert float(out[:, H:].abs().max() if pad_h else 0.0) == 0.0, "bottom border"
+        assert float(out[:, :, W:].abs().max() if pad_w else 0.0) == 0.0, "right border"
+        assert not bool((out == 7.0).any()), "an element was never written"
+        return out[:, :H, :W]
+
+    def conv(xx, ww, bb):
+        return torch_ref.mish(torch.nn.functional.conv2d(xx.permute(0, 3, 1, 2), ww, bb, padding=1)).permute(0, 2, 3, 1)
+
+    taps = ops.conv3x3_taps(w.to(DEV))
+    y32 = run(L.qpwc_conv3x3_mish_fwd, x.to(DEV), taps, torch.float32)
+    torch.testing.assert_close(y32, conv(x, w, b), rtol=0, atol=2e-5 if C <= 32 else 5e-5)
+
+    xh, wh = x.half(), w.half()
+    y16 = run(L.qpwc_conv3x3_mish_f16_fwd, xh.to(DEV), ops.conv3x3_taps(wh.to(DEV), torch.float16), torch.float16)
+    ref16 = conv(xh.float(), wh.float(), b)
+    assert float(((y16.float() - ref16).abs() - (2.0 ** -11) * ref16.abs()).max()) <= 2e-5
+
+    y3 = run(L.qpwc_conv3x3_mish_x3_fwd, x.to(DEV), ops.split_bf16x3(taps), torch.float32)
+    ref64 = torch.nn.functional.mish(torch.nn.functional.conv2d(
+        x.double().permute(0, 3, 1, 2), w.double(), b.double(), padding=1)).permute(0, 2, 3, 1)
+    e32 = float((y32.double() - ref64).abs().max())
+    e3 = float((y3.double() - ref64).abs().max())
+    # test_gpu_x3's budget: within TOL, and no worse than twice the fp32 instructions' error + one output rounding
+    assert e3 < TOL and e3 <= 2.0 * e32 + 2.0 ** -23 * float(ref64.abs().max()), (e3, e32)
 
 
 @pytest.mark.parametrize("hw", [(16, 32), (34, 50), (64, 128)])
