@@ -19,6 +19,7 @@ VIS_MAX_TILE, VIS_TILE = 2048, 1024     # csrc/vis.hip: source pixels per partia
 REVIEW_TILE = 256                       # csrc/review.hip: pixels per workgroup of the panel launch
 QUALITY_TILE = (16, 32)                 # csrc/quality.hip: SSIM positions (rows, columns) per workgroup
 QUALITY_CLIP, QUALITY_U8 = 1, 2
+FLOW_QUALITY_CHUNK = 4096               # csrc/flow_quality.hip: consecutive pixels per workgroup of the tile launch
 WARP_CLAMP, WARP_TFWARP = 0, 1
 BCAST_B, BCAST_H, BCAST_W = 1, 2, 4
 LOSS_FLOW_MSE_V2, LOSS_FLOW_MSE, LOSS_FLOW_FINETUNE, LOSS_AUTORESIZE_MSE = 0, 1, 2, 3
@@ -159,6 +160,14 @@ REVIEW_PROTOTYPES = {
     "qpwc_review_panels_fwd_kernel": (_str, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci]),
 }
 
+# The flow evaluation metrics (EPE splits, Fl-all, accuracy, AAE), declared in include/qpwc_flow_quality.h: a table of
+# its own under the same rules, held to its header by tests/test_flow_quality_cpu.py.
+FLOW_QUALITY_PROTOTYPES = {
+    "qpwc_flow_quality_workspace_floats": (_i64, [_ci, _ci, _ci]),
+    "qpwc_flow_quality_fwd": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci] + [_cf] * 7 + [_vp, _vp, _vp, _vp]),
+    "qpwc_flow_quality_fwd_kernel": (_str, [_ci, _ci, _ci]),
+}
+
 _lib = None
 
 
@@ -191,7 +200,7 @@ def lib():
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
     later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES, **QUALITY_PROTOTYPES,
-                 **REVIEW_PROTOTYPES)
+                 **REVIEW_PROTOTYPES, **FLOW_QUALITY_PROTOTYPES)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
         if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)

@@ -6,6 +6,7 @@
 
 #include <initializer_list>
 
+#include "../../include/qpwc_flow_quality.h"
 #include "../../include/qpwc_optim.h"
 #include "../../include/qpwc_quality.h"
 #include "../../include/qpwc_review.h"
@@ -169,6 +170,14 @@ static int quality_check_shapes(int B, int H, int W, int C) {
     if (H < 11 || W < 11) return fail(QPWC_E_SHAPE, "H=%d W=%d: both must be at least 11, the filter size", H, W);
     if (!image_quality_shape_ok(B, H, W, C))
         return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d C=%d: the element count or a launch grid overflows 32 bits", B, H, W, C);
+    return QPWC_OK;
+}
+
+// the shape rules of the flow metrics, shared by qpwc_flow_quality_workspace_floats / _fwd / _fwd_kernel
+static int flow_quality_check_shapes(int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return fail(QPWC_E_SHAPE, "non-positive extent B=%d H=%d W=%d", B, H, W);
+    if (!flow_quality_shape_ok(B, H, W))
+        return fail(QPWC_E_SHAPE, "B=%d H=%d W=%d: the pixel count or a launch grid overflows 32 bits", B, H, W);
     return QPWC_OK;
 }
 
@@ -1616,6 +1625,55 @@ int qpwc_image_quality_fwd(const void* truth, int truth_dtype, const void* pred,
     return image_quality_fwd_launch(truth, truth_dtype == QPWC_F16, pred, pred_dtype == QPWC_F16, B, H, W, C, layout,
                                     offset_truth, offset_pred, flags, max_val, (float*)out, (double*)state, (float*)ws,
                                     (hipStream_t)stream);
+}
+
+int64_t qpwc_flow_quality_workspace_floats(int B, int H, int W) {
+    const int rc = flow_quality_check_shapes(B, H, W);
+    if (rc != QPWC_OK) return rc;
+    return flow_quality_workspace_floats(B, H, W);
+}
+
+const char* qpwc_flow_quality_fwd_kernel(int B, int H, int W) {
+    if (flow_quality_check_shapes(B, H, W) != QPWC_OK) return "";
+    return flow_quality_fwd_kernel();
+}
+
+int qpwc_flow_quality_fwd(const void* truth, const void* pred, int pred_dtype, const void* valid, const void* occluded,
+                          int B, int H, int W, int layout, float out_abs, float out_rel, float t0, float t1, float t2,
+                          float s0, float s1, void* out, void* state, void* ws, void* stream) {
+    int rc = check_nonnull({{truth, "truth"}, {pred, "pred"}, {out, "out"}, {ws, "ws"}});
+    if (rc != QPWC_OK) return rc;
+    if (pred_dtype != QPWC_F32 && pred_dtype != QPWC_F16) return fail(QPWC_E_DTYPE, "pred: unsupported dtype %d", pred_dtype);
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if ((rc = flow_quality_check_shapes(B, H, W)) != QPWC_OK) return rc;
+    // written so that a NaN fails each test
+    const struct {
+        float v;
+        const char* name;
+    } params[7] = {{out_abs, "out_abs"}, {out_rel, "out_rel"}, {t0, "t0"}, {t1, "t1"}, {t2, "t2"}, {s0, "s0"}, {s1, "s1"}};
+    for (const auto& a : params)
+        if (!(a.v - a.v == 0.0f)) return fail(QPWC_E_RANGE, "%s=%g is not finite", a.name, a.v);
+    if (!(out_abs > 0.0f)) return fail(QPWC_E_RANGE, "out_abs=%g must be > 0", out_abs);
+    if (!(out_rel >= 0.0f)) return fail(QPWC_E_RANGE, "out_rel=%g must be >= 0", out_rel);
+    if (!(t0 > 0.0f && t0 < t1 && t1 < t2)) return fail(QPWC_E_RANGE, "t0=%g t1=%g t2=%g must be 0 < t0 < t1 < t2", t0, t1, t2);
+    if (!(s0 > 0.0f && s0 < s1)) return fail(QPWC_E_RANGE, "s0=%g s1=%g must be 0 < s0 < s1", s0, s1);
+    // the flows and the masks are only read and may be one buffer; out, the workspace and the state are written.  A
+    // (B,H,W,2) pixel is one load of both components; a (B,2,H,W) plane is read element by element.
+    const size_t px = (size_t)B * H * W, es = esize(pred_dtype), pixel = layout == QPWC_NHWC ? 2 : 1;
+    BufCheck bufs[7];
+    int k = 0;
+    bufs[k++] = indexed_buf(truth, px * 2 * 4, pixel * 4, "truth", 0);
+    bufs[k++] = indexed_buf(pred, px * 2 * es, pixel * es, "pred", 0);
+    if (valid) bufs[k++] = indexed_buf(valid, px, 1, "valid", 0);
+    if (occluded) bufs[k++] = indexed_buf(occluded, px, 1, "occluded", 0);
+    const int n_in = k;
+    bufs[k++] = indexed_buf(out, (size_t)B * 12 * 4, 4, "out", 0);
+    bufs[k++] = indexed_buf(ws, (size_t)flow_quality_workspace_floats(B, H, W) * 4, 4, "ws", 0);
+    if (state) bufs[k++] = indexed_buf(state, 17 * 8, 8, "state", 0);
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return flow_quality_fwd_launch((const float*)truth, pred, pred_dtype == QPWC_F16, (const unsigned char*)valid,
+                                   (const unsigned char*)occluded, B, H, W, layout, out_abs, out_rel, t0, t1, t2, s0, s1,
+                                   (float*)out, (double*)state, (float*)ws, (hipStream_t)stream);
 }
 
 int64_t qpwc_review_workspace_floats(int n_flows, int B, int h, int w) {

@@ -190,6 +190,15 @@ int image_quality_fwd_launch(const void* truth, bool f16_t, const void* pred, bo
                              int layout, float off_t, float off_p, int flags, float max_val, float* out, double* state,
                              float* ws, hipStream_t s);
 
+// flow_quality.hip (include/qpwc_flow_quality.h)
+bool flow_quality_shape_ok(int B, int H, int W);
+int64_t flow_quality_workspace_floats(int B, int H, int W);
+const char* flow_quality_fwd_kernel();
+int flow_quality_fwd_launch(const float* truth, const void* pred, bool f16, const unsigned char* valid,
+                            const unsigned char* occluded, int B, int H, int W, int layout, float out_abs,
+                            float out_rel, float t0, float t1, float t2, float s0, float s1, float* out, double* state,
+                            float* ws, hipStream_t s);
+
 // review.hip (include/qpwc_review.h)
 bool review_shape_ok(int n_flows, int B, int H, int W, int h, int w);
 int64_t review_workspace_floats(int n_flows, int B, int h, int w);

@@ -9,6 +9,12 @@ Image quality of the frame interpolator: ``image_quality`` (per-image MSE, PSNR 
 (qpwcnet/app/pre_train.py:71 feeds ``compiled_metrics``; pre_train_test.py:61-77 is the 8-bit export the defaults
 score).  HIP tensors take two launches (``qpwc_image_quality_fwd``, include/qpwc_quality.h, DESIGN.md section 4.23);
 CPU tensors take ``image_quality_torch``, the same chain from torch operators.
+
+Scoring the flow model: ``flow_quality`` (per-image EPE with its matched / unmatched and speed splits, Fl-all, accuracy
+at 1 / 3 / 5 px and the average angular error, over the valid pixels) and ``FlowQuality``, the pixel-weighted running
+scores of an evaluation loop, optionally summed over the ranks.  HIP tensors take two launches
+(``qpwc_flow_quality_fwd``, include/qpwc_flow_quality.h); CPU tensors take
+``flow_quality_torch``.
 """
 import collections
 import math
@@ -206,6 +212,228 @@ class InterpolationQuality:
         sums = [0.0] * 4 if self.state is None else self.state.cpu().tolist()
         n = sums[3]
         return {k: (v / n if n else 0.0) for k, v in zip(ImageQuality._fields, sums)}
+
+    def reset_state(self):
+        if self.state is not None:
+            self.state.zero_()
+
+
+# ---- scoring the flow model -------------------------------------------------------------------------------------------
+FlowScores = collections.namedtuple("FlowScores", ["epe", "aae", "fl", "acc1", "acc3", "acc5", "epe_noc", "epe_occ",
+                                                   "epe_s0_10", "epe_s10_40", "epe_s40", "valid"])
+
+# (numerator, denominator) of every FlowScores field but `valid`, as indices into the 15 sums of
+# include/qpwc_flow_quality.h; epe_noc is (sum e - sum e (occluded)) / (n_valid - n_occ)
+_FLOW_RATIOS = ((1, 0), (2, 0), (3, 0), (4, 0), (5, 0), (6, 0), None, (8, 7), (10, 9), (12, 11), (14, 13))
+FLOW_UNKNOWN = 1e9      # a ground-truth component above it in magnitude marks the pixel unknown (the .flo convention)
+
+
+def _flow_scores(sums, pixels):
+    """FlowScores' twelve values from float64 sums [..., 15] and a pixel count, in float64; 0 / 0 is NaN."""
+    vals = []
+    for r in _FLOW_RATIOS:
+        num, den = (sums[..., 1] - sums[..., 8], sums[..., 0] - sums[..., 7]) if r is None else (sums[..., r[0]],
+                                                                                                 sums[..., r[1]])
+        vals.append(num / den)
+    vals.append(sums[..., 0] / pixels)
+    return vals
+
+
+def _flow_f32(*groups):
+    """The thresholds as the kernel receives them: rounded to float32."""
+    return [[float(torch.tensor(float(x), dtype=torch.float32)) for x in g] for g in groups]
+
+
+def _flow_sums_torch(t, p, valid, occluded, outlier, accuracy, speed, axis):
+    """float64 [B, 15]: the per-image sums of include/qpwc_flow_quality.h from torch operators, fp32 per pixel."""
+    t, p = t.float(), p.float()
+    u, v, up, vp = t.select(axis, 0), t.select(axis, 1), p.select(axis, 0), p.select(axis, 1)
+    du, dv = u - up, v - vp
+    sq = du * du + dv * dv
+    e, m, c = torch.sqrt(sq), torch.sqrt(u * u + v * v), u * vp - v * up
+    ang = torch.atan2(torch.sqrt(sq + c * c), (u * up + v * vp) + 1.0) * float(torch.tensor(180.0 / math.pi).float())
+    ok = (u.abs() <= FLOW_UNKNOWN) & (v.abs() <= FLOW_UNKNOWN)           # false for NaN and +-inf
+    if valid is not None:
+        ok = ok & (valid != 0)
+    occ = torch.zeros_like(ok) if occluded is None else ok & (occluded != 0)
+    zero = torch.zeros((), dtype=torch.float32, device=t.device)
+    e, ang = torch.where(ok, e, zero), torch.where(ok, ang, zero)
+    b0, b2 = ok & (m < speed[0]), ok & (m >= speed[1])
+    b1 = ok & ~b0 & ~b2
+    count = lambda mask: mask.sum(dim=(1, 2)).double()
+    total = lambda x, mask=None: (x if mask is None else torch.where(mask, x, zero)).double().sum(dim=(1, 2))
+    cols = [count(ok), total(e), total(ang), count(ok & (e > outlier[0]) & (e > outlier[1] * m))]
+    cols += [count(ok & (e < a)) for a in accuracy]
+    cols += [count(occ), total(e, occ)]
+    for b in (b0, b1, b2):
+        cols += [count(b), total(e, b)]
+    return torch.stack(cols, dim=1)
+
+
+def flow_quality_torch(y_true, y_pred, valid=None, occluded=None, outlier=(3.0, 0.05), accuracy=(1.0, 3.0, 5.0),
+                       speed=(10.0, 40.0), data_format=CHANNELS_LAST):
+    """``flow_quality`` composed from torch operators, on any device: the path CPU tensors take and the baseline the
+    kernels are timed against.  The chain of include/qpwc_flow_quality.h in fp32 per pixel, with the sums taken in
+    float64.  Batched (rank 4) inputs, masks (B,H,W) of any dtype (``!= 0``) or None; -> FlowScores of float32 [B]
+    tensors."""
+    axis = get_axis(data_format)
+    H, W = (y_true.shape[1], y_true.shape[2]) if axis == 3 else (y_true.shape[2], y_true.shape[3])
+    with torch.no_grad():
+        sums = _flow_sums_torch(y_true.detach(), y_pred.detach(), valid, occluded, *_flow_f32(outlier, accuracy, speed),
+                                axis)
+        return FlowScores(*(x.float() for x in _flow_scores(sums, float(H * W))))
+
+
+def _flow_thresholds(outlier, accuracy, speed):
+    try:
+        outlier, accuracy, speed = (tuple(float(x) for x in g) for g in (outlier, accuracy, speed))
+    except TypeError:
+        raise TypeError("outlier, accuracy and speed must be sequences of numbers")
+    if len(outlier) != 2 or len(accuracy) != 3 or len(speed) != 2:
+        raise ValueError("outlier takes 2 values (pixels, share), accuracy 3 thresholds and speed 2 bin edges, got "
+                         "{}, {} and {}".format(outlier, accuracy, speed))
+    if not all(math.isfinite(x) for x in outlier + accuracy + speed):
+        raise ValueError("outlier, accuracy and speed must be finite, got {}, {} and {}".format(outlier, accuracy, speed))
+    if not (outlier[0] > 0.0 and outlier[1] >= 0.0):
+        raise ValueError("outlier = (pixels > 0, share >= 0), got {}".format(outlier))
+    if not 0.0 < accuracy[0] < accuracy[1] < accuracy[2]:
+        raise ValueError("accuracy must be three rising thresholds above 0, got {}".format(accuracy))
+    if not 0.0 < speed[0] < speed[1]:
+        raise ValueError("speed must be two rising bin edges above 0, got {}".format(speed))
+    return outlier, accuracy, speed
+
+
+def _flow_mask(name, m, like, dims):
+    """A (B,H,W) mask as uint8 on the flows' device: bool and uint8 are reinterpreted, a floating mask takes the one
+    ``!= 0`` launch."""
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor):
+        raise TypeError("{} must be a torch.Tensor or None".format(name))
+    if tuple(m.shape) != dims:
+        raise ValueError("{} must have shape {}, got {}".format(name, dims, tuple(m.shape)))
+    if m.device != like.device:
+        raise ValueError("{} is on {}; the flows are on {}".format(name, m.device, like.device))
+    if m.dtype == torch.uint8:
+        return m
+    if m.dtype == torch.bool:
+        return m.view(torch.uint8)
+    if m.is_floating_point():
+        return (m != 0).view(torch.uint8)
+    raise TypeError("{} must be bool, uint8 or floating, got {}".format(name, m.dtype))
+
+
+def flow_quality(y_true, y_pred, valid=None, occluded=None, outlier=(3.0, 0.05), accuracy=(1.0, 3.0, 5.0),
+                 speed=(10.0, 40.0), data_format=None, state=None):
+    """The figures a flow model is judged by, per image, over the valid pixels: ``y_true`` (float32) and ``y_pred``
+    (float32 or float16) are (B,H,W,2) / (B,2,H,W) by ``data_format`` (default ``backend.image_data_format()``) or one
+    flow of rank 3.  A pixel is valid where both ground-truth components are finite and at most 1e9 in magnitude (the
+    .flo "unknown" convention) and ``valid`` -- bool, uint8 or floating, (B,H,W), ``!= 0`` -- allows it.
+    -> FlowScores of float32 [B] tensors on the inputs' device (scalars for one flow):
+      epe, aae       mean end-point error (pixels) and mean angular error (degrees, between (u, v, 1) and (u', v', 1))
+      fl             KITTI Fl-all: the share with error > outlier[0] pixels and > outlier[1] of the ground-truth speed
+      acc1/3/5       the share with error below accuracy[0..2] pixels
+      epe_noc/_occ   Sintel's matched / unmatched split by ``occluded`` (a mask like ``valid``, or "estimate":
+                     ``occlusion.estimate_occlusion_map(y_true)``); without one epe_noc == epe and epe_occ is NaN
+      epe_s0_10 ...  mean end-point error by ground-truth speed: below speed[0], up to speed[1], from speed[1]
+      valid          the share of valid pixels
+    A mean over an empty set is NaN.  ``state``: a float64 tensor of 17 elements on the same device, to which the call
+    adds its 15 sums, its image count and its pixel count (``FlowQuality`` holds one).  No gradient flows.  HIP
+    tensors: two launches (one more to convert a floating mask), no host synchronisation; CPU tensors:
+    ``flow_quality_torch``."""
+    if data_format is None:
+        data_format = image_data_format()
+    axis = get_axis(data_format)
+    for name, t in (("y_true", y_true), ("y_pred", y_pred)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+    if y_true.dtype != torch.float32:
+        raise ValueError("y_true must be float32, got {}".format(y_true.dtype))
+    if y_pred.dtype not in (torch.float32, torch.float16):
+        raise ValueError("y_pred: unsupported dtype {}".format(y_pred.dtype))
+    if y_true.shape != y_pred.shape or y_true.device != y_pred.device:
+        raise ValueError("y_true {} on {} and y_pred {} on {} must have one shape and one device".format(
+            tuple(y_true.shape), y_true.device, tuple(y_pred.shape), y_pred.device))
+    if y_true.dim() not in (3, 4):
+        raise ValueError("flows must be of rank 3 or 4, got shape {}".format(tuple(y_true.shape)))
+    single = y_true.dim() == 3
+    shape = tuple(y_true.shape[-3:])
+    H, W, C = shape if axis == 3 else (shape[1], shape[2], shape[0])
+    if C != 2 or H < 1 or W < 1 or (not single and y_true.shape[0] < 1):
+        raise ValueError("flows must have 2 channels and no empty extent, got shape {} ({})".format(
+            tuple(y_true.shape), data_format))
+    outlier, accuracy, speed = _flow_thresholds(outlier, accuracy, speed)
+    if state is not None and not (isinstance(state, torch.Tensor) and state.dtype == torch.float64
+                                  and state.numel() == 17 and state.device == y_true.device):
+        raise ValueError("state must be a float64 tensor of 17 elements on {}".format(y_true.device))
+    estimate = isinstance(occluded, str)
+    if estimate and occluded != "estimate":
+        raise ValueError("occluded must be a mask, None or 'estimate', got '{}'".format(occluded))
+    with torch.no_grad():
+        t, p = y_true.detach(), y_pred.detach()
+        if single:
+            t, p = t[None], p[None]
+            valid, occluded = (m[None] if isinstance(m, torch.Tensor) and m.dim() == 2 else m for m in (valid, occluded))
+        dims = (int(t.shape[0]), int(H), int(W))
+        if estimate:
+            from . import occlusion
+            occluded = occlusion.estimate_occlusion_map(t, data_format)
+        valid, occluded = _flow_mask("valid", valid, t, dims), _flow_mask("occluded", occluded, t, dims)
+        if t.is_cuda:
+            res = FlowScores(*ops.flow_quality(t, p, valid, occluded, data_format, outlier, accuracy, speed, state))
+        else:
+            sums = _flow_sums_torch(t, p, valid, occluded, *_flow_f32(outlier, accuracy, speed), axis)
+            res = FlowScores(*(x.float() for x in _flow_scores(sums, float(H * W))))
+            if state is not None:
+                # image by image, in float64, as the fold kernel adds them
+                flat = state.view(-1)
+                flat[:15] = torch.cumsum(torch.cat([flat[None, :15], sums]), 0)[-1]
+                flat[15] += float(dims[0])
+                flat[16] += float(dims[0] * H * W)
+    return FlowScores(*(v[0] for v in res)) if single else res
+
+
+class FlowQuality:
+    """Running flow scores of an evaluation loop -- what stands in for ``epe_error`` as a ``compile`` metric
+    (qpwcnet/app/optical_flow/train.py:247-253, 299, 374).  ``update_state`` returns the per-image FlowScores and adds
+    the batch's 15 sums, images and pixels to 17 float64 numbers on the inputs' device, reading nothing back;
+    ``result()`` does the one host read and gives the pixel-weighted means over everything seen -- totals over totals,
+    the Sintel / KITTI convention, not means of per-image means."""
+
+    def __init__(self, outlier=(3.0, 0.05), accuracy=(1.0, 3.0, 5.0), speed=(10.0, 40.0), occluded=None,
+                 data_format=None):
+        if occluded not in (None, "estimate"):
+            raise ValueError("occluded must be None or 'estimate' (a mask goes to update_state), got {!r}".format(occluded))
+        self.outlier, self.accuracy, self.speed = _flow_thresholds(outlier, accuracy, speed)
+        self.occluded, self.data_format = occluded, data_format
+        self.state = None
+
+    def update_state(self, y_true, y_pred, valid=None, occluded=None):
+        if self.state is None or self.state.device != y_true.device:
+            if self.state is not None and float(self.state[15]) != 0.0:
+                raise ValueError("FlowQuality holds sums on {}; got flows on {}".format(self.state.device, y_true.device))
+            self.state = torch.zeros(17, dtype=torch.float64, device=y_true.device)
+        return flow_quality(y_true, y_pred, valid=valid, occluded=self.occluded if occluded is None else occluded,
+                            outlier=self.outlier, accuracy=self.accuracy, speed=self.speed,
+                            data_format=self.data_format, state=self.state)
+
+    def result(self, all_reduce=False):
+        """{the twelve FlowScores fields, 'images', 'pixels'}: pixel-weighted means over every flow seen since the last
+        reset, 0.0 everywhere before the first; afterwards a mean over an empty set is NaN.  all_reduce: with an
+        initialised ``torch.distributed`` group, a copy of the 17 sums is first summed over the ranks -- every entry is
+        additive, so every rank gets the whole dataset's scores."""
+        state = torch.zeros(17, dtype=torch.float64) if self.state is None else self.state
+        if all_reduce:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                state = state.clone()
+                dist.all_reduce(state)
+        sums = state.cpu()
+        images, pixels = float(sums[15]), float(sums[16])
+        if images == 0.0:
+            return dict({k: 0.0 for k in FlowScores._fields}, images=0.0, pixels=0.0)
+        vals = [float(x) for x in _flow_scores(sums[:15], pixels)]
+        return dict(zip(FlowScores._fields, vals), images=images, pixels=pixels)
 
     def reset_state(self):
         if self.state is not None:

@@ -1517,6 +1517,83 @@ def image_quality(truth, pred, data_format=CHANNELS_LAST, offsets=(0.0, 0.0), fl
     return out[0], out[1], out[2]
 
 
+def flow_quality_kernel(B, H, W):
+    """Form of ``qpwc_flow_quality_fwd``'s tile kernel for this shape ('flow_quality_tile_kernel': it has one; host
+    only).  '' for arguments the entry point refuses."""
+    name = _hip.lib().qpwc_flow_quality_fwd_kernel(int(B), int(H), int(W))
+    return name.decode() if name else ""
+
+
+def _dense_on_grid(t, align):
+    """t dense, with its first byte on a multiple of `align`: a fresh copy where it is not (a slice of a larger tensor)."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % align else t
+
+
+def flow_quality(truth, pred, valid=None, occluded=None, data_format=CHANNELS_LAST, outlier=(3.0, 0.05),
+                 accuracy=(1.0, 3.0, 5.0), speed=(10.0, 40.0), state=None):
+    """Per-image flow metrics of ``pred`` against ``truth`` over the valid pixels in two launches (qpwc_flow_quality_fwd,
+    include/qpwc_flow_quality.h).  truth (float32), pred (float32 or float16): (B,H,W,2) / (B,2,H,W) by data_format, one
+    shape, on one HIP device; valid, occluded: None or uint8 (B,H,W) on that device; outlier = (pixels, share of the
+    ground-truth speed), accuracy = three rising thresholds, speed = the two bin edges; state: None or a float64 tensor
+    of 17 elements on the same device, to which the call adds its 15 sums, its images and its pixels.  -> twelve float32
+    [B] views of one tensor, in the header's order.  An operand that is not dense, or whose first byte is off the grid its
+    loads need, is copied first.  The workspace comes from torch's allocator on the current stream.  Enqueues and
+    returns: no host synchronisation."""
+    get_axis(data_format)
+    nhwc = data_format == CHANNELS_LAST
+    for name, t in (("truth", truth), ("pred", pred)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a torch.Tensor".format(name))
+        if not t.is_cuda:
+            raise RuntimeError("qpwcnet_amd: {} is on '{}'; ops.flow_quality runs on a HIP device only (metrics.* has "
+                               "the CPU path)".format(name, t.device))
+        if t.dim() != 4:
+            raise ValueError("{} must be rank 4 (batched), got shape {}".format(name, tuple(t.shape)))
+    if truth.dtype != torch.float32:
+        raise ValueError("truth must be float32, got {}".format(truth.dtype))
+    if pred.dtype not in _DTYPES:
+        raise ValueError("pred: unsupported dtype {}".format(pred.dtype))
+    if truth.shape != pred.shape or truth.device != pred.device:
+        raise ValueError("truth {} on {} and pred {} on {} must have one shape and one device".format(
+            tuple(truth.shape), truth.device, tuple(pred.shape), pred.device))
+    B, H, W, C = (int(v) for v in (truth.shape if nhwc else (truth.shape[0],) + tuple(truth.shape[2:]) + (truth.shape[1],)))
+    if C != 2:
+        raise ValueError("flows have 2 channels, got {} ({}, shape {})".format(C, data_format, tuple(truth.shape)))
+    if min(B, H, W) < 1:
+        raise ValueError("empty tensor: B={} H={} W={}".format(B, H, W))
+    dev = truth.device
+    for name, m in (("valid", valid), ("occluded", occluded)):
+        if m is not None and not (isinstance(m, torch.Tensor) and m.dtype == torch.uint8 and tuple(m.shape) == (B, H, W)
+                                  and m.device == dev):
+            raise ValueError("{} must be a uint8 tensor of shape {} on {}".format(name, (B, H, W), dev))
+    if state is not None:
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.float64 and state.numel() == 17
+                and state.is_contiguous() and state.device == dev):
+            raise ValueError("state must be a contiguous float64 tensor of 17 elements on {}".format(dev))
+    if len(outlier) != 2 or len(accuracy) != 3 or len(speed) != 2:
+        raise ValueError("outlier takes 2 values, accuracy 3 and speed 2")
+    params = [float(v) for v in tuple(outlier) + tuple(accuracy) + tuple(speed)]
+    truth = _dense_on_grid(truth, 8 if nhwc else 4)
+    pred = _dense_on_grid(pred, (2 if nhwc else 1) * pred.element_size())
+    valid = None if valid is None else valid.contiguous()
+    occluded = None if occluded is None else occluded.contiguous()
+    L = _hip.lib()
+    nws = L.qpwc_flow_quality_workspace_floats(B, H, W)
+    _hip.check(min(int(nws), 0))
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+        out = torch.empty((12, B), dtype=torch.float32, device=dev)
+        with _timed("flow_quality", (B, H, W, 2)):
+            rc = L.qpwc_flow_quality_fwd(
+                truth.data_ptr(), pred.data_ptr(), _DTYPES[pred.dtype],
+                None if valid is None else valid.data_ptr(), None if occluded is None else occluded.data_ptr(),
+                B, H, W, _hip.NHWC if nhwc else _hip.NCHW, *params, out.data_ptr(),
+                None if state is None else state.data_ptr(), ws.data_ptr(), _stream(truth))
+    _hip.check(rc)
+    return tuple(out[i] for i in range(12))
+
+
 def _loss_layout(y_true, preds, data_format):
     """-> (y_true, preds, layout code, nhwc_view): 'channels_first' operands that are all physically NHWC (torch
     channels_last memory) are read through their permuted views; everything else dense in its declared layout."""
