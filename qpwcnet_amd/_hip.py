@@ -168,6 +168,18 @@ FLOW_QUALITY_PROTOTYPES = {
     "qpwc_flow_quality_fwd_kernel": (_str, [_ci, _ci, _ci]),
 }
 
+# The valid-masked flow losses, declared in include/qpwc_masked_loss.h: a table of its own under the same rules, held to
+# its header by tests/test_masked_loss_cpu.py.
+MASKED_LOSS_PROTOTYPES = {
+    "qpwc_masked_loss_workspace_floats": (_i64, [_ci, _ci, _ci, _ci, _ci, _pi, _pi, _ci]),
+    "qpwc_masked_loss_fwd": (_ci, [_ci, _cf, _cf, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _pvp, _pi, _pi, _pi, _ci, _vp, _vp,
+                                   _pvp, _pvp, _pvp, _vp, _vp]),
+    "qpwc_masked_loss_fwd_kernel": (_str, [_ci, _ci, _ci, _ci, _ci, _pi, _pi, _ci]),
+    "qpwc_masked_loss_bwd": (_ci, [_ci, _pvp, _vp, _vp, _pvp, _pi64, _pi, _ci, _vp]),
+}
+MASKED_LOSS_TILE_BLOCKS, MASKED_LOSS_PIX_BLOCKS = 2048, 1024   # csrc/masked_loss.hip: the grid caps of its two forward kernels
+MASKED_LOSS_THREADS, MASKED_LOSS_TILE = 256, 32                # threads per workgroup, tile edge
+
 _lib = None
 
 
@@ -200,7 +212,7 @@ def lib():
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
     later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES, **QUALITY_PROTOTYPES,
-                 **REVIEW_PROTOTYPES, **FLOW_QUALITY_PROTOTYPES)
+                 **REVIEW_PROTOTYPES, **FLOW_QUALITY_PROTOTYPES, **MASKED_LOSS_PROTOTYPES)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
         if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)

@@ -7,6 +7,7 @@
 #include <initializer_list>
 
 #include "../../include/qpwc_flow_quality.h"
+#include "../../include/qpwc_masked_loss.h"
 #include "../../include/qpwc_optim.h"
 #include "../../include/qpwc_quality.h"
 #include "../../include/qpwc_review.h"
@@ -132,6 +133,14 @@ static int loss_check_shapes(int kind, int B, int H, int W, int C, const int* h,
             return fail(QPWC_E_SHAPE, "level %d: %dx%d is not a whole-block area reduction of %dx%d", i, h[i], w[i], H, W);
     }
     return QPWC_OK;
+}
+
+// the shape rules of the masked flow losses, shared by qpwc_masked_loss_workspace_floats / _fwd / _fwd_kernel: those of
+// the dense losses for the three flow kinds
+static int masked_loss_check_shapes(int kind, int B, int H, int W, int C, const int* h, const int* w, int n_levels) {
+    if (kind < QPWC_LOSS_FLOW_MSE_V2 || kind > QPWC_LOSS_FLOW_FINETUNE)
+        return fail(QPWC_E_MODE, "loss kind %d is not one of the three flow losses", kind);
+    return loss_check_shapes(kind, B, H, W, C, h, w, n_levels);
 }
 
 // the shape rules of the input pipeline, shared by qpwc_augment_workspace_floats / _fwd / _fwd_kernel
@@ -1674,6 +1683,89 @@ int qpwc_flow_quality_fwd(const void* truth, const void* pred, int pred_dtype, c
     return flow_quality_fwd_launch((const float*)truth, pred, pred_dtype == QPWC_F16, (const unsigned char*)valid,
                                    (const unsigned char*)occluded, B, H, W, layout, out_abs, out_rel, t0, t1, t2, s0, s1,
                                    (float*)out, (double*)state, (float*)ws, (hipStream_t)stream);
+}
+
+int64_t qpwc_masked_loss_workspace_floats(int kind, int B, int H, int W, int C, const int* h, const int* w, int n_levels) {
+    const int rc = masked_loss_check_shapes(kind, B, H, W, C, h, w, n_levels);
+    return rc != QPWC_OK ? rc : masked_loss_workspace_floats(n_levels);
+}
+
+const char* qpwc_masked_loss_fwd_kernel(int kind, int B, int H, int W, int C, const int* h, const int* w, int n_levels) {
+    if (masked_loss_check_shapes(kind, B, H, W, C, h, w, n_levels) != QPWC_OK) return "";
+    return masked_loss_fwd_kernel(kind, H, W, h, w, n_levels);
+}
+
+int qpwc_masked_loss_fwd(int kind, float p0, float p1, const void* y_true, const void* valid, int B, int H, int W, int C,
+                         int layout, const void* const* y_pred, const int* h, const int* w, const int* pred_dtype,
+                         int n_levels, void* out_losses, void* out_counts, void* const* dpred, void* const* gt_out,
+                         void* const* valid_out, void* workspace, void* stream) {
+    int rc = check_nonnull({{y_true, "y_true"}, {y_pred, "y_pred"}, {pred_dtype, "pred_dtype"}, {out_losses, "out_losses"},
+                            {out_counts, "out_counts"}, {workspace, "workspace"}, {h, "h"}, {w, "w"}});
+    if (rc != QPWC_OK) return rc;
+    if ((rc = masked_loss_check_shapes(kind, B, H, W, C, h, w, n_levels)) != QPWC_OK) return rc;
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if (kind == QPWC_LOSS_FLOW_MSE_V2 && !(p0 >= 0.0f)) return fail(QPWC_E_RANGE, "Huber delta %g < 0", (double)p0);
+    for (int i = 0; i < n_levels; ++i)
+        if (pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported prediction dtype %d", i, pred_dtype[i]);
+    // y_true and the mask are read in 16-byte and 4-byte pieces and there is no element-wise form behind them: the
+    // inputs first, then everything that is written
+    const size_t px = (size_t)B * H * W;
+    BufCheck bufs[2 + 8 + 3 + 24];
+    int k = 0;
+    bufs[k++] = indexed_buf(y_true, px * 2 * 4, 16, "y_true", 0);
+    if (valid) bufs[k++] = indexed_buf(valid, px, 4, "valid", 0);
+    for (int i = 0; i < n_levels; ++i) {
+        const bool other = (gt_out && gt_out[i]) || (valid_out && valid_out[i]);
+        if (!y_pred[i] && !other) return fail(QPWC_E_NULL, "null prediction at level %d", i);
+        if (dpred && !dpred[i]) return fail(QPWC_E_NULL, "null dpred buffer at level %d", i);
+        const size_t es = esize(pred_dtype[i]);
+        if (y_pred[i]) bufs[k++] = indexed_buf(y_pred[i], (size_t)B * h[i] * w[i] * 2 * es, es, "y_pred[%d]", i);
+    }
+    const int n_in = k;
+    bufs[k++] = indexed_buf(out_losses, (size_t)n_levels * 4, 4, "out_losses", 0);
+    bufs[k++] = indexed_buf(out_counts, (size_t)n_levels * 8, 8, "out_counts", 0);
+    bufs[k++] = indexed_buf(workspace, (size_t)masked_loss_workspace_floats(n_levels) * 4, 4, "workspace", 0);
+    for (int i = 0; i < n_levels; ++i) {
+        const size_t lp = (size_t)B * h[i] * w[i];
+        if (dpred) bufs[k++] = indexed_buf(dpred[i], lp * 2 * 4, 4, "dpred[%d]", i);
+        if (gt_out && gt_out[i]) bufs[k++] = indexed_buf(gt_out[i], lp * 2 * 4, 4, "gt_out[%d]", i);
+        if (valid_out && valid_out[i]) bufs[k++] = indexed_buf(valid_out[i], lp, 1, "valid_out[%d]", i);
+    }
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return masked_loss_fwd_launch(kind, p0, p1, (const float*)y_true, (const unsigned char*)valid, B, H, W, layout, y_pred,
+                                  h, w, pred_dtype, n_levels, (float*)out_losses, (int64_t*)out_counts, dpred, gt_out,
+                                  valid_out, (float*)workspace, (hipStream_t)stream);
+}
+
+int qpwc_masked_loss_bwd(int kind, const void* const* dpred, const void* counts, const void* grad_losses,
+                         void* const* grad_pred, const int64_t* n_elems, const int* pred_dtype, int n_levels,
+                         void* stream) {
+    int rc = check_nonnull({{dpred, "dpred"}, {counts, "counts"}, {grad_losses, "grad_losses"}, {grad_pred, "grad_pred"},
+                            {n_elems, "n_elems"}, {pred_dtype, "pred_dtype"}});
+    if (rc != QPWC_OK) return rc;
+    if (kind < QPWC_LOSS_FLOW_MSE_V2 || kind > QPWC_LOSS_FLOW_FINETUNE)
+        return fail(QPWC_E_MODE, "loss kind %d is not one of the three flow losses", kind);
+    if (n_levels < 1 || n_levels > 8) return fail(QPWC_E_SHAPE, "n_levels %d outside [1,8]", n_levels);
+    BufCheck bufs[2 + 16];
+    int k = 0;
+    bufs[k++] = indexed_buf(counts, (size_t)n_levels * 8, 8, "counts", 0);
+    bufs[k++] = indexed_buf(grad_losses, (size_t)n_levels * 4, 4, "grad_losses", 0);
+    for (int i = 0; i < n_levels; ++i) {
+        if (!dpred[i] || !grad_pred[i]) return fail(QPWC_E_NULL, "null buffer at level %d", i);
+        if (pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported prediction dtype %d", i, pred_dtype[i]);
+        if (n_elems[i] <= 0) return fail(QPWC_E_SHAPE, "level %d has no elements", i);
+        bufs[k++] = indexed_buf(dpred[i], (size_t)n_elems[i] * 4, 16, "dpred[%d]", i);
+    }
+    const int n_in = k;
+    for (int i = 0; i < n_levels; ++i) {
+        const size_t es = esize(pred_dtype[i]);
+        bufs[k++] = indexed_buf(grad_pred[i], (size_t)n_elems[i] * es, 4 * es, "grad_pred[%d]", i);
+    }
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return masked_loss_bwd_launch(kind, dpred, (const int64_t*)counts, (const float*)grad_losses, grad_pred, n_elems,
+                                  pred_dtype, n_levels, (hipStream_t)stream);
 }
 
 int64_t qpwc_review_workspace_floats(int n_flows, int B, int h, int w) {

@@ -190,6 +190,16 @@ int image_quality_fwd_launch(const void* truth, bool f16_t, const void* pred, bo
                              int layout, float off_t, float off_p, int flags, float max_val, float* out, double* state,
                              float* ws, hipStream_t s);
 
+// masked_loss.hip (include/qpwc_masked_loss.h)
+int64_t masked_loss_workspace_floats(int n_levels);
+const char* masked_loss_fwd_kernel(int kind, int H, int W, const int* h, const int* w, int n);
+int masked_loss_fwd_launch(int kind, float p0, float p1, const float* gt, const unsigned char* valid, int B, int H, int W,
+                           int layout, const void* const* pred, const int* h, const int* w, const int* pred_dtype, int n,
+                           float* out, int64_t* counts, void* const* dpred, void* const* gt_out, void* const* valid_out,
+                           float* ws, hipStream_t s);
+int masked_loss_bwd_launch(int kind, const void* const* dpred, const int64_t* counts, const float* grad_losses,
+                           void* const* grad_pred, const int64_t* n_elems, const int* pred_dtype, int n, hipStream_t s);
+
 // flow_quality.hip (include/qpwc_flow_quality.h)
 bool flow_quality_shape_ok(int B, int H, int W);
 int64_t flow_quality_workspace_floats(int B, int H, int W);

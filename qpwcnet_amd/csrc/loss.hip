@@ -7,18 +7,15 @@
 // are folded by shuffles and a fixed-order LDS step; no atomics.
 #include "common.h"
 #include "launch.h"
+#include "loss_common.h"
 
 namespace qpwc {
 
-constexpr int kLossMaxLevels = 8;
 constexpr int kLossThreads = 256;
 constexpr int kLossPixBlocks = 1024;    // pixel path: partial sums per level
 constexpr int kLossTileBlocks = 2048;   // tile path: at most this many workgroups, each walks its tiles
 constexpr int kLossTile = 32;           // tile path: 32 x 32 ground-truth pixels per tile (8 KB of fp32 flow)
-constexpr int kLossMaxSteps = 10;       // tile path: 2x2 / 2x1 / 1x2 sum steps from 1x1 up to 32x32
 constexpr int kLossBwdBlocks = 1024;
-
-typedef float loss_f32x4 __attribute__((ext_vector_type(4)));
 
 struct LossLevels {
     const void* pred[kLossMaxLevels];   // NULL: taken as zero (gt_out only)
@@ -39,67 +36,6 @@ struct LossLevels {
 };
 
 namespace {
-
-__device__ __forceinline__ float loss_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float2 f2add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-
-__device__ __forceinline__ float huber(float e, float d) {
-    const float a = fabsf(e);
-    return a <= d ? 0.5f * e * e : d * a - 0.5f * d * d;     // Keras Huber: the quadratic branch at |e| <= delta
-}
-
-__device__ __forceinline__ float huber_grad(float e, float d) { return fabsf(e) <= d ? e : copysignf(d, e); }
-
-__device__ __forceinline__ float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
-
-__device__ __forceinline__ float ld_pred(const void* p, int64_t i, int f16) {
-    if (!p) return 0.0f;
-    return f16 ? __half2float(reinterpret_cast<const __half*>(p)[i]) : reinterpret_cast<const float*>(p)[i];
-}
-
-// One flow pixel: (gx, gy) the resampled, flow-scaled ground truth, (px, py) the prediction.  Returns the pixel's
-// term (FlowMseLossV2: the sum of its two per-element terms); (dx, dy) = d term / d (px, py).
-template <int KIND>
-__device__ __forceinline__ float flow_term(float gx, float gy, float px, float py, float lscale, float p0, float p1,
-                                           float& dx, float& dy) {
-    if (KIND == QPWC_LOSS_FLOW_MSE_V2) {
-        // Keras Huber(delta = p0) of y_true = s * gt, y_pred = s * pred: error = y_pred - y_true
-        const float ex = lscale * px - lscale * gx, ey = lscale * py - lscale * gy;
-        dx = lscale * huber_grad(ex, p0);
-        dy = lscale * huber_grad(ey, p0);
-        return huber(ex, p0) + huber(ey, p0);
-    } else if (KIND == QPWC_LOSS_FLOW_MSE) {
-        const float rx = gx - px, ry = gy - py;
-        const float n = sqrtf(rx * rx + ry * ry);
-        const float inv = n > 0.0f ? 1.0f / n : 0.0f;        // 0 at a zero residual (TF: NaN, zeroed by train_step)
-        dx = -rx * inv;
-        dy = -ry * inv;
-        return n;
-    } else {                                                  // FlowMseLossFineTune: (|rx| + |ry| + eps)^q
-        const float rx = gx - px, ry = gy - py;
-        const float base = fabsf(rx) + fabsf(ry) + p1;
-        const float t = powf(base, p0);
-        const float c = base > 0.0f ? p0 * t / base : 0.0f;  // q * base^(q-1); sign(0) = 0 below
-        dx = -c * sgn(rx);
-        dy = -c * sgn(ry);
-        return t;
-    }
-}
-
-// element offset of channel 0 of pixel (b, y, x) of a (B, h, w, C) / (B, C, h, w) tensor, and the channel stride
-template <int LAYOUT>
-__device__ __forceinline__ int64_t pix_offset(int64_t b, int y, int x, int h, int w, int C) {
-    return LAYOUT == QPWC_NHWC ? ((b * h + y) * w + x) * C : (b * C * h + y) * (int64_t)w + x;
-}
-template <int LAYOUT>
-__device__ __forceinline__ int64_t chan_stride(int h, int w) {
-    return LAYOUT == QPWC_NHWC ? 1 : (int64_t)h * w;
-}
 
 // the two channels of prediction pixel (b, y, x) of level l as fp32
 template <int LAYOUT>
@@ -372,48 +308,12 @@ __global__ __launch_bounds__(kLossThreads) void loss_bwd_kernel(LossGrads lg, co
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-// The tile path's sum steps for these levels, or false when it does not apply: H, W multiples of 32; every factor a
-// power of two <= 32 with sh * sw >= 4; the factors nested (ordered by area, each divides the next), none repeated.
-static bool loss_tile_plan(int H, int W, const int* h, const int* w, int n, LossLevels& lv) {
-    if (H % kLossTile || W % kLossTile) return false;
-    int order[kLossMaxLevels];
-    for (int i = 0; i < n; ++i) {
-        if (H % h[i] || W % w[i]) return false;
-        const int sh = H / h[i], sw = W / w[i];
-        if (!pow2(sh) || !pow2(sw) || sh > kLossTile || sw > kLossTile || sh * sw < 4) return false;
-        int k = i;
-        while (k > 0 && (H / h[order[k - 1]]) * (W / w[order[k - 1]]) > sh * sw) {
-            order[k] = order[k - 1];
-            --k;
-        }
-        order[k] = i;
-    }
-    int cy = 1, cx = 1, ns = 0;
-    for (int i = 0; i < n; ++i) {
-        const int l = order[i], ty = H / h[l], tx = W / w[l];
-        if (ty < cy || tx < cx || (ty == cy && tx == cx)) return false;   // not nested, or a repeated factor
-        while (cy != ty || cx != tx) {
-            const int ry = cy < ty ? 2 : 1, rx = cx < tx ? 2 : 1;
-            cy *= ry;
-            cx *= rx;
-            lv.step_ry[ns] = ry;
-            lv.step_rx[ns] = rx;
-            lv.step_level[ns] = (cy == ty && cx == tx) ? l : -1;
-            ++ns;
-        }
-    }
-    lv.nsteps = ns;
-    return true;
-}
-
 int64_t loss_workspace_floats(int n_levels) { return (int64_t)n_levels * kLossTileBlocks; }
 
 // Which forward kernel loss_fwd_launch takes for these arguments (host only).
 const char* loss_fwd_kernel(int kind, int H, int W, const int* h, const int* w, int n, const void* gt) {
     LossLevels lv = {};
-    if (kind == QPWC_LOSS_FLOW_MSE_V2 && (uintptr_t)gt % 16 == 0 && loss_tile_plan(H, W, h, w, n, lv))
+    if (kind == QPWC_LOSS_FLOW_MSE_V2 && (uintptr_t)gt % 16 == 0 && loss_tile_plan<kLossTile>(H, W, h, w, n, lv))
         return "loss_area_tile_kernel";
     return "loss_pixel_kernel";
 }
@@ -444,7 +344,7 @@ int loss_fwd_launch(int kind, float p0, float p1, const float* gt, int B, int H,
         lv.rx_scale[i] = (float)W / (float)w[i];
     }
     int nblk;
-    if (kind == QPWC_LOSS_FLOW_MSE_V2 && (uintptr_t)gt % 16 == 0 && loss_tile_plan(H, W, h, w, n, lv)) {
+    if (kind == QPWC_LOSS_FLOW_MSE_V2 && (uintptr_t)gt % 16 == 0 && loss_tile_plan<kLossTile>(H, W, h, w, n, lv)) {
         const int64_t ntiles = (int64_t)B * (H / kLossTile) * (W / kLossTile);
         nblk = (int)(ntiles < kLossTileBlocks ? ntiles : kLossTileBlocks);
         if (layout == QPWC_NHWC)

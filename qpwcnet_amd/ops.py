@@ -1730,6 +1730,146 @@ def area_ground_truth(flow_gt, shapes, data_format=CHANNELS_LAST):
     return out
 
 
+def masked_loss_kernel(kind, B, H, W, shapes):
+    """The forward kernel ``qpwc_masked_loss_fwd`` takes for these levels ('masked_loss_tile_kernel' /
+    'masked_loss_pixel_kernel'; host only).  '' for arguments the entry point refuses."""
+    n = len(shapes)
+    ha, wa = (ctypes.c_int * n)(*[int(h) for h, _ in shapes]), (ctypes.c_int * n)(*[int(w) for _, w in shapes])
+    name = _hip.lib().qpwc_masked_loss_fwd_kernel(int(kind), int(B), int(H), int(W), 2, ha, wa, n)
+    return name.decode() if name else ""
+
+
+def masked_loss_fwd(kind, y_true, y_preds, valid=None, data_format=CHANNELS_LAST, p0=0.0, p1=0.0, want_dpred=False,
+                    want_gt=False, want_valid=False, shapes=None):
+    """Per-level flow loss over the valid pixels of 1..8 predictions against one full-resolution ground truth
+    (qpwc_masked_loss_fwd, include/qpwc_masked_loss.h; kind one of the three _hip.LOSS_FLOW_*) -> (losses: fp32 [L],
+    counts: int64 [L] valid level pixels, dpred, gt, valid_out), all on the device.  valid: None or uint8 (B,H,W) on
+    y_true's device.  dpred (want_dpred): fp32 d term / d y_preds[l], not yet divided by the count (masked_loss_bwd does
+    it); gt (want_gt): each level's ground truth, 0 where it has none; valid_out (want_valid): uint8 (B,h,w).
+    y_preds=None with shapes=[(h, w), ...]: the ground truth and validity only.  A y_true whose first byte is off the
+    16-byte grid, or a mask off the 4-byte grid (a view into a larger tensor), is copied first.  Enqueues and returns: no
+    host synchronisation."""
+    if not isinstance(y_true, torch.Tensor):
+        raise TypeError("y_true must be a torch.Tensor")
+    if _wants_grad(y_true):
+        raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
+                         "would be dropped (detach it)")
+    _check_tensor("y_true", y_true)
+    if y_true.dtype != torch.float32:
+        raise ValueError("y_true must be float32, got {}".format(y_true.dtype))
+    preds = [None] * len(shapes) if y_preds is None else list(y_preds)
+    n = len(preds)
+    if not 1 <= n <= 8:
+        raise ValueError("the losses take 1..8 prediction levels, got {}".format(n))
+    for i, p in enumerate(preds):
+        if p is not None:
+            _check_tensor("y_pred[%d]" % i, p)
+            if p.device != y_true.device:
+                raise ValueError("y_pred[{}] is on {}, y_true on {}".format(i, p.device, y_true.device))
+    gt, preds, layout, view = _loss_layout(y_true, preds, data_format)
+    nhwc = layout == _hip.NHWC
+    B, H, W, C = gt.shape if nhwc else (gt.shape[0], gt.shape[2], gt.shape[3], gt.shape[1])
+    dev = gt.device
+    if valid is not None and not (isinstance(valid, torch.Tensor) and valid.dtype == torch.uint8
+                                  and tuple(valid.shape) == (B, H, W) and valid.device == dev):
+        raise ValueError("valid must be a uint8 tensor of shape {} on {}".format((B, H, W), dev))
+    hs, ws_ = [], []
+    for i, p in enumerate(preds):
+        if p is None:
+            pb, pc, (h, w) = B, C, shapes[i]
+        else:
+            pb, h, w, pc = p.shape if nhwc else (p.shape[0], p.shape[2], p.shape[3], p.shape[1])
+        if pb != B or pc != C:
+            raise ValueError("level {}: prediction of batch {} / {} channels against a ground truth of {} / {}".format(
+                i, pb, pc, B, C))
+        hs.append(int(h))
+        ws_.append(int(w))
+    L = _hip.lib()
+    ha, wa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws_)
+    nws = L.qpwc_masked_loss_workspace_floats(int(kind), B, H, W, C, ha, wa, n)
+    _hip.check(min(int(nws), 0))
+    gt = _dense_on_grid(gt, 16)
+    valid = None if valid is None else _dense_on_grid(valid, 4)
+
+    def buffers():
+        return [torch.empty((B, h, w, C) if nhwc else (B, C, h, w), dtype=torch.float32, device=dev)
+                for h, w in zip(hs, ws_)]
+
+    ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+    pp = (ctypes.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in preds])
+    pdt = (ctypes.c_int * n)(*[_hip.F32 if p is None else _DTYPES[p.dtype] for p in preds])
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        dbuf = buffers() if want_dpred else None
+        gbuf = buffers() if want_gt else None
+        vbuf = [torch.empty((B, h, w), dtype=torch.uint8, device=dev) for h, w in zip(hs, ws_)] if want_valid else None
+        with _timed("masked_loss", (B, H, W, C)):
+            rc = L.qpwc_masked_loss_fwd(int(kind), float(p0), float(p1), gt.data_ptr(),
+                                        None if valid is None else valid.data_ptr(), B, H, W, C, layout, pp, ha, wa, pdt,
+                                        n, out.data_ptr(), counts.data_ptr(), ptrs(dbuf), ptrs(gbuf), ptrs(vbuf),
+                                        ws.data_ptr(), _stream(gt))
+    _hip.check(rc)
+    back = (lambda ts: [t.permute(0, 3, 1, 2) for t in ts]) if view else (lambda ts: ts)
+    return out, counts, (back(dbuf) if dbuf else None), (back(gbuf) if gbuf else None), vbuf
+
+
+def masked_loss_bwd(kind, dpreds, counts, grad_losses, dtypes):
+    """grad_pred[l] = grad_losses[l] * dpreds[l] / max(counts[l], 1) (the Huber kind: over twice that) in dtypes[l], all
+    levels in one launch (qpwc_masked_loss_bwd); dpreds and counts from masked_loss_fwd(want_dpred=True) with the same
+    kind, grad_losses [L] on the device.  The counts stay on the device."""
+    n = len(dpreds)
+    g = grad_losses.to(torch.float32).contiguous()
+    if g.numel() != n or not g.is_cuda:
+        raise ValueError("grad_losses must be a device vector of {} elements".format(n))
+    grads = [torch.empty_like(d, dtype=dt) for d, dt in zip(dpreds, dtypes)]   # same strides: same memory order
+    with torch.cuda.device(g.device), _timed("masked_loss_bwd", (n,)):
+        rc = _hip.lib().qpwc_masked_loss_bwd(int(kind), (ctypes.c_void_p * n)(*[d.data_ptr() for d in dpreds]),
+                                             counts.data_ptr(), g.data_ptr(),
+                                             (ctypes.c_void_p * n)(*[t.data_ptr() for t in grads]),
+                                             (ctypes.c_int64 * n)(*[d.numel() for d in dpreds]),
+                                             (ctypes.c_int * n)(*[_DTYPES[dt] for dt in dtypes]), n, _stream(g))
+    _hip.check(rc)
+    return grads
+
+
+class _MaskedLossFn(torch.autograd.Function):
+    """masked_loss_fwd() with qpwc_masked_loss_bwd as its gradient, as _LossFn: the forward stores d term / d y_pred, the
+    backward scales it by the incoming per-level gradient over the level's count, which never leaves the device."""
+
+    @staticmethod
+    def forward(ctx, cfg, y_true, valid, *y_preds):
+        kind, data_format, p0, p1 = cfg
+        losses, counts, dpred, _, _ = masked_loss_fwd(kind, y_true, y_preds, valid, data_format, p0, p1, want_dpred=True)
+        ctx.kind, ctx.dpred, ctx.counts = kind, dpred, counts
+        ctx.dtypes = [p.dtype for p in y_preds]
+        ctx.mark_non_differentiable(counts)
+        ctx.set_materialize_grads(False)       # no zeros tensor (a fill launch) for the counts' gradient
+        return losses, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_losses, _grad_counts):
+        _refuse_capture("the masked loss backward")
+        if grad_losses is None:
+            return (None,) * (3 + len(ctx.dtypes))
+        grads = masked_loss_bwd(ctx.kind, ctx.dpred, ctx.counts, grad_losses, ctx.dtypes)
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
+def masked_loss(kind, y_true, y_preds, valid=None, data_format=CHANNELS_LAST, p0=0.0, p1=0.0):
+    """(losses fp32 [L], counts int64 [L]) of masked_loss_fwd(); the losses are differentiable in y_preds when grad is
+    enabled and one of them requires it."""
+    if isinstance(y_true, torch.Tensor) and _wants_grad(y_true):
+        raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
+                         "would be dropped (detach it)")
+    if _wants_grad(*y_preds):
+        _refuse_capture("the masked loss")
+        return _MaskedLossFn.apply((int(kind), data_format, float(p0), float(p1)), y_true, valid, *y_preds)
+    return masked_loss_fwd(kind, y_true, y_preds, valid, data_format, p0, p1)[:2]
+
+
 def _dw_sources(sources):
     """-> (kept tensors, ctypes pointer/channel/stride arrays, B, H, W, C) for 1..3 sources."""
     import ctypes
