@@ -1607,6 +1607,67 @@ def _loss_layout(y_true, preds, data_format):
             _hip.NHWC if data_format == CHANNELS_LAST else _hip.NCHW, False)
 
 
+class _LossOperands:
+    """What both loss forwards make of their operands: y_true and the predictions checked and in the layout the kernels
+    read (gt, preds, layout, nhwc), the extents B, H, W, C, n and hs, ws_, the ctypes arrays ha, wa, pp, pdt, and the
+    helpers buffers() (one fp32 tensor per level, shaped like its prediction), ptrs() and back() (the caller's view of
+    such buffers).  y_preds=None with shapes=[(h, w), ...]: no predictions.  check(self): the caller's own operand check,
+    run once B, H, W, C and dev are known and before the levels' shapes are looked at."""
+
+    def __init__(self, y_true, y_preds, data_format, shapes, check=None):
+        if not isinstance(y_true, torch.Tensor):
+            raise TypeError("y_true must be a torch.Tensor")
+        if _wants_grad(y_true):
+            raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
+                             "would be dropped (detach it)")
+        _check_tensor("y_true", y_true)
+        if y_true.dtype != torch.float32:
+            raise ValueError("y_true must be float32, got {}".format(y_true.dtype))
+        preds = [None] * len(shapes) if y_preds is None else list(y_preds)
+        self.n = n = len(preds)
+        if not 1 <= n <= 8:
+            raise ValueError("the losses take 1..8 prediction levels, got {}".format(n))
+        for i, p in enumerate(preds):
+            if p is not None:
+                _check_tensor("y_pred[%d]" % i, p)
+                if p.device != y_true.device:
+                    raise ValueError("y_pred[{}] is on {}, y_true on {}".format(i, p.device, y_true.device))
+        self.gt, self.preds, self.layout, self.view = _loss_layout(y_true, preds, data_format)
+        self.nhwc = nhwc = self.layout == _hip.NHWC
+        unpack = lambda t: t.shape if nhwc else (t.shape[0], t.shape[2], t.shape[3], t.shape[1])
+        self.B, self.H, self.W, self.C = B, H, W, C = unpack(self.gt)
+        self.dev = self.gt.device
+        if check is not None:
+            check(self)
+        self.hs, self.ws_ = [], []
+        for i, p in enumerate(self.preds):
+            if p is None:
+                pb, pc, (h, w) = B, C, shapes[i]
+            else:
+                pb, h, w, pc = unpack(p)
+            if pb != B or pc != C:
+                raise ValueError("level {}: prediction of batch {} / {} channels against a ground truth of {} / {}".format(
+                    i, pb, pc, B, C))
+            self.hs.append(int(h))
+            self.ws_.append(int(w))
+        self.ha, self.wa = (ctypes.c_int * n)(*self.hs), (ctypes.c_int * n)(*self.ws_)
+        self.pp = (ctypes.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in self.preds])
+        self.pdt = (ctypes.c_int * n)(*[_hip.F32 if p is None else _DTYPES[p.dtype] for p in self.preds])
+
+    def buffers(self):
+        B, C = self.B, self.C
+        return [torch.empty((B, h, w, C) if self.nhwc else (B, C, h, w), dtype=torch.float32, device=self.dev)
+                for h, w in zip(self.hs, self.ws_)]
+
+    def ptrs(self, ts):
+        return None if ts is None else (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in ts])
+
+    def back(self, ts):
+        if not ts:
+            return None
+        return [t.permute(0, 3, 1, 2) for t in ts] if self.view else ts
+
+
 def loss_fwd(kind, y_true, y_preds, data_format=CHANNELS_LAST, p0=0.0, p1=0.0, want_dpred=False, want_gt=False,
              shapes=None):
     """Per-level training loss of 1..8 predictions against one full-resolution ground truth (qpwc_loss_fwd; kind
@@ -1614,75 +1675,42 @@ def loss_fwd(kind, y_true, y_preds, data_format=CHANNELS_LAST, p0=0.0, p1=0.0, w
     dpred (want_dpred): fp32 d losses[l] / d y_preds[l], shaped like each prediction; gt (want_gt): each level's
     resampled, flow-scaled ground truth.  y_preds=None with shapes=[(h, w), ...]: the ground truth only (want_gt).
     Enqueues and returns: no host synchronisation."""
-    if not isinstance(y_true, torch.Tensor):
-        raise TypeError("y_true must be a torch.Tensor")
-    if _wants_grad(y_true):
-        raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
-                         "would be dropped (detach it)")
-    _check_tensor("y_true", y_true)
-    if y_true.dtype != torch.float32:
-        raise ValueError("y_true must be float32, got {}".format(y_true.dtype))
-    preds = [None] * len(shapes) if y_preds is None else list(y_preds)
-    n = len(preds)
-    if not 1 <= n <= 8:
-        raise ValueError("the losses take 1..8 prediction levels, got {}".format(n))
-    for i, p in enumerate(preds):
-        if p is not None:
-            _check_tensor("y_pred[%d]" % i, p)
-            if p.device != y_true.device:
-                raise ValueError("y_pred[{}] is on {}, y_true on {}".format(i, p.device, y_true.device))
-    gt, preds, layout, view = _loss_layout(y_true, preds, data_format)
-    nhwc = layout == _hip.NHWC
-    B, H, W, C = gt.shape if nhwc else (gt.shape[0], gt.shape[2], gt.shape[3], gt.shape[1])
-    hs, ws_ = [], []
-    for i, p in enumerate(preds):
-        if p is None:
-            pb, pc, (h, w) = B, C, shapes[i]
-        else:
-            pb, h, w, pc = p.shape if nhwc else (p.shape[0], p.shape[2], p.shape[3], p.shape[1])
-        if pb != B or pc != C:
-            raise ValueError("level {}: prediction of batch {} / {} channels against a ground truth of {} / {}".format(
-                i, pb, pc, B, C))
-        hs.append(int(h))
-        ws_.append(int(w))
+    o = _LossOperands(y_true, y_preds, data_format, shapes)
+    B, H, W, C, n, dev = o.B, o.H, o.W, o.C, o.n, o.dev
     L = _hip.lib()
-    ha, wa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws_)
-    nws = L.qpwc_loss_workspace_floats(int(kind), B, H, W, C, ha, wa, n)
+    nws = L.qpwc_loss_workspace_floats(int(kind), B, H, W, C, o.ha, o.wa, n)
     _hip.check(min(int(nws), 0))
-    dev = gt.device
     ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
     out = torch.empty(n, dtype=torch.float32, device=dev)
-
-    def buffers():
-        return [torch.empty((B, h, w, C) if nhwc else (B, C, h, w), dtype=torch.float32, device=dev)
-                for h, w in zip(hs, ws_)]
-
-    dbuf = buffers() if want_dpred else None
-    gbuf = buffers() if want_gt else None
-    ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-    pp = (ctypes.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in preds])
-    pdt = (ctypes.c_int * n)(*[_hip.F32 if p is None else _DTYPES[p.dtype] for p in preds])
+    dbuf = o.buffers() if want_dpred else None
+    gbuf = o.buffers() if want_gt else None
     with torch.cuda.device(dev), _timed("loss", (B, H, W, C)):
-        rc = L.qpwc_loss_fwd(int(kind), float(p0), float(p1), gt.data_ptr(), B, H, W, C, layout, pp, ha, wa, pdt, n,
-                             out.data_ptr(), ptrs(dbuf), ptrs(gbuf), ws.data_ptr(), _stream(gt))
+        rc = L.qpwc_loss_fwd(int(kind), float(p0), float(p1), o.gt.data_ptr(), B, H, W, C, o.layout, o.pp, o.ha, o.wa,
+                             o.pdt, n, out.data_ptr(), o.ptrs(dbuf), o.ptrs(gbuf), ws.data_ptr(), _stream(o.gt))
     _hip.check(rc)
-    back = (lambda ts: [t.permute(0, 3, 1, 2) for t in ts]) if view else (lambda ts: ts)
-    return out, (back(dbuf) if dbuf else None), (back(gbuf) if gbuf else None)
+    return out, o.back(dbuf), o.back(gbuf)
 
 
-def loss_bwd(dpreds, grad_losses, dtypes):
-    """grad_pred[l] = grad_losses[l] * dpreds[l] in dtypes[l], all levels in one launch (qpwc_loss_bwd); dpreds from
-    loss_fwd(want_dpred=True), grad_losses [L] on the device."""
+def _loss_grads(dpreds, grad_losses, dtypes):
+    """-> (g: grad_losses as a dense fp32 device vector, grads: one empty tensor per level in dtypes[l], the ctypes
+    arguments of both backward entry points after grad_losses: grad_pred, n_elems, pred_dtype, n)."""
     n = len(dpreds)
     g = grad_losses.to(torch.float32).contiguous()
     if g.numel() != n or not g.is_cuda:
         raise ValueError("grad_losses must be a device vector of {} elements".format(n))
     grads = [torch.empty_like(d, dtype=dt) for d, dt in zip(dpreds, dtypes)]   # same strides: same memory order
+    return g, grads, ((ctypes.c_void_p * n)(*[d.data_ptr() for d in dpreds]),
+                      (ctypes.c_void_p * n)(*[t.data_ptr() for t in grads]),
+                      (ctypes.c_int64 * n)(*[d.numel() for d in dpreds]),
+                      (ctypes.c_int * n)(*[_DTYPES[dt] for dt in dtypes]), n)
+
+
+def loss_bwd(dpreds, grad_losses, dtypes):
+    """grad_pred[l] = grad_losses[l] * dpreds[l] in dtypes[l], all levels in one launch (qpwc_loss_bwd); dpreds from
+    loss_fwd(want_dpred=True), grad_losses [L] on the device."""
+    g, grads, (dp, gp, ne, dt, n) = _loss_grads(dpreds, grad_losses, dtypes)
     with torch.cuda.device(g.device), _timed("loss_bwd", (n,)):
-        rc = _hip.lib().qpwc_loss_bwd((ctypes.c_void_p * n)(*[d.data_ptr() for d in dpreds]), g.data_ptr(),
-                                      (ctypes.c_void_p * n)(*[t.data_ptr() for t in grads]),
-                                      (ctypes.c_int64 * n)(*[d.numel() for d in dpreds]),
-                                      (ctypes.c_int * n)(*[_DTYPES[dt] for dt in dtypes]), n, _stream(g))
+        rc = _hip.lib().qpwc_loss_bwd(dp, g.data_ptr(), gp, ne, dt, n, _stream(g))
     _hip.check(rc)
     return grads
 
@@ -1749,87 +1777,41 @@ def masked_loss_fwd(kind, y_true, y_preds, valid=None, data_format=CHANNELS_LAST
     y_preds=None with shapes=[(h, w), ...]: the ground truth and validity only.  A y_true whose first byte is off the
     16-byte grid, or a mask off the 4-byte grid (a view into a larger tensor), is copied first.  Enqueues and returns: no
     host synchronisation."""
-    if not isinstance(y_true, torch.Tensor):
-        raise TypeError("y_true must be a torch.Tensor")
-    if _wants_grad(y_true):
-        raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
-                         "would be dropped (detach it)")
-    _check_tensor("y_true", y_true)
-    if y_true.dtype != torch.float32:
-        raise ValueError("y_true must be float32, got {}".format(y_true.dtype))
-    preds = [None] * len(shapes) if y_preds is None else list(y_preds)
-    n = len(preds)
-    if not 1 <= n <= 8:
-        raise ValueError("the losses take 1..8 prediction levels, got {}".format(n))
-    for i, p in enumerate(preds):
-        if p is not None:
-            _check_tensor("y_pred[%d]" % i, p)
-            if p.device != y_true.device:
-                raise ValueError("y_pred[{}] is on {}, y_true on {}".format(i, p.device, y_true.device))
-    gt, preds, layout, view = _loss_layout(y_true, preds, data_format)
-    nhwc = layout == _hip.NHWC
-    B, H, W, C = gt.shape if nhwc else (gt.shape[0], gt.shape[2], gt.shape[3], gt.shape[1])
-    dev = gt.device
-    if valid is not None and not (isinstance(valid, torch.Tensor) and valid.dtype == torch.uint8
-                                  and tuple(valid.shape) == (B, H, W) and valid.device == dev):
-        raise ValueError("valid must be a uint8 tensor of shape {} on {}".format((B, H, W), dev))
-    hs, ws_ = [], []
-    for i, p in enumerate(preds):
-        if p is None:
-            pb, pc, (h, w) = B, C, shapes[i]
-        else:
-            pb, h, w, pc = p.shape if nhwc else (p.shape[0], p.shape[2], p.shape[3], p.shape[1])
-        if pb != B or pc != C:
-            raise ValueError("level {}: prediction of batch {} / {} channels against a ground truth of {} / {}".format(
-                i, pb, pc, B, C))
-        hs.append(int(h))
-        ws_.append(int(w))
+    def check_valid(o):
+        if valid is not None and not (isinstance(valid, torch.Tensor) and valid.dtype == torch.uint8
+                                      and tuple(valid.shape) == (o.B, o.H, o.W) and valid.device == o.dev):
+            raise ValueError("valid must be a uint8 tensor of shape {} on {}".format((o.B, o.H, o.W), o.dev))
+
+    o = _LossOperands(y_true, y_preds, data_format, shapes, check_valid)
+    B, H, W, C, n, dev = o.B, o.H, o.W, o.C, o.n, o.dev
     L = _hip.lib()
-    ha, wa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws_)
-    nws = L.qpwc_masked_loss_workspace_floats(int(kind), B, H, W, C, ha, wa, n)
+    nws = L.qpwc_masked_loss_workspace_floats(int(kind), B, H, W, C, o.ha, o.wa, n)
     _hip.check(min(int(nws), 0))
-    gt = _dense_on_grid(gt, 16)
+    gt = _dense_on_grid(o.gt, 16)
     valid = None if valid is None else _dense_on_grid(valid, 4)
-
-    def buffers():
-        return [torch.empty((B, h, w, C) if nhwc else (B, C, h, w), dtype=torch.float32, device=dev)
-                for h, w in zip(hs, ws_)]
-
-    ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-    pp = (ctypes.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in preds])
-    pdt = (ctypes.c_int * n)(*[_hip.F32 if p is None else _DTYPES[p.dtype] for p in preds])
     with torch.cuda.device(dev):
         ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
         out = torch.empty(n, dtype=torch.float32, device=dev)
         counts = torch.empty(n, dtype=torch.int64, device=dev)
-        dbuf = buffers() if want_dpred else None
-        gbuf = buffers() if want_gt else None
-        vbuf = [torch.empty((B, h, w), dtype=torch.uint8, device=dev) for h, w in zip(hs, ws_)] if want_valid else None
+        dbuf = o.buffers() if want_dpred else None
+        gbuf = o.buffers() if want_gt else None
+        vbuf = [torch.empty((B, h, w), dtype=torch.uint8, device=dev) for h, w in zip(o.hs, o.ws_)] if want_valid else None
         with _timed("masked_loss", (B, H, W, C)):
             rc = L.qpwc_masked_loss_fwd(int(kind), float(p0), float(p1), gt.data_ptr(),
-                                        None if valid is None else valid.data_ptr(), B, H, W, C, layout, pp, ha, wa, pdt,
-                                        n, out.data_ptr(), counts.data_ptr(), ptrs(dbuf), ptrs(gbuf), ptrs(vbuf),
-                                        ws.data_ptr(), _stream(gt))
+                                        None if valid is None else valid.data_ptr(), B, H, W, C, o.layout, o.pp, o.ha,
+                                        o.wa, o.pdt, n, out.data_ptr(), counts.data_ptr(), o.ptrs(dbuf), o.ptrs(gbuf),
+                                        o.ptrs(vbuf), ws.data_ptr(), _stream(gt))
     _hip.check(rc)
-    back = (lambda ts: [t.permute(0, 3, 1, 2) for t in ts]) if view else (lambda ts: ts)
-    return out, counts, (back(dbuf) if dbuf else None), (back(gbuf) if gbuf else None), vbuf
+    return out, counts, o.back(dbuf), o.back(gbuf), vbuf
 
 
 def masked_loss_bwd(kind, dpreds, counts, grad_losses, dtypes):
     """grad_pred[l] = grad_losses[l] * dpreds[l] / max(counts[l], 1) (the Huber kind: over twice that) in dtypes[l], all
     levels in one launch (qpwc_masked_loss_bwd); dpreds and counts from masked_loss_fwd(want_dpred=True) with the same
     kind, grad_losses [L] on the device.  The counts stay on the device."""
-    n = len(dpreds)
-    g = grad_losses.to(torch.float32).contiguous()
-    if g.numel() != n or not g.is_cuda:
-        raise ValueError("grad_losses must be a device vector of {} elements".format(n))
-    grads = [torch.empty_like(d, dtype=dt) for d, dt in zip(dpreds, dtypes)]   # same strides: same memory order
+    g, grads, (dp, gp, ne, dt, n) = _loss_grads(dpreds, grad_losses, dtypes)
     with torch.cuda.device(g.device), _timed("masked_loss_bwd", (n,)):
-        rc = _hip.lib().qpwc_masked_loss_bwd(int(kind), (ctypes.c_void_p * n)(*[d.data_ptr() for d in dpreds]),
-                                             counts.data_ptr(), g.data_ptr(),
-                                             (ctypes.c_void_p * n)(*[t.data_ptr() for t in grads]),
-                                             (ctypes.c_int64 * n)(*[d.numel() for d in dpreds]),
-                                             (ctypes.c_int * n)(*[_DTYPES[dt] for dt in dtypes]), n, _stream(g))
+        rc = _hip.lib().qpwc_masked_loss_bwd(int(kind), dp, counts.data_ptr(), g.data_ptr(), gp, ne, dt, n, _stream(g))
     _hip.check(rc)
     return grads
 

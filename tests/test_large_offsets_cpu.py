@@ -631,7 +631,7 @@ def test_loss_validator_refuses_what_the_kernels_decode_in_32_bits(hip_lib):
     ground truth's tiles in an `int`: an image, or a level, of 2^31 pixels and a ground truth of 2^31 tiles are refused
     by name, one step below they are admitted."""
     from qpwcnet_amd import _hip
-    text = open(os.path.join(CSRC, "loss.hip")).read()
+    text = "".join(open(os.path.join(CSRC, f)).read() for f in ("loss_common.h", "loss.hip", "masked_loss.hip"))
     assert text.count("const int r = (int)(i - b * plane);") == 1 and text.count("const int ntiles = B * tiles_y * tiles_x;") == 1
     I = ctypes.c_int
 

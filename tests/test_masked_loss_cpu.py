@@ -12,6 +12,7 @@ Bounds: 1e-12 relative for losses, ground truths (of the level's largest value) 
 largest gradient); masks and counts exact."""
 import ctypes
 import os
+import re
 import sys
 
 import numpy as np
@@ -455,12 +456,17 @@ def test_masked_loss_prototypes_match_their_header():
     assert len(argtypes) == 22
     table["qpwc_masked_loss_fwd"] = (restype, argtypes[:-1])
     assert mismatches(table, protos) == ["qpwc_masked_loss_fwd: 22 parameters, table has 21"]
-    with open(os.path.join(ROOT, "qpwcnet_amd", "csrc", "masked_loss.hip")) as f:
+    with open(os.path.join(ROOT, "qpwcnet_amd", "csrc", "masked_loss.hip")) as f:   # under the family's names
         src = f.read()
-    assert "kMaskedTileBlocks = {};".format(_hip.MASKED_LOSS_TILE_BLOCKS) in src
-    assert "kMaskedPixBlocks = {};".format(_hip.MASKED_LOSS_PIX_BLOCKS) in src
-    assert "kMaskedThreads = {};".format(_hip.MASKED_LOSS_THREADS) in src
-    assert "kMaskedTile = {};".format(_hip.MASKED_LOSS_TILE) in src
+    assert "kLossTileBlocks = {};".format(_hip.MASKED_LOSS_TILE_BLOCKS) in src
+    assert "kLossPixBlocks = {};".format(_hip.MASKED_LOSS_PIX_BLOCKS) in src
+    assert "kLossThreads = {};".format(_hip.MASKED_LOSS_THREADS) in src
+    assert "kLossTile = {};".format(_hip.MASKED_LOSS_TILE) in src
+    # both translation units state the family's grid constants before loss_common.h: the two statements are one text
+    with open(os.path.join(ROOT, "qpwcnet_amd", "csrc", "loss.hip")) as f:
+        dense = f.read()
+    grid = lambda text: re.findall(r"^constexpr int (kLoss\w+) = (\d+);", text, re.M)
+    assert grid(src) == grid(dense) and len(grid(src)) == 5
 
 
 def test_the_library_exports_the_table(hip_lib):
