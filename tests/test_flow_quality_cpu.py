@@ -163,18 +163,20 @@ def chunk_flows(seed=3):
     return truth, pred
 
 
-def masks(seed, hw, valid_share=(0.52, 0.93), occluded_share=0.3):
-    """(valid, occluded), bool (B,H,W), independent random patterns: valid keeps valid_share[n] of image n (pixel 0 and
-    the last chunk always); occluded marks occluded_share of image 0 and, in image 1, the last chunk only."""
+def masks(seed, hw, valid_share=(0.52, 0.93), occluded_share=0.3, batch=B, last=LAST):
+    """(valid, occluded), bool (batch,H,W), independent random patterns: valid keeps valid_share[n % 2] of image n (pixel
+    0 and the last `last` pixels -- by default the last chunk -- always); occluded marks occluded_share of every image
+    but image 1, where it marks the last `last` pixels only."""
     rng = np.random.default_rng(seed)
     H, W = hw
-    valid = rng.random((B, H * W)) < np.asarray(valid_share).reshape(B, 1)
+    share = np.asarray([valid_share[n % len(valid_share)] for n in range(batch)])
+    valid = rng.random((batch, H * W)) < share.reshape(batch, 1)
     valid[:, 0] = True
-    valid[:, -LAST:] = True
-    occluded = rng.random((B, H * W)) < occluded_share
+    valid[:, -last:] = True
+    occluded = rng.random((batch, H * W)) < occluded_share
     occluded[1] = False
-    occluded[1, -LAST:] = True
-    return valid.reshape(B, H, W), occluded.reshape(B, H, W)
+    occluded[1, -last:] = True
+    return valid.reshape(batch, H, W), occluded.reshape(batch, H, W)
 
 
 def tensor(a):
@@ -499,10 +501,11 @@ def state_scenario(device="cpu"):
     return m, per, np.concatenate(sums), CHUNKS[0] * CHUNKS[1]
 
 
-def check_state(m, per, sums, pixels):
+def check_state(m, per, sums, pixels, images=2 * B):
+    """The 17 running sums of m against the float64 sums [images, 15] of every image it has seen, in image order."""
     state = m.state.cpu().numpy()
     assert m.state.dtype == torch.float64 and state.shape == (17,)
-    assert state[15] == 2 * B and state[16] == 2 * B * pixels
+    assert len(sums) == images and state[15] == images and state[16] == images * pixels
     total = sums.sum(axis=0)
     for i in range(15):
         if i in (1, 8, 10, 12, 14):                       # sums of e: the bound of a mean times its count
@@ -512,8 +515,8 @@ def check_state(m, per, sums, pixels):
         else:
             assert state[i] == total[i], i                # counts
     res = m.result()
-    want = ref_scores(total, 2 * B * pixels)
-    assert res["images"] == 2 * B and res["pixels"] == 2 * B * pixels
+    want = ref_scores(total, images * pixels)
+    assert res["images"] == images and res["pixels"] == images * pixels
     bad, err = violations({k: np.float32(res[k]) for k in FIELDS}, want)
     assert not bad, err
     # pixel-weighted, not the mean of the per-image means: the batches differ in valid share and error level

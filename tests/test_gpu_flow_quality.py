@@ -17,6 +17,10 @@ for:
   unknown_gt             NaN, +-inf and +-1e10 planted in the ground truth: excluded;
   all_invalid            image 0 fully masked out: NaN ratios and valid = 0, image 1 normal;
   near_equal             prediction = truth + N(0, 0.01): acosf of the normalised dot product would miss aae.
+Beside the values: operands the wrapper has to copy (a flow 4 bytes off the 8-byte grid, an fp16 prediction 2 bytes off the
+4-byte grid, masks that are strided views) and uint8 masks holding 2, 128 or 255 for 1 give the same bits.  Larger batches
+and longer images, where the fold kernel's loops iterate: tests/test_gpu_eval_scale.py; past 2^31 elements:
+tests/test_gpu_large_offsets.py.
 Measured on an MI355X: see the docstrings of the tests and DESIGN.md section 4.25."""
 import os
 import sys
@@ -113,6 +117,59 @@ def test_flows_off_the_8_byte_grid_take_the_wrappers_copy():
         got = metrics.flow_quality(ops_in["truth"], ops_in["pred"], valid=valid, occluded=occluded,
                                    data_format="channels_last")
         assert same_bits(got, want), which
+
+
+def test_fp16_prediction_off_the_4_byte_grid_takes_the_wrappers_copy():
+    """An fp16 channels-last prediction whose first byte is 2 off the 4-byte grid of the __half2 pixel load: the wrapper
+    copies it, and the scores are those of the aligned clone, bit for bit."""
+    c = CASES["chunks_f16_pred"]
+    want, _ = run_case("chunks_f16_pred", DEV)
+    pred = tensor(c["pred"]).to(DEV)
+    room = torch.empty(pred.numel() + 1, dtype=torch.float16, device=DEV)
+    room[1:] = pred.reshape(-1)
+    off = room[1:].view(pred.shape)
+    assert off.dtype == torch.float16 and off.data_ptr() % 4 == 2 and off.is_contiguous()
+    got = metrics.flow_quality(tensor(c["truth"]).to(DEV), off, data_format="channels_last")
+    assert same_bits(got, want)
+    assert violations(got, reference("chunks_f16_pred"))[0] == []
+
+
+def test_a_strided_mask_is_copied():
+    """Masks that are strided views (every second column of a wider tensor, a transposed tensor): same bits."""
+    c = CASES["both_masks"]
+    want, _ = run_case("both_masks", DEV)
+    t, p = tensor(c["truth"]).to(DEV), tensor(c["pred"]).to(DEV)
+    H, W = CHUNKS
+    views = {}
+    for k in ("valid", "occluded"):
+        m = tensor(c[k]).to(DEV)
+        wide = torch.ones(B, H, 2 * W, dtype=torch.bool, device=DEV)
+        wide[:, :, ::2] = m
+        views[k] = wide[:, :, ::2]
+        assert not views[k].is_contiguous() and torch.equal(views[k], m)
+    got = metrics.flow_quality(t, p, valid=views["valid"], occluded=views["occluded"], data_format="channels_last")
+    assert same_bits(got, want)
+    turned = {k: tensor(c[k]).to(DEV).transpose(1, 2).contiguous().transpose(1, 2) for k in ("valid", "occluded")}
+    assert not turned["valid"].is_contiguous()
+    got = metrics.flow_quality(t, p, valid=turned["valid"].view(torch.uint8), occluded=turned["occluded"],
+                               data_format="channels_last")
+    assert same_bits(got, want)
+
+
+@pytest.mark.parametrize("byte", [2, 128, 255])
+def test_any_nonzero_mask_byte_is_set(byte):
+    """include/qpwc_flow_quality.h: a mask byte counts where it is nonzero.  uint8 masks holding 2, 128 or 255 where the
+    case's masks hold 1 give the same bits, in both layouts."""
+    for name in ("both_masks", "chunks_channels_first"):
+        c = CASES[name]
+        v, o = (tensor(CASES["both_masks"][k]).to(DEV).to(torch.uint8) * byte for k in ("valid", "occluded"))
+        assert int(v.max()) == byte and int(o.max()) == byte and int(v.min()) == 0
+        t, p = tensor(c["truth"]).to(DEV), tensor(c["pred"]).to(DEV)
+        ones = tuple(tensor(CASES["both_masks"][k]).to(DEV) for k in ("valid", "occluded"))
+        want = metrics.flow_quality(t, p, valid=ones[0], occluded=ones[1], data_format=c["data_format"])
+        got = metrics.flow_quality(t, p, valid=v, occluded=o, data_format=c["data_format"])
+        assert same_bits(got, want), name
+    assert violations(want, reference("both_masks"))[0] == []          # the same flows in the other layout
 
 
 def test_occluded_estimate_is_the_map_passed_explicitly():

@@ -1,7 +1,9 @@
 """GPU suite of the training kernels where element offsets pass 2^29, 2^30 and 2^31 (byte offsets 2^31 and 2^32, and the
 `int` index limit): one entry of CASES per kernel family, each B = 3 with ragged H x W so that the three boundaries of
 its main operand fall into three different images (tests/test_large_offsets_cpu.py proves that for every entry, and
-that the validators admit the shape).
+that the validators admit the shape).  The entries added for the byte-indexed masks differ: the masked losses' tile case
+is a square of 32-multiples (the smallest whose pixel count passes 2^31), the flow metrics have B = 5 (each image under
+2^29 floats).
 
 No whole-array float64 reference exists at 8 GB per operand.  The oracles are
 
@@ -26,6 +28,12 @@ The losses and the EPE are sums over the batch only: the prediction equals the l
 windows (the area loss takes the kernel's own gt_out, itself held to float64 on crops; a full-resolution level takes a
 copy of the ground truth), so value and grad_pred follow from the windows' crops in float64.  Their magnitudes are
 1e-6 and below, so their bound is relative (LOSS_REL, derived at its definition), not the 1e-4 of the layers.
+
+The masked losses and the flow metrics (the last three entries of CASES) index a uint8 mask by pixel, so a byte offset
+is an index: their shapes put 2^31 (masked losses, tile path) and 2^30 (the others) pixels into the batch, and the tile
+path's ground truth reaches 2^32 elements (BOUNDARIES_32).  Validity is zero (masked losses) or the prediction is the
+truth (flow metrics) except in planted windows, so the float64 answer needs the windows' crops and the masks' counts
+only; see the comments at their sections.
 
 Where a family departs from this: grad_img of the warp is a scatter of float atomics, so it is held to (b) only; the
 cost-volume backward is fed a random saved output (it reads it for the LeakyReLU mask only) and gives its two
@@ -66,22 +74,30 @@ Measured on an MI355X (peak of torch.cuda.max_memory_allocated, wall time of the
   avgpool_pyramid            8.04 (8.04)         0.01         0 (exact)
   loss tile path            14.01 (16.02)        0.4          relative: loss 5.8e-8, grad_pred 9.0e-8 (bound 1e-5)
   loss pixel paths, EPE     32.05 (32.05)        0.1          relative: losses 4.3e-8, grad_pred 1.3e-7, EPE 7.7e-10 (bound 1e-5)
-The whole module: 15 tests, 3 - 16 s (the seconds are test bodies in different runs).  The peaks above the plan are the boolean of torch.equal on one image (0.67 GiB);
-ops.py itself allocates what is planned and nothing else.  The negative controls moved the sums by 1300 - 20500 bounds.
+  masked_loss tile path     34.14 (34.64)        0.6          relative: losses 5.0e-9, grad_pred 1.3e-7 (bound 1e-5); gt_out 1.7e-8 of the level's largest (bound 1e-6)
+  masked_loss pixel paths   33.06 (34.06)        0.1          relative: losses 1.6e-8, grad_pred 1.2e-7 (bound 1e-5); gt_out exact
+  flow_quality              22.01 (22.01)        2.1          relative: means 2.7e-7 (bound 1e-5); 1.7e-7 px, 3.5e-13 degrees, count ratios 0.50 ulp
+The whole module: 18 tests, 3 - 16 s (the seconds are test bodies in different runs).  The peaks above the plan are the boolean of torch.equal on one image (0.67 GiB);
+ops.py itself allocates what is planned and nothing else.  The negative controls moved the sums by 1300 - 20500 bounds;
+those of the masked losses moved the loss or grad_pred by 190 - 200000 bounds, those of the flow metrics an image's epe by
+7100 - 100000.
 """
 import gc
 import os
 import sys
 import time
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from oracle import torch_ref
-from qpwcnet_amd import ops
+from qpwcnet_amd import metrics, ops
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_flow_quality_cpu import (COUNT_FIELDS, EPE_FIELDS, away_from_thresholds, check, make_flows,  # noqa: E402
+                                   ref_scores, ref_sums)
 from test_gpu_conv_grad import same_pad  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -102,13 +118,19 @@ CASES = {
     "avgpool_pyramid": (3, 15456, 15488, 3, 5),          # (B, H, W, C, levels): 2.154 G input floats
     "loss": (3, 18912, 18944, 2),                        # (B, H, W, 2) ground truth, H and W multiples of 32: the tile path
     "epe": (3, 18931, 18937, 2),                         # (B, H, W, 2) odd: pixel and bilinear losses, both EPE kernels
+    "masked_loss": (3, 26784, 26784, 2),                 # 2.152 G pixels: the mask's byte index passes 2^31, the ground
+                                                         # truth's element index 2^32; multiples of 32: the tile path
+    "masked_loss_pixel": (3, 18931, 18937, 2),           # the "epe" shape: the masked pixel walks, the scalar backward
+    "flow_quality": (5, 14653, 14661, 2),                # 1.074 G pixels (the cap is 2^31 - 1 elements a flow): truth and
+                                                         # an fp32 pred pass 2^31 elements, the masks 2^30 bytes
 }
+BOUNDARIES_32 = BOUNDARIES + (1 << 32,)                  # ... and the unsigned index limit, for operands that reach it
 
 
 # ---- where the boundaries lie (pure; shared with the CPU companion) ------------------------------------------------
-def crossed(n_elems):
+def crossed(n_elems, boundaries=BOUNDARIES):
     """The boundaries that an operand of n_elems floats crosses: its last element lies beyond them."""
-    return [b for b in BOUNDARIES if n_elems - 1 > b]
+    return [b for b in boundaries if n_elems - 1 > b]
 
 
 def locate(elem, rows, cols, ch):
@@ -788,11 +810,11 @@ def test_warp_bwd(mode, arena):
 
 
 # ---- the interpolator's pieces ---------------------------------------------------------------------------------------
-def pixel_windows(B, H, W, C):
+def pixel_windows(B, H, W, C, boundaries=BOUNDARIES):
     """[(tag, n, y0, y1, x0, x1)]: WIN x WIN pixels at the start of image 0, in the rows just behind the pixel that holds
     each boundary of a dense (B,H,W,C) operand, and in the bottom-right corner of the last image."""
     wins = [("first", 0, 0, WIN, 0, WIN)]
-    for b in crossed(B * H * W * C):
+    for b in crossed(B * H * W * C, boundaries):
         n, y, x = locate(b, H, W, C)
         assert y + 1 + WIN <= H, (b, y)
         wins.append((">2^%d" % (b.bit_length() - 1), n, y + 1, y + 1 + WIN) + _span(x, WIN, W))
@@ -800,14 +822,14 @@ def pixel_windows(B, H, W, C):
     return wins
 
 
-def wrapped_pixel_regions(B, H, W, C, reg):
+def wrapped_pixel_regions(B, H, W, C, reg, elem_bytes=4):
     """conv_wrapped_regions for an operand that is read pixel by pixel: the window itself at its first element's byte
-    offset mod 2^31 and mod 2^32, where that differs."""
+    offset mod 2^31 and mod 2^32, where that differs.  elem_bytes: 4 for fp32, 1 for a uint8 mask."""
     _, n, y0, y1, x0, x1 = reg
     first = ((n * H + y0) * W + x0) * C
     out = []
     for mod in (1 << 31, 1 << 32):
-        e = (first * 4 % mod) // 4
+        e = (first * elem_bytes % mod) // elem_bytes
         if e != first:
             m, y, x = locate(e, H, W, C)
             y, x = min(y, H - (y1 - y0)), min(x, W - (x1 - x0))
@@ -1223,5 +1245,437 @@ def test_loss_pixel_paths_and_epe(arena):
     peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
     print("loss pixel / epe: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
         peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- masked losses: a byte-indexed mask past 2^31, a ground truth past 2^32 elements ---------------------------------
+# The masked flow losses are sums over the valid pixels only: validity is zero except planted WIN x WIN windows, so the
+# counts, the level masks, the level ground truths, the loss and grad_pred follow in float64 from the windows' crops,
+# and whatever lies elsewhere -- random ground truth, random predictions -- must reach nothing.  A mask read at a
+# wrapped byte offset finds zeros (the window drops out: the count fails), a ground truth read at a wrapped offset
+# finds other values.  Bounds: LOSS_REL for the loss and grad_pred; the project's 1e-6 of the level's largest for the
+# level ground truth; counts and masks exact; gradients exactly 0 outside the windows, over the whole tensor.
+GT_REL = 1e-6                    # tests/test_gpu_masked_loss.py's bound of the level ground truth
+
+
+def masked_loss_windows(key, level=None):
+    """[(tag, n, y0, y1, x0, x1)] in ground-truth pixels: pixel_windows of the ground truth with the boundary at 2^32
+    elements added, of the mask (a byte a pixel) and, with `level` = (h, w), of the level's own tensors (prediction,
+    dpred, grad_pred); one entry per distinct place."""
+    B, H, W, C = key
+    wins = pixel_windows(B, H, W, C, BOUNDARIES_32)
+    seen = {x[1:] for x in wins}
+    more = [("mask" + x[0],) + x[1:] for x in pixel_windows(B, H, W, 1, BOUNDARIES_32)[1:-1]]
+    if level is not None:
+        h, w = level
+        sh, sw = H // h, W // w
+        more += [("pred" + t, n, sh * y0, sh * y0 + WIN) + _span(sw * x0, WIN, W)
+                 for t, n, y0, _, x0, _ in pixel_windows(B, h, w, C, BOUNDARIES_32)[1:-1]]
+    for x in more:
+        if x[1:] not in seen:
+            seen.add(x[1:])
+            wins.insert(-1, x)
+    return wins
+
+
+def aligned_region(win, tile, H, W):
+    """The window's enclosing region of whole tile x tile blocks -> (tag, n, y0, y1, x0, x1)."""
+    tag, n, y0, y1, x0, x1 = win
+    up = lambda v, lim: min(-(-v // tile) * tile, lim)
+    return (tag, n, y0 // tile * tile, up(y1, H), x0 // tile * tile, up(x1, W))
+
+
+def region_around(win, reg, at, H, W):
+    """Where a window's aligned region lies when the window itself is found at `at` = (n, y0, y1, x0, x1)."""
+    n, y, _, x, _ = at
+    hh, ww = reg[3] - reg[2], reg[5] - reg[4]
+    y = min(max(y - (win[2] - reg[2]), 0), H - hh)
+    x = min(max(x - (win[4] - reg[4]), 0), W - ww)
+    return (n, y, y + hh, x, x + ww)
+
+
+def masked_area_level_ref(gt_crop, ok_crop, sh, sw, fscale):
+    """The masked FlowMseLossV2 level of a crop in float64: the mean over each sh x sw block's valid pixels times the flow
+    scale, 0 where the block has none -> (gl (1,hh,ww,2), m (1,hh,ww) bool)."""
+    _, hh, ww, c = gt_crop.shape
+    ok = ok_crop.reshape(1, hh, ww) != 0
+    x = torch.where(ok[..., None], gt_crop.double(), torch.zeros((), dtype=torch.float64))
+    s = x.reshape(1, hh // sh, sh, ww // sw, sw, c).sum((2, 4))
+    n = ok.reshape(1, hh // sh, sh, ww // sw, sw).sum((2, 4))
+    return s / n.clamp(min=1)[..., None] * fscale, n >= 1
+
+
+def masked_window_ref(kind, crops, hw, scale=1.0):
+    """loss_window_ref for a masked loss: crops = [(gl, m, p)] with m the level's validity on the window.  An invalid
+    pixel is given a zero residual, whose term and gradient are 0 in both kinds, and the mean runs over the count
+    -> (scale * loss, [d / d p], count)."""
+    count = sum(int(m.sum()) for _, m, _ in crops)
+    fed = [(gl, torch.where(m[..., None], p.double(), gl.double())) for gl, m, p in crops]
+    value, grads = loss_window_ref(kind, fed, max(count, 1), hw, scale)
+    return value, grads, count
+
+
+def masked_loss_controls(kind, crops, moved, hw):
+    """loss_controls for a masked loss -> [(what, change / bound)], the change being the larger of what the two asserted
+    quantities show: the loss (relative, LOSS_REL) and grad_pred on the windows (LOSS_REL of each window's largest).  The
+    loss is a mean over the valid pixels, so a window left out takes its pixels out of the count as well and may leave
+    the mean nearly where it was; its own gradient then vanishes, and every other window's grows with the count."""
+    rv, rg, _ = masked_window_ref(kind, crops, hw)
+
+    def change(alt_crops, at):
+        """at: the positions of alt_crops' windows in crops."""
+        av, ag, _ = masked_window_ref(kind, alt_crops, hw)
+        grads = dict(zip(at, ag))
+        moved_by = [float(((grads[k] if k in grads else torch.zeros_like(g)) - g).abs().max()) / (LOSS_REL * float(g.abs().max()))
+                    for k, g in enumerate(rg)]
+        return max([abs(float(av - rv)) / (LOSS_REL * abs(float(rv)))] + moved_by)
+
+    every = list(range(len(crops)))
+    out = [("without window %d" % k, change(crops[:k] + crops[k + 1:], every[:k] + every[k + 1:])) for k in every]
+    for what, k, gl in moved:
+        out.append((what, change(crops[:k] + [(gl, crops[k][1], crops[k][2])] + crops[k + 1:], every)))
+    return out
+
+
+def masked_loss_planned_bytes(key, levels, held):
+    """The ground truth, its mask, and `held` fp32 tensors per level at the fullest moment (prediction, dpred, grad_pred;
+    a fourth where a second gradient or the level's ground truth is held beside them) with a byte a level pixel."""
+    B, H, W, C = key
+    return 4 * B * H * W * C + B * H * W + sum((4 * held * C + 1) * B * h * w for h, w in levels)
+
+
+def _fill_grid(t, gen, lim=16):
+    """Multiples of 1/16 in [-lim/16, lim/16] drawn in place, an image at a time (no temporary of the tensor's size)."""
+    for n in range(t.shape[0]):
+        t[n].random_(-lim, lim + 1, generator=gen).mul_(1 / 16)
+    return t
+
+
+def _nonzero(t, rows=2048):
+    """count_nonzero of a (B,H,...) tensor, a block of rows at a time."""
+    return sum(int(torch.count_nonzero(t[n, y:y + rows])) for n in range(t.shape[0]) for y in range(0, t.shape[1], rows))
+
+
+def _cut3(t, n, y0, y1, x0, x1):
+    return t.detach()[n:n + 1, y0:y1, x0:x1].cpu()
+
+
+def _masked_run(kind_id, gt, preds, valid, scale):
+    """ops.masked_loss through autograd -> (per-level losses, counts, [grad of each prediction])."""
+    xs = [p.detach().requires_grad_() for p in preds]
+    losses, counts = ops.masked_loss(kind_id, gt, xs, valid, p0=LOSS_DELTA)
+    (losses * scale).sum().backward()
+    return losses.detach(), counts, [x.grad for x in xs]
+
+
+def _masked_level_crops(gt, valid, pred, regs, factor, fscale):
+    """[(gl, m, p)] of one level on the windows' regions, from crops of the device tensors."""
+    sh, sw = factor
+    out = []
+    for _, n, y0, y1, x0, x1 in regs:
+        gl, m = masked_area_level_ref(_cut(gt, n, y0, y1, x0, x1), _cut3(valid, n, y0, y1, x0, x1), sh, sw, fscale)
+        out.append((gl, m, _cut(pred, n, y0 // sh, y1 // sh, x0 // sw, x1 // sw)))
+    return out
+
+
+def _check_masked_level(what, crops, regs, factor, hw, value, count, grad, gt_out, valid_out, kind, scale):
+    """One level of a masked loss against float64 from the windows' crops: the loss and grad_pred within LOSS_REL, the
+    count and the level mask exact, the level ground truth within GT_REL, and over the whole tensors nothing but the
+    windows: grad_pred and gt_out exactly 0 elsewhere, valid_out 0."""
+    sh, sw = factor
+    rv, rg, rcount = masked_window_ref(kind, crops, hw, scale)
+    assert int(count) == rcount > 0, (what, int(count), rcount)
+    worst = {"loss": _rel_check(value * scale, rv, what + " loss")}
+    level_reg = lambda r: (r[1], r[2] // sh, r[3] // sh, r[4] // sw, r[5] // sw)
+    worst["grad_pred"] = max(_rel_check(_cut(grad, *level_reg(r)), g, "%s grad_pred %s" % (what, r[0])) for r, g in zip(regs, rg))
+    inside = sum(int(torch.count_nonzero(_cut(grad, *level_reg(r)))) for r in regs)
+    assert 0 < inside == _nonzero(grad), (what, inside)                     # exactly 0 outside the windows
+    for r, (gl, m, _) in zip(regs, crops):
+        assert not _cut(grad, *level_reg(r))[~m].any(), (what, r[0])         # and at the windows' own invalid pixels
+    if gt_out is not None:
+        top = max(float(gl.abs().max()) for gl, _, _ in crops)
+        d = max(float((_cut(gt_out, *level_reg(r)).double() - gl).abs().max()) for r, (gl, _, _) in zip(regs, crops))
+        print("{} gt_out: max|d| = {:.3e}, bound {:.3e}".format(what, d, GT_REL * top))
+        assert d <= GT_REL * top, (what, d, top)
+        worst["gt_out"] = d / top
+        assert sum(int(torch.count_nonzero(_cut(gt_out, *level_reg(r)))) for r in regs) == _nonzero(gt_out)
+        for r, (_, m, _) in zip(regs, crops):
+            assert torch.equal(_cut3(valid_out, *level_reg(r)) != 0, m), (what, r[0])
+        assert _nonzero(valid_out) == rcount and valid_out.dtype == torch.uint8
+    return worst
+
+
+def test_masked_loss_tile_path(arena):
+    """FlowMseLossV2 over the valid pixels on masked_loss_tile_kernel at 2.152 G ground-truth pixels with levels at
+    factors (2,2) and (32,32): the mask's byte index passes 2^31, the ground truth's element index 2^29 .. 2^32, the
+    level tensors' 2^29 and 2^30.  Ground truth and predictions are random on the 1/16 grid everywhere; validity is
+    zero except WIN x WIN windows at the start, behind every boundary and in the last corner.  Once with the mask;
+    once more on the same buffers with valid=None and NaN outside the windows, which must give the same bits.
+    Measured: peak 34.14 GiB (planned 34.64), 0.6 s; of the bounds, losses 0.0005, grad_pred 0.013, gt_out 0.017; the
+    controls moved the loss or grad_pred by 190 .. 100000 bounds."""
+    key = CASES["masked_loss"]
+    B, H, W, C = key
+    hip = ops._hip
+    factors = [(2, 2), (32, 32)]
+    levels = [(H // sh, W // sw) for sh, sw in factors]
+    planned = masked_loss_planned_bytes(key, levels, 4)
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(18)
+    a = arena
+    assert ops.masked_loss_kernel(hip.LOSS_FLOW_MSE_V2, B, H, W, levels) == "masked_loss_tile_kernel"
+    a["gt"] = gt = _fill_grid(torch.empty((B, H, W, C), device=DEV), gen)
+    assert B * H * W > 1 << 31 and gt.numel() > 1 << 32 and gt.data_ptr() % 16 == 0
+    a["valid"] = valid = torch.zeros((B, H, W), dtype=torch.uint8, device=DEV)
+    wins = masked_loss_windows(key, levels[0])
+    regs = [aligned_region(x, 32, H, W) for x in wins]
+    for _, n, y0, y1, x0, x1 in wins:
+        valid[n, y0:y1, x0:x1] = 1
+    assert _nonzero(valid) == len(wins) * WIN * WIN
+    a["preds"] = preds = [_fill_grid(torch.empty((B, h, w, C), device=DEV), gen) for h, w in levels]
+    crops = [_masked_level_crops(gt, valid, p, regs, f, 1.0 / f[0]) for p, f in zip(preds, factors)]
+    moved = [[], []]
+    for k, (win, reg) in enumerate(zip(wins, regs)):
+        for mod, at in wrapped_pixel_regions(B, H, W, C, win):
+            at = region_around(win, reg, at, H, W)
+            for l, f in enumerate(factors):
+                gl = masked_area_level_ref(_cut(gt, *at), _cut3(valid, *reg[1:]), f[0], f[1], 1.0 / f[0])[0]
+                moved[l].append(("window %d (%s) gt read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k, gl))
+        for mod, at in wrapped_pixel_regions(B, H, W, 1, win, 1):               # the mask at a wrapped byte offset: zeros
+            assert not _cut3(valid, *at).any(), (win, mod, at)
+    losses, counts, grads = _masked_run(hip.LOSS_FLOW_MSE_V2, gt, preds, valid, 7.0)
+    a["grads"] = grads
+    _, counts2, _, gt_out, valid_out = ops.masked_loss_fwd(hip.LOSS_FLOW_MSE_V2, gt, None, valid, p0=LOSS_DELTA,
+                                                           want_gt=True, want_valid=True, shapes=levels)
+    assert torch.equal(counts, counts2)
+    worst, controls = {}, []
+    for l, f in enumerate(factors):
+        w_ = _check_masked_level("masked tile level %d" % l, crops[l], regs, f, levels[l], losses[l], counts[l], grads[l],
+                                 gt_out[l], valid_out[l], "v2", 7.0)
+        worst.update({"%s[%d]" % (k, l): v for k, v in w_.items()})
+        controls += masked_loss_controls("v2", crops[l], moved[l], levels[l])
+    assert len(controls) >= 2 * (len(wins) + 2) and min(r for _, r in controls) >= 100.0, controls
+    assert len(wins) * (WIN // 2) ** 2 <= int(counts[0]) <= len(wins) * (WIN // 2 + 1) ** 2 and len(wins) <= int(counts[1]) <= 4 * len(wins)
+    del gt_out, valid_out
+    # the same validity by NaN: no mask, NaN outside the windows, on the same buffers
+    for n in range(B):
+        gt[n].masked_fill_((valid[n] == 0).unsqueeze(-1), float("nan"))
+    losses_b, counts_b, grads_b = _masked_run(hip.LOSS_FLOW_MSE_V2, gt, preds, None, 7.0)
+    assert torch.equal(losses_b, losses) and torch.equal(counts_b, counts)
+    for l in range(len(levels)):
+        assert all(torch.equal(grads_b[l][n], grads[l][n]) for n in range(B)), l
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("masked loss tile: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
+        peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+def test_masked_loss_pixel_paths(arena):
+    """masked_loss_pixel_kernel at 1.075 G pixels with one full-resolution level: the area walk (FlowMseLossV2, 1 x 1
+    blocks) and the bilinear walk with renormalised corners (FlowMseLoss; the sample points are the pixel centres), the
+    mask read by pixel index past 2^30 bytes, valid_out written there, and masked_loss_bwd_kernel's scalar form at
+    2.15 G elements (no multiple of 4).  The window oracle of test_masked_loss_tile_path.
+    Measured: peak 33.06 GiB (planned 34.06), 0.1 s; of the bound, losses 0.0016, grad_pred 0.012; gt_out exact."""
+    key = CASES["masked_loss_pixel"]
+    B, H, W, C = key
+    hip = ops._hip
+    planned = masked_loss_planned_bytes(key, [(H, W)], 3)
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(19)
+    a = arena
+    a["gt"] = gt = _fill_grid(torch.empty((B, H, W, C), device=DEV), gen)
+    assert B * H * W > 1 << 30 and gt.numel() > 1 << 31 and gt.numel() % 4 == 2
+    a["valid"] = valid = torch.zeros((B, H, W), dtype=torch.uint8, device=DEV)
+    wins = masked_loss_windows(key)
+    for _, n, y0, y1, x0, x1 in wins:
+        valid[n, y0:y1, x0:x1] = 1
+    a["pred"] = pred = _fill_grid(torch.empty((B, H, W, C), device=DEV), gen)
+    crops = _masked_level_crops(gt, valid, pred, wins, (1, 1), 1.0)
+    assert all(bool(m.all()) for _, m, _ in crops)
+    moved = []
+    for k, reg in enumerate(wins):
+        for mod, at in wrapped_pixel_regions(B, H, W, C, reg):
+            moved.append(("window %d (%s) gt read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k, _cut(gt, *at).double()))
+        for mod, at in wrapped_pixel_regions(B, H, W, 1, reg, 1):
+            assert not _cut3(valid, *at).any(), (reg, mod, at)
+    worst = {}
+    for name, kind_id, kind in (("masked v2 pixel", hip.LOSS_FLOW_MSE_V2, "v2"), ("masked bilinear", hip.LOSS_FLOW_MSE, "norm")):
+        assert ops.masked_loss_kernel(kind_id, B, H, W, [(H, W)]) == "masked_loss_pixel_kernel"
+        losses, counts, grads = _masked_run(kind_id, gt, [pred], valid, 7.0)
+        assert grads[0].numel() % 4 != 0                                      # masked_loss_bwd_kernel's scalar form
+        w_ = _check_masked_level(name, crops, wins, (1, 1), (H, W), losses[0], counts[0], grads[0], None, None, kind, 7.0)
+        del grads
+        _, _, _, gt_out, valid_out = ops.masked_loss_fwd(kind_id, gt, None, valid, p0=LOSS_DELTA, want_gt=True,
+                                                         want_valid=True, shapes=[(H, W)])
+        for r, (gl, m, _) in zip(wins, crops):
+            assert torch.equal(_cut(gt_out[0], *r[1:]).double(), gl) and torch.equal(_cut3(valid_out[0], *r[1:]) != 0, m)
+        assert _nonzero(valid_out[0]) == int(counts[0]) == len(wins) * WIN * WIN
+        assert sum(int(torch.count_nonzero(_cut(gt_out[0], *r[1:]))) for r in wins) == _nonzero(gt_out[0])
+        del gt_out, valid_out
+        worst.update({"%s %s" % (name, k): v for k, v in w_.items()})
+        controls = masked_loss_controls(kind, crops, moved, (H, W))
+        assert len(controls) >= len(wins) + 2 and min(r for _, r in controls) >= 100.0, controls
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("masked loss pixel: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
+        peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- flow metrics: truth and prediction past 2^31 elements, the masks past 2^30 bytes --------------------------------
+# Per-image figures, so both oracles apply.  (a): an image of the batched launch is the image run alone bit for bit (which
+# lane sums which pixel depends on the position inside the image only), and the state is that of the B calls in order;
+# one image stays under 2^29 floats.  (c): the prediction equals the truth outside planted windows and the truth there is
+# slower than 6 px, so a valid pixel outside the windows has e = 0, angle 0, and falls into the first speed bin: the 15
+# sums follow in float64 from the windows' crops and from the masks' counts (torch.count_nonzero, an image at a time).
+# The windows' flows come from seeds on the CPU (flow_window_data), so that tests/test_large_offsets_cpu.py can hold
+# them away from every threshold.  Bounds: tests/test_flow_quality_cpu.py's (count ratios 1 ulp, means 1e-4 px, aae 1e-3
+# degrees) and, since a mean over 150 M pixels of a few hundred non-zero terms is far below those, LOSS_REL relative on
+# every mean and on the state's sums, which are such sums.
+def flow_window_data(k, half=False):
+    """(truth, pred) of window k, numpy (1,WIN,WIN,2): a full period of a 45 px wave (all three speed bins) plus texture,
+    the prediction 0.3 px (even k) or 4 px (odd k) off, in fp32 or fp16 values; no pixel within MARGIN of a threshold."""
+    t, p = make_flows(300 + k, (WIN, WIN), sigmas=((0.3, 4.0)[k % 2],), amplitude=(45.0,), batch=1)
+    return away_from_thresholds(t, p, np.float16 if half else np.float32)
+
+
+def flow_window_oracle(B, pixels, planted, n_valid, n_occ):
+    """float64 (scores {field: [B]}, sums [B, 15]) of a batch whose prediction equals its slow (< 10 px) truth outside
+    the windows: planted = [(image, truth, pred, valid, occluded)] crops, n_valid / n_occ [B] the images' counts of
+    valid and of valid occluded pixels."""
+    sums = np.zeros((B, 15))
+    for n, t, p, v, o in planted:
+        sums[n] += ref_sums(t, p, v, o)[0]
+    rest, rest_occ = np.asarray(n_valid, np.float64) - sums[:, 0], np.asarray(n_occ, np.float64) - sums[:, 7]
+    assert (rest >= 0).all() and (rest_occ >= 0).all()
+    for i in (0, 4, 5, 6, 9):                     # valid; e < each accuracy threshold; the first speed bin
+        sums[:, i] += rest
+    sums[:, 7] += rest_occ
+    return ref_scores(sums, pixels), sums
+
+
+def flow_controls(B, pixels, planted, moved, n_valid, n_occ):
+    """[(what, |change of its image's epe| / LOSS_REL of it)]: every window left out in turn (the prediction is the truth
+    there); every moved = (what, window index, the truth as a wrapped offset finds it) in its window's place."""
+    ref = flow_window_oracle(B, pixels, planted, n_valid, n_occ)[0]["epe"]
+    out = []
+    for k, (n, t, p, v, o) in enumerate(planted):
+        alt = flow_window_oracle(B, pixels, planted[:k] + [(n, t, t, v, o)] + planted[k + 1:], n_valid, n_occ)[0]["epe"]
+        out.append(("without window %d" % k, abs(alt[n] - ref[n]) / (LOSS_REL * ref[n])))
+    for what, k, t2 in moved:
+        n, t, p, v, o = planted[k]
+        alt = flow_window_oracle(B, pixels, planted[:k] + [(n, t2, p, v, o)] + planted[k + 1:], n_valid, n_occ)[0]["epe"]
+        out.append((what, abs(alt[n] - ref[n]) / (LOSS_REL * ref[n])))
+    return out
+
+
+def flow_quality_planned_bytes(key):
+    """The fuller of the two phases: the channels-last run (truth, fp32 prediction, two masks) and the change of layout
+    (truth in both layouts, the fp16 prediction, two masks)."""
+    B, H, W, C = key
+    flow = 4 * B * H * W * C
+    return max(2 * flow, 2 * flow + flow // 2) + 2 * B * H * W
+
+
+def _check_flow_scores(what, got, want):
+    """check()'s bounds, and LOSS_REL relative on every mean (a mean that is 0 in float64 must be 0)."""
+    err = check(what, got, want)
+    worst = 0.0
+    for k in EPE_FIELDS + ("aae",):
+        g, w = getattr(got, k).double().cpu().numpy(), want[k]
+        keep = ~np.isnan(w)
+        assert (np.abs(g[keep] - w[keep]) <= LOSS_REL * np.abs(w[keep])).all(), (what, k, g, w)
+        nz = keep & (w != 0)
+        worst = max([worst] + list(np.abs(g[nz] - w[nz]) / np.abs(w[nz])))
+    return worst, max(err[k] for k in COUNT_FIELDS)
+
+
+def _flow_run(truth, pred, valid, occluded, data_format):
+    """The batched launch with a state, then image by image on another state -> (scores, state); asserts oracle (a)."""
+    B = truth.shape[0]
+    state, one_state = (torch.zeros(17, dtype=torch.float64, device=DEV) for _ in range(2))
+    res = metrics.flow_quality(truth, pred, valid=valid, occluded=occluded, data_format=data_format, state=state)
+    for n in range(B):
+        s = slice(n, n + 1)
+        one = metrics.flow_quality(truth[s], pred[s], valid=valid[s], occluded=occluded[s], data_format=data_format,
+                                   state=one_state)
+        assert all(torch.equal(a[s].view(torch.int32), b.view(torch.int32)) for a, b in zip(res, one)), n
+    assert torch.equal(state, one_state), (state - one_state).tolist()
+    return res, state
+
+
+def test_flow_quality(arena):
+    """flow_quality_tile_kernel / flow_quality_fold_kernel at 1.074 G pixels in five images: `img + p` of truth and of an
+    fp32 prediction passes 2^29, 2^30 and 2^31 elements (as float2: byte 2^31 and 2^32 of an 8-byte pixel at pixel 2^28
+    and 2^29), the masks' 2^29 and 2^30 bytes; then channels-first with an fp16 prediction, where `2 * img + p + hw`,
+    the v plane, passes 2^31 in the last image.  Oracles (a) and (c) above, 52,449 chunks an image (820 trips of the fold's lanes).
+    Measured: peak 22.01 GiB (planned 22.01), 2.1 s; the means 2.7e-7 relative (0.027 of LOSS_REL), 1.7e-7 px (0.002 of
+    the 1e-4 bound), aae 3.5e-13 degrees, count ratios at most 0.50 ulp; the controls moved an image's epe by 7100 .. 100000
+    bounds."""
+    key = CASES["flow_quality"]
+    B, H, W, C = key
+    planned = flow_quality_planned_bytes(key)
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(20)
+    a = arena
+    assert ops.flow_quality_kernel(B, H, W) == "flow_quality_tile_kernel"
+    a["truth"] = truth = _fill_grid(torch.empty((B, H, W, C), device=DEV), gen, lim=64)        # |u|, |v| <= 4: m < 6
+    assert truth.numel() > 1 << 31 and H * W * C < 1 << 29
+    a["valid"] = valid = torch.empty((B, H, W), dtype=torch.uint8, device=DEV)
+    a["occluded"] = occluded = torch.empty((B, H, W), dtype=torch.uint8, device=DEV)
+    for n in range(B):
+        valid[n].random_(0, 10, generator=gen).lt_(7)                      # 70 % valid, 30 % occluded, independent
+        occluded[n].random_(0, 10, generator=gen).lt_(3)
+    wins = pixel_windows(B, H, W, C)
+    assert all(x[1:] in {y[1:] for y in wins} for x in pixel_windows(B, H, W, 1))       # the masks' boundaries: the same places
+    n_valid = [int(torch.count_nonzero(valid[n])) for n in range(B)]
+    n_occ = [int(torch.count_nonzero(valid[n] & occluded[n])) for n in range(B)]
+    a["pred"] = pred = truth.clone()
+    worst = {}
+
+    def plant(half, channels_first):
+        """The windows' flows into truth and the prediction at hand -> (planted, moved)."""
+        planted, moved = [], []
+        for k, reg in enumerate(wins):
+            n, y0, y1, x0, x1 = reg[1:]
+            for mod, at in ([] if channels_first else wrapped_pixel_regions(B, H, W, C, reg)):
+                moved.append(("window %d (%s) truth read mod 2^%d bytes" % (k, reg[0], mod.bit_length() - 1), k,
+                              _cut(a["truth"], *at).numpy()))
+            t, p = flow_window_data(k, half)
+            for name, crop in (("truth", t), ("pred", p)):
+                crop = torch.from_numpy(crop[0]).to(DEV)
+                if channels_first:
+                    a[name][n, :, y0:y1, x0:x1] = crop.permute(2, 0, 1)
+                else:
+                    a[name][n, y0:y1, x0:x1, :] = crop
+            planted.append((n, t, p, _cut3(valid, *reg[1:]).numpy(), _cut3(occluded, *reg[1:]).numpy()))
+        return planted, moved
+
+    for tag, half, fmt in (("f32 channels_last", False, "channels_last"), ("f16 channels_first", True, "channels_first")):
+        if half:
+            a["pred"] = pred = torch.empty((B, C, H, W), dtype=torch.float16, device=DEV).copy_(truth.permute(0, 3, 1, 2))
+            a["truth"] = truth = truth.permute(0, 3, 1, 2).contiguous()        # the old layouts are released here
+            assert truth.shape == (B, C, H, W) and truth.numel() > 1 << 31           # `o + hw` of the last image's v plane
+        planted, moved = plant(half, half)
+        res, state = _flow_run(truth, pred, valid, occluded, fmt)
+        want, sums = flow_window_oracle(B, H * W, planted, n_valid, n_occ)
+        worst[tag] = _check_flow_scores("hip large " + tag, res, want)
+        total, st = sums.sum(axis=0), state.cpu().numpy()
+        assert st[15] == B and st[16] == float(B) * H * W
+        for i in range(15):
+            if i in (1, 2, 8, 10, 12, 14):
+                assert abs(st[i] - total[i]) <= LOSS_REL * total[i], (tag, i, st[i], total[i])
+            else:
+                assert st[i] == total[i], (tag, i, st[i], total[i])               # counts
+        assert float(res.epe[3]) == 0.0 and float(res.acc1[3]) == 1.0 and float(res.aae[3]) == 0.0    # no window in image 3
+        controls = flow_controls(B, H * W, planted, moved, n_valid, n_occ)
+        assert len(controls) >= len(wins) + (0 if half else 2) and min(r for _, r in controls) >= 100.0, controls
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("flow quality: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst (relative mean, count ulp) {}, controls {:.0f} .. "
+          "{:.0f} bounds".format(peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
     assert planned <= 48 * GIB
     assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)

@@ -8,7 +8,9 @@ gradient; fp16 gradients F16_EPS |g| + 1e-5 max + 2^-24; ground truth 1e-6 of th
 exact; gradients at invalid level pixels exactly 0.
 Measured on an MI355X, the worst case of the module as a share of its bound: losses 0.015, fp32 gradients 0.038, fp16
 gradients 0.97 (the half ulp of fp16 itself), ground truth 0.16; all valid against loss.multiscale: losses 6e-8 relative,
-gradients 2.2e-7 of the level's largest (bound 2e-5).  test_zz_report_the_observed_errors prints them (pytest -s)."""
+gradients 2.2e-7 of the level's largest (bound 2e-5).  test_zz_report_the_observed_errors prints them (pytest -s).
+B = 2 and factors 2 / 4 / 8 throughout: the scalar backward, sum plans with unequal steps and the pixel walks' further trips
+run in tests/test_gpu_eval_scale.py, a mask past 2^31 bytes in tests/test_gpu_large_offsets.py."""
 import os
 import sys
 
@@ -235,6 +237,32 @@ def test_views_off_the_grid_are_copied():
     assert off_gt.data_ptr() % 16 == 8 and off_mask.data_ptr() % 4 == 1
     got = loss.multiscale_masked(obj, off_gt, xs, off_mask)
     assert torch.equal(got[1], want[1]) and torch.equal(got[2], want[2])
+
+
+@pytest.mark.parametrize("data_format", ["channels_last", "channels_first"])
+@pytest.mark.parametrize("byte", [2, 128, 255])
+def test_any_nonzero_mask_byte_is_valid(cases, byte, data_format):
+    """include/qpwc_masked_loss.h: a mask byte allows its pixel where it is nonzero.  The tile kernel unpacks the bytes
+    out of a 16-bit load (channels-last) or a 32-bit load (channels-first) with shifts and & 0xff, the pixel kernel
+    compares the byte: uint8 masks holding 2, 128 or 255 where the case's mask holds 1 give the bits of the mask of
+    ones -- losses, counts, gradients, ground truths and level masks (which stay 0 / 1)."""
+    for kind in ("v2", "mse"):                                   # the tile kernel, the pixel kernel
+        case = cases[("pyramid_mask30", kind)]
+        obj = make_loss(kind, data_format)
+        gt, preds, valid = _tensors(case, data_format, torch.float32)
+        shapes = [tuple(p.shape[1:3]) for p in case["preds"]]
+        runs = []
+        for mask in (valid.to(DEV), valid.to(DEV).to(torch.uint8) * byte):
+            xs = [p.to(DEV).requires_grad_() for p in preds]
+            total, per, counts = loss.multiscale_masked(obj, gt.to(DEV), xs, mask)
+            total.backward()
+            gts, masks = loss.masked_ground_truth(obj, gt.to(DEV), shapes, mask)
+            runs.append((per.detach(), counts, [x.grad for x in xs], gts, masks))
+        assert int(mask.max()) == byte and 0 < int(runs[0][1].min())
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+        for k in (2, 3, 4):
+            assert all(torch.equal(a, b) for a, b in zip(runs[0][k], runs[1][k])), (kind, k)
+        assert all(int(m.max()) == 1 for m in runs[1][4])
 
 
 def test_two_runs_and_another_level_order_give_the_same_bits(cases):

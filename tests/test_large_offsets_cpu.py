@@ -3,7 +3,10 @@
 GPU test relies on, and is still admitted by the validators; the workspace regions cross what DESIGN.md 4.17 says
 they cross; the planned device memory stays under 48 GiB; the float64 restatement on crops and windows agrees with
 the fp32 torch composition within the bounds the GPU test uses; the negative controls move the window sums by at
-least 100 bounds; and the ctypes table carries every size that can pass 2^31 as a 64-bit integer.
+least 100 bounds; and the ctypes table carries every size that can pass 2^31 as a 64-bit integer.  For the masked
+losses and the flow metrics, whose masks are indexed by byte, also: the windows lie behind the masks' byte boundaries
+and the ground truth's 2^32nd element, a mask read at a wrapped byte offset meets no window, and the windows' flows
+keep the metrics' thresholds at a distance.
 
 The plans are restated from the constants read out of the kernel sources (tests/test_conv_grad_cpu.py::_plan) and
 compared with the library's own host functions, so a changed plan constant that pulls a region back under a boundary
@@ -13,6 +16,7 @@ import os
 import re
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -881,3 +885,225 @@ def test_loss_negative_controls(name, kind):
     controls = lo.loss_controls(kind, crops, moved, B * h * w, (h, w))
     assert len(controls) == len(crops) + len(moved) and len(moved) >= 2
     assert min(r for _, r in controls) >= 100.0, controls
+
+
+# ---- masked losses and flow metrics: byte-indexed masks, 2^32 elements -------------------------------------------------
+P32 = 1 << 32
+
+
+def _disjoint(a, b):
+    return a[1] != b[1] or a[3] <= b[2] or b[3] <= a[2] or a[5] <= b[4] or b[5] <= a[4]
+
+
+def test_masked_loss_cases_cross_what_they_claim(hip_lib):
+    from qpwcnet_amd import _hip, ops
+    from test_eval_scale_cpu import ML
+    I = ctypes.c_int
+    assert lo.BOUNDARIES_32 == (P29, P30, P31, P32)
+    # the tile case: the smallest 32-multiple square at B = 3 whose pixel count passes 2^31
+    key = lo.CASES["masked_loss"]
+    B, H, W, C = key
+    assert B == 3 and C == 2 and H % ML["kLossTile"] == 0 and W % ML["kLossTile"] == 0
+    assert B * H * W > P31 > B * (H - 32) * (W - 32)                             # the mask's byte index passes 2^31
+    assert lo.crossed(B * H * W * C, lo.BOUNDARIES_32) == [P29, P30, P31, P32]   # the ground truth's element index
+    assert [lo.locate(b, H, W, C)[0] for b in lo.BOUNDARIES_32] == [0, 0, 1, 2]
+    assert [lo.locate(b, H, W, 1)[0] for b in (P29, P30, P31)] == [0, 1, 2]
+    factors = [(2, 2), (32, 32)]
+    levels = [(H // sh, W // sw) for sh, sw in factors]
+    assert lo.crossed(B * levels[0][0] * levels[0][1] * C, lo.BOUNDARIES_32) == [P29, P30]
+    assert H * W <= 2 ** 31 - 1 and B * (H // 32) * (W // 32) <= 2 ** 31 - 1    # what loss_check_shapes caps: not B * H * W
+    hs, ws_ = (I * 2)(*[h for h, _ in levels]), (I * 2)(*[w for _, w in levels])
+    assert hip_lib.qpwc_masked_loss_workspace_floats(_hip.LOSS_FLOW_MSE_V2, B, H, W, C, hs, ws_, 2) == 2 * 2 * ML["kLossTileBlocks"]
+    assert ops.masked_loss_kernel(_hip.LOSS_FLOW_MSE_V2, B, H, W, levels) == "masked_loss_tile_kernel"
+    tiles = B * (H // 32) * (W // 32)
+    assert tiles > 1000 * ML["kLossTileBlocks"] and tiles % ML["kLossTileBlocks"]
+    assert (B * levels[0][0] * levels[0][1] * C) % 4 == 0                        # the float4 backward at level 0
+    wins = lo.masked_loss_windows(key, levels[0])
+    assert [x[0] for x in wins] == ["first", ">2^29", ">2^30", ">2^31", ">2^32", "pred>2^29", "pred>2^30", "last"]
+    regs = [lo.aligned_region(x, 32, H, W) for x in wins]
+    assert all(_disjoint(a, b) for i, a in enumerate(regs) for b in regs[i + 1:])
+    for x, r in zip(wins, regs):
+        assert r[2] % 32 == 0 and r[4] % 32 == 0 and (r[3] - r[2]) % 32 == 0 and (r[5] - r[4]) % 32 == 0
+        assert r[2] <= x[2] and x[3] <= r[3] and r[4] <= x[4] and x[5] <= r[5] and r[3] <= H and r[5] <= W
+    first = lambda x, rows, cols, ch, f=1: ((x[1] * rows + x[2] // f) * cols + x[4] // f) * ch
+    for b, x in zip(lo.BOUNDARIES_32, wins[1:5]):                    # behind each boundary of the ground truth ...
+        assert b < first(x, H, W, C) < b + 2 * W * C
+    for b, x in zip((P29, P30, P31), wins[2:5]):                     # ... which is where the mask's byte boundaries lie
+        assert b < first(x, H, W, 1) < b + 2 * W
+    for b, x in zip((P29, P30), wins[5:7]):                          # and of the level's prediction, dpred and grad_pred
+        assert b < first(x, levels[0][0], levels[0][1], C, 2) < b + 2 * levels[0][1] * C
+    # a wrapped read: of the ground truth, other values inside the tensor; of the mask, no window
+    moved = [lo.wrapped_pixel_regions(B, H, W, C, x) for x in wins]
+    assert {mod for m in moved for mod, _ in m} == {1 << 31, 1 << 32} and all(m for m in moved[2:])
+    mask_moved = [lo.wrapped_pixel_regions(B, H, W, 1, x, 1) for x in wins]
+    assert any(m for m in mask_moved) and mask_moved[0] == []
+    for m in mask_moved:
+        for _, at in m:
+            assert all(_disjoint(("at",) + at, x) for x in wins), at
+    planned = lo.masked_loss_planned_bytes(key, levels, 4)
+    assert 4 * B * H * W * C + B * H * W + 4 * 4 * B * levels[0][0] * levels[0][1] * C <= planned <= 48 * lo.GIB
+    assert 36e9 < planned < 38e9 and 1.10 * planned <= 64 * lo.GIB
+    # the pixel case: the odd "epe" shape with one full-resolution level
+    key = lo.CASES["masked_loss_pixel"]
+    assert key == lo.CASES["epe"]
+    B, H, W, C = key
+    assert lo.crossed(B * H * W * C, lo.BOUNDARIES_32) == [P29, P30, P31] and lo.crossed(B * H * W, lo.BOUNDARIES_32) == [P29, P30]
+    assert (B * H * W * C) % 4 == 2 and B * H * W * C > ML["kLossBwdBlocks"] * ML["kLossThreads"]
+    for kind in (_hip.LOSS_FLOW_MSE_V2, _hip.LOSS_FLOW_MSE):
+        assert ops.masked_loss_kernel(kind, B, H, W, [(H, W)]) == "masked_loss_pixel_kernel"
+    assert B * H * W > 4096 * ML["kLossPixBlocks"] * ML["kLossThreads"]          # thousands of trips of the pixel walk
+    wins = lo.masked_loss_windows(key)
+    assert [x[0] for x in wins] == ["first", ">2^29", ">2^30", ">2^31", "last"]
+    assert all(_disjoint(a, b) for i, a in enumerate(wins) for b in wins[i + 1:])
+    for b, x in zip((P29, P30), wins[2:4]):
+        assert b < first(x, H, W, 1) < b + 2 * W
+    for x in wins:
+        for _, at in lo.wrapped_pixel_regions(B, H, W, 1, x, 1):
+            assert all(_disjoint(("at",) + at, y) for y in wins), at
+    assert lo.masked_loss_planned_bytes(key, [(H, W)], 3) <= 48 * lo.GIB
+    # the sizes that pass 2^31 travel as 64-bit integers
+    protos = {name: (ret, params) for name, ret, params in parse_header(os.path.join(os.path.dirname(CSRC), "..", "include",
+                                                                                     "qpwc_masked_loss.h"))}
+    assert protos["qpwc_masked_loss_bwd"][1].count("const int64_t*") == 1
+    assert any(getattr(t, "_type_", None) is ctypes.c_int64 for t in _hip.MASKED_LOSS_PROTOTYPES["qpwc_masked_loss_bwd"][1])
+
+
+@pytest.mark.parametrize("kind", ["v2", "norm"])
+def test_masked_window_reference_is_the_masked_loss(kind):
+    """masked_area_level_ref / masked_window_ref on the windows' regions alone against loss.multiscale_masked_torch and
+    masked_ground_truth_torch in float64 on whole (small) tensors whose validity is zero outside the windows, with
+    random predictions everywhere."""
+    from qpwcnet_amd import loss
+    gen = torch.Generator().manual_seed(21)
+    B, H, W = 2, 96, 128
+    gt = _grid(gen, (B, H, W, 2), 1 / 16)
+    valid = torch.zeros(B, H, W, dtype=torch.uint8)
+    wins = [("a", 0, 0, 16, 0, 16), ("b", 1, 37, 53, 71, 87), ("c", 1, 80, 96, 112, 128)]
+    for _, n, y0, y1, x0, x1 in wins:
+        valid[n, y0:y1, x0:x1] = 1
+    factors = [(2, 2), (32, 32)] if kind == "v2" else [(1, 1)]
+    obj = loss.FlowMseLossV2() if kind == "v2" else loss.FlowMseLoss("channels_last")
+    if kind == "v2":
+        obj.delta = lo.LOSS_DELTA
+    levels = [(H // sh, W // sw) for sh, sw in factors]
+    preds = [_grid(gen, (B, h, w, 2), 1 / 16) for h, w in levels]
+    xs = [p.clone().requires_grad_() for p in preds]
+    _, per, counts = loss.multiscale_masked_torch(obj, gt, xs, valid)
+    (7.0 * per).sum().backward()
+    gts, masks_ = loss.masked_ground_truth_torch(obj, gt, levels, valid)
+    regs = [lo.aligned_region(x, 32 if kind == "v2" else 1, H, W) for x in wins]
+    for l, (sh, sw) in enumerate(factors):
+        crops = []
+        for _, n, y0, y1, x0, x1 in regs:
+            gl, m = lo.masked_area_level_ref(gt[n:n + 1, y0:y1, x0:x1], valid[n:n + 1, y0:y1, x0:x1], sh, sw, 1.0 / sh)
+            cut = lambda t: t[n:n + 1, y0 // sh:y1 // sh, x0 // sw:x1 // sw]
+            assert float((gl - cut(gts[l])).abs().max()) <= 1e-15 and torch.equal(m, cut(masks_[l]) != 0)
+            crops.append((gl, m, cut(preds[l])))
+        value, grads, count = lo.masked_window_ref(kind, crops, levels[l], 7.0)
+        assert count == int(counts[l]) == int(masks_[l].sum()) > 0
+        assert abs(float(value) - 7.0 * float(per[l].detach())) <= 1e-12 * abs(float(value))
+        inside = torch.zeros_like(xs[l].grad, dtype=torch.bool)
+        for (_, n, y0, y1, x0, x1), g in zip(regs, grads):
+            got = xs[l].grad[n:n + 1, y0 // sh:y1 // sh, x0 // sw:x1 // sw]
+            assert float((got - g).abs().max()) <= 1e-12 * float(g.abs().max())
+            inside[n:n + 1, y0 // sh:y1 // sh, x0 // sw:x1 // sw] = True
+        assert not xs[l].grad[~inside].any()
+
+
+@pytest.mark.parametrize("name,kind", [("masked_loss", "v2"), ("masked_loss_pixel", "v2"), ("masked_loss_pixel", "norm")])
+def test_masked_loss_negative_controls(name, kind):
+    key = lo.CASES[name]
+    B, H, W, C = key
+    tile = name == "masked_loss"
+    factors = [(2, 2), (32, 32)] if tile else [(1, 1)]
+    wins = lo.masked_loss_windows(key, (H // 2, W // 2) if tile else None)
+    regs = [lo.aligned_region(x, 32 if tile else 1, H, W) for x in wins]
+    gen = torch.Generator().manual_seed(22)
+    data = []
+    for x, r in zip(wins, regs):
+        ok = torch.zeros(1, r[3] - r[2], r[5] - r[4], dtype=torch.uint8)
+        ok[:, x[2] - r[2]:x[3] - r[2], x[4] - r[4]:x[5] - r[4]] = 1
+        data.append((_grid(gen, (1, r[3] - r[2], r[5] - r[4], 2), 1 / 16), ok))
+    for sh, sw in factors:
+        crops, moved = [], []
+        for k, ((g, ok), x, r) in enumerate(zip(data, wins, regs)):
+            gl, m = lo.masked_area_level_ref(g, ok, sh, sw, 1.0 / sh)
+            crops.append((gl, m, _grid(gen, tuple(gl.shape), 1 / 16)))
+            for mod, _ in lo.wrapped_pixel_regions(B, H, W, C, x):            # random data read elsewhere: another draw
+                moved.append(("window %d mod %d" % (k, mod), k, lo.masked_area_level_ref(_grid(gen, tuple(g.shape), 1 / 16), ok, sh, sw, 1.0 / sh)[0]))
+        controls = lo.masked_loss_controls(kind, crops, moved, (H // sh, W // sw))
+        assert len(controls) == len(crops) + len(moved) and len(moved) >= 2
+        assert min(r_ for _, r_ in controls) >= 100.0, controls
+        # the fp32 composition of the windows' sum stays within a tenth of the bound
+        v64 = lo.masked_window_ref(kind, crops, (H // sh, W // sw))[0]
+        v32 = lo.masked_window_ref(kind, [(gl.float().double(), m, p) for gl, m, p in crops], (H // sh, W // sw))[0]
+        assert abs(float(v32 - v64)) <= 0.1 * lo.LOSS_REL * abs(float(v64))
+
+
+def test_flow_quality_case_crosses_what_it_claims(hip_lib):
+    from qpwcnet_amd import _hip, ops
+    from test_eval_scale_cpu import FQ
+    key = lo.CASES["flow_quality"]
+    B, H, W, C = key
+    assert B == 5 and C == 2 and H % 2 and W % 2 and H != W
+    assert B * H * W <= 2 ** 31 - 1                                                    # flow_quality_shape_ok's cap
+    assert lo.crossed(B * H * W * C) == [P29, P30, P31] and lo.crossed(H * W * C) == []   # one image crosses nothing
+    assert [lo.locate(b, H, W, C)[0] for b in lo.BOUNDARIES] == [1, 2, 4]
+    assert lo.crossed(B * H * W) == [P29, P30] and [lo.locate(b, H, W, 1)[0] for b in (P29, P30)] == [2, 4]
+    # channels-first: `o = 2 * img + p` stays below 2^31 and `o + hw`, the v plane, passes it in the last image, before
+    # the pixels of the ">2^31" window and of the last one
+    assert 2 * (B - 1) * H * W + H * W < P31 < 2 * B * H * W
+    wins = lo.pixel_windows(B, H, W, C)
+    assert all(x[1] == B - 1 and 2 * (B - 1) * H * W + x[2] * W + x[4] + H * W > P31 for x in wins[3:])
+    chunks = -(-H * W // FQ["kFlowQualChunk"])
+    assert chunks > 800 * 64 and hip_lib.qpwc_flow_quality_workspace_floats(B, H, W) == B * chunks * 15
+    assert ops.flow_quality_kernel(B, H, W) == "flow_quality_tile_kernel" and ops.flow_quality_kernel(2 * B, H, W) == ""
+    wins = lo.pixel_windows(B, H, W, C)
+    assert [x[0] for x in wins] == ["first", ">2^29", ">2^30", ">2^31", "last"]
+    assert sorted({x[1] for x in wins}) == [0, 1, 2, 4]                                # image 3 holds no window
+    assert all(_disjoint(a, b) for i, a in enumerate(wins) for b in wins[i + 1:])
+    assert {x[1:] for x in lo.pixel_windows(B, H, W, 1)} <= {x[1:] for x in wins}       # the masks' boundaries: the same places
+    for b, x in zip(lo.BOUNDARIES, wins[1:4]):
+        assert b < ((x[1] * H + x[2]) * W + x[4]) * C < b + 2 * W * C
+    moved = [lo.wrapped_pixel_regions(B, H, W, C, x) for x in wins]
+    assert moved[0] == [] and all(m for m in moved[1:]) and {mod for m in moved for mod, _ in m} == {1 << 31, 1 << 32}
+    planned = lo.flow_quality_planned_bytes(key)
+    assert 4 * 2 * B * H * W * C + 2 * B * H * W <= planned <= 48 * lo.GIB and 19e9 < planned < 25e9
+
+
+def test_flow_windows_and_their_oracle():
+    """The windows' flows keep the bounds' precondition (no pixel within MARGIN of a threshold, in fp32 and in fp16) and
+    fill all three speed bins; flow_window_oracle on the crops and the mask counts is ref_flow_quality of whole (small)
+    tensors built the way the GPU test builds them; the controls move an image's epe by at least 100 bounds."""
+    from test_flow_quality_cpu import FIELDS, near_a_threshold, ref_flow_quality, violations
+    n_windows = len(lo.pixel_windows(*lo.CASES["flow_quality"]))
+    for half in (False, True):
+        for k in range(n_windows):
+            t, p = lo.flow_window_data(k, half)
+            assert t.shape == (1, lo.WIN, lo.WIN, 2) and p.dtype == (np.float16 if half else np.float32)
+            assert not near_a_threshold(t, p).any()
+            m = np.hypot(t[..., 0].astype(np.float64), t[..., 1])
+            assert (m < 10).any() and ((m >= 10) & (m < 40)).any() and (m >= 40).any()
+    rng = np.random.default_rng(23)
+    B, H, W = 3, 40, 50
+    truth = (rng.integers(-64, 65, (B, H, W, 2)) / 16).astype(np.float32)
+    pred = truth.copy()
+    valid, occ = rng.random((B, H, W)) < 0.7, rng.random((B, H, W)) < 0.3
+    wins = [(0, 0, 0), (0, 20, 30), (2, 24, 34)]
+    planted = []
+    for k, (n, y, x) in enumerate(wins):
+        t, p = lo.flow_window_data(k)
+        truth[n, y:y + lo.WIN, x:x + lo.WIN], pred[n, y:y + lo.WIN, x:x + lo.WIN] = t[0], p[0]
+        planted.append((n, t, p, valid[n:n + 1, y:y + lo.WIN, x:x + lo.WIN], occ[n:n + 1, y:y + lo.WIN, x:x + lo.WIN]))
+    n_valid, n_occ = valid.sum(axis=(1, 2)), (valid & occ).sum(axis=(1, 2))
+    got, sums = lo.flow_window_oracle(B, H * W, planted, n_valid, n_occ)
+    want = ref_flow_quality(truth, pred, valid, occ)
+    assert violations(got, want)[0] == []
+    for k in FIELDS:
+        keep = ~np.isnan(want[k])
+        assert np.array_equal(np.isnan(got[k]), np.isnan(want[k])) and np.abs(got[k][keep] - want[k][keep]).max() <= 1e-12
+    assert got["epe"][1] == 0 and got["acc1"][1] == 1
+    moved = [("window 1 elsewhere", 1, truth[1:2, 3:3 + lo.WIN, 5:5 + lo.WIN])]
+    big = [150_000_000] * B                                           # the GPU case's counts: the ratios do not depend on them
+    controls = lo.flow_controls(B, H * W, planted, moved, big, [45_000_000] * B)
+    assert len(controls) == 4 and min(r for _, r in controls) >= 100.0, controls
