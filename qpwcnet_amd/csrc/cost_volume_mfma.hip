@@ -84,6 +84,16 @@ __device__ __forceinline__ uint4 load_foff(int lane, int out_pix_stride = 81) {
                                 : *reinterpret_cast<const uint4*>(&kFoffTable.v[lane][0]);
 }
 
+// Element e = 81*px + 9*ky + kx of a 4 px x 81 tile row: its pixel, its frame offset in floats (window origin
+// (py, px) + (ky, kx)) and its offset in the output row.
+__device__ __forceinline__ void row_element(int e, int out_pix_stride, int& epx, int& foff, unsigned& goff) {
+    epx = e / 81;
+    const int k = e - 81 * epx;
+    const int ky = k / 9, kx = k - 9 * ky;
+    foff = epx * kFramePS + epx + ky * 12 + kx;
+    goff = (unsigned)(epx * out_pix_stride + k);
+}
+
 // `tab` = load_foff(lane), fetched by the caller long before the epilogue.
 // Returns true when the dense path ran (exactly 8 store instructions per wave).
 template <typename T, bool PAD84>
@@ -163,13 +173,8 @@ __device__ __forceinline__ bool store_tile_impl(const float* fr, T* ob, int lane
     int epx[6];
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
-        const int e = lane + 64 * s;     // element of the 4 px * 81 row
-        const int ee = e < 324 ? e : 0;  // s == 5 covers elements 320..323 only
-        epx[s] = ee / 81;
-        const int k = ee - 81 * epx[s];
-        const int ky = k / 9, kx = k - 9 * ky;
-        foff[s] = epx[s] * kFramePS + epx[s] + ky * 12 + kx;  // window origin (py, px) + (ky, kx)
-        goff[s] = (unsigned)(epx[s] * out_pix_stride + k);
+        const int e = lane + 64 * s;  // s == 5 covers elements 320..323 only
+        row_element(e < 324 ? e : 0, out_pix_stride, epx[s], foff[s], goff[s]);
     }
     float v[4][6];
 #pragma unroll
@@ -215,6 +220,105 @@ __device__ __forceinline__ u32x4 blend_clamp_chunk(float ax, float ay, u32x4 tl,
         v[e] = __float_as_uint(blend<QPWC_WARP_CLAMP>(t, __uint_as_float(tl[e]), __uint_as_float(tr[e]),
                                                       __uint_as_float(bl[e]), __uint_as_float(br[e])));
     return v;
+}
+// The same for fp16 storage: one 32-bit word = two halves, fp32 arithmetic on the fp16 corners, ONE rounding to fp16.
+__device__ __forceinline__ void unpack_half2(unsigned w, float& lo, float& hi) {
+    const float2 f = __half22float2(*reinterpret_cast<const __half2*>(&w));
+    lo = f.x;
+    hi = f.y;
+}
+__device__ __forceinline__ u32x4 blend_clamp_chunk_f16(float ax, float ay, u32x4 tl, u32x4 tr, u32x4 bl, u32x4 br) {
+    u32x4 v;
+    Taps t;
+    t.ax = ax;
+    t.ay = ay;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float tl0, tl1, tr0, tr1, bl0, bl1, br0, br1;
+        unpack_half2(tl[e], tl0, tl1);
+        unpack_half2(tr[e], tr0, tr1);
+        unpack_half2(bl[e], bl0, bl1);
+        unpack_half2(br[e], br0, br1);
+        const __half2 h = __floats2half2_rn(blend<QPWC_WARP_CLAMP>(t, tl0, tr0, bl0, br0),
+                                            blend<QPWC_WARP_CLAMP>(t, tl1, tr1, bl1, br1));
+        v[e] = *reinterpret_cast<const unsigned*>(&h);
+    }
+    return v;
+}
+
+// ---- device bodies shared by the kernels of this file --------------------------------------------
+// A kernel keeps what is its own: its staging map, its rounds per step and where its barriers sit.
+
+// One descriptor per operand covering exactly image b (H * W * C * sizeof(T) < 2^31, checked on the host): rows
+// above / below the image fall outside it (negative offsets wrap to >= 2^31) and read as zero; columns left / right
+// of the image are sent out of range explicitly (kOob).
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const T* p, int b, int H, int W, int C) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p) + (int64_t)b * H * W * C, 0,
+                                             H * W * C * (int)sizeof(T), 0x00020000);
+}
+
+// Fused front end, the record of one nxt piece: byte offset of the top-left corner of pixel (yy, xx)'s bilinear
+// sample inside image b (kOob for a pixel outside the image: every corner reads zero) and the two lerp factors.
+__device__ __forceinline__ uint4 warp_record(const float* flo, int b, int yy, int xx, bool inside, int H, int W,
+                                             unsigned pixb) {
+    float2 f = make_float2(0.f, 0.f);
+    if (inside) f = *reinterpret_cast<const float2*>(flo + ((int64_t)(b * H + yy) * W + xx) * 2);
+    const Taps t = taps_clamp(yy, xx, f.x, f.y, H, W);
+    uint4 r;
+    r.x = inside ? (unsigned)(t.y0 * W + t.x0) * pixb : kOob;
+    r.y = __float_as_uint(t.ax);
+    r.z = __float_as_uint(t.ay);
+    r.w = 0u;
+    return r;
+}
+// ... read back by the lane that stages chunk sc of the piece
+__device__ __forceinline__ void read_record(const char* rec, int sc, unsigned& off, float& ax, float& ay) {
+    const uint4 r = *reinterpret_cast<const uint4*>(rec);
+    off = r.x + (unsigned)sc * 16u;
+    ax = __uint_as_float(r.y);
+    ay = __uint_as_float(r.z);
+}
+// The four corner chunks of a piece.  The corner deltas ride in the scalar offset (clamp mode: all four corners of a
+// pixel inside the image are inside the image; a pixel outside has voffset >= 2^31 = out of range).
+__device__ __forceinline__ void gather_corners(__amdgpu_buffer_rsrc_t rn, unsigned o, int soff, unsigned pixb,
+                                               unsigned rowb, u32x4 (&c)[4]) {
+    c[0] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff, 0);
+    c[1] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)pixb, 0);
+    c[2] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)rowb, 0);
+    c[3] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)(rowb + pixb), 0);
+}
+
+// NOT shared: the 32-channel fp32 matrix step, which the 8 x 8, 8 x 16 and 16 x 16 kernels each spell out -- as one
+// template it measured slower on two of them ("Shared bodies").
+
+// Epilogue of a workgroup-shared kernel, after the barrier that turns the staging area into the output frames, in
+// two halves (the 8 x 8 kernel's diagnostic build stamps between them).
+// Accumulators -> the wave's frame: lane (pixel p = n, neighbour row g).
+__device__ __forceinline__ void write_frame(float* fr, int n, int g, const f32x4 (&acc)[3][3]) {
+    float* dst = fr + n * kFramePS + g * 12;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) *reinterpret_cast<f32x4*>(dst + 48 * i + 4 * j) = acc[i][j];
+    __builtin_amdgcn_wave_barrier();  // same-wave LDS traffic is ordered; keep the compiler in line
+}
+// The wave's frame -> the rows of its tile (x0, y0), if the tile is on the image.
+template <typename T>
+__device__ __forceinline__ void store_frame(const float* fr, int lane, T* out, int b, int x0, int y0, int H, int W,
+                                            int C, int out_pix_stride, float slope, float inv_c, uint4 tab,
+                                            int pad84) {
+    if (x0 >= W || y0 >= H) return;
+    T* ob = out + ((int64_t)(b * H + y0) * W + x0) * out_pix_stride;
+    store_tile<T>(fr, ob, lane, x0, y0, H, W, out_pix_stride, slope, inv_c, (float)C, tab, pad84 != 0);
+}
+template <typename T>
+__device__ __forceinline__ void tile_epilogue(char* smem, int wave, int lane, const f32x4 (&acc)[3][3], T* out,
+                                              int b, int x0, int y0, int H, int W, int C, int out_pix_stride,
+                                              float slope, float inv_c, uint4 tab, int pad84) {
+    float* fr = reinterpret_cast<float*>(smem) + wave * kFrameFloats;
+    write_frame(fr, lane & 15, lane >> 4, acc);
+    store_frame(fr, lane, out, b, x0, y0, H, W, C, out_pix_stride, slope, inv_c, tab, pad84);
 }
 
 // Region order of the workgroup-shared kernels: column STRIPS of 128 pixels, row-major inside a strip.  An XCD takes a
@@ -292,11 +396,6 @@ struct OperandLoad<8, float> {
         for (int i = 0; i < 8; ++i) f[i] = __uint_as_float(v[i]);
     }
 };
-__device__ __forceinline__ void unpack_half2(unsigned w, float& lo, float& hi) {
-    const float2 f = __half22float2(*reinterpret_cast<const __half2*>(&w));
-    lo = f.x;
-    hi = f.y;
-}
 template <>
 struct OperandLoad<4, __half> {
     static constexpr int NREG = 2, QBYTES = 8;
@@ -362,14 +461,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void cost_volume_mfma_kernel(
         for (int j = 0; j < 3; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     if (active) {
-        // One descriptor per operand covering exactly image b: rows above / below the
-        // image fall outside it (negative offsets wrap to >= 2^31) and read as zero;
-        // columns left / right of the image are sent out of range explicitly.
-        const int img_bytes = H * W * C * ES;  // < 2^31, checked on the host
-        const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<T*>(prv) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<T*>(nxt) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rp = image_rsrc(prv, b, H, W, C), rn = image_rsrc(nxt, b, H, W, C);
         using OL = OperandLoad<CPL, T>;
         constexpr int NREG = OL::NREG;
         const int tile_off = ((y0 - 4) * W + (x0 - 4)) * C * ES;  // scalar, may be negative
@@ -425,19 +517,9 @@ __global__ __launch_bounds__(64 * WPB, 4) void cost_volume_mfma_kernel(
         }
     }
 
-    // ---- accumulators -> frame: lane (pixel p = n, neighbour row g) ----------
     float* fr = frames + wave * kFrameFloats;
-    {
-        float* dst = fr + n * kFramePS + g * 12;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) *reinterpret_cast<f32x4*>(dst + 48 * i + 4 * j) = acc[i][j];
-    }
-    if (KS > 1)
-        __syncthreads();
-    else
-        __builtin_amdgcn_wave_barrier();  // same-wave LDS traffic is ordered; keep the compiler in line
+    write_frame(fr, n, g, acc);
+    if (KS > 1) __syncthreads();
 
     // ---- frame window -> 81 channels, whole tile rows of 4 px * 81 floats ----
     if (!active) return;
@@ -456,11 +538,10 @@ __global__ __launch_bounds__(64 * WPB, 4) void cost_volume_mfma_kernel(
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int e = lane + 64 * s;  // element of the 4 px * 81 row
-        const int epx = e / 81, k = e - 81 * epx;
-        const int ky = k / 9, kx = k - 9 * ky;
+        int epx, foff;
+        unsigned goff;
+        row_element(e, out_pix_stride, epx, foff, goff);
         const bool e_ok = e < 324 && x0 + epx < W;
-        const int foff = epx * kFramePS + epx + ky * 12 + kx;  // window origin (py, px) + (ky, kx)
-        const unsigned goff = (unsigned)(epx * out_pix_stride + k);
 #pragma unroll
         for (int row = 0; row < 4; ++row) {
             if (KS > 1 && (row * 6 + s) % KS != ks) continue;  // the KS waves share the 24 items
@@ -535,11 +616,7 @@ __global__ __launch_bounds__(256, WARP ? QPWC_WARP_OCC : 4) void cost_volume_mfm
 #endif
     CV_STAMP();
 
-    const int img_bytes = H * W * C * 4;  // < 2^31, checked on the host
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(prv) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(nxt) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = image_rsrc(prv, b, H, W, C), rn = image_rsrc(nxt, b, H, W, C);
 
     // ---- staging map: piece idx = it*256 + tid -> block 2*it + (tid>>7), pixel, chunk
     const int hi = tid >> 7, within = tid & 127, sn = within >> 3, sc = within & 7;
@@ -572,24 +649,11 @@ __global__ __launch_bounds__(256, WARP ? QPWC_WARP_OCC : 4) void cost_volume_mfm
         // this lane's share: piece it = sc, i.e. nxt block (sc >> 1, 2 (sc & 1) + hi), pixel (spy, spx)
         const int yy = Y0 - 4 + 4 * (sc >> 1) + spy, xx = X0 - 4 + 4 * (2 * (sc & 1) + hi) + spx;
         const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W;
-        float2 f = make_float2(0.f, 0.f);
-        if (inside) f = *reinterpret_cast<const float2*>(flo + ((int64_t)(b * H + yy) * W + xx) * 2);
-        const Taps t = taps_clamp(yy, xx, f.x, f.y, H, W);
-        uint4 rec;
-        rec.x = inside ? (unsigned)(t.y0 * W + t.x0) * pixb : kOob;   // outside: every corner reads zero
-        rec.y = __float_as_uint(t.ax);
-        rec.z = __float_as_uint(t.ay);
-        rec.w = 0u;
         char* xch = smem + wave * 1024 + (lane >> 3) * 128;   // 8 records of the lane group
-        *reinterpret_cast<uint4*>(xch + sc * 16) = rec;
+        *reinterpret_cast<uint4*>(xch + sc * 16) = warp_record(flo, b, yy, xx, inside, H, W, pixb);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const uint4 r = *reinterpret_cast<const uint4*>(xch + it * 16);
-            goff[it] = r.x + (unsigned)sc * 16u;
-            wax[it] = __uint_as_float(r.y);
-            way[it] = __uint_as_float(r.z);
-        }
+        for (int it = 0; it < 8; ++it) read_record(xch + it * 16, sc, goff[it], wax[it], way[it]);
         __builtin_amdgcn_wave_barrier();   // the records are in registers before this wave's staging writes
     }
 
@@ -618,15 +682,7 @@ __global__ __launch_bounds__(256, WARP ? QPWC_WARP_OCC : 4) void cost_volume_mfm
             u32x4 c[PR][4];
             auto issue = [&](int it) {
 #pragma unroll
-                for (int q = 0; q < PR; ++q) {
-                    // the corner deltas ride in the scalar offset (clamp mode: all four corners of a pixel inside
-                    // the image are inside the image; a pixel outside has voffset >= 2^31 = out of range)
-                    const unsigned o = goff[it + q];
-                    c[q][0] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff, 0);
-                    c[q][1] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)pixb, 0);
-                    c[q][2] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)rowb2, 0);
-                    c[q][3] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)(rowb2 + pixb), 0);
-                }
+                for (int q = 0; q < PR; ++q) gather_corners(rn, goff[it + q], soff, pixb, rowb2, c[q]);
             };
             issue(0);
             if (!FIRST) __syncthreads();  // previous step's operand reads are done
@@ -634,16 +690,8 @@ __global__ __launch_bounds__(256, WARP ? QPWC_WARP_OCC : 4) void cost_volume_mfm
             for (int it = 0; it < 8; it += PR) {
                 u32x4 v[PR];
 #pragma unroll
-                for (int q = 0; q < PR; ++q) {
-                    Taps t;
-                    t.ax = wax[it + q];
-                    t.ay = way[it + q];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        v[q][e] = __float_as_uint(blend<QPWC_WARP_CLAMP>(
-                            t, __uint_as_float(c[q][0][e]), __uint_as_float(c[q][1][e]),
-                            __uint_as_float(c[q][2][e]), __uint_as_float(c[q][3][e])));
-                }
+                for (int q = 0; q < PR; ++q)
+                    v[q] = blend_clamp_chunk(wax[it + q], way[it + q], c[q][0], c[q][1], c[q][2], c[q][3]);
                 if (it + PR < 8) issue(it + PR);
 #pragma unroll
                 for (int q = 0; q < PR; ++q) *reinterpret_cast<u32x4*>(smem + lds_w + (it + q) * 4096) = v[q];
@@ -691,22 +739,10 @@ __global__ __launch_bounds__(256, WARP ? QPWC_WARP_OCC : 4) void cost_volume_mfm
     CV_STAMP();       // matrix work issued
     __syncthreads();  // staging area becomes the four output frames
     CV_STAMP();
-
     float* fr = reinterpret_cast<float*>(smem) + wave * kFrameFloats;
-    {
-        float* dst = fr + n * kFramePS + g * 12;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) *reinterpret_cast<f32x4*>(dst + 48 * i + 4 * j) = acc[i][j];
-    }
-    __builtin_amdgcn_wave_barrier();
+    write_frame(fr, n, g, acc);
     CV_STAMP();       // frame written (includes the wait for the last matrix results)
-
-    const int x0 = X0 + 4 * tj, y0 = Y0 + 4 * ti;
-    if (x0 >= W || y0 >= H) return;
-    float* ob = out + ((int64_t)(b * H + y0) * W + x0) * out_pix_stride;
-    store_tile<float>(fr, ob, lane, x0, y0, H, W, out_pix_stride, slope, inv_c, (float)C, tab, pad84 != 0);
+    store_frame(fr, lane, out, b, X0 + 4 * tj, Y0 + 4 * ti, H, W, C, out_pix_stride, slope, inv_c, tab, pad84);
     CV_STAMP();       // read back, activated, stores issued
 #ifdef QPWC_CV_STAMP
     asm volatile("s_waitcnt vmcnt(0)");
@@ -715,10 +751,10 @@ __global__ __launch_bounds__(256, WARP ? QPWC_WARP_OCC : 4) void cost_volume_mfm
 }
 
 // ---------------------------------------------------------------------------
-// 16 x 16 pixel regions (round 3): the same scheme with SIXTEEN waves per workgroup (4 x 4 tiles), one workgroup
-// per CU.  Why: a region's 16 + 8 wide neighbourhood is staged once for 16 tiles, so every nxt pixel is staged by
-// 2.25 workgroups instead of 4 (36 + 16 = 52 block loads per 16 tiles = 3.25 per tile instead of 5) -- for the
-// fused front end (WARP), whose staging step is a 4-corner gather per piece and is bound by the L1's 64 B/clk
+// 16 x 16 pixel regions (round 3), fused front end only: the same scheme with SIXTEEN waves per workgroup (4 x 4
+// tiles), one workgroup per CU.  Why: a region's 16 + 8 wide neighbourhood is staged once for 16 tiles, so every nxt
+// pixel is staged by 2.25 workgroups instead of 4 (36 + 16 = 52 block loads per 16 tiles = 3.25 per tile instead of
+// 5) -- for the fused front end, whose staging step is a 4-corner gather per piece and is bound by the L1's 64 B/clk
 // (round 2's counters: 3.3 x the vector-memory instructions of the unfused kernel, texture addresser the busiest
 // unit), that is 44 % fewer gather instructions and 44 % less L2 -> L1 traffic; at BASELINE config 4's size, where
 // a level's nxt no longer sits in the L2s, it is HBM traffic as well.
@@ -726,8 +762,11 @@ __global__ __launch_bounds__(256, WARP ? QPWC_WARP_OCC : 4) void cost_volume_mfm
 //            blocks 0..35 = nxt (bi, bj) = (B / 6, B % 6) of the 24 x 24 neighbourhood, 36..51 = prv tile B - 36.
 //            Waves 0..7 stage 5 nxt + 2 prv pieces per lane and step, waves 8..15 4 + 2 (wave-uniform).
 //   LDS    : 52 x 2 KB staging image (swizzled as above), aliased by the sixteen 9.25 KB output frames (148 KB).
-//   the rest (operand reads, 72 matrix instructions per wave and 32-channel step, frame, store_tile) is the
-//   8 x 8 kernel's code: the result is bit-identical to it.
+//   the rest is the 8 x 8 kernel's: records, gather, blend and epilogue through the shared bodies above, the operand
+//   reads and 72 matrix instructions per wave and 32-channel step as its own copy: the result is bit-identical to it.
+// Only WARP = true is instantiated: the plain cost volume never takes these regions (use_regions16).  The plain staging
+// path (`goffn`, the `else` of the step) is kept all the same: with it deleted the compiler allocates and orders the
+// fused kernel's staging part differently, and that measured 1-2 % slower at config 4's L1 / L2.
 constexpr int kR16NxtBlocks = 36, kR16Blocks = 52;
 constexpr int kR16StageBytes = kR16Blocks * 2048;
 constexpr int kR16FrameBytes = 16 * kFrameFloats * 4;
@@ -748,11 +787,8 @@ __global__ __launch_bounds__(1024) void cost_volume_mfma_lds16_kernel(
     region_coords<8>(region, regs_x, regs_y, rx, ry, b);
     const int X0 = rx * 16, Y0 = ry * 16;
 
-    const int img_bytes = H * W * C * 4;  // (H + 24) * (W + 24) * C * 4 < 2^31, checked on the host
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(prv) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(nxt) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
+    // (H + 24) * (W + 24) * C * 4 < 2^31, checked on the host
+    const __amdgpu_buffer_rsrc_t rp = image_rsrc(prv, b, H, W, C), rn = image_rsrc(nxt, b, H, W, C);
 
     // ---- staging map ------------------------------------------------------------------------------------
     const int h = wave >> 1;                       // scalar: block column of a round
@@ -787,15 +823,7 @@ __global__ __launch_bounds__(1024) void cost_volume_mfma_lds16_kernel(
         const int B = sc * 8 + h, bi = B / 6, bj = B - 6 * bi;
         const int yy = Y0 - 4 + 4 * bi + spy, xx = X0 - 4 + 4 * bj + spx;
         const bool inside = B < kR16NxtBlocks && sc < 5 && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        float2 f = make_float2(0.f, 0.f);
-        if (inside) f = *reinterpret_cast<const float2*>(flo + ((int64_t)(b * H + yy) * W + xx) * 2);
-        const Taps t = taps_clamp(yy, xx, f.x, f.y, H, W);
-        uint4 r;
-        r.x = inside ? (unsigned)(t.y0 * W + t.x0) * pixb : kOob;   // outside: every corner reads zero
-        r.y = __float_as_uint(t.ax);
-        r.z = __float_as_uint(t.ay);
-        r.w = 0u;
-        *reinterpret_cast<uint4*>(rec + sc * 16) = r;
+        *reinterpret_cast<uint4*>(rec + sc * 16) = warp_record(flo, b, yy, xx, inside, H, W, pixb);
         __builtin_amdgcn_wave_barrier();   // same-wave LDS traffic is ordered
     }
 
@@ -811,96 +839,62 @@ __global__ __launch_bounds__(1024) void cost_volume_mfma_lds16_kernel(
     auto step = [&](int s, auto first) {
         constexpr bool FIRST = decltype(first)::value;
         const int soff = s * 128;
+        auto put = [&](int it, u32x4 v) { *reinterpret_cast<u32x4*>(smem + lds_w + it * 16384) = v; };
         if (WARP) {
+            // a piece's record -> its four gathers in flight in `p`; its blended chunk -> block row `it` of the image
+            struct Piece {
+                u32x4 c[4];
+                float ax, ay;
+            };
+            auto issue = [&](int it, Piece& p) {
+                unsigned o;
+                read_record(rec + it * 16, sc, o, p.ax, p.ay);
+                gather_corners(rn, o, soff, pixb, rowb, p.c);
+            };
+            auto mix = [&](const Piece& p) { return blend_clamp_chunk(p.ax, p.ay, p.c[0], p.c[1], p.c[2], p.c[3]); };
             // three rounds of at most eight loads: pieces (0, 1), (2, 3), then (4 | the two prv pieces) -- with the 36
             // accumulators live in the later steps that is what 128 registers hold without spilling
-            u32x4 c[2][4];
-            float ax[2], ay[2];
-            auto issue = [&](int it, int q) {
-                const uint4 r = *reinterpret_cast<const uint4*>(rec + it * 16);
-                const unsigned o = r.x + (unsigned)sc * 16u;
-                ax[q] = __uint_as_float(r.y);
-                ay[q] = __uint_as_float(r.z);
-                c[q][0] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff, 0);
-                c[q][1] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)pixb, 0);
-                c[q][2] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)rowb, 0);
-                c[q][3] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)(rowb + pixb), 0);
-            };
-            auto mix = [&](int q) {
-                Taps t;
-                t.ax = ax[q];
-                t.ay = ay[q];
-                u32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    v[e] = __float_as_uint(blend<QPWC_WARP_CLAMP>(
-                        t, __uint_as_float(c[q][0][e]), __uint_as_float(c[q][1][e]), __uint_as_float(c[q][2][e]),
-                        __uint_as_float(c[q][3][e])));
-                return v;
-            };
+            Piece a[2];
             if (FIRST) {
                 // no accumulator is live yet: every gather of the step is issued before the first one is used (one
                 // memory round trip instead of three -- with one workgroup per CU nobody else hides them)
-                u32x4 c4[3][4], p0, p1;
-                float ax4[3], ay4[3];
-                auto issue4 = [&](int it, int q) {
-                    const uint4 r = *reinterpret_cast<const uint4*>(rec + it * 16);
-                    const unsigned o = r.x + (unsigned)sc * 16u;
-                    ax4[q] = __uint_as_float(r.y);
-                    ay4[q] = __uint_as_float(r.z);
-                    c4[q][0] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff, 0);
-                    c4[q][1] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)pixb, 0);
-                    c4[q][2] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)rowb, 0);
-                    c4[q][3] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)(rowb + pixb), 0);
-                };
-                auto mix4 = [&](int q) {
-                    Taps t;
-                    t.ax = ax4[q];
-                    t.ay = ay4[q];
-                    u32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        v[e] = __float_as_uint(blend<QPWC_WARP_CLAMP>(
-                            t, __uint_as_float(c4[q][0][e]), __uint_as_float(c4[q][1][e]),
-                            __uint_as_float(c4[q][2][e]), __uint_as_float(c4[q][3][e])));
-                    return v;
-                };
-                issue(0, 0);
-                issue(1, 1);
-                issue4(2, 0);
-                issue4(3, 1);
-                if (low) issue4(4, 2);
-                p0 = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[0], soff, 0);
-                p1 = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[1], soff, 0);
-                *reinterpret_cast<u32x4*>(smem + lds_w + 0 * 16384) = mix(0);
-                *reinterpret_cast<u32x4*>(smem + lds_w + 1 * 16384) = mix(1);
-                *reinterpret_cast<u32x4*>(smem + lds_w + 2 * 16384) = mix4(0);
-                *reinterpret_cast<u32x4*>(smem + lds_w + 3 * 16384) = mix4(1);
-                if (low) *reinterpret_cast<u32x4*>(smem + lds_w + 4 * 16384) = mix4(2);
-                *reinterpret_cast<u32x4*>(smem + lds_w + itp * 16384) = p0;
-                *reinterpret_cast<u32x4*>(smem + lds_w + (itp + 1) * 16384) = p1;
+                Piece w[3];
+                issue(0, a[0]);
+                issue(1, a[1]);
+                issue(2, w[0]);
+                issue(3, w[1]);
+                if (low) issue(4, w[2]);
+                const u32x4 p0 = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[0], soff, 0);
+                const u32x4 p1 = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[1], soff, 0);
+                put(0, mix(a[0]));
+                put(1, mix(a[1]));
+                put(2, mix(w[0]));
+                put(3, mix(w[1]));
+                if (low) put(4, mix(w[2]));
+                put(itp, p0);
+                put(itp + 1, p1);
             } else {
-                issue(0, 0);
-                issue(1, 1);
+                issue(0, a[0]);
+                issue(1, a[1]);
                 __syncthreads();  // previous step's operand reads are done
                 {
-                    const u32x4 v0 = mix(0), v1 = mix(1);
-                    issue(2, 0);
-                    issue(3, 1);
-                    *reinterpret_cast<u32x4*>(smem + lds_w + 0 * 16384) = v0;
-                    *reinterpret_cast<u32x4*>(smem + lds_w + 1 * 16384) = v1;
+                    const u32x4 v0 = mix(a[0]), v1 = mix(a[1]);
+                    issue(2, a[0]);
+                    issue(3, a[1]);
+                    put(0, v0);
+                    put(1, v1);
                 }
                 {
-                    const u32x4 v0 = mix(0), v1 = mix(1);
-                    if (low) issue(4, 0);
-                    c[1][0] = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[0], soff, 0);
-                    c[1][1] = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[1], soff, 0);
-                    *reinterpret_cast<u32x4*>(smem + lds_w + 2 * 16384) = v0;
-                    *reinterpret_cast<u32x4*>(smem + lds_w + 3 * 16384) = v1;
+                    const u32x4 v0 = mix(a[0]), v1 = mix(a[1]);
+                    if (low) issue(4, a[0]);
+                    a[1].c[0] = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[0], soff, 0);
+                    a[1].c[1] = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[1], soff, 0);
+                    put(2, v0);
+                    put(3, v1);
                 }
-                if (low) *reinterpret_cast<u32x4*>(smem + lds_w + 4 * 16384) = mix(0);
-                *reinterpret_cast<u32x4*>(smem + lds_w + itp * 16384) = c[1][0];
-                *reinterpret_cast<u32x4*>(smem + lds_w + (itp + 1) * 16384) = c[1][1];
+                if (low) put(4, mix(a[0]));
+                put(itp, a[1].c[0]);
+                put(itp + 1, a[1].c[1]);
             }
         } else {
             u32x4 st[5], sp[2];
@@ -911,10 +905,10 @@ __global__ __launch_bounds__(1024) void cost_volume_mfma_lds16_kernel(
             for (int k = 0; k < 2; ++k) sp[k] = __builtin_amdgcn_raw_buffer_load_b128(rp, goffp[k], soff, 0);
             if (!FIRST) __syncthreads();
 #pragma unroll
-            for (int it = 0; it < 4; ++it) *reinterpret_cast<u32x4*>(smem + lds_w + it * 16384) = st[it];
-            if (low) *reinterpret_cast<u32x4*>(smem + lds_w + 4 * 16384) = st[4];
+            for (int it = 0; it < 4; ++it) put(it, st[it]);
+            if (low) put(4, st[4]);
 #pragma unroll
-            for (int k = 0; k < 2; ++k) *reinterpret_cast<u32x4*>(smem + lds_w + (itp + k) * 16384) = sp[k];
+            for (int k = 0; k < 2; ++k) put(itp + k, sp[k]);
         }
         if (FIRST) asm volatile("" : "+v"(tab.x), "+v"(tab.y), "+v"(tab.z), "+v"(tab.w));
         __syncthreads();
@@ -942,21 +936,8 @@ __global__ __launch_bounds__(1024) void cost_volume_mfma_lds16_kernel(
     step(0, std::true_type{});
     for (int s = 1; s < nsteps; ++s) step(s, std::false_type{});
     __syncthreads();  // staging area becomes the sixteen output frames
-
-    float* fr = reinterpret_cast<float*>(smem) + wave * kFrameFloats;
-    {
-        float* dst = fr + n * kFramePS + g * 12;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) *reinterpret_cast<f32x4*>(dst + 48 * i + 4 * j) = acc[i][j];
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    const int x0 = X0 + 4 * tj, y0 = Y0 + 4 * ti;
-    if (x0 >= W || y0 >= H) return;
-    float* ob = out + ((int64_t)(b * H + y0) * W + x0) * out_pix_stride;
-    store_tile<float>(fr, ob, lane, x0, y0, H, W, out_pix_stride, slope, inv_c, (float)C, tab, pad84 != 0);
+    tile_epilogue(smem, wave, lane, acc, out, b, X0 + 4 * tj, Y0 + 4 * ti, H, W, C, out_pix_stride, slope, inv_c, tab,
+                  pad84);
 }
 
 // ---------------------------------------------------------------------------
@@ -986,11 +967,8 @@ __global__ __launch_bounds__(512, 2) void cost_volume_mfma_lds8x16_warp_kernel(
     region_coords<8>(region, regs_x, regs_y, rx, ry, b);
     const int X0 = rx * 16, Y0 = ry * 8;
 
-    const int img_bytes = H * W * C * 4;  // (H + 16) * (W + 24) * C * 4 < 2^31, checked on the host
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(prv) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(nxt) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
+    // (H + 16) * (W + 24) * C * 4 < 2^31, checked on the host
+    const __amdgpu_buffer_rsrc_t rp = image_rsrc(prv, b, H, W, C), rn = image_rsrc(nxt, b, H, W, C);
 
     const int h = wave >> 1;                       // scalar: block of a round
     const int sn = (tid & 127) >> 3, sc = tid & 7;
@@ -1011,15 +989,7 @@ __global__ __launch_bounds__(512, 2) void cost_volume_mfma_lds8x16_warp_kernel(
         const int B = sc * 4 + h, bi = B / 6, bj = B - 6 * bi;
         const int yy = Y0 - 4 + 4 * bi + spy, xx = X0 - 4 + 4 * bj + spx;
         const bool inside = sc < 6 && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        float2 f = make_float2(0.f, 0.f);
-        if (inside) f = *reinterpret_cast<const float2*>(flo + ((int64_t)(b * H + yy) * W + xx) * 2);
-        const Taps t = taps_clamp(yy, xx, f.x, f.y, H, W);
-        uint4 r;
-        r.x = inside ? (unsigned)(t.y0 * W + t.x0) * pixb : kOob;   // outside: every corner reads zero
-        r.y = __float_as_uint(t.ax);
-        r.z = __float_as_uint(t.ay);
-        r.w = 0u;
-        *reinterpret_cast<uint4*>(rec + sc * 16) = r;
+        *reinterpret_cast<uint4*>(rec + sc * 16) = warp_record(flo, b, yy, xx, inside, H, W, pixb);
         __builtin_amdgcn_wave_barrier();
     }
 
@@ -1039,14 +1009,9 @@ __global__ __launch_bounds__(512, 2) void cost_volume_mfma_lds8x16_warp_kernel(
         u32x4 c[PR][4];
         float ax[PR], ay[PR];
         auto issue = [&](int it, int q) __attribute__((always_inline)) {
-            const uint4 r = *reinterpret_cast<const uint4*>(rec + it * 16);
-            const unsigned o = r.x + (unsigned)sc * 16u;
-            ax[q] = __uint_as_float(r.y);
-            ay[q] = __uint_as_float(r.z);
-            c[q][0] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff, 0);
-            c[q][1] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)pixb, 0);
-            c[q][2] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)rowb, 0);
-            c[q][3] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)(rowb + pixb), 0);
+            unsigned o;
+            read_record(rec + it * 16, sc, o, ax[q], ay[q]);
+            gather_corners(rn, o, soff, pixb, rowb, c[q]);
         };
         auto mix = [&](int q) __attribute__((always_inline)) {
             return blend_clamp_chunk(ax[q], ay[q], c[q][0], c[q][1], c[q][2], c[q][3]);
@@ -1099,21 +1064,8 @@ __global__ __launch_bounds__(512, 2) void cost_volume_mfma_lds8x16_warp_kernel(
     step(0, std::true_type{});
     for (int s = 1; s < nsteps; ++s) step(s, std::false_type{});
     __syncthreads();  // staging area (and the records) become the eight output frames
-
-    float* fr = reinterpret_cast<float*>(smem) + wave * kFrameFloats;
-    {
-        float* dst = fr + n * kFramePS + g * 12;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) *reinterpret_cast<f32x4*>(dst + 48 * i + 4 * j) = acc[i][j];
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    const int x0 = X0 + 4 * tj, y0 = Y0 + 4 * ti;
-    if (x0 >= W || y0 >= H) return;
-    float* ob = out + ((int64_t)(b * H + y0) * W + x0) * out_pix_stride;
-    store_tile<float>(fr, ob, lane, x0, y0, H, W, out_pix_stride, slope, inv_c, (float)C, tab, pad84 != 0);
+    tile_epilogue(smem, wave, lane, acc, out, b, X0 + 4 * tj, Y0 + 4 * ti, H, W, C, out_pix_stride, slope, inv_c, tab,
+                  pad84);
 }
 
 // ---------------------------------------------------------------------------
@@ -1143,11 +1095,7 @@ __global__ __launch_bounds__(256, WARP ? 3 : 4) void cost_volume_mfma_lds_f16_ke
     region_coords<16>(region, regs_x, regs_y, rx, ry, b);
     const int X0 = rx * 8, Y0 = ry * 8;
 
-    const int img_bytes = H * W * C * 2;
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<__half*>(prv) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<__half*>(nxt) + (int64_t)b * H * W * C, 0, img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = image_rsrc(prv, b, H, W, C), rn = image_rsrc(nxt, b, H, W, C);
 
     // staging map: piece idx = it*256 + tid -> block 4*it + wave, pixel lane>>2, chunk lane&3
     const int sn = lane >> 2, sc = lane & 3;
@@ -1175,24 +1123,11 @@ __global__ __launch_bounds__(256, WARP ? 3 : 4) void cost_volume_mfma_lds_f16_ke
         const int blk = 4 * sc + wave;   // this lane's share: piece it = sc
         const int yy = Y0 - 4 + 4 * (blk >> 2) + spy, xx = X0 - 4 + 4 * (blk & 3) + spx;
         const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W;
-        float2 f = make_float2(0.f, 0.f);
-        if (inside) f = *reinterpret_cast<const float2*>(flo + ((int64_t)(b * H + yy) * W + xx) * 2);
-        const Taps t = taps_clamp(yy, xx, f.x, f.y, H, W);
-        uint4 rec;
-        rec.x = inside ? (unsigned)(t.y0 * W + t.x0) * pixb : kOob;
-        rec.y = __float_as_uint(t.ax);
-        rec.z = __float_as_uint(t.ay);
-        rec.w = 0u;
         char* xch = smem + wave * 1024 + (lane >> 2) * 64;   // 4 records of the lane group
-        *reinterpret_cast<uint4*>(xch + sc * 16) = rec;
+        *reinterpret_cast<uint4*>(xch + sc * 16) = warp_record(flo, b, yy, xx, inside, H, W, pixb);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const uint4 r = *reinterpret_cast<const uint4*>(xch + it * 16);
-            goff[it] = r.x + (unsigned)sc * 16u;
-            wax[it] = __uint_as_float(r.y);
-            way[it] = __uint_as_float(r.z);
-        }
+        for (int it = 0; it < 4; ++it) read_record(xch + it * 16, sc, goff[it], wax[it], way[it]);
         __builtin_amdgcn_wave_barrier();
     }
 
@@ -1218,30 +1153,10 @@ __global__ __launch_bounds__(256, WARP ? 3 : 4) void cost_volume_mfma_lds_f16_ke
             for (int it = 0; it < 4; it += 2) {
                 u32x4 c[2][4];
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const unsigned o = goff[it + q];
-                    c[q][0] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff, 0);
-                    c[q][1] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)pixb, 0);
-                    c[q][2] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)rowb2, 0);
-                    c[q][3] = __builtin_amdgcn_raw_buffer_load_b128(rn, o, soff + (int)(rowb2 + pixb), 0);
-                }
+                for (int q = 0; q < 2; ++q) gather_corners(rn, goff[it + q], soff, pixb, rowb2, c[q]);
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    Taps t;
-                    t.ax = wax[it + q];
-                    t.ay = way[it + q];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {   // one 32-bit word = two halves
-                        float tl0, tl1, tr0, tr1, bl0, bl1, br0, br1;
-                        unpack_half2(c[q][0][e], tl0, tl1);
-                        unpack_half2(c[q][1][e], tr0, tr1);
-                        unpack_half2(c[q][2][e], bl0, bl1);
-                        unpack_half2(c[q][3][e], br0, br1);
-                        const __half2 h = __floats2half2_rn(blend<QPWC_WARP_CLAMP>(t, tl0, tr0, bl0, br0),
-                                                            blend<QPWC_WARP_CLAMP>(t, tl1, tr1, bl1, br1));
-                        st[it + q][e] = *reinterpret_cast<const unsigned*>(&h);
-                    }
-                }
+                for (int q = 0; q < 2; ++q)
+                    st[it + q] = blend_clamp_chunk_f16(wax[it + q], way[it + q], c[q][0], c[q][1], c[q][2], c[q][3]);
             }
         } else {
 #pragma unroll
@@ -1261,46 +1176,67 @@ __global__ __launch_bounds__(256, WARP ? 3 : 4) void cost_volume_mfma_lds_f16_ke
             }
     }
     __syncthreads();
+    tile_epilogue(smem, wave, lane, acc, out, b, X0 + 4 * tj, Y0 + 4 * ti, H, W, C, out_pix_stride, slope, inv_c, tab,
+                  pad84);
+}
 
-    float* fr = reinterpret_cast<float*>(smem) + wave * kFrameFloats;
-    {
-        float* dst = fr + n * kFramePS + g * 12;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) *reinterpret_cast<f32x4*>(dst + 48 * i + 4 * j) = acc[i][j];
-    }
-    __builtin_amdgcn_wave_barrier();
+// ---- launchers ----------------------------------------------------------------------------------------------------
+// This library reads NO environment variable: every rank of a multi-GPU job runs the same kernels.
 
-    const int x0 = X0 + 4 * tj, y0 = Y0 + 4 * ti;
-    if (x0 >= W || y0 >= H) return;
-    __half* ob = out + ((int64_t)(b * H + y0) * W + x0) * out_pix_stride;
-    store_tile<__half>(fr, ob, lane, x0, y0, H, W, out_pix_stride, slope, inv_c, (float)C, tab, pad84 != 0);
+// What a launch cuts the image into: regions (or the per-wave kernel's tiles) of ry x rx pixels, whose staged
+// neighbourhood widens the byte range that a 32-bit offset must span by hy rows and hx columns.
+struct Regions {
+    int ry, rx, hy, hx;
+};
+constexpr Regions kTiles4{4, 4, 8, 8}, kRegions8{8, 8, 8, 8}, kRegions8x16{8, 16, 16, 24}, kRegions16{16, 16, 24, 24};
+
+static int64_t count_regions(Regions r, int B, int H, int W) {
+    return (int64_t)((W + r.rx - 1) / r.rx) * ((H + r.ry - 1) / r.ry) * B;
+}
+// 32-bit region index, 32-bit byte offsets inside one image (buffer descriptors) and 32-bit element offsets inside
+// one output image
+static bool fits_32bit(Regions r, int B, int H, int W, int C, int64_t es, int64_t ops) {
+    return count_regions(r, B, H, W) <= INT32_MAX && (int64_t)(H + r.hy) * (W + r.hx) * C * es < 0x7fffffff &&
+           (int64_t)H * W * ops <= INT32_MAX;
+}
+static int too_large() {
+    set_error("image too large for 32-bit tile indexing");
+    return QPWC_E_SHAPE;
+}
+// `inv_c` > 0 tells a kernel that C is a power of two: mean = sum * (1/C) is exact
+static float exact_inv(int C) { return (C & (C - 1)) == 0 ? 1.0f / (float)C : 0.0f; }
+
+// `name` is what a dry run reports, `what` names the launch in an error
+template <typename K, typename... A>
+static int launch(const char* name, const char* what, K kernel, int64_t nblk, int threads, hipStream_t s, A... args) {
+    if (dry_run(name)) return QPWC_OK;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(threads), 0, s, args...);
+    return check_launch(what);
+}
+
+// a workgroup-shared kernel: one workgroup per region
+template <typename T>
+static int launch_regions(const char* name, const char* what,
+                          void (*kernel)(const T*, const T*, const float*, T*, int, int, int, int, int, int, float,
+                                         float, int),
+                          Regions r, int threads, const T* prv, const T* nxt, const float* flo, T* out, int B, int H,
+                          int W, int C, int64_t ops, float slope, int pad84, hipStream_t s) {
+    if (!fits_32bit(r, B, H, W, C, sizeof(T), ops)) return too_large();
+    const int regs_x = (W + r.rx - 1) / r.rx, regs_y = (H + r.ry - 1) / r.ry;
+    return launch(name, what, kernel, count_regions(r, B, H, W), threads, s, prv, nxt, flo, out, H, W, C, regs_x,
+                  regs_y, (int)ops, slope, exact_inv(C), pad84);
 }
 
 static int launch_lds_f16(const __half* prv, const __half* nxt, const float* flo, __half* out, int B, int H, int W,
                           int C, int64_t ops, float slope, int pad84, hipStream_t s) {
-    const int regs_x = (W + 7) / 8, regs_y = (H + 7) / 8;
-    const int64_t nblk = (int64_t)regs_x * regs_y * B;
-    if (nblk > INT32_MAX || (int64_t)(H + 8) * (W + 8) * C * 2 >= 0x7fffffff ||
-        (int64_t)H * W * ops > INT32_MAX) {
-        set_error("image too large for 32-bit tile indexing");
-        return QPWC_E_SHAPE;
-    }
-    const float inv_c = (C & (C - 1)) == 0 ? 1.0f / (float)C : 0.0f;
-    if (flo) {
-        if (dry_run("cost_volume_mfma_lds_f16_kernel<true>")) return QPWC_OK;
-        hipLaunchKernelGGL(cost_volume_mfma_lds_f16_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, s, prv, nxt, flo,
-                           out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
-        return check_launch("cost_volume_mfma_lds_f16_kernel<warp>");
-    }
-    if (dry_run("cost_volume_mfma_lds_f16_kernel")) return QPWC_OK;
-    hipLaunchKernelGGL(cost_volume_mfma_lds_f16_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, s, prv, nxt,
-                       (const float*)nullptr, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
-    return check_launch("cost_volume_mfma_lds_f16_kernel");
+    if (flo)
+        return launch_regions("cost_volume_mfma_lds_f16_kernel<true>", "cost_volume_mfma_lds_f16_kernel<warp>",
+                              cost_volume_mfma_lds_f16_kernel<true>, kRegions8, 256, prv, nxt, flo, out, B, H, W, C,
+                              ops, slope, pad84, s);
+    return launch_regions("cost_volume_mfma_lds_f16_kernel", "cost_volume_mfma_lds_f16_kernel",
+                          cost_volume_mfma_lds_f16_kernel<false>, kRegions8, 256, prv, nxt, flo, out, B, H, W, C, ops,
+                          slope, pad84, s);
 }
-
-// This library reads NO environment variable: every rank of a multi-GPU job runs the same kernels.
 
 // Region size policy of the workgroup-shared fp32 kernels (measured, tools/kbench.py --regions):
 // 16 x 16 regions need one workgroup of 16 waves per CU to be worth it.
@@ -1311,9 +1247,10 @@ static int launch_lds_f16(const __half* prv, const __half* nxt, const float* flo
 #define QPWC_R16_MIN_WARP 512    // 16 x 16 regions per launch from which the fused front end takes them (two rounds of
                                  // one-per-CU workgroups; see use_regions16)
 #endif
-static bool use_regions16(int B, int H, int W, int C, bool warp) {
-    const int64_t regs16 = (int64_t)((W + 15) / 16) * ((H + 15) / 16) * B;
-    if ((int64_t)(H + 24) * (W + 24) * C * 4 >= 0x7fffffff) return false;
+static bool use_regions16(int B, int H, int W, int C, int64_t ops, bool warp) {
+    // (only the halo term can fail here: cost_volume_mfma_launch has already applied kTiles4's stricter count and
+    // output limits, as it has for every launcher below)
+    if (!fits_32bit(kRegions16, B, H, W, C, 4, ops)) return false;
     // One workgroup per CU means nothing overlaps a region's staging, matrix and store phases: with a single
     // 32-channel step (C = 32, the finest level) the three phases are of comparable length and the 8 x 8 kernel's
     // three workgroups per CU win (B=8 L4: 48.7 vs 52.7 us); from two steps on the staging share grows and the
@@ -1324,68 +1261,31 @@ static bool use_regions16(int B, int H, int W, int C, bool warp) {
     // 50.7 -> ~45 us in the step's kernel trace, step 1.2027 -> 1.1988 ms (three interleaved pairs of one call).
     // The plain cost volume: never (B=8 L3 19.4 vs 17.6 us, config 4 L1-L3 +5 ... +14 %: its staging is 10 plain loads
     // per lane, not the limiter -- DESIGN.md 4.5).
-    return warp && C >= 64 && regs16 >= QPWC_R16_MIN_WARP;
-}
-
-static int launch_lds16(const float* prv, const float* nxt, const float* flo, float* out, int B, int H, int W, int C,
-                        int64_t ops, float slope, int pad84, hipStream_t s) {
-    const int regs_x = (W + 15) / 16, regs_y = (H + 15) / 16;
-    const int64_t nblk = (int64_t)regs_x * regs_y * B;
-    if (nblk > INT32_MAX || (int64_t)H * W * ops > INT32_MAX) {
-        set_error("image too large for 32-bit tile indexing");
-        return QPWC_E_SHAPE;
-    }
-    const float inv_c = (C & (C - 1)) == 0 ? 1.0f / (float)C : 0.0f;
-    if (flo) {
-        if (dry_run("cost_volume_mfma_lds16_kernel<true>")) return QPWC_OK;
-        hipLaunchKernelGGL(cost_volume_mfma_lds16_kernel<true>, dim3((unsigned)nblk), dim3(1024), 0, s, prv, nxt,
-                           flo, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
-        return check_launch("cost_volume_mfma_lds16_kernel<warp>");
-    }
-    set_error("cost volume on 16 x 16 regions: fused front end only in this build");
-    return QPWC_E_SHAPE;
+    return warp && C >= 64 && count_regions(kRegions16, B, H, W) >= QPWC_R16_MIN_WARP;
 }
 
 #ifndef QPWC_R8X16_MIN
 #define QPWC_R8X16_MIN 512    // 8 x 16 regions per launch from which the single-step fused front end takes them (2 per CU)
 #endif
-static int launch_lds8x16_warp(const float* prv, const float* nxt, const float* flo, float* out, int B, int H, int W,
-                               int C, int64_t ops, float slope, int pad84, hipStream_t s) {
-    const int regs_x = (W + 15) / 16, regs_y = (H + 7) / 8;
-    const int64_t nblk = (int64_t)regs_x * regs_y * B;
-    const float inv_c = (C & (C - 1)) == 0 ? 1.0f / (float)C : 0.0f;
-    if (dry_run("cost_volume_mfma_lds8x16_warp_kernel")) return QPWC_OK;
-    hipLaunchKernelGGL(cost_volume_mfma_lds8x16_warp_kernel, dim3((unsigned)nblk), dim3(512), 0, s, prv, nxt, flo, out,
-                       H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
-    return check_launch("cost_volume_mfma_lds8x16_warp_kernel");
-}
-
 static int launch_lds(const float* prv, const float* nxt, const float* flo, float* out, int B, int H, int W, int C,
                       int64_t ops, float slope, int pad84, hipStream_t s) {
-    if (use_regions16(B, H, W, C, flo != nullptr))
-        return launch_lds16(prv, nxt, flo, out, B, H, W, C, ops, slope, pad84, s);
+    if (use_regions16(B, H, W, C, ops, flo != nullptr))
+        return launch_regions("cost_volume_mfma_lds16_kernel<true>", "cost_volume_mfma_lds16_kernel<warp>",
+                              cost_volume_mfma_lds16_kernel<true>, kRegions16, 1024, prv, nxt, flo, out, B, H, W, C,
+                              ops, slope, pad84, s);
     // 8 x 16 regions for every channel count the 16 x 16 form does not take
-    if (flo && QPWC_R8X16_MIN > 0 && (int64_t)((W + 15) / 16) * ((H + 7) / 8) * B >= QPWC_R8X16_MIN &&
-        (int64_t)(H + 16) * (W + 24) * C * 4 < 0x7fffffff && (int64_t)H * W * ops <= INT32_MAX)
-        return launch_lds8x16_warp(prv, nxt, flo, out, B, H, W, C, ops, slope, pad84, s);
-    const int regs_x = (W + 7) / 8, regs_y = (H + 7) / 8;
-    const int64_t nblk = (int64_t)regs_x * regs_y * B;
-    if (nblk > INT32_MAX || (int64_t)(H + 8) * (W + 8) * C * 4 >= 0x7fffffff ||
-        (int64_t)H * W * ops > INT32_MAX) {
-        set_error("image too large for 32-bit tile indexing");
-        return QPWC_E_SHAPE;
-    }
-    const float inv_c = (C & (C - 1)) == 0 ? 1.0f / (float)C : 0.0f;
-    if (flo) {
-        if (dry_run("cost_volume_mfma_lds_kernel<true>")) return QPWC_OK;
-        hipLaunchKernelGGL(cost_volume_mfma_lds_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, s, prv, nxt,
-                           flo, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
-        return check_launch("cost_volume_mfma_lds_kernel<warp>");
-    }
-    if (dry_run("cost_volume_mfma_lds_kernel")) return QPWC_OK;
-    hipLaunchKernelGGL(cost_volume_mfma_lds_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, s, prv, nxt,
-                       (const float*)nullptr, out, H, W, C, regs_x, regs_y, (int)ops, slope, inv_c, pad84);
-    return check_launch("cost_volume_mfma_lds_kernel");
+    if (flo && QPWC_R8X16_MIN > 0 && count_regions(kRegions8x16, B, H, W) >= QPWC_R8X16_MIN &&
+        fits_32bit(kRegions8x16, B, H, W, C, 4, ops))
+        return launch_regions("cost_volume_mfma_lds8x16_warp_kernel", "cost_volume_mfma_lds8x16_warp_kernel",
+                              cost_volume_mfma_lds8x16_warp_kernel, kRegions8x16, 512, prv, nxt, flo, out, B, H, W, C,
+                              ops, slope, pad84, s);
+    if (flo)
+        return launch_regions("cost_volume_mfma_lds_kernel<true>", "cost_volume_mfma_lds_kernel<warp>",
+                              cost_volume_mfma_lds_kernel<true>, kRegions8, 256, prv, nxt, flo, out, B, H, W, C, ops,
+                              slope, pad84, s);
+    return launch_regions("cost_volume_mfma_lds_kernel", "cost_volume_mfma_lds_kernel",
+                          cost_volume_mfma_lds_kernel<false>, kRegions8, 256, prv, nxt, flo, out, B, H, W, C, ops,
+                          slope, pad84, s);
 }
 
 template <typename T, int CPL, int KS>
@@ -1394,25 +1294,17 @@ static int launch_mfma(const T* prv, const T* nxt, T* out, int B, int H, int W, 
     constexpr int WPB = KS <= 4 ? 4 : KS;
     constexpr int G = WPB / KS;
     const int tiles_x = (W + 3) / 4, tiles_y = (H + 3) / 4;
-    const int64_t n_tiles = (int64_t)tiles_x * tiles_y * B;
-    const int64_t nblk = (n_tiles + G - 1) / G;
-    if (nblk > INT32_MAX || (int64_t)(H + 8) * (W + 8) * C * (int64_t)sizeof(T) >= 0x7fffffff ||
-        (int64_t)H * W * ops > INT32_MAX) {
-        set_error("image too large for 32-bit tile indexing");
-        return QPWC_E_SHAPE;
-    }
-    const float inv_c = (C & (C - 1)) == 0 ? 1.0f / (float)C : 0.0f;  // exact for powers of two
-    if (dry_run("cost_volume_mfma_kernel")) return QPWC_OK;
-    hipLaunchKernelGGL((cost_volume_mfma_kernel<T, CPL, KS, WPB>), dim3((unsigned)nblk),
-                       dim3(64 * WPB), 0, s, prv, nxt, out, H, W, C, tiles_x, tiles_y, (int)n_tiles,
-                       (int)ops, slope, inv_c, pad84);
-    return check_launch("cost_volume_mfma_kernel");
+    const int64_t n_tiles = count_regions(kTiles4, B, H, W);
+    if (!fits_32bit(kTiles4, B, H, W, C, sizeof(T), ops)) return too_large();
+    return launch("cost_volume_mfma_kernel", "cost_volume_mfma_kernel", cost_volume_mfma_kernel<T, CPL, KS, WPB>,
+                  (n_tiles + G - 1) / G, 64 * WPB, s, prv, nxt, out, H, W, C, tiles_x, tiles_y, (int)n_tiles, (int)ops,
+                  slope, exact_inv(C), pad84);
 }
 
 template <typename T, int CPL>
 static int dispatch_mfma(const T* prv, const T* nxt, T* out, int B, int H, int W, int C, int64_t ops,
                          float slope, int pad84, hipStream_t s) {
-    const int64_t n_tiles = (int64_t)((W + 3) / 4) * ((H + 3) / 4) * B;
+    const int64_t n_tiles = count_regions(kTiles4, B, H, W);
     const int nsteps = C / (4 * CPL);
     // enough waves for ~4 per SIMD on 1024 SIMDs; split channels when tiles are few
     int ks = 1;
@@ -1438,15 +1330,11 @@ int cost_volume_mfma_launch(const void* prv, const void* nxt, const void* flo, v
     if (pads_written) *pads_written = false;
     if (C % 16 != 0 || (reinterpret_cast<uintptr_t>(prv) | reinterpret_cast<uintptr_t>(nxt)) % 16)
         return 1;
-    const int64_t regions8 = (int64_t)((W + 7) / 8) * ((H + 7) / 8) * B;
+    const int64_t regions8 = count_regions(kRegions8, B, H, W);
     if (flo && (C % 32 != 0 || reinterpret_cast<uintptr_t>(flo) % 8 || H < 2 || W < 2 || regions8 < QPWC_FUSED_MIN_REGIONS))
         return 1;
-    // 32-bit byte offsets inside one image (buffer descriptors) and 32-bit element offsets
-    // inside one output image: larger problems take the 64-bit vector kernel instead
-    const int64_t es = dtype == QPWC_F16 ? 2 : 4;
-    if ((int64_t)(H + 8) * (W + 8) * C * es >= 0x7fffffff || (int64_t)H * W * ops > INT32_MAX ||
-        (int64_t)((W + 3) / 4) * ((H + 3) / 4) * B > INT32_MAX)
-        return 1;
+    // larger problems take the 64-bit vector kernel instead
+    if (!fits_32bit(kTiles4, B, H, W, C, dtype == QPWC_F16 ? 2 : 4, ops)) return 1;
     if (dtype == QPWC_F32) {
         // >= one region per CU: share the staged neighbourhood across a workgroup (L2 of the 256x512
         // pyramid, 256 regions x 4 steps: 10.2 us vs 11.8 us on the per-wave split-K kernel)
@@ -1463,7 +1351,7 @@ int cost_volume_mfma_launch(const void* prv, const void* nxt, const void* flo, v
         return dispatch_mfma<float, 4>((const float*)prv, (const float*)nxt, (float*)out, B, H, W, C,
                                        ops, slope, pad84, s);
     }
-    if (C % 32 == 0 && (int64_t)((W + 7) / 8) * ((H + 7) / 8) * B >= 256) {
+    if (C % 32 == 0 && regions8 >= 256) {
         if (pads_written)   // dense 8-byte rows of 4 px x 84 halves
             *pads_written = pad84 && W % 4 == 0 && H % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
         return launch_lds_f16((const __half*)prv, (const __half*)nxt, (const float*)flo, (__half*)out, B, H, W, C, ops,

@@ -350,17 +350,34 @@ def test_matrix_core_kernels_ragged_edges(shape):
     np.testing.assert_allclose(outh, refh, rtol=1e-3, atol=1e-3)
 
 
-@pytest.mark.parametrize("shape", [(32, 36, 52, 32), (40, 30, 44, 64), (20, 33, 47, 128), (8, 128, 256, 32),
-                                   (32, 36, 52, 64), (30, 33, 47, 128), (2, 150, 290, 32), (8, 40, 290, 64),
-                                   (32, 50, 70, 64), (44, 33, 60, 128), (48, 33, 47, 96)])   # >= 512 16 x 16 regions; 8 x 16 at C = 96
+# shape -> the fp32 kernel that the fused front end runs on it (fp16 has one workgroup-shared kernel)
+FUSED_SHAPES = {
+    (32, 36, 52, 32): "cost_volume_mfma_lds8x16_warp_kernel",
+    (40, 30, 44, 64): "cost_volume_mfma_lds_kernel<true>",
+    (20, 33, 47, 128): "cost_volume_mfma_lds_kernel<true>",
+    (8, 128, 256, 32): "cost_volume_mfma_lds8x16_warp_kernel",
+    (32, 36, 52, 64): "cost_volume_mfma_lds8x16_warp_kernel",
+    (30, 33, 47, 128): "cost_volume_mfma_lds_kernel<true>",
+    (2, 150, 290, 32): "cost_volume_mfma_lds8x16_warp_kernel",
+    (8, 40, 290, 64): "cost_volume_mfma_lds8x16_warp_kernel",
+    (32, 50, 70, 64): "cost_volume_mfma_lds16_kernel<true>",       # >= 512 16 x 16 regions
+    (44, 33, 60, 128): "cost_volume_mfma_lds16_kernel<true>",
+    (48, 33, 47, 96): "cost_volume_mfma_lds8x16_warp_kernel",      # 8 x 16 at C = 96
+}
+
+
+@pytest.mark.parametrize("shape", list(FUSED_SHAPES))
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=["f32", "f16"])
 def test_fused_front_end_on_the_matrix_cores_ragged_edges_and_far_flows(shape, dtype):
     """qpwc_warp_cost_volume_fwd where the workgroup-shared matrix-core kernel takes it (>= 256 regions, C % 32 == 0):
     H, W not multiples of the 8 x 8 region, flows that leave the image on every side (clamp-to-border taps) and
     land exactly on the last row / column; every output form (dense 81, 84 with zero pads, strided into a concat
     buffer).  The gather blends with the WarpV2 kernel's own code: the result must equal warp -> cost volume bit for
-    bit, and the C oracle within the fp32 / fp16-rounding bound."""
+    bit, and the C oracle within the fp32 / fp16-rounding bound.  The shapes reach every form of the kernel; each
+    names the one it is here for, so that a threshold change cannot quietly stop covering a form."""
     assert non_layers.fused_kernel_applies(torch.empty(shape, device=DEV, dtype=dtype))
+    assert ops.cost_volume_kernel(*shape, dtype, fused=True) == (
+        FUSED_SHAPES[shape] if dtype == torch.float32 else "cost_volume_mfma_lds_f16_kernel<true>")
     B, H, W, C = shape
     g = torch.Generator(device=DEV).manual_seed(H * W + C)
     prv = torch.randn(*shape, device=DEV, generator=g).to(dtype)
