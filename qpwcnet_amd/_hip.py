@@ -180,6 +180,14 @@ MASKED_LOSS_PROTOTYPES = {
 MASKED_LOSS_TILE_BLOCKS, MASKED_LOSS_PIX_BLOCKS = 2048, 1024   # csrc/masked_loss.hip: the grid caps of its two forward kernels
 MASKED_LOSS_THREADS, MASKED_LOSS_TILE = 256, 32                # threads per workgroup, tile edge
 
+# The sparse-ground-truth input pipeline, declared in include/qpwc_sparse_augment.h: a table of its own under the same
+# rules, held to its header by tests/test_sparse_augment_capi_cpu.py.
+SPARSE_AUGMENT_PROTOTYPES = {
+    "qpwc_augment_sparse_fwd": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp,
+                                      _vp]),
+    "qpwc_augment_sparse_fwd_kernel": (_str, [_ci, _ci, _ci]),
+}
+
 _lib = None
 
 
@@ -212,7 +220,8 @@ def lib():
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     L = ctypes.CDLL(LIB_PATH)
     later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES, **QUALITY_PROTOTYPES,
-                 **REVIEW_PROTOTYPES, **FLOW_QUALITY_PROTOTYPES, **MASKED_LOSS_PROTOTYPES)
+                 **REVIEW_PROTOTYPES, **FLOW_QUALITY_PROTOTYPES, **MASKED_LOSS_PROTOTYPES,
+                 **SPARSE_AUGMENT_PROTOTYPES)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
         if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)

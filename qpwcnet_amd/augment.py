@@ -11,7 +11,13 @@ also what ``tools/augbench.py`` times against the kernels.  Outputs are float32.
 The random draw is separate from the arithmetic: ``sample_params`` returns the per-sample parameters as two device
 tensors (``AugmentParams``), which the kernels read from device memory -- no host synchronisation anywhere.
 
-The frame interpolator's pipeline is the second half of the module: three ``(B,H,W,3)`` frames per sample through
+Sparse ground truth (KITTI, Sintel's unknown pixels) goes through ``preprocess_sparse`` / ``preprocess_no_op_sparse`` /
+``image_augment_sparse`` / ``image_resize_sparse``: the same frames, the flow resampled over its valid pixels only and
+a uint8 ``(B,h,w)`` mask of the output pixels that have a label, what ``loss.multiscale_masked`` and
+``metrics.flow_quality`` take as ``valid=`` (``ops.augment_sparse``; ``sparse_torch`` on the CPU).  The reference has
+no such path: its pipeline is dense.
+
+The frame interpolator's pipeline is the last part of the module: three ``(B,H,W,3)`` frames per sample through
 ``preprocess_triplet`` / ``augment_triplet`` (one launch behind ``ops.augment_triplet``; ``triplet_torch`` on the
 CPU), with ``sample_triplet_params`` / ``identity_triplet_params`` as its draws.
 """
@@ -247,6 +253,110 @@ def preprocess_no_op(ims, flo, data_format=CHANNELS_FIRST, out_shape=(256, 512))
     _check_inputs(ims, flo, (torch.uint8, torch.float32))
     B, H, W, _ = ims.shape
     return _run(ims, flo, resize_params(B, (H, W), out_shape, ims.device), out_shape, False, True, data_format)
+
+
+# ---- sparse ground truth (include/qpwc_sparse_augment.h): beyond the reference, whose pipeline is dense ---------------
+def _axis_f32(first, n_in, n_resized, count, flip):
+    """One axis of the kernels' resampling for `count` output indices from first (B,) on: the fp32 source coordinate
+    of ``aug_axis`` (csrc/augment_common.h), every operation separately rounded -> the clamped neighbours lo, hi
+    (B,count) int64, mirrored where flip (B,) is set, and the weight t (B,count) float32 of hi."""
+    i = (first.reshape(-1, 1) + torch.arange(count, device=first.device, dtype=first.dtype)).to(torch.float32)
+    scale = torch.full_like(n_resized, float(n_in), dtype=torch.float32) / n_resized.to(torch.float32)
+    s = (i + 0.5) * scale.reshape(-1, 1) - 0.5
+    f = torch.floor(s)
+    lo, hi = (torch.nan_to_num(v, nan=0.0).clamp(0.0, float(n_in - 1)).to(torch.int64) for v in (f, torch.ceil(s)))
+    mirror = (flip != 0).reshape(-1, 1)
+    return torch.where(mirror, n_in - 1 - lo, lo), torch.where(mirror, n_in - 1 - hi, hi), s - f
+
+
+def flow_validity(flo, valid=None):
+    """(B,H,W) bool: both components of the (B,H,W,2) flow at most ``metrics.FLOW_UNKNOWN`` in magnitude (false for NaN
+    and +-inf) and, with a mask, ``valid != 0``: the rule of the masked losses and the flow scores."""
+    from .metrics import FLOW_UNKNOWN
+    ok = (flo[..., 0].abs() <= FLOW_UNKNOWN) & (flo[..., 1].abs() <= FLOW_UNKNOWN)
+    return ok if valid is None else ok & (valid != 0)
+
+
+def sparse_torch(ims, flo, valid, params, out_shape, colour=True, finish=True, data_format=CHANNELS_LAST):
+    """What ``ops.augment_sparse`` computes, composed from torch operators on the tensors' own device: the CPU path, and
+    the baseline tools/sparseaugbench.py times the kernel against.  The frames are ``augment_torch``'s.  The flow's
+    corners and weights are the kernel's fp32 values (``_axis_f32``); invalid pixels are zeroed by a select before
+    anything reads them; an output pixel with four valid corners takes ``augment_torch``'s flow of the zero-filled
+    source (the dense value), one with one to three the weighted sum over the sum of the valid weights, one with none
+    zero.  -> (ims, flo, valid), valid uint8 (B,h,w)."""
+    get_axis(data_format)
+    h, w = (int(v) for v in out_shape)
+    B, H, W, _ = ims.shape
+    ok = flow_validity(flo, valid)
+    flo = torch.where(ok.unsqueeze(-1), flo, torch.zeros((), dtype=flo.dtype, device=flo.device))
+    o_ims, dense = augment_torch(ims, flo, params, out_shape, colour=colour, finish=finish, data_format=CHANNELS_LAST)
+    ip, fp = params.iparams.to(ims.device), params.fparams.to(ims.device)
+    y0, y1, ty = _axis_f32(ip[:, 2], H, ip[:, 0], h, ip[:, 4])
+    x0, x1, tx = _axis_f32(ip[:, 3], W, ip[:, 1], w, ip[:, 5])
+    ty, tx = ty.reshape(B, h, 1), tx.reshape(B, 1, w)
+    ly, lx = (1.0 - ty, ty), (1.0 - tx, tx)
+    b = torch.arange(B, device=ims.device).reshape(B, 1, 1)
+    zero = torch.zeros((), dtype=torch.float32, device=ims.device)
+    S, num, n = None, None, None
+    for ky, yy in enumerate((y0, y1)):                                         # corners 00, 01, 10, 11, in this order
+        for kx, xx in enumerate((x0, x1)):
+            at = (b, yy.reshape(B, h, 1), xx.reshape(B, 1, w))
+            v = ok[at]
+            wk = torch.where(v, ly[ky] * lx[kx], zero)
+            term = wk.unsqueeze(-1) * flo[at]
+            S, num, n = (wk, term, v.to(torch.int32)) if S is None else (S + wk, num + term, n + v)
+    some = n > 0
+    part = num / torch.where(some, S, torch.ones_like(S)).unsqueeze(-1) * fp[:, None, None, 0:2]
+    o_flo = torch.where((n == 4).unsqueeze(-1), dense, torch.where(some.unsqueeze(-1), part, zero))
+    o_valid = some.to(torch.uint8)
+    if data_format == CHANNELS_FIRST:
+        return o_ims.permute(0, 3, 1, 2).contiguous(), o_flo.permute(0, 3, 1, 2).contiguous(), o_valid
+    return o_ims.contiguous(), o_flo.contiguous(), o_valid
+
+
+def _run_sparse(ims, flo, valid, params, out_shape, colour, finish, data_format):
+    from .metrics import _flow_mask
+    valid = _flow_mask("valid", valid, flo, tuple(flo.shape[:3]))
+    if ims.is_cuda:
+        return ops.augment_sparse(ims, flo, None if valid is None else valid.contiguous(), params.iparams, params.fparams,
+                                  out_shape, colour=colour, finish=finish, data_format=data_format)
+    return sparse_torch(ims, flo, valid, params, out_shape, colour=colour, finish=finish, data_format=data_format)
+
+
+def image_augment_sparse(ims, flo, out_shape, valid=None, base_scale=1.0, params=None, generator=None):
+    """``image_augment`` for sparse ground truth -> (ims, flo, valid), channels_last: the same frames; the flow over its
+    valid pixels only (``flow_validity``; valid: None, bool, uint8 or floating (B,H,W)), exactly 0 where no corner is
+    valid; valid uint8 (B,h,w), what ``loss.multiscale_masked`` and ``metrics.flow_quality`` take."""
+    _check_inputs(ims, flo, (torch.float32,))
+    return _run_sparse(ims, flo, valid, _drawn(ims, out_shape, base_scale, params, generator), out_shape, True, False,
+                       CHANNELS_LAST)
+
+
+def image_resize_sparse(ims, flo, shape, valid=None):
+    """``image_resize`` for sparse ground truth -> (ims, flo, valid), channels_last (``image_augment_sparse``)."""
+    _check_inputs(ims, flo, (torch.float32,))
+    B, H, W, _ = ims.shape
+    return _run_sparse(ims, flo, valid, resize_params(B, (H, W), shape, ims.device), shape, False, False, CHANNELS_LAST)
+
+
+def preprocess_sparse(ims, flo, valid=None, data_format=CHANNELS_FIRST, base_scale=1.0, out_shape=(256, 512),
+                      params=None, generator=None):
+    """``preprocess`` for sparse ground truth (KITTI, Sintel's unknown pixels) -> (ims, flo, valid): the frames of
+    ``preprocess`` bit for bit, the flow in data_format resampled over its valid pixels only -- no false zero next to
+    a hole, no blend with a 1e10 "unknown" -- and the uint8 (B,h,w) mask of the output pixels that have a label."""
+    get_axis(data_format)
+    _check_inputs(ims, flo, (torch.uint8, torch.float32))
+    return _run_sparse(ims, flo, valid, _drawn(ims, out_shape, base_scale, params, generator), out_shape, True, True,
+                       data_format)
+
+
+def preprocess_no_op_sparse(ims, flo, valid=None, data_format=CHANNELS_FIRST, out_shape=(256, 512)):
+    """``preprocess_no_op`` (the validation path) for sparse ground truth -> (ims, flo, valid) (``preprocess_sparse``)."""
+    get_axis(data_format)
+    _check_inputs(ims, flo, (torch.uint8, torch.float32))
+    B, H, W, _ = ims.shape
+    return _run_sparse(ims, flo, valid, resize_params(B, (H, W), out_shape, ims.device), out_shape, False, True,
+                       data_format)
 
 
 # ---- the frame interpolator's triplets (qpwcnet/data/triplet_dataset_ops.py, data/augment.py:10-59,

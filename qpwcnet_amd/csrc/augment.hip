@@ -11,6 +11,10 @@
 // Lanes of a wave read neighbouring source pixels (a 6-byte uint8 pixel is three 2-byte loads: pixel addresses are even,
 // never dword aligned) and, in the <vec4> form, the workgroup's 256 pixels leave through LDS in the output's own memory
 // order as 16-byte stores.  No atomics: two runs are bit-identical.
+// Sparse ground truth (augment_sparse_pixel_kernel, include/qpwc_sparse_augment.h) is the same pass 1 with another flow
+// rule: the four flow corners and their mask bytes are loaded like the frames', the invalid ones are selected out, the
+// rest are weighted over their own sum, and the pixel's validity leaves as a byte beside the flow.  A gather: every
+// output pixel is written once, by the lane that owns it.
 #include "augment_common.h"
 #include "launch.h"
 #include "pixel_io.h"
@@ -62,18 +66,54 @@ __device__ __forceinline__ void aug_colour(float& r, float& g, float& b, float b
 
 __device__ __forceinline__ float aug_scrub(float v) { return v != v ? 0.0f : v; }
 
+constexpr float kAugFlowUnknown = 1e9f;   // a flow component above it in magnitude marks the pixel unknown
+
+// The flow of one output pixel from its four corners (00, 01, 10, 11) over the valid ones only
+// (include/qpwc_sparse_augment.h): ok[k] = both components within kAugFlowUnknown and the mask byte non-zero.  An
+// invalid corner's components are replaced before any arithmetic sees them.  Four valid corners give aug_lerp2's value;
+// fewer the weighted sum over the sum of the valid weights, which is positive where there is one; none 0.
+// Returns the number of valid corners.
+__device__ __forceinline__ int aug_sparse_flow(const float2* f, const unsigned* m, float tx, float ty, float& u, float& v) {
+    bool ok[4];
+    float fx[4], fy[4];
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        ok[k] = fabsf(f[k].x) <= kAugFlowUnknown && fabsf(f[k].y) <= kAugFlowUnknown && m[k] != 0;   // NaN: false
+        fx[k] = ok[k] ? f[k].x : 0.0f;
+        fy[k] = ok[k] ? f[k].y : 0.0f;
+        n += ok[k] ? 1 : 0;
+    }
+    const float ly0 = 1.0f - ty, lx0 = 1.0f - tx;
+    const float wgt[4] = {ly0 * lx0, ly0 * tx, ty * lx0, ty * tx};
+    float S = 0.0f, su = 0.0f, sv = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float wk = ok[k] ? wgt[k] : 0.0f;
+        S += wk;
+        su += wk * fx[k];
+        sv += wk * fy[k];
+    }
+    const float du = aug_lerp2(fx[0], fx[1], fx[2], fx[3], tx, ty), dv = aug_lerp2(fy[0], fy[1], fy[2], fy[3], tx, ty);
+    const float safe = n > 0 ? S : 1.0f;                 // n = 0: 0 / 1
+    u = n == 4 ? du : su / safe;
+    v = n == 4 ? dv : sv / safe;
+    return n;
+}
+
 }  // namespace
 
-// blockIdx.x = sample * nblk + chunk; the chunk's 256 consecutive pixels (row-major over the h x w output), one per lane.
-template <bool U8, int LAYOUT, bool VEC>
-__global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* __restrict__ ims,
-                                                                   const float* __restrict__ flo, int H, int W,
-                                                                   const int* __restrict__ iparams,
-                                                                   const float* __restrict__ fparams, int h, int w,
-                                                                   int nblk, int flags, float* __restrict__ out_ims,
-                                                                   float* __restrict__ out_flo,
-                                                                   float* __restrict__ partial) {
+// Pass 1 of both pipelines.  blockIdx.x = sample * nblk + chunk; the chunk's 256 consecutive pixels (row-major over the
+// h x w output), one per lane.  SPARSE: the flow over its valid corners and out_valid; MASKED: `valid` is given.
+template <bool U8, int LAYOUT, bool VEC, bool SPARSE, bool MASKED>
+__device__ __forceinline__ void aug_pixel_pass(const void* __restrict__ ims, const float* __restrict__ flo,
+                                               const uint8_t* __restrict__ valid_in, int H, int W,
+                                               const int* __restrict__ iparams, const float* __restrict__ fparams,
+                                               int h, int w, int nblk, int flags, float* __restrict__ out_ims,
+                                               float* __restrict__ out_flo, uint8_t* __restrict__ out_valid,
+                                               float* __restrict__ partial) {
     __shared__ pix_f32x4 stage4[kAugThreads * 8 / 4];   // <vec4>: the chunk in output order, image then flow (8 KB)
+    __shared__ uint32_t stagem[SPARSE && VEC ? kAugThreads / 4 : 1];   // <vec4>, sparse: the chunk's mask bytes
     __shared__ float red[3][kAugThreads / 64];
     const int tid = threadIdx.x;
     const int b = blockIdx.x / nblk, chunk = blockIdx.x - b * nblk;
@@ -91,6 +131,7 @@ __global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* 
     float v[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) v[c] = 0.0f;
+    int corners = 0;                                     // sparse: the pixel's valid flow corners
     if (valid) {
         const int y = pix / w, x = pix - y * w;
         const AugAxis ay = aug_axis(oy + y, H, rh), ax = aug_axis(ox + x, W, rw);
@@ -119,10 +160,23 @@ __global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* 
         c_[6] = fc.x; c_[7] = fc.y;
         d[6] = fd.x; d[7] = fd.y;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = aug_lerp2(a[c], bb[c], c_[c], d[c], tx, ty);
+        for (int c = 0; c < (SPARSE ? 6 : 8); ++c) v[c] = aug_lerp2(a[c], bb[c], c_[c], d[c], tx, ty);
+        if (SPARSE) {
+            // the four mask bytes are loaded like the flow corners, whatever they will be selected to
+            const float2 fk[4] = {fa, fb, fc, fd};
+            unsigned mk[4] = {1u, 1u, 1u, 1u};
+            if (MASKED) {
+                mk[0] = valid_in[p00];
+                mk[1] = valid_in[p01];
+                mk[2] = valid_in[p10];
+                mk[3] = valid_in[p11];
+            }
+            corners = aug_sparse_flow(fk, mk, tx, ty, v[6], v[7]);
+        }
         v[6] *= mu;
         v[7] *= mv;
-        if (!raw) {
+        if (SPARSE && corners == 0) v[6] = v[7] = 0.0f;   // + 0 whatever the multipliers' signs
+        if (!SPARSE && !raw) {
             v[6] = aug_scrub(v[6]);
             v[7] = aug_scrub(v[7]);
         }
@@ -159,11 +213,37 @@ __global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* 
 #pragma unroll
         for (int c = 0; c < 2; ++c) Flo::put(sflo, out_flo, obase, hw, base, tid, c, v[6 + c]);
     }
+    using Msk = TileStore<VEC, LAYOUT, 1, kAugThreads, kAugThreads, uint8_t>;
+    uint8_t* smsk = reinterpret_cast<uint8_t*>(stagem);
+    if (SPARSE && (VEC || valid)) Msk::put(smsk, out_valid, obase, hw, base, tid, 0, (uint8_t)(corners > 0));
     if (!VEC) return;
     __syncthreads();
     const int n = min(kAugThreads, hw - base);
     Ims::flush(sims, out_ims, obase, hw, base, n);
     Flo::flush(sflo, out_flo, obase, hw, base, n);
+    if (SPARSE) Msk::flush(smsk, out_valid, obase, hw, base, n);
+}
+
+template <bool U8, int LAYOUT, bool VEC>
+__global__ __launch_bounds__(kAugThreads) void augment_pixel_kernel(const void* __restrict__ ims,
+                                                                   const float* __restrict__ flo, int H, int W,
+                                                                   const int* __restrict__ iparams,
+                                                                   const float* __restrict__ fparams, int h, int w,
+                                                                   int nblk, int flags, float* __restrict__ out_ims,
+                                                                   float* __restrict__ out_flo,
+                                                                   float* __restrict__ partial) {
+    aug_pixel_pass<U8, LAYOUT, VEC, false, false>(ims, flo, nullptr, H, W, iparams, fparams, h, w, nblk, flags, out_ims,
+                                                  out_flo, nullptr, partial);
+}
+
+template <bool U8, int LAYOUT, bool VEC, bool MASKED>
+__global__ __launch_bounds__(kAugThreads) void augment_sparse_pixel_kernel(
+    const void* __restrict__ ims, const float* __restrict__ flo, const uint8_t* __restrict__ valid, int H, int W,
+    const int* __restrict__ iparams, const float* __restrict__ fparams, int h, int w, int nblk, int flags,
+    float* __restrict__ out_ims, float* __restrict__ out_flo, uint8_t* __restrict__ out_valid,
+    float* __restrict__ partial) {
+    aug_pixel_pass<U8, LAYOUT, VEC, true, MASKED>(ims, flo, valid, H, W, iparams, fparams, h, w, nblk, flags, out_ims,
+                                                  out_flo, out_valid, partial);
 }
 
 // blockIdx.x = sample * nblk2 + chunk of kAugPass2Pixels pixels: adjust_contrast with the mean of each colour channel
@@ -244,6 +324,20 @@ static bool aug_vec(int h, int w, const void* out_ims, const void* out_flo) {
     return ((int64_t)h * w) % 4 == 0 && (uintptr_t)out_ims % 16 == 0 && (uintptr_t)out_flo % 16 == 0;
 }
 
+// pass 2 of both pipelines
+static int aug_contrast_launch(int B, const float* fparams, int h, int w, int nblk, int flags, int layout, bool vec,
+                               float* out_ims, const float* ws, hipStream_t s) {
+    const int nblk2 = (int)ceil_div((int64_t)h * w, kAugPass2Pixels);
+    const dim3 grid2((unsigned)(B * nblk2)), block(kAugThreads);
+    dispatch_layout(layout, [&](auto L) {
+        dispatch_bool(vec, [&](auto V) {
+            hipLaunchKernelGGL((augment_contrast_kernel<decltype(L)::value, decltype(V)::value>), grid2, block, 0, s,
+                               out_ims, ws, fparams, h, w, nblk, nblk2, flags & QPWC_AUGMENT_RAW);
+        });
+    });
+    return check_launch("augment_contrast_kernel");
+}
+
 const char* augment_fwd_kernel(int h, int w, const void* out_ims, const void* out_flo) {
     return aug_vec(h, w, out_ims, out_flo) ? "augment_pixel_kernel<vec4>" : "augment_pixel_kernel<scalar>";
 }
@@ -262,17 +356,41 @@ int augment_fwd_launch(const void* ims, bool u8, const float* flo, int B, int H,
             });
         });
     });
-    int rc = check_launch("augment_pixel_kernel");
+    const int rc = check_launch("augment_pixel_kernel");
     if (rc != QPWC_OK || !(flags & QPWC_AUGMENT_COLOR)) return rc;
-    const int nblk2 = (int)ceil_div((int64_t)h * w, kAugPass2Pixels);
-    const dim3 grid2((unsigned)(B * nblk2));
-    dispatch_layout(layout, [&](auto L) {
-        dispatch_bool(vec, [&](auto V) {
-            hipLaunchKernelGGL((augment_contrast_kernel<decltype(L)::value, decltype(V)::value>), grid2, block, 0, s,
-                               out_ims, ws, fparams, h, w, nblk, nblk2, flags & QPWC_AUGMENT_RAW);
+    return aug_contrast_launch(B, fparams, h, w, nblk, flags, layout, vec, out_ims, ws, s);
+}
+
+// the sparse pipeline's form follows from the shape alone: qpwc_augment_sparse_fwd refuses outputs off its grid
+static bool aug_sparse_vec(int h, int w) { return ((int64_t)h * w) % 4 == 0; }
+
+const char* augment_sparse_fwd_kernel(int h, int w) {
+    return aug_sparse_vec(h, w) ? "augment_sparse_pixel_kernel<vec4>" : "augment_sparse_pixel_kernel<scalar>";
+}
+
+size_t augment_sparse_out_align(int h, int w) { return aug_sparse_vec(h, w) ? 16 : 4; }
+
+int augment_sparse_fwd_launch(const void* ims, bool u8, const float* flo, const unsigned char* valid, int B, int H, int W,
+                              const int* iparams, const float* fparams, int h, int w, int flags, int layout,
+                              float* out_ims, float* out_flo, unsigned char* out_valid, float* ws, hipStream_t s) {
+    const int nblk = (int)aug_nblk(h, w);
+    const bool vec = aug_sparse_vec(h, w);
+    const dim3 grid((unsigned)(B * nblk)), block(kAugThreads);
+    dispatch_bool(u8, [&](auto U) {
+        dispatch_layout(layout, [&](auto L) {
+            dispatch_bool(vec, [&](auto V) {
+                dispatch_bool(valid != nullptr, [&](auto M) {
+                    hipLaunchKernelGGL((augment_sparse_pixel_kernel<decltype(U)::value, decltype(L)::value,
+                                                                    decltype(V)::value, decltype(M)::value>),
+                                       grid, block, 0, s, ims, flo, valid, H, W, iparams, fparams, h, w, nblk, flags,
+                                       out_ims, out_flo, out_valid, ws);
+                });
+            });
         });
     });
-    return check_launch("augment_contrast_kernel");
+    const int rc = check_launch("augment_sparse_pixel_kernel");
+    if (rc != QPWC_OK || !(flags & QPWC_AUGMENT_COLOR)) return rc;
+    return aug_contrast_launch(B, fparams, h, w, nblk, flags, layout, vec, out_ims, ws, s);
 }
 
 }  // namespace qpwc

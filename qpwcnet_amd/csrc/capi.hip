@@ -11,6 +11,7 @@
 #include "../../include/qpwc_optim.h"
 #include "../../include/qpwc_quality.h"
 #include "../../include/qpwc_review.h"
+#include "../../include/qpwc_sparse_augment.h"
 #include "../../include/qpwc_triplet.h"
 #include "../../include/qpwc_vis.h"
 #include "launch.h"
@@ -652,6 +653,45 @@ int qpwc_augment_fwd(const void* ims, int ims_dtype, const void* flo, int B, int
     return augment_fwd_launch(ims, u8, (const float*)flo, B, H, W, (const int*)iparams, (const float*)fparams, h, w,
                               flags, layout, (float*)out_ims, (float*)out_flo, (float*)workspace,
                               (hipStream_t)stream);
+}
+
+const char* qpwc_augment_sparse_fwd_kernel(int B, int h, int w) {
+    if (augment_check_shapes(B, 1, 1, h, w) != QPWC_OK) return "";
+    return augment_sparse_fwd_kernel(h, w);
+}
+
+int qpwc_augment_sparse_fwd(const void* ims, int ims_dtype, const void* flo, const void* valid, int B, int H, int W,
+                            const void* iparams, const void* fparams, int h, int w, int flags, int layout, void* out_ims,
+                            void* out_flo, void* out_valid, void* workspace, void* stream) {
+    if (flags & ~(QPWC_AUGMENT_COLOR | QPWC_AUGMENT_RAW)) return fail(QPWC_E_MODE, "unknown augment flags 0x%x", flags);
+    const bool colour = flags & QPWC_AUGMENT_COLOR;
+    if (!ims || !flo || !iparams || !fparams || !out_ims || !out_flo || !out_valid || (colour && !workspace))
+        return fail(QPWC_E_NULL, "null pointer argument");
+    if (ims_dtype != QPWC_F32 && ims_dtype != QPWC_U8) return fail(QPWC_E_DTYPE, "unsupported image dtype %d", ims_dtype);
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    int rc = augment_check_shapes(B, H, W, h, w);
+    if (rc != QPWC_OK) return rc;
+    const bool u8 = ims_dtype == QPWC_U8;
+    const size_t src_px = (size_t)B * H * W, out_px = (size_t)B * h * w;
+    // the sources as qpwc_augment_fwd reads them, the mask byte by byte; the form follows from the shape and decides the
+    // grid the outputs must be on: the kernel does not look at the pointers
+    const size_t oalign = augment_sparse_out_align(h, w);
+    BufCheck bufs[9];
+    int k = 0;
+    bufs[k++] = indexed_buf(ims, src_px * 6 * (u8 ? 1 : 4), u8 ? 2 : 8, "ims", 0);
+    bufs[k++] = indexed_buf(flo, src_px * 2 * 4, 8, "flo", 0);
+    if (valid) bufs[k++] = indexed_buf(valid, src_px, 1, "valid", 0);
+    bufs[k++] = indexed_buf(iparams, (size_t)B * 6 * 4, 4, "iparams", 0);
+    bufs[k++] = indexed_buf(fparams, (size_t)B * 6 * 4, 4, "fparams", 0);
+    const int n_in = k;
+    bufs[k++] = indexed_buf(out_ims, out_px * 6 * 4, oalign, "out_ims", 0);
+    bufs[k++] = indexed_buf(out_flo, out_px * 2 * 4, oalign, "out_flo", 0);
+    bufs[k++] = indexed_buf(out_valid, out_px, oalign / 4, "out_valid", 0);
+    if (colour) bufs[k++] = indexed_buf(workspace, (size_t)augment_workspace_floats(B, h, w) * 4, 4, "workspace", 0);
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return augment_sparse_fwd_launch(ims, u8, (const float*)flo, (const unsigned char*)valid, B, H, W,
+                                     (const int*)iparams, (const float*)fparams, h, w, flags, layout, (float*)out_ims,
+                                     (float*)out_flo, (unsigned char*)out_valid, (float*)workspace, (hipStream_t)stream);
 }
 
 int qpwc_epe_workspace_floats(void) { return epe_workspace_floats(); }

@@ -147,6 +147,13 @@ const char* augment_fwd_kernel(int h, int w, const void* out_ims, const void* ou
 int augment_fwd_launch(const void* ims, bool u8, const float* flo, int B, int H, int W, const int* iparams,
                        const float* fparams, int h, int w, int flags, int layout, float* out_ims, float* out_flo,
                        float* ws, hipStream_t s);
+// the sparse-ground-truth pipeline (include/qpwc_sparse_augment.h); out_align: what out_ims and out_flo must be aligned
+// to in the form the shape takes, out_valid to a quarter of it
+const char* augment_sparse_fwd_kernel(int h, int w);
+size_t augment_sparse_out_align(int h, int w);
+int augment_sparse_fwd_launch(const void* ims, bool u8, const float* flo, const unsigned char* valid, int B, int H, int W,
+                              const int* iparams, const float* fparams, int h, int w, int flags, int layout,
+                              float* out_ims, float* out_flo, unsigned char* out_valid, float* ws, hipStream_t s);
 
 // interp.hip
 int64_t image_head_bwd_workspace_floats(int64_t M);

@@ -1178,20 +1178,14 @@ def augment_kernel(B, h, w, out_ims=None, out_flo=None):
     return name.decode() if name else ""
 
 
-def augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, data_format=CHANNELS_LAST):
-    """The training input pipeline of one batch (qpwc_augment_fwd; qpwcnet/data/augment.py:83-173, train.py:54-94):
-    ims (B,H,W,6) uint8 (taken times 1/255) or float32, flo (B,H,W,2) float32, both dense channels-last on one HIP
-    device; iparams (B,6) int32 = rh, rw, oy, ox, flip_ud, flip_lr and fparams (B,6) float32 = mu, mv, brightness,
-    saturation, hue, contrast on the same device (include/qpwc.h) -> (ims, flo) fp32 of spatial size out_shape in
-    data_format, written in that layout by the kernels.  colour=False: no colour stage; finish=False: no - 0.5 and no
-    NaN scrub.  Enqueues and returns: no host synchronisation."""
-    get_axis(data_format)
+def _augment_operands(what, ims, flo, iparams, fparams, out_shape):
+    """The checks ``augment`` and ``augment_sparse`` share -> (B, H, W, h, w)."""
     for name, t, dt, c in (("ims", ims, (torch.uint8, torch.float32), 6), ("flo", flo, (torch.float32,), 2)):
         if not isinstance(t, torch.Tensor):
             raise TypeError("{} must be a torch.Tensor".format(name))
         if not t.is_cuda:
-            raise RuntimeError("qpwcnet_amd: {} is on '{}'; ops.augment runs on a HIP device only (augment.* has the "
-                               "CPU path)".format(name, t.device))
+            raise RuntimeError("qpwcnet_amd: {} is on '{}'; ops.{} runs on a HIP device only (augment.* has the "
+                               "CPU path)".format(name, t.device, what))
         if t.dtype not in dt:
             raise ValueError("{}: unsupported dtype {}".format(name, t.dtype))
         if t.dim() != 4 or t.shape[3] != c:
@@ -1209,10 +1203,11 @@ def augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, dat
     h, w = (int(v) for v in out_shape)
     if h <= 0 or w <= 0:
         raise ValueError("non-positive output shape {}".format((h, w)))
-    L = _hip.lib()
-    dev = ims.device
-    flags = (_hip.AUGMENT_COLOR if colour else 0) | (0 if finish else _hip.AUGMENT_RAW)
-    nhwc = data_format == CHANNELS_LAST
+    return B, H, W, h, w
+
+
+def _augment_outputs(L, B, h, w, colour, nhwc, dev):
+    """out_ims, out_flo and the colour stage's workspace (None without it), fresh from torch's allocator."""
     out_ims = torch.empty((B, h, w, 6) if nhwc else (B, 6, h, w), dtype=torch.float32, device=dev)
     out_flo = torch.empty((B, h, w, 2) if nhwc else (B, 2, h, w), dtype=torch.float32, device=dev)
     ws = None
@@ -1220,6 +1215,23 @@ def augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, dat
         nws = L.qpwc_augment_workspace_floats(B, h, w)
         _hip.check(min(int(nws), 0))
         ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+    return out_ims, out_flo, ws
+
+
+def augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, data_format=CHANNELS_LAST):
+    """The training input pipeline of one batch (qpwc_augment_fwd; qpwcnet/data/augment.py:83-173, train.py:54-94):
+    ims (B,H,W,6) uint8 (taken times 1/255) or float32, flo (B,H,W,2) float32, both dense channels-last on one HIP
+    device; iparams (B,6) int32 = rh, rw, oy, ox, flip_ud, flip_lr and fparams (B,6) float32 = mu, mv, brightness,
+    saturation, hue, contrast on the same device (include/qpwc.h) -> (ims, flo) fp32 of spatial size out_shape in
+    data_format, written in that layout by the kernels.  colour=False: no colour stage; finish=False: no - 0.5 and no
+    NaN scrub.  Enqueues and returns: no host synchronisation."""
+    get_axis(data_format)
+    B, H, W, h, w = _augment_operands("augment", ims, flo, iparams, fparams, out_shape)
+    L = _hip.lib()
+    dev = ims.device
+    flags = (_hip.AUGMENT_COLOR if colour else 0) | (0 if finish else _hip.AUGMENT_RAW)
+    nhwc = data_format == CHANNELS_LAST
+    out_ims, out_flo, ws = _augment_outputs(L, B, h, w, colour, nhwc, dev)
     with torch.cuda.device(dev), _timed("augment", (B, H, W, h, w)):
         rc = L.qpwc_augment_fwd(ims.data_ptr(), _hip.U8 if ims.dtype == torch.uint8 else _hip.F32, flo.data_ptr(), B, H, W,
                                 iparams.data_ptr(), fparams.data_ptr(), h, w, flags,
@@ -1227,6 +1239,42 @@ def augment(ims, flo, iparams, fparams, out_shape, colour=True, finish=True, dat
                                 None if ws is None else ws.data_ptr(), _stream(ims))
     _hip.check(rc)
     return out_ims, out_flo
+
+
+def augment_sparse_kernel(B, h, w):
+    """Form of the first launch of ``qpwc_augment_sparse_fwd`` for a (h, w) output
+    ('augment_sparse_pixel_kernel<vec4>' / 'augment_sparse_pixel_kernel<scalar>', by the shape alone; host only).  ''
+    for shapes the entry point refuses."""
+    name = _hip.lib().qpwc_augment_sparse_fwd_kernel(int(B), int(h), int(w))
+    return name.decode() if name else ""
+
+
+def augment_sparse(ims, flo, valid, iparams, fparams, out_shape, colour=True, finish=True, data_format=CHANNELS_LAST):
+    """The training input pipeline for sparse ground truth (qpwc_augment_sparse_fwd, include/qpwc_sparse_augment.h;
+    beyond the reference, whose pipeline is dense): the operands of ``augment`` and valid, None or a dense uint8
+    (B,H,W) tensor on the same device -> (ims, flo, valid): ``augment``'s frames bit for bit, the flow resampled over
+    its valid corners only (finite where the mask is 1, exactly 0 where it is 0) and the level-0 mask, uint8 (B,h,w)
+    in both layouts.  The outputs are allocated here, on the grid the kernels' stores need.  Enqueues and returns: no
+    host synchronisation."""
+    get_axis(data_format)
+    B, H, W, h, w = _augment_operands("augment_sparse", ims, flo, iparams, fparams, out_shape)
+    dev = ims.device
+    if valid is not None and not (isinstance(valid, torch.Tensor) and valid.dtype == torch.uint8
+                                  and tuple(valid.shape) == (B, H, W) and valid.device == dev and valid.is_contiguous()):
+        raise ValueError("valid must be None or a dense uint8 tensor of shape {} on {}".format((B, H, W), dev))
+    L = _hip.lib()
+    flags = (_hip.AUGMENT_COLOR if colour else 0) | (0 if finish else _hip.AUGMENT_RAW)
+    nhwc = data_format == CHANNELS_LAST
+    out_ims, out_flo, ws = _augment_outputs(L, B, h, w, colour, nhwc, dev)
+    out_valid = torch.empty((B, h, w), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _timed("augment_sparse", (B, H, W, h, w)):
+        rc = L.qpwc_augment_sparse_fwd(ims.data_ptr(), _hip.U8 if ims.dtype == torch.uint8 else _hip.F32, flo.data_ptr(),
+                                       None if valid is None else valid.data_ptr(), B, H, W, iparams.data_ptr(),
+                                       fparams.data_ptr(), h, w, flags, _hip.NHWC if nhwc else _hip.NCHW,
+                                       out_ims.data_ptr(), out_flo.data_ptr(), out_valid.data_ptr(),
+                                       None if ws is None else ws.data_ptr(), _stream(ims))
+    _hip.check(rc)
+    return out_ims, out_flo, out_valid
 
 
 def augment_triplet_kernel(B, h, w, out_pair=None, out_mid=None):
