@@ -13,6 +13,7 @@
 #include "../../include/qpwc_review.h"
 #include "../../include/qpwc_sparse_augment.h"
 #include "../../include/qpwc_triplet.h"
+#include "../../include/qpwc_unsup_loss.h"
 #include "../../include/qpwc_vis.h"
 #include "launch.h"
 
@@ -142,6 +143,32 @@ static int masked_loss_check_shapes(int kind, int B, int H, int W, int C, const 
     if (kind < QPWC_LOSS_FLOW_MSE_V2 || kind > QPWC_LOSS_FLOW_FINETUNE)
         return fail(QPWC_E_MODE, "loss kind %d is not one of the three flow losses", kind);
     return loss_check_shapes(kind, B, H, W, C, h, w, n_levels);
+}
+
+// the kind and shape rules of the label-free losses, shared by qpwc_unsup_loss_workspace_floats / _fwd / _fwd_kernel /
+// _bwd: the kernels index a level's pixels and all levels' tiles in 32 bits
+static int unsup_loss_check_shapes(int kind, int B, const int* h, const int* w, int n_levels) {
+    if (kind != QPWC_UNSUP_CENSUS && kind != QPWC_UNSUP_CHARBONNIER)
+        return fail(QPWC_E_MODE, "unknown photometric kind %d", kind);
+    if (n_levels < 1 || n_levels > 8) return fail(QPWC_E_SHAPE, "n_levels %d outside [1,8]", n_levels);
+    if (B <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d", B);
+    for (int i = 0; i < n_levels; ++i) {
+        if (h[i] <= 0 || w[i] <= 0) return fail(QPWC_E_SHAPE, "level %d: non-positive extent %dx%d", i, h[i], w[i]);
+        if ((int64_t)B * h[i] * w[i] > INT32_MAX)
+            return fail(QPWC_E_SHAPE, "level %d: B=%d %dx%d is more than 2^31 - 1 pixels", i, B, h[i], w[i]);
+    }
+    if (unsup_loss_total_tiles(B, h, w, n_levels) > INT32_MAX)
+        return fail(QPWC_E_SHAPE, "B=%d: more than 2^31 - 1 tiles in all levels", B);
+    return QPWC_OK;
+}
+
+// the parameter ranges the label-free losses share (a NaN fails both comparisons)
+static int unsup_loss_check_range(std::initializer_list<float> positive, std::initializer_list<float> non_negative) {
+    for (float v : positive)
+        if (!(v > 0.0f)) return fail(QPWC_E_RANGE, "q, eps and smooth_eps must be > 0, got %g", (double)v);
+    for (float v : non_negative)
+        if (!(v >= 0.0f)) return fail(QPWC_E_RANGE, "edge and smooth_weight must be >= 0, got %g", (double)v);
+    return QPWC_OK;
 }
 
 // the shape rules of the input pipeline, shared by qpwc_augment_workspace_floats / _fwd / _fwd_kernel
@@ -1806,6 +1833,87 @@ int qpwc_masked_loss_bwd(int kind, const void* const* dpred, const void* counts,
     if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
     return masked_loss_bwd_launch(kind, dpred, (const int64_t*)counts, (const float*)grad_losses, grad_pred, n_elems,
                                   pred_dtype, n_levels, (hipStream_t)stream);
+}
+
+int64_t qpwc_unsup_loss_workspace_floats(int kind, int B, const int* h, const int* w, int n_levels) {
+    if (!h || !w) return fail(QPWC_E_NULL, "null pointer argument");
+    const int rc = unsup_loss_check_shapes(kind, B, h, w, n_levels);
+    return rc != QPWC_OK ? rc : unsup_loss_workspace_floats(B, h, w, n_levels);
+}
+
+const char* qpwc_unsup_loss_fwd_kernel(int kind, int B, const int* h, const int* w, int n_levels) {
+    if (!h || !w || unsup_loss_check_shapes(kind, B, h, w, n_levels) != QPWC_OK) return "";
+    return unsup_loss_fwd_kernel(kind);
+}
+
+int qpwc_unsup_loss_fwd(int kind, float q, float eps, float smooth_weight, float edge, float smooth_eps,
+                        const void* const* prv, const void* const* nxt, const void* const* flow,
+                        const void* const* occluded, int B, const int* h, const int* w, const int* flow_dtype, int layout,
+                        int n_levels, void* out_losses, void* out_photo, void* out_smooth, void* out_counts,
+                        void* workspace, void* stream) {
+    int rc = check_nonnull({{prv, "prv"}, {nxt, "nxt"}, {flow, "flow"}, {h, "h"}, {w, "w"}, {flow_dtype, "flow_dtype"},
+                            {out_losses, "out_losses"}, {out_photo, "out_photo"}, {out_smooth, "out_smooth"},
+                            {out_counts, "out_counts"}, {workspace, "workspace"}});
+    if (rc != QPWC_OK) return rc;
+    if ((rc = unsup_loss_check_shapes(kind, B, h, w, n_levels)) != QPWC_OK) return rc;
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if ((rc = unsup_loss_check_range({q, eps, smooth_eps}, {edge, smooth_weight})) != QPWC_OK) return rc;
+    for (int i = 0; i < n_levels; ++i)
+        if (flow_dtype[i] != QPWC_F32 && flow_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported flow dtype %d", i, flow_dtype[i]);
+    BufCheck bufs[4 * 8 + 5];
+    int k = 0;
+    for (int i = 0; i < n_levels; ++i) {
+        if (!prv[i] || !nxt[i] || !flow[i]) return fail(QPWC_E_NULL, "null frame or flow at level %d", i);
+        const size_t px = (size_t)B * h[i] * w[i], es = esize(flow_dtype[i]);
+        bufs[k++] = indexed_buf(prv[i], px * 3 * 4, 4, "prv[%d]", i);
+        bufs[k++] = indexed_buf(nxt[i], px * 3 * 4, 4, "nxt[%d]", i);
+        bufs[k++] = indexed_buf(flow[i], px * 2 * es, es, "flow[%d]", i);
+        if (occluded && occluded[i]) bufs[k++] = indexed_buf(occluded[i], px, 1, "occluded[%d]", i);
+    }
+    const int n_in = k;
+    bufs[k++] = indexed_buf(out_losses, (size_t)n_levels * 4, 4, "out_losses", 0);
+    bufs[k++] = indexed_buf(out_photo, (size_t)n_levels * 4, 4, "out_photo", 0);
+    bufs[k++] = indexed_buf(out_smooth, (size_t)n_levels * 4, 4, "out_smooth", 0);
+    bufs[k++] = indexed_buf(out_counts, (size_t)n_levels * 8, 8, "out_counts", 0);
+    bufs[k++] = indexed_buf(workspace, (size_t)unsup_loss_workspace_floats(B, h, w, n_levels) * 4, 4, "workspace", 0);
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return unsup_loss_fwd_launch(kind, q, eps, smooth_weight, edge, smooth_eps, prv, nxt, flow, occluded, B, h, w,
+                                 flow_dtype, layout, n_levels, (float*)out_losses, (float*)out_photo, (float*)out_smooth,
+                                 (int64_t*)out_counts, (float*)workspace, (hipStream_t)stream);
+}
+
+int qpwc_unsup_loss_bwd(int kind, float smooth_weight, float smooth_eps, const void* const* flow, const void* workspace,
+                        const void* counts, const void* grad_losses, void* const* grad_flow, int B, const int* h,
+                        const int* w, const int* flow_dtype, int layout, int n_levels, void* stream) {
+    int rc = check_nonnull({{flow, "flow"}, {workspace, "workspace"}, {counts, "counts"}, {grad_losses, "grad_losses"},
+                            {grad_flow, "grad_flow"}, {h, "h"}, {w, "w"}, {flow_dtype, "flow_dtype"}});
+    if (rc != QPWC_OK) return rc;
+    if ((rc = unsup_loss_check_shapes(kind, B, h, w, n_levels)) != QPWC_OK) return rc;
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if ((rc = unsup_loss_check_range({smooth_eps}, {smooth_weight})) != QPWC_OK) return rc;
+    for (int i = 0; i < n_levels; ++i)
+        if (flow_dtype[i] != QPWC_F32 && flow_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported flow dtype %d", i, flow_dtype[i]);
+    BufCheck bufs[3 + 2 * 8];
+    int k = 0;
+    bufs[k++] = indexed_buf(workspace, (size_t)unsup_loss_workspace_floats(B, h, w, n_levels) * 4, 4, "workspace", 0);
+    bufs[k++] = indexed_buf(counts, (size_t)n_levels * 8, 8, "counts", 0);
+    bufs[k++] = indexed_buf(grad_losses, (size_t)n_levels * 4, 4, "grad_losses", 0);
+    for (int i = 0; i < n_levels; ++i) {
+        if (!flow[i] || !grad_flow[i]) return fail(QPWC_E_NULL, "null buffer at level %d", i);
+        const size_t es = esize(flow_dtype[i]);
+        bufs[k++] = indexed_buf(flow[i], (size_t)B * h[i] * w[i] * 2 * es, es, "flow[%d]", i);
+    }
+    const int n_in = k;
+    for (int i = 0; i < n_levels; ++i) {
+        const size_t es = esize(flow_dtype[i]);
+        bufs[k++] = indexed_buf(grad_flow[i], (size_t)B * h[i] * w[i] * 2 * es, es, "grad_flow[%d]", i);
+    }
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return unsup_loss_bwd_launch(kind, smooth_weight, smooth_eps, flow, (const float*)workspace, (const int64_t*)counts,
+                                 (const float*)grad_losses, grad_flow, B, h, w, flow_dtype, layout, n_levels,
+                                 (hipStream_t)stream);
 }
 
 int64_t qpwc_review_workspace_floats(int n_flows, int B, int h, int w) {

@@ -207,6 +207,19 @@ int masked_loss_fwd_launch(int kind, float p0, float p1, const float* gt, const 
 int masked_loss_bwd_launch(int kind, const void* const* dpred, const int64_t* counts, const float* grad_losses,
                            void* const* grad_pred, const int64_t* n_elems, const int* pred_dtype, int n, hipStream_t s);
 
+// unsup_loss.hip (include/qpwc_unsup_loss.h)
+int64_t unsup_loss_total_tiles(int B, const int* h, const int* w, int n);
+int64_t unsup_loss_workspace_floats(int B, const int* h, const int* w, int n);
+const char* unsup_loss_fwd_kernel(int kind);
+int unsup_loss_fwd_launch(int kind, float q, float eps, float smooth_weight, float edge, float eps_s,
+                          const void* const* prv, const void* const* nxt, const void* const* flow,
+                          const void* const* occluded, int B, const int* h, const int* w, const int* flow_dtype,
+                          int layout, int n, float* out_losses, float* out_photo, float* out_smooth, int64_t* out_counts,
+                          float* ws, hipStream_t s);
+int unsup_loss_bwd_launch(int kind, float smooth_weight, float eps_s, const void* const* flow, const float* ws,
+                          const int64_t* counts, const float* grad_losses, void* const* grad_flow, int B, const int* h,
+                          const int* w, const int* flow_dtype, int layout, int n, hipStream_t s);
+
 // flow_quality.hip (include/qpwc_flow_quality.h)
 bool flow_quality_shape_ok(int B, int H, int W);
 int64_t flow_quality_workspace_floats(int B, int H, int W);

@@ -12,6 +12,9 @@ as they are.  No CPU path.  Keras' ``sample_weight`` / ``reduction`` are not sup
 
 ``multiscale_masked`` / ``masked_ground_truth`` are the valid-masked twins of the three flow losses for sparse ground
 truth (below; include/qpwc_masked_loss.h); they do have a torch chain, taken for CPU tensors.
+
+``PhotometricLoss`` / ``multiscale_unsupervised`` are the label-free losses (census or Charbonnier photometric term plus
+edge-aware smoothness; at the end of this file; include/qpwc_unsup_loss.h), which go beyond the reference as well.
 """
 import torch
 
@@ -278,3 +281,238 @@ def masked_ground_truth(loss, y_true, shapes, valid=None):
         gts += [t.contiguous() for t in g]
         masks += m
     return gts, masks
+
+
+# ---- the label-free flow losses (include/qpwc_unsup_loss.h) ------------------------------------------------------------
+# For raw video and for the unlabelled part of sparse frames; the reference has no such loss.  The UnFlow / UFlow recipe:
+# a photometric term between prv and nxt warped by the flow (UFlow's soft ternary census on a 7 x 7 patch, or Charbonnier
+# on RGB), over the pixels whose sample stays inside the image and is not occluded, plus edge-aware first-order
+# smoothness.  Frames are constants, only the flow is differentiated.  HIP tensors take qpwc_unsup_loss_fwd / _bwd; CPU
+# tensors take the torch chain below.  Non-finite flows are out of scope.
+
+_UNSUP_KINDS = {"census": _hip.UNSUP_CENSUS, "charbonnier": _hip.UNSUP_CHARBONNIER}
+
+
+class PhotometricLoss:
+    """The label-free loss of one or more flow levels: ``kind`` 'census' (term = (dist + eps)^q of the soft ternary
+    census distance) or 'charbonnier' (term = mean_c ((prv_c - warped_c)^2 + eps^2)^q), averaged over the unmasked pixels,
+    plus ``smooth_weight`` times the edge-aware smoothness (weights exp(-edge * mean_c |d prv|), penalty
+    sqrt(d flow^2 + smooth_eps^2)).  q and eps carry the names and defaults of FlowMseLossFineTune; smooth_weight = 2.0 is
+    a starting point, not a tuned value.  ``loss(pairs, flow, occluded=None)`` is one level; ``multiscale_unsupervised``
+    takes the network's list.  There is no ground truth: the first argument is the frame pair the network saw."""
+
+    def __init__(self, kind="census", q=0.4, eps=0.01, smooth_weight=2.0, edge=150.0, smooth_eps=1e-3, data_format=None,
+                 name=None):
+        if kind not in _UNSUP_KINDS:
+            raise ValueError("kind must be 'census' or 'charbonnier', got {!r}".format(kind))
+        q, eps, smooth_weight, edge, smooth_eps = (float(v) for v in (q, eps, smooth_weight, edge, smooth_eps))
+        if not (q > 0.0 and eps > 0.0 and smooth_eps > 0.0):
+            raise ValueError("q, eps and smooth_eps must be > 0, got {}, {} and {}".format(q, eps, smooth_eps))
+        if not (edge >= 0.0 and smooth_weight >= 0.0):
+            raise ValueError("edge and smooth_weight must be >= 0, got {} and {}".format(edge, smooth_weight))
+        self.kind, self.q, self.eps, self.smooth_weight, self.edge, self.smooth_eps = kind, q, eps, smooth_weight, edge, smooth_eps
+        self.data_format = image_data_format() if data_format is None else data_format
+        self.axis = get_axis(self.data_format)
+        self.name = name
+
+    def __call__(self, pairs, flow, occluded=None):
+        if isinstance(occluded, torch.Tensor):
+            occluded = [occluded]
+        return multiscale_unsupervised(self, pairs, [flow], occluded)[1].reshape(())
+
+    def call(self, pairs, flow, occluded=None):
+        return self(pairs, flow, occluded)
+
+    def get_config(self):
+        return {"name": self.name, "kind": self.kind, "q": self.q, "eps": self.eps, "smooth_weight": self.smooth_weight,
+                "edge": self.edge, "smooth_eps": self.smooth_eps, "data_format": self.data_format}
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+def _unsup_args(obj, pairs, flows, occluded):
+    """-> (flows, level shapes, pooling exponents, occluded as a list or 'estimate') after the checks both paths share."""
+    if not isinstance(obj, PhotometricLoss):
+        raise TypeError("multiscale_unsupervised takes a PhotometricLoss, got {}".format(type(obj).__name__))
+    if not isinstance(pairs, torch.Tensor):
+        raise TypeError("pairs must be a torch.Tensor")
+    if pairs.dim() != 4 or pairs.shape[obj.axis] != 6:
+        raise ValueError("pairs must be the frame pair the network saw, 6 channels on axis {} ({}), got shape {}: this "
+                         "loss has no ground truth".format(obj.axis, obj.data_format, tuple(pairs.shape)))
+    flows = list(flows)
+    if not 1 <= len(flows) <= 8:
+        raise ValueError("the losses take 1..8 flow levels, got {}".format(len(flows)))
+    H, W = (pairs.shape[1], pairs.shape[2]) if obj.axis == 3 else (pairs.shape[2], pairs.shape[3])
+    shapes, exps = [], []
+    for i, f in enumerate(flows):
+        if not isinstance(f, torch.Tensor) or f.dim() != 4 or f.shape[obj.axis] != 2 or f.shape[0] != pairs.shape[0]:
+            raise ValueError("flows[{}] must be a batched 2-channel flow ({}) of batch {}".format(i, obj.data_format,
+                                                                                                pairs.shape[0]))
+        h, w = (f.shape[1], f.shape[2]) if obj.axis == 3 else (f.shape[2], f.shape[3])
+        k = max((H // h).bit_length() - 1, 0) if h else 0
+        if h < 1 or w < 1 or h << k != H or w << k != W:
+            raise ValueError("level {}: {}x{} is not {}x{} over one power of two on both axes".format(i, h, w, H, W))
+        shapes.append((int(h), int(w)))
+        exps.append(k)
+    if isinstance(occluded, str):
+        if occluded != "estimate":
+            raise ValueError("occluded must be None, a list of masks or 'estimate', got '{}'".format(occluded))
+    elif occluded is not None:
+        occluded = list(occluded)
+        if len(occluded) != len(flows):
+            raise ValueError("{} masks for {} flow levels".format(len(occluded), len(flows)))
+        occluded = [metrics._flow_mask("occluded[%d]" % i, m, f, (int(f.shape[0]),) + s)
+                    for i, (m, f, s) in enumerate(zip(occluded, flows, shapes))]
+    return flows, shapes, exps, occluded
+
+
+def _unsup_sample_torch(img, flow):
+    """img (B,h,w,C) sampled bilinearly at (x, y) + flow (B,h,w,2) by the CLAMP rule, written out with gathers ->
+    (values (B,h,w,C), inside (B,h,w)).  floor carries no gradient, alpha passes it on [0, 1], and a sample outside the
+    image passes none."""
+    B, h, w, C = img.shape
+    ys = torch.arange(h, dtype=flow.dtype, device=flow.device).view(1, h, 1)
+    xs = torch.arange(w, dtype=flow.dtype, device=flow.device).view(1, 1, w)
+    qx, qy = xs + flow[..., 0], ys + flow[..., 1]
+    inside = (qx >= 0) & (qx <= w - 1) & (qy >= 0) & (qy <= h - 1)
+    qx, qy = torch.where(inside, qx, qx.detach()), torch.where(inside, qy, qy.detach())
+    fx, fy = qx.detach().floor().clamp(0, max(w - 2, 0)), qy.detach().floor().clamp(0, max(h - 2, 0))
+    ax, ay = (qx - fx).clamp(0, 1)[..., None], (qy - fy).clamp(0, 1)[..., None]
+    x0, y0 = fx.long(), fy.long()
+    x1, y1 = (x0 + 1).clamp(max=w - 1), (y0 + 1).clamp(max=h - 1)
+    flat = img.reshape(B, h * w, C)
+    tap = lambda yi, xi: flat.gather(1, (yi * w + xi).reshape(B, h * w, 1).expand(-1, -1, C)).reshape(B, h, w, C)
+    tl, tr, bl, br = tap(y0, x0), tap(y0, x1), tap(y1, x0), tap(y1, x1)
+    top, bot = ax * (tr - tl) + tl, ax * (br - bl) + bl
+    return ay * (bot - top) + top, inside
+
+
+def _unsup_grey(img):
+    return 255.0 * ((0.2989 * img[..., 0] + 0.587 * img[..., 1]) + 0.114 * img[..., 2])
+
+
+def _unsup_ternary(g):
+    """(B,h,w) -> (B,h-6,w-6,48): D / sqrt(0.81 + D^2) of the 48 neighbours of every interior pixel."""
+    h, w = g.shape[1:]
+    c = g[:, 3:h - 3, 3:w - 3]
+    out = []
+    for dy in range(7):
+        for dx in range(7):
+            if (dy, dx) != (3, 3):
+                d = g[:, dy:dy + h - 6, dx:dx + w - 6] - c
+                out.append(d / torch.sqrt(0.81 + d * d))
+    return torch.stack(out, dim=-1)
+
+
+def _unsup_level_torch(obj, prv, nxt, flow, occ):
+    """(photometric, smoothness, count) of one level: prv, nxt (B,h,w,3) and flow (B,h,w,2) in one dtype, occ None or
+    (B,h,w) uint8."""
+    B, h, w, _ = prv.shape
+    zero = torch.zeros((), dtype=prv.dtype, device=prv.device)
+    keep = torch.ones((B, h, w), dtype=torch.bool, device=prv.device) if occ is None else occ == 0
+    if obj.kind == "census":
+        if h < 7 or w < 7:
+            photo, count = flow.sum() * 0, torch.zeros((), dtype=torch.int64, device=prv.device)
+        else:
+            gw, inside = _unsup_sample_torch(_unsup_grey(nxt)[..., None], flow)
+            e = (_unsup_ternary(_unsup_grey(prv)) - _unsup_ternary(gw[..., 0])) ** 2
+            term = ((e / (0.1 + e)).sum(-1) + obj.eps) ** obj.q
+            m = (inside & keep)[:, 3:h - 3, 3:w - 3]
+            count = m.sum()
+            photo = torch.where(m, term, zero).sum() / count.clamp(min=1)
+    else:
+        warped, inside = _unsup_sample_torch(nxt, flow)
+        term = (((prv - warped) ** 2 + obj.eps ** 2) ** obj.q).sum(-1) / 3.0
+        m = inside & keep
+        count = m.sum()
+        photo = torch.where(m, term, zero).sum() / count.clamp(min=1)
+    robust = lambda d: torch.sqrt(d * d + obj.smooth_eps ** 2)
+    sx = sy = zero
+    if w > 1:
+        wx = torch.exp(-obj.edge * (prv[:, :, 1:] - prv[:, :, :-1]).abs().mean(-1))
+        sx = (wx[..., None] * robust(flow[:, :, 1:] - flow[:, :, :-1])).mean()
+    if h > 1:
+        wy = torch.exp(-obj.edge * (prv[:, 1:] - prv[:, :-1]).abs().mean(-1))
+        sy = (wy[..., None] * robust(flow[:, 1:] - flow[:, :-1])).mean()
+    return photo, (sx + sy) / 2, count
+
+
+def _unsup_pool_torch(x, k):
+    """k successive 2 x 2 means of x (N,H,W,C), each ((a + b) + c + d) / 4 in row-major order, as
+    qpwc_avgpool_pyramid_fwd forms them."""
+    for _ in range(k):
+        N, H, W, C = x.shape
+        x = x.reshape(N, H // 2, 2, W // 2, 2, C)
+        x = (((x[:, :, 0, :, 0] + x[:, :, 0, :, 1]) + x[:, :, 1, :, 0]) + x[:, :, 1, :, 1]) / 4
+    return x
+
+
+def _unsup_frames(pairs, axis, exps, pool):
+    """The frame pair -> per level (prv, nxt) channels-last, pooled by 2^k with pool(stacked frames, k)."""
+    prv, nxt = torch.chunk(pairs.detach(), 2, dim=axis)
+    stacked = torch.cat([prv, nxt], dim=0)
+    stacked = (stacked if axis == 3 else stacked.permute(0, 2, 3, 1)).contiguous()
+    B, made, out = pairs.shape[0], {}, []
+    for k in exps:
+        if k not in made:
+            made[k] = stacked if k == 0 else pool(stacked, k)
+        out.append((made[k][:B], made[k][B:]))
+    return out
+
+
+def multiscale_unsupervised_torch(obj, pairs, flows, occluded=None):
+    """``multiscale_unsupervised`` composed from torch operators, on any device, in pairs' dtype (float64 inputs give the
+    float64 reference) and differentiable in the flows through torch autograd: the path CPU tensors take and the baseline
+    the kernels are timed against.  occluded='estimate' needs HIP tensors (occlusion.estimate_occlusion_map)."""
+    flows, shapes, exps, occluded = _unsup_args(obj, pairs, flows, occluded)
+    if isinstance(occluded, str):
+        from . import occlusion
+        occluded = [metrics._flow_mask("occluded", occlusion.estimate_occlusion_map(f.detach(), obj.data_format), f,
+                                       (int(f.shape[0]),) + s) for f, s in zip(flows, shapes)]
+    occluded = [None] * len(flows) if occluded is None else occluded
+    photo, smooth, counts = [], [], []
+    for (prv, nxt), f, occ in zip(_unsup_frames(pairs, obj.axis, exps, _unsup_pool_torch), flows, occluded):
+        f = (f if obj.axis == 3 else f.permute(0, 2, 3, 1)).to(pairs.dtype)
+        p, s, c = _unsup_level_torch(obj, prv, nxt, f, occ)
+        photo.append(p)
+        smooth.append(s)
+        counts.append(c)
+    photo, smooth = torch.stack(photo), torch.stack(smooth)
+    per_level = photo + obj.smooth_weight * smooth
+    return per_level.sum(), per_level, {"photometric": photo.detach(), "smoothness": smooth.detach(),
+                                        "counts": torch.stack(counts)}
+
+
+def _unsup_pool_hip(x, k):
+    while k > 0:                       # qpwc_avgpool_pyramid_fwd pools up to 6 levels a launch
+        x, k = ops.avgpool_pyramid(x, min(k, 6)), k - min(k, 6)
+    return x
+
+
+def multiscale_unsupervised(obj, pairs, flows, occluded=None):
+    """The label-free loss of 1..8 flow levels against the frame pair the network saw -> (total, per_level, parts):
+    per_level [L] (what autograd differentiates, in the flows only), total = per_level.sum(), parts = {'photometric' [L],
+    'smoothness' [L], 'counts' int64 [L]}, all on the inputs' device with nothing read back.  ``obj``: a PhotometricLoss;
+    ``pairs``: (B,H,W,6) / (B,6,H,W) by obj.data_format; ``flows``: what FlowerModel returns, each (H / 2^k, W / 2^k) in
+    level pixels (anything else is a ValueError), fp32 or fp16.  Per level the frames are the block mean of the pair
+    (qpwc_avgpool_pyramid_fwd, both frames stacked on the batch axis, one launch per distinct factor; factor 1: the frames
+    themselves).  ``occluded``: None, a list of per-level (B,h,w) masks (bool, uint8 or floating; entries may be None),
+    or 'estimate': occlusion.estimate_occlusion_map of each detached level flow.  The backward direction is a second call
+    with the frames swapped.  HIP tensors (pairs float32): the frames, then one forward launch for all levels plus a
+    fold, and one backward launch; CPU tensors: ``multiscale_unsupervised_torch``."""
+    if isinstance(pairs, torch.Tensor) and not pairs.is_cuda:
+        return multiscale_unsupervised_torch(obj, pairs, flows, occluded)
+    flows, shapes, exps, occluded = _unsup_args(obj, pairs, flows, occluded)
+    if pairs.dtype != torch.float32:
+        raise ValueError("pairs must be float32, got {}".format(pairs.dtype))
+    if isinstance(occluded, str):
+        from . import occlusion
+        occluded = [metrics._flow_mask("occluded", occlusion.estimate_occlusion_map(f.detach(), obj.data_format), f,
+                                       (int(f.shape[0]),) + s) for f, s in zip(flows, shapes)]
+    frames = _unsup_frames(pairs, obj.axis, exps, _unsup_pool_hip)
+    per_level, photo, smooth, counts = ops.unsup_loss(
+        _UNSUP_KINDS[obj.kind], [p for p, _ in frames], [n for _, n in frames], flows, occluded, obj.data_format, obj.q,
+        obj.eps, obj.smooth_weight, obj.edge, obj.smooth_eps)
+    return per_level.sum(), per_level, {"photometric": photo, "smoothness": smooth, "counts": counts}

@@ -1900,6 +1900,139 @@ def masked_loss(kind, y_true, y_preds, valid=None, data_format=CHANNELS_LAST, p0
     return masked_loss_fwd(kind, y_true, y_preds, valid, data_format, p0, p1)[:2]
 
 
+class _UnsupOperands:
+    """What both label-free loss entry points make of their operands: per level the fp32 channels-last frames, the flow
+    dense in `data_format` (fp32 or fp16) and the optional uint8 occlusion mask, all checked against one another; B, the
+    level shapes and the ctypes arrays."""
+
+    def __init__(self, prvs, nxts, flows, occluded, data_format):
+        get_axis(data_format)
+        prvs, nxts, flows = list(prvs), list(nxts), list(flows)
+        self.n = n = len(flows)
+        if not 1 <= n <= 8:
+            raise ValueError("the losses take 1..8 levels, got {}".format(n))
+        occluded = [None] * n if occluded is None else list(occluded)
+        if not len(prvs) == len(nxts) == len(occluded) == n:
+            raise ValueError("{} flows against {} / {} frames and {} masks".format(n, len(prvs), len(nxts), len(occluded)))
+        self.nhwc = nhwc = data_format == CHANNELS_LAST
+        self.layout = _hip.NHWC if nhwc else _hip.NCHW
+        self.prvs, self.nxts, self.flows, self.occ, self.hs, self.ws_ = [], [], [], [], [], []
+        for i, (p, x, f, m) in enumerate(zip(prvs, nxts, flows, occluded)):
+            for name, t in (("prv", p), ("nxt", x), ("flow", f)):
+                _check_tensor("{}[{}]".format(name, i), t)
+                if t.device != flows[0].device:
+                    raise ValueError("{}[{}] is on {}, flow[0] on {}".format(name, i, t.device, flows[0].device))
+            B, h, w, c = f.shape if nhwc else (f.shape[0], f.shape[2], f.shape[3], f.shape[1])
+            if c != 2 or (i and B != self.B):
+                raise ValueError("flow[{}] must be a 2-channel flow ({}) of one batch size, got {}".format(
+                    i, data_format, tuple(f.shape)))
+            self.B = int(B)
+            for name, t in (("prv", p), ("nxt", x)):
+                if t.dtype != torch.float32 or tuple(t.shape) != (B, h, w, 3):
+                    raise ValueError("{}[{}] must be float32 {}, got {} {}".format(name, i, (B, h, w, 3), t.dtype,
+                                                                                  tuple(t.shape)))
+                if _wants_grad(t):
+                    raise ValueError("{}[{}] requires grad: the frames are constants, only the flow is differentiated "
+                                     "(detach it)".format(name, i))
+            if m is not None and not (isinstance(m, torch.Tensor) and m.dtype == torch.uint8
+                                      and tuple(m.shape) == (B, h, w) and m.device == f.device):
+                raise ValueError("occluded[{}] must be None or a uint8 tensor of shape {} on {}".format(i, (B, h, w),
+                                                                                                       f.device))
+            self.prvs.append(p.contiguous())
+            self.nxts.append(x.contiguous())
+            self.flows.append(f.contiguous())
+            self.occ.append(None if m is None else m.contiguous())
+            self.hs.append(int(h))
+            self.ws_.append(int(w))
+        self.dev = self.flows[0].device
+        self.ha, self.wa = (ctypes.c_int * n)(*self.hs), (ctypes.c_int * n)(*self.ws_)
+        self.fdt = (ctypes.c_int * n)(*[_DTYPES[f.dtype] for f in self.flows])
+
+    def ptrs(self, ts):
+        return (ctypes.c_void_p * self.n)(*[0 if t is None else t.data_ptr() for t in ts])
+
+
+def unsup_loss_fwd(kind, prvs, nxts, flows, occluded=None, data_format=CHANNELS_LAST, q=0.4, eps=0.01,
+                   smooth_weight=0.0, edge=150.0, smooth_eps=1e-3):
+    """The label-free flow loss of 1..8 levels (qpwc_unsup_loss_fwd, include/qpwc_unsup_loss.h; kind _hip.UNSUP_CENSUS /
+    _hip.UNSUP_CHARBONNIER) -> (losses, photometric, smoothness: fp32 [L], counts: int64 [L], saved), all on the device.
+    prvs[l], nxts[l]: fp32 (B,h,w,3) channels-last; flows[l]: fp32 or fp16 in data_format; occluded: None or a list of
+    None / uint8 (B,h,w).  saved: what unsup_loss_bwd takes (the operands and the workspace the forward filled).  One
+    launch plus the fold; enqueues and returns: no host synchronisation."""
+    o = _UnsupOperands(prvs, nxts, flows, occluded, data_format)
+    n, dev = o.n, o.dev
+    L = _hip.lib()
+    nws = L.qpwc_unsup_loss_workspace_floats(int(kind), o.B, o.ha, o.wa, n)
+    _hip.check(min(int(nws), 0))
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+        out = torch.empty((3, n), dtype=torch.float32, device=dev)
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        with _timed("unsup_loss", (o.B, o.hs[0], o.ws_[0], n)):
+            rc = L.qpwc_unsup_loss_fwd(int(kind), float(q), float(eps), float(smooth_weight), float(edge),
+                                       float(smooth_eps), o.ptrs(o.prvs), o.ptrs(o.nxts), o.ptrs(o.flows),
+                                       o.ptrs(o.occ), o.B, o.ha, o.wa, o.fdt, o.layout, n, out[0].data_ptr(),
+                                       out[1].data_ptr(), out[2].data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                       _stream(ws))
+    _hip.check(rc)
+    return out[0], out[1], out[2], counts, (o, ws)
+
+
+def unsup_loss_bwd(kind, saved, counts, grad_losses, smooth_weight=0.0, smooth_eps=1e-3):
+    """d losses / d flows times grad_losses [L] (on the device) in each flow's dtype and layout, all levels in one launch
+    (qpwc_unsup_loss_bwd); saved and counts from unsup_loss_fwd with the same kind and parameters.  The counts stay on the
+    device."""
+    o, ws = saved
+    g = grad_losses.to(torch.float32).contiguous()
+    if g.numel() != o.n or g.device != o.dev:
+        raise ValueError("grad_losses must be a device vector of {} elements".format(o.n))
+    with torch.cuda.device(o.dev):
+        grads = [torch.empty_like(f) for f in o.flows]
+        with _timed("unsup_loss_bwd", (o.n,)):
+            rc = _hip.lib().qpwc_unsup_loss_bwd(int(kind), float(smooth_weight), float(smooth_eps), o.ptrs(o.flows),
+                                                ws.data_ptr(), counts.data_ptr(), g.data_ptr(), o.ptrs(grads), o.B, o.ha,
+                                                o.wa, o.fdt, o.layout, o.n, _stream(g))
+    _hip.check(rc)
+    return grads
+
+
+class _UnsupLossFn(torch.autograd.Function):
+    """unsup_loss_fwd() with qpwc_unsup_loss_bwd as its gradient: the forward saves per pixel what the backward's gather
+    needs; the frames and the masks are constants."""
+
+    @staticmethod
+    def forward(ctx, cfg, prvs, nxts, occluded, *flows):
+        kind, data_format, q, eps, smooth_weight, edge, smooth_eps = cfg
+        losses, photo, smooth, counts, saved = unsup_loss_fwd(kind, prvs, nxts, flows, occluded, data_format, q, eps,
+                                                              smooth_weight, edge, smooth_eps)
+        ctx.cfg, ctx.saved, ctx.counts, ctx.n = cfg, saved, counts, len(flows)
+        ctx.mark_non_differentiable(photo, smooth, counts)
+        ctx.set_materialize_grads(False)
+        return losses, photo, smooth, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_losses, *_others):
+        _refuse_capture("the unsupervised loss backward")
+        if grad_losses is None:
+            return (None,) * (4 + ctx.n)
+        kind, _, _, _, smooth_weight, _, smooth_eps = ctx.cfg
+        grads = unsup_loss_bwd(kind, ctx.saved, ctx.counts, grad_losses, smooth_weight, smooth_eps)
+        return (None,) * 4 + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
+
+
+def unsup_loss(kind, prvs, nxts, flows, occluded=None, data_format=CHANNELS_LAST, q=0.4, eps=0.01, smooth_weight=0.0,
+               edge=150.0, smooth_eps=1e-3):
+    """(losses, photometric, smoothness fp32 [L], counts int64 [L]) of unsup_loss_fwd(); the losses are differentiable in
+    the flows when grad is enabled and one of them requires it (the parts are reported, not differentiated)."""
+    flows = list(flows)
+    if _wants_grad(*flows):
+        _refuse_capture("the unsupervised loss")
+        cfg = (int(kind), data_format, float(q), float(eps), float(smooth_weight), float(edge), float(smooth_eps))
+        return _UnsupLossFn.apply(cfg, list(prvs), list(nxts), None if occluded is None else list(occluded), *flows)
+    return unsup_loss_fwd(kind, prvs, nxts, flows, occluded, data_format, q, eps, smooth_weight, edge, smooth_eps)[:4]
+
+
 def _dw_sources(sources):
     """-> (kept tensors, ctypes pointer/channel/stride arrays, B, H, W, C) for 1..3 sources."""
     import ctypes
