@@ -35,6 +35,22 @@ path's ground truth reaches 2^32 elements (BOUNDARIES_32).  Validity is zero (ma
 truth (flow metrics) except in planted windows, so the float64 answer needs the windows' crops and the masks' counts
 only; see the comments at their sections.
 
+The label-free losses and the input pipelines (the last two entries of CASES) have a trivial background instead -- one
+colour, zero flow, everything occluded; zero sources with a zero mask -- so that their float64 answers need crops only;
+see the comments at their sections.  On paper, for these two: the casts in the sources are redundant one by one --
+`pix = (b * h + y) * (int64_t)w + x` of unsup_loss_fwd_kernel has an int64_t `b`, and the validator keeps B * h * w
+itself below 2^31, so dropping that cast changes no value; `p00 = img + (int64_t)y0 * W + x0` of aug_pixel_pass has an
+int64_t `img` and a y0 * W below 2^31 -- and what a 32-bit offset takes is a narrower type.  `int64_t b` to `int b` in
+unsup_ld_rgb makes `((b * h + y) * w + x) * 3` wrap at element 2^31, pixel (15213, 5955) of image 2: from there on the
+frames are read 2^32 elements lower, before the tensor.  The windows ">2^31" (rows 15214 on) and "last" lie there; the
+value and the gradient need their texture, and the control shows that other frames in one window move the value by
+185 bounds or more.  `const int64_t np` to `const int np` makes `3 * np` .. `6 * np` wrap: planes 3 .. 6 of every pixel
+(d gw / d q, the edge weights) are stored and gathered 2^32 floats lower, plane 6 on top of plane 0 and the others
+before the workspace, over whatever lies there; the gradient of every window and the zeros around them go.  `const
+int64_t p00` to `const int p00` makes sample 2 read the source rows behind its boundary pixel 2^32 pixels lower; the
+control reads them 2^31 lower, finds the zeros that lie there, and every output moves by thousands of bounds.  `int64_t
+pix` to `int pix` in aug_load_pixel wraps `pix * 6` from pixel 357,913,942 on: all three windows lie beyond.
+
 Where a family departs from this: grad_img of the warp is a scatter of float atomics, so it is held to (b) only; the
 cost-volume backward is fed a random saved output (it reads it for the LeakyReLU mask only) and gives its two
 gradients in two launches; the SeparableConv2D case calls the backward op without running the fused forward; the
@@ -77,10 +93,16 @@ Measured on an MI355X (peak of torch.cuda.max_memory_allocated, wall time of the
   masked_loss tile path     34.14 (34.64)        0.6          relative: losses 5.0e-9, grad_pred 1.3e-7 (bound 1e-5); gt_out 1.7e-8 of the level's largest (bound 1e-6)
   masked_loss pixel paths   33.06 (34.06)        0.1          relative: losses 1.6e-8, grad_pred 1.2e-7 (bound 1e-5); gt_out exact
   flow_quality              22.01 (22.01)        2.1          relative: means 2.7e-7 (bound 1e-5); 1.7e-7 px, 3.5e-13 degrees, count ratios 0.50 ulp
-The whole module: 18 tests, 3 - 16 s (the seconds are test bodies in different runs).  The peaks above the plan are the boolean of torch.equal on one image (0.67 GiB);
+  unsup_loss (census)       46.32 (46.32)        1.5          relative: photometric 4.7e-9, smoothness 1.3e-8 (bound 1e-5); grad_flow 6.4e-9 of a largest 2.4e-3 (bound 2.6e-8)
+  augment, dense + sparse   30.18 (30.18)        1.9          frames 4.5e-7, flow 3.8e-6 px, sparse flow 7.6e-6 px (bound 1e-4); masks equal
+unsup_loss: 10 windows, count 1871; the windows' share of the smoothness sum is 0.888 at smooth_eps = 2^-20; the bounds,
+4 x the float32 chain on the same crops, came out at their floor of 1e-5 for both values and at 2.6e-8 (4 x 6.5e-9, of
+a largest gradient of 2.4e-3) for grad_flow.
+The whole module: 20 tests, 3 - 16 s (the seconds are test bodies in different runs).  The peaks above the plan are the boolean of torch.equal on one image (0.67 GiB);
 ops.py itself allocates what is planned and nothing else.  The negative controls moved the sums by 1300 - 20500 bounds;
 those of the masked losses moved the loss or grad_pred by 190 - 200000 bounds, those of the flow metrics an image's epe by
-7100 - 100000.
+7100 - 100000; those of the label-free loss moved the photometric value by 185 - 10500 bounds, those of the input pipelines
+every output by 6300 - 11500.
 """
 import gc
 import os
@@ -123,6 +145,10 @@ CASES = {
     "masked_loss_pixel": (3, 18931, 18937, 2),           # the "epe" shape: the masked pixel walks, the scalar backward
     "flow_quality": (5, 14653, 14661, 2),                # 1.074 G pixels (the cap is 2^31 - 1 elements a flow): truth and
                                                          # an fp32 pred pass 2^31 elements, the masks 2^30 bytes
+    "unsup_loss": (3, 15489, 15497),                     # (B, h, w) of one level: 0.720 G pixels, the frames 2.160 G floats,
+                                                         # the saved planes 5.04 G, the mask 2^29 bytes and more
+    "augment": (3, 26833, 26839),                        # (B, H, W) of the source: 2.161 G pixels of 6 bytes, a float2 and a
+                                                         # mask byte each
 }
 BOUNDARIES_32 = BOUNDARIES + (1 << 32,)                  # ... and the unsigned index limit, for operands that reach it
 
@@ -1677,5 +1703,358 @@ def test_flow_quality(arena):
     peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
     print("flow quality: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst (relative mean, count ulp) {}, controls {:.0f} .. "
           "{:.0f} bounds".format(peak / GIB, planned / GIB, secs, worst, min(r for _, r in controls), max(r for _, r in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- the label-free losses: frames past 2^31 elements, the saved planes past 2^32, the mask past 2^29 bytes ----------
+# unsup_loss_fwd_kernel / unsup_loss_bwd_kernel index the frames by ((b*h+y)*w+x)*3, the flow by pixel * 2, the mask by
+# pixel and the seven saved planes by k * (B*h*w) + pixel.  The background is trivial -- prv = nxt = one colour, flow 0,
+# everything occluded -- so the float64 answer needs crops only: around WIN x WIN windows (textured frames, make_case's
+# flows on the 1/16 grid up to UNSUP_REACH pixels, its 20 % mask) the frames are textured UNSUP_MARGIN = 4 + UNSUP_REACH
+# pixels further (3 for the census patch, 1 for the second tap, the reach of a sample), and the crop is one pixel wider,
+# so that every pair of neighbours outside all crops is a background pair: weight 1, difference 0, term smooth_eps, which
+# at 2^-20 the kernel sums exactly.  The crops' own terms are the float64 chain's on each crop -- a window pixel's
+# sample, patch and neighbours lie inside its crop, or outside the image where the crop ends at the image's border --
+# rescaled from the crop's count and pairs to the whole level's.
+UNSUP_REACH = 9                                  # make_case(WIN, WIN): flows up to w / 2, an integer moved by 1/2
+UNSUP_MARGIN = 4 + UNSUP_REACH
+UNSUP_COLOUR = 0.25
+UNSUP_PARAMS = dict(q=0.4, eps=0.01, smooth_weight=1.5, edge=40.0, smooth_eps=2.0 ** -20)
+
+
+def unsup_windows(key):
+    """[(tag, n, y0, y1, x0, x1)]: pixel_windows of the frames (3 floats a pixel), and behind the pixel under every
+    boundary of the flow (2 a pixel), of the mask (a byte a pixel) and of the saved planes (plane k at k * B*H*W + pixel,
+    boundaries up to 2^32); one entry per distinct place."""
+    B, H, W = key
+    wins = pixel_windows(B, H, W, 3)
+    more = [("flow" + x[0],) + x[1:] for x in pixel_windows(B, H, W, 2)[1:-1]]
+    more += [("mask" + x[0],) + x[1:] for x in pixel_windows(B, H, W, 1)[1:-1]]
+    npix = B * H * W
+    for b in crossed(7 * npix, BOUNDARIES_32):
+        plane, pix = divmod(b, npix)
+        n, y, x = locate(pix, H, W, 1)
+        assert y + 1 + WIN <= H, (b, y)
+        more.append(("plane%d>2^%d" % (plane, b.bit_length() - 1), n, y + 1, y + 1 + WIN) + _span(x, WIN, W))
+    seen = {x[1:] for x in wins}
+    for x in more:
+        if x[1:] not in seen:
+            seen.add(x[1:])
+            wins.insert(-1, x)
+    return wins
+
+
+def unsup_grown(win, by, H, W):
+    """The window grown by `by` pixels on every side, cut at the image -> (tag, n, y0, y1, x0, x1)."""
+    tag, n, y0, y1, x0, x1 = win
+    return (tag, n, max(y0 - by, 0), min(y1 + by, H), max(x0 - by, 0), min(x1 + by, W))
+
+
+def unsup_plant(k, win, key):
+    """What window k holds, on the CPU: textured frames on the window grown by UNSUP_MARGIN, make_case's flow and mask
+    on the window -> {"textured": region, "crop": region, "prv", "nxt" (1,ph,pw,3), "flow" (1,WIN,WIN,2), "occ"}."""
+    from test_unsup_loss_cpu import make_case
+    B, H, W = key
+    tex, side = unsup_grown(win, UNSUP_MARGIN, H, W), WIN + 2 * UNSUP_MARGIN
+    # every window its own contrast ((k + 2) / 16) and, every other one, its axes swapped: a wrapped offset that finds
+    # another window's frames must not find the like of its own
+    pairs = torch.from_numpy(make_case(side, side, 200 + k, B=1, levels=1)["pairs"]) * ((k + 2) / 16.0)
+    pairs = pairs.transpose(1, 2) if k % 2 else pairs
+    oy, ox = tex[2] - (win[2] - UNSUP_MARGIN), tex[4] - (win[4] - UNSUP_MARGIN)
+    pairs = pairs[:, oy:oy + tex[3] - tex[2], ox:ox + tex[5] - tex[4]]
+    small = make_case(WIN, WIN, 300 + k, B=1, levels=1)
+    flow = torch.from_numpy(small["flows"][0])
+    assert float(flow.abs().max()) <= UNSUP_REACH
+    return {"textured": tex, "crop": unsup_grown(win, UNSUP_MARGIN + 1, H, W), "prv": pairs[..., :3].contiguous(),
+            "nxt": pairs[..., 3:].contiguous(), "flow": flow, "occ": torch.from_numpy(small["masks"][0])}
+
+
+def unsup_fill(prv, nxt, flow, occ, wins, plants):
+    """The windows' contents into the full-size tensors (on any device)."""
+    for win, p in zip(wins, plants):
+        _, n, y0, y1, x0, x1 = p["textured"]
+        prv[n, y0:y1, x0:x1] = p["prv"][0].to(prv.device)
+        nxt[n, y0:y1, x0:x1] = p["nxt"][0].to(prv.device)
+        _, n, y0, y1, x0, x1 = win
+        flow[n, y0:y1, x0:x1] = p["flow"][0].to(prv.device)
+        occ[n, y0:y1, x0:x1] = p["occ"][0].to(prv.device)
+
+
+def unsup_cut(prv, nxt, flow, occ, reg, frames_at=None):
+    """One crop of the four tensors on the CPU; frames_at = (n, y0, y1, x0, x1): the frames read there instead."""
+    at = reg[1:] if frames_at is None else frames_at
+    return {"prv": _cut(prv, *at), "nxt": _cut(nxt, *at), "flow": _cut(flow, *reg[1:]), "occ": _cut3(occ, *reg[1:])}
+
+
+def unsup_window_ref(kind, crops, key, dtype, params=UNSUP_PARAMS):
+    """The level's photometric value, smoothness, count and gradient from the crops alone, in `dtype`:
+    photo = sum_c photo_c count_c / count, sx = (the crops' pair terms + 2 smooth_eps per background pair) over the
+    header's normaliser 2 B h (w - 1), sy alike -> (photo, smooth, count, [d loss / d flow of each crop], the crops'
+    share of the smoothness sum)."""
+    from qpwcnet_amd import loss
+    B, H, W = key
+    nx, ny = B * H * (W - 1), B * (H - 1) * W
+    eps_s, edge, sw = params["smooth_eps"], params["edge"], params["smooth_weight"]
+    obj = loss.PhotometricLoss(kind, q=params["q"], eps=params["eps"], smooth_weight=0.0, edge=edge, smooth_eps=eps_s,
+                               data_format="channels_last")
+    xs, photo, count, sx, sy, px, py = [], 0.0, 0, 0.0, 0.0, 0, 0
+    for c in crops:
+        x = c["flow"].detach().to(dtype).clone().requires_grad_()
+        prv = c["prv"].to(dtype)
+        _, per, parts = loss.multiscale_unsupervised_torch(obj, torch.cat([prv, c["nxt"].to(dtype)], dim=3), [x], [c["occ"]])
+        n_c = int(parts["counts"][0])
+        photo, count = photo + per[0] * n_c, count + n_c
+        robust = lambda d: torch.sqrt(d * d + eps_s ** 2)
+        wx = torch.exp(-edge * (prv[:, :, 1:] - prv[:, :, :-1]).abs().mean(-1))
+        wy = torch.exp(-edge * (prv[:, 1:] - prv[:, :-1]).abs().mean(-1))
+        sx = sx + (wx[..., None] * robust(x[:, :, 1:] - x[:, :, :-1])).sum()
+        sy = sy + (wy[..., None] * robust(x[:, 1:] - x[:, :-1])).sum()
+        px, py = px + wx.numel(), py + wy.numel()
+        xs.append(x)
+    photo = photo / max(count, 1)
+    back = 0.5 * (2.0 * (nx - px) * eps_s / (2.0 * nx) + 2.0 * (ny - py) * eps_s / (2.0 * ny))
+    smooth = 0.5 * (sx / (2.0 * nx) + sy / (2.0 * ny)) + back
+    (photo + sw * smooth).backward()
+    return (photo.detach().double(), smooth.detach().double(), count, [x.grad.double() for x in xs],
+            1.0 - back / float(smooth.detach()))
+
+
+def unsup_bounds(ref, ref32):
+    """The module's rule at its definition: 4 x |float32 chain - float64 chain| on the same crops, never below 1e-5 --
+    relative for the values, of the largest gradient for the gradients -> {"photo", "smooth", "grad"}."""
+    top = max(float(g.abs().max()) for g in ref[3])
+    err = max(float((a - b).abs().max()) for a, b in zip(ref[3], ref32[3]))
+    return {"photo": max(4.0 * abs(float(ref[0] - ref32[0])), 1e-5 * abs(float(ref[0]))),
+            "smooth": max(4.0 * abs(float(ref[1] - ref32[1])), 1e-5 * abs(float(ref[1]))),
+            "grad": max(4.0 * err, 1e-5 * top)}
+
+
+def unsup_planned_bytes(key):
+    """Both frames, the flow, its gradient, the mask, and the workspace: 4 floats a tile and 7 planes."""
+    B, H, W = key
+    npix, tiles = B * H * W, B * -(-H // 8) * -(-W // 32)
+    return 4 * (2 * 3 * npix + 2 * 2 * npix + 7 * npix + 4 * tiles) + npix
+
+
+def _unsup_run(kind_id, prv, nxt, flow, occ):
+    p = UNSUP_PARAMS
+    x = flow.detach().requires_grad_()
+    losses, photo, smooth, counts = ops.unsup_loss(kind_id, [prv], [nxt], [x], [occ], "channels_last", p["q"], p["eps"],
+                                                   p["smooth_weight"], p["edge"], p["smooth_eps"])
+    losses.sum().backward()
+    return losses.detach(), photo, smooth, counts, x.grad
+
+
+def test_unsup_loss(arena):
+    """The census loss, forward and backward, at 3 x 15489 x 15497 pixels: the frames' element index passes 2^29, 2^30 and
+    2^31 in images 0, 1 and 2, the flow's 2^29 and 2^30, the mask's byte index 2^29, the saved planes' 2^29 .. 2^32.
+    count, the photometric value, the smoothness and grad_flow against float64 from the windows' crops; grad_flow
+    exactly 0 outside the crops over the whole tensor; a second launch gives the same bits; a window's frames read at
+    their offset wrapped mod 2^31 / 2^32 bytes and elements must move the photometric value by 100 bounds.
+    Measured: peak 46.32 GiB (planned 46.32), 1.5 s; of the bounds, photometric 0.0005, smoothness 0.0013, grad_flow 0.24;
+    the controls moved the photometric value by 185 .. 10500 bounds."""
+    key = CASES["unsup_loss"]
+    B, H, W = key
+    hip = ops._hip
+    planned = unsup_planned_bytes(key)
+    t0 = time.perf_counter()
+    a = arena
+    a["prv"] = prv = torch.full((B, H, W, 3), UNSUP_COLOUR, device=DEV)
+    a["nxt"] = nxt = torch.full((B, H, W, 3), UNSUP_COLOUR, device=DEV)
+    a["flow"] = flow = torch.zeros((B, H, W, 2), device=DEV)
+    a["occ"] = occ = torch.ones((B, H, W), dtype=torch.uint8, device=DEV)
+    assert prv.numel() > 1 << 31 and 7 * B * H * W > 1 << 32 and occ.numel() > 1 << 29
+    wins = unsup_windows(key)
+    plants = [unsup_plant(k, win, key) for k, win in enumerate(wins)]
+    unsup_fill(prv, nxt, flow, occ, wins, plants)
+    regs = [p["crop"] for p in plants]
+    crops = [unsup_cut(prv, nxt, flow, occ, r) for r in regs]
+    ref = unsup_window_ref("census", crops, key, torch.float64)
+    bounds = unsup_bounds(ref, unsup_window_ref("census", crops, key, torch.float32))
+    photo64, smooth64, count64, grads64, share = ref
+    assert count64 > 50 * len(wins) and share > 0.5, (count64, share)
+
+    losses, photo, smooth, counts, grad = _unsup_run(hip.UNSUP_CENSUS, prv, nxt, flow, occ)
+    assert int(counts[0]) == count64, (int(counts[0]), count64)
+    worst = {}
+    for name, got, want in (("photo", photo[0], photo64), ("smooth", smooth[0], smooth64),
+                            ("loss", losses[0], photo64 + UNSUP_PARAMS["smooth_weight"] * smooth64)):
+        d, bound = abs(float(got) - float(want)), bounds["photo"] + UNSUP_PARAMS["smooth_weight"] * bounds["smooth"] \
+            if name == "loss" else bounds[name]
+        print("unsup {}: {:.9e} against {:.9e}, |d| = {:.3e}, bound {:.3e}".format(name, float(got), float(want), d, bound))
+        assert d <= bound, (name, float(got), float(want), bound)
+        worst[name] = d / bound
+    kept, inside = [], 0
+    for r, g in zip(regs, grads64):
+        got = _cut(grad, *r[1:])
+        d = float((got.double() - g).abs().max())
+        print("unsup grad_flow {}: max|d| = {:.3e}, bound {:.3e}".format(r[0], d, bounds["grad"]))
+        assert d <= bounds["grad"], (r[0], d, bounds["grad"])
+        worst["grad"] = max(worst.get("grad", 0.0), d / bounds["grad"])
+        assert got.any(), r[0]
+        inside += int(torch.count_nonzero(got))
+        kept.append(got)
+    assert 0 < inside == _nonzero(grad), inside                                   # exactly 0 outside the crops
+    first = (losses, photo, smooth, counts)
+    del grad, losses, photo, smooth, counts
+
+    # the same bits again: zero outside the crops both times, so the crops decide
+    again = _unsup_run(hip.UNSUP_CENSUS, prv, nxt, flow, occ)
+    assert all(torch.equal(x, y) for x, y in zip(first, again[:4]))
+    assert all(torch.equal(_cut(again[4], *r[1:]), g) for r, g in zip(regs, kept)) and _nonzero(again[4]) == inside
+    del again
+
+    # the negative control, on the device's own data: a window's frames as a wrapped offset finds them
+    controls = []
+    for k, r in enumerate(regs):
+        for elem_bytes in (4, 1):                          # byte offsets mod 2^31, 2^32; element offsets mod 2^31, 2^32
+            for mod, at in wrapped_pixel_regions(B, H, W, 3, r, elem_bytes):
+                alt = crops[:k] + [unsup_cut(prv, nxt, flow, occ, r, frames_at=at)] + crops[k + 1:]
+                moved = abs(float(unsup_window_ref("census", alt, key, torch.float64)[0] - photo64)) / bounds["photo"]
+                controls.append(("window %d (%s) frames read mod 2^%d %s" % (
+                    k, r[0], mod.bit_length() - 1, "bytes" if elem_bytes == 4 else "elements"), moved))
+    assert len(controls) >= len(wins) and min(m for _, m in controls) >= 100.0, controls
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("unsup_loss: {} windows, count {}, the crops' share of the smoothness {:.3f}, peak {:.2f} GiB, planned {:.2f} "
+          "GiB, {:.2f} s, worst/bound {}, bounds {}, controls {:.0f} .. {:.0f} bounds".format(
+              len(wins), count64, share, peak / GIB, planned / GIB, secs, worst, bounds, min(m for _, m in controls),
+              max(m for _, m in controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- the input pipelines: source pixels past 2^29, 2^30 and 2^31 -------------------------------------------------------
+# aug_pixel_pass reads four source pixels p00 .. p11 = b * H * W + y * W + x per output pixel: the frames at 6 bytes a
+# pixel, the flow as a float2, the mask as a byte.  Only the 64 x 64 output window of each sample is computed, so the
+# oracle needs the source pixels under it: ref_augment / ref_augment_sparse on that crop as an image of its own, the
+# window's offsets shifted.  The scale is 2 (rh = 2 H, rw = 2 W): the fp32 source coordinate (i + 0.5) * 0.5 - 0.5 is
+# then exact at any i below 2^22, the weights are 0.25 and 0.75, and the crop's coordinates differ from the image's by
+# an integer -- at a ratio that fp32 rounds, a coordinate near 26000 would be good to 2e-3 pixels only.
+AUG_OUT = (64, 64)
+AUG_PAD = 2                                      # source pixels kept around those the window reads
+
+
+def augment_placement(key, boundaries=BOUNDARIES):
+    """Per sample n the window across the pixel that holds boundary n of the pixel index (2^29, 2^30, 2^31), each with
+    another flip pair -> [{"pixel": (n, y, x), "ip": the sample's iparams row, "src": (n, r0, r1, c0, c1) the source
+    pixels kept, "crop_ip": the iparams of the same window on that crop alone}]."""
+    import math
+    B, H, W = key
+    h, w = AUG_OUT
+    out = []
+    for n, (b, (ud, lr)) in enumerate(zip(boundaries, ((0, 1), (1, 0), (1, 1)))):
+        m, y, x = locate(b, H, W, 1)
+        assert m == n, (b, m)
+        ax = []
+        for size, at, flip, extent in ((H, y, ud, h), (W, x, lr, w)):
+            f = size - 1 - at if flip else at                 # the boundary pixel as the flipped image counts it
+            o = 2 * f - extent // 2                           # the window's middle lies on it
+            lo = math.floor((o + 0.5) * 0.5 - 0.5) - AUG_PAD
+            hi = math.ceil((o + extent - 0.5) * 0.5 - 0.5) + AUG_PAD + 1
+            assert 0 <= lo and hi <= size and 0 <= o <= 2 * size - extent, (n, o, lo, hi)
+            ax.append((o, lo, hi, (size - hi, size - lo) if flip else (lo, hi)))
+        (oy, ly, hy, (r0, r1)), (ox, lx, hx, (c0, c1)) = ax
+        out.append({"pixel": (n, y, x), "ip": (2 * H, 2 * W, oy, ox, ud, lr), "src": (n, r0, r1, c0, c1),
+                    "crop_ip": (2 * (hy - ly), 2 * (hx - lx), oy - 2 * ly, ox - 2 * lx, ud, lr)})
+    return out
+
+
+AUG_FPARAMS = ((0.05, 1.2, 0.1, 0.8), (-0.1, 0.7, -0.1, 1.3), (0.12, 1.0, 0.19, 0.55))   # brightness, saturation, hue, contrast
+
+
+def augment_fparams(places):
+    """(B, 6) float32: the flow multipliers of scale 2 with the flips' signs, and colour parameters of the small suite."""
+    return np.array([(2.0 * (1 - 2 * p["ip"][5]), 2.0 * (1 - 2 * p["ip"][4])) + c for p, c in zip(places, AUG_FPARAMS)],
+                    np.float32)
+
+
+def augment_source(n, place):
+    """The source pixels of one window: random uint8 frames, a smooth flow of up to 32 px, a half-density mask."""
+    from test_augment_cpu import smooth_flow
+    _, r0, r1, c0, c1 = place["src"]
+    rng = np.random.default_rng(400 + n)
+    return (rng.integers(0, 256, (1, r1 - r0, c1 - c0, 6), dtype=np.uint8), smooth_flow(1, r1 - r0, c1 - c0, seed=n),
+            (rng.random((1, r1 - r0, c1 - c0)) < 0.5).astype(np.uint8))
+
+
+def augment_window_ref(place, ims, flo, valid, fp_row, colour):
+    """Both restatements of one sample on its crop -> (ims, flo) dense and (ims, flo, valid) sparse, float64."""
+    from test_augment_cpu import ref_augment
+    from test_sparse_augment_cpu import ref_augment_sparse
+    ip = np.array([place["crop_ip"]], np.int32)
+    fp = np.asarray(fp_row, np.float32).reshape(1, 6)
+    return (ref_augment(ims, flo, ip, fp, AUG_OUT, colour=colour),
+            ref_augment_sparse(ims, flo, valid, ip, fp, AUG_OUT, colour=colour))
+
+
+def augment_planned_bytes(key):
+    B, H, W = key
+    return (6 + 8 + 1) * B * H * W
+
+
+def test_augment(arena):
+    """qpwc_augment_fwd and qpwc_augment_sparse_fwd on uint8 frames at 3 x 26833 x 26839 source pixels: p00 .. p11 pass
+    2^29, 2^30 and 2^31 in samples 0, 1 and 2 (the mask's byte index, the flow's float2 index, the frames' 6-byte pixel
+    index), each sample's 64 x 64 window lying across its boundary pixel under another flip pair.  Everything but the
+    windows' sources is zero, the mask included.  Both restatements on the crops at BOUND, the mask equal in every
+    pixel, with and without the colour stage; the sources read at the pixel index wrapped at the boundary move every
+    output by 100 bounds.  Measured: peak 30.18 GiB (planned 30.18), 1.9 s; frames 4.5e-7, flow 3.8e-6 px, sparse flow
+    7.6e-6 px against the bound of 1e-4; the controls moved every output by 6300 .. 11500 bounds."""
+    from test_augment_cpu import BOUND
+    key = CASES["augment"]
+    B, H, W = key
+    planned = augment_planned_bytes(key)
+    t0 = time.perf_counter()
+    a = arena
+    a["ims"] = ims = torch.zeros((B, H, W, 6), dtype=torch.uint8, device=DEV)
+    a["flo"] = flo = torch.zeros((B, H, W, 2), device=DEV)
+    a["valid"] = valid = torch.zeros((B, H, W), dtype=torch.uint8, device=DEV)
+    assert B * H * W > 1 << 31 and H * W < 1 << 30
+    places = augment_placement(key)
+    for n, p in enumerate(places):
+        _, r0, r1, c0, c1 = p["src"]
+        for t, crop in zip((ims, flo, valid), augment_source(n, p)):
+            t[n, r0:r1, c0:c1] = torch.from_numpy(crop[0]).to(DEV)
+    ip = torch.tensor([p["ip"] for p in places], dtype=torch.int32, device=DEV)
+    fparams = augment_fparams(places)
+    fp = torch.from_numpy(fparams).to(DEV)
+    crops = [(_cut(ims, *p["src"]).numpy(), _cut(flo, *p["src"]).numpy(), _cut3(valid, *p["src"]).numpy()) for p in places]
+    assert all(c[0].any() and c[2].any() and not c[2].all() for c in crops)
+    worst, controls = {}, []
+    for colour in (True, False):
+        d_ims, d_flo = ops.augment(ims, flo, ip, fp, AUG_OUT, colour=colour)
+        s_ims, s_flo, s_valid = ops.augment_sparse(ims, flo, valid, ip, fp, AUG_OUT, colour=colour)
+        assert torch.equal(d_ims, s_ims) and s_valid.dtype == torch.uint8
+        got = [t.cpu().numpy() for t in (d_ims, d_flo, s_flo, s_valid)]
+        for n, (p, c) in enumerate(zip(places, crops)):
+            (r_ims, r_flo), (q_ims, q_flo, q_valid) = augment_window_ref(p, c[0], c[1], c[2], fparams[n], colour)
+            assert np.array_equal(got[3][n], q_valid[0]) and 0.5 < q_valid.mean() < 1.0, n
+            assert not got[2][n][q_valid[0] == 0].any()
+            errs = {"ims": np.abs(got[0][n] - r_ims[0]).max(), "flo": np.abs(got[1][n] - r_flo[0]).max(),
+                    "sparse flo": np.abs(got[2][n] - q_flo[0]).max()}
+            print("augment sample {} colour={}: {}".format(n, colour, {k: "%.2e" % v for k, v in errs.items()}))
+            for k, v in errs.items():
+                assert v <= BOUND, (n, colour, k, v)
+                worst[k] = max(worst.get(k, 0.0), float(v))
+            assert np.abs(r_flo[0]).max() > 8.0 and np.abs(r_ims[0]).max() > 0.25
+            # the control: the source rows behind the boundary pixel as an index wrapped at the boundary finds them
+            _, y, x = p["pixel"]
+            _, r0, r1, c0, c1 = p["src"]
+            m, yy, xx = locate((n * H + y + 1) * W + c0 - BOUNDARIES[n], H, W, 1)
+            at = (m, yy, yy + r1 - y - 1, min(xx, W - (c1 - c0)), min(xx, W - (c1 - c0)) + c1 - c0)
+            alt = [x_.copy() for x_ in c]
+            for t, full, cut in zip(alt, (ims, flo, valid), (_cut, _cut, _cut3)):
+                t[:, y + 1 - r0:] = cut(full, *at).numpy()
+            (w_ims, w_flo), (_, v_flo, v_valid) = augment_window_ref(p, alt[0], alt[1], alt[2], fparams[n], colour)
+            controls.append(min(np.abs(w_ims - r_ims).max(), np.abs(w_flo - r_flo).max(), np.abs(v_flo - q_flo).max()) / BOUND)
+            assert not np.array_equal(v_valid, q_valid)
+        del d_ims, d_flo, s_ims, s_flo, s_valid
+    assert len(controls) == 2 * B and min(controls) >= 100.0, controls
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("augment: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
+        peak / GIB, planned / GIB, secs, worst, min(controls), max(controls)))
     assert planned <= 48 * GIB
     assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)

@@ -6,7 +6,9 @@ the fp32 torch composition within the bounds the GPU test uses; the negative con
 least 100 bounds; and the ctypes table carries every size that can pass 2^31 as a 64-bit integer.  For the masked
 losses and the flow metrics, whose masks are indexed by byte, also: the windows lie behind the masks' byte boundaries
 and the ground truth's 2^32nd element, a mask read at a wrapped byte offset meets no window, and the windows' flows
-keep the metrics' thresholds at a distance.
+keep the metrics' thresholds at a distance.  For the label-free losses and the input pipelines, whose oracles are crops
+of a trivial background: the shapes cross what they claim, the crops are disjoint, and the crop oracles equal the whole
+float64 restatement on a level and a source small enough to have one.
 
 The plans are restated from the constants read out of the kernel sources (tests/test_conv_grad_cpu.py::_plan) and
 compared with the library's own host functions, so a changed plan constant that pulls a region back under a boundary
@@ -1107,3 +1109,146 @@ def test_flow_windows_and_their_oracle():
     big = [150_000_000] * B                                           # the GPU case's counts: the ratios do not depend on them
     controls = lo.flow_controls(B, H * W, planted, moved, big, [45_000_000] * B)
     assert len(controls) == 4 and min(r for _, r in controls) >= 100.0, controls
+
+
+# ---- the label-free losses ---------------------------------------------------------------------------------------------
+def test_unsup_case_crosses_what_it_claims(hip_lib):
+    """3 x 15489 x 15497: the frames' element index passes 2^29, 2^30 and 2^31 in images 0, 1 and 2, the flow's 2^29 and
+    2^30, the mask's byte index 2^29, the saved planes' 2^29 .. 2^32; the validator admits it and refuses the batch that
+    passes 2^31 - 1 pixels; a window lies behind every one of these places, the crops are disjoint, and the plan fits."""
+    from qpwcnet_amd import _hip
+    key = lo.CASES["unsup_loss"]
+    B, H, W = key
+    npix = B * H * W
+    assert B == 3 and H % 2 and W % 2 and H != W and H % 8 and W % 32                  # ragged: partial tiles on both axes
+    assert lo.crossed(3 * npix) == [P29, P30, P31] and [lo.locate(b, H, W, 3)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert lo.crossed(2 * npix) == [P29, P30] and lo.crossed(npix) == [P29]
+    assert lo.crossed(7 * npix, lo.BOUNDARIES_32) == list(lo.BOUNDARIES_32)
+    ha, wa = (ctypes.c_int * 1)(H), (ctypes.c_int * 1)(W)
+    tiles = B * -(-H // _hip.UNSUP_LOSS_TILE[0]) * -(-W // _hip.UNSUP_LOSS_TILE[1])
+    assert hip_lib.qpwc_unsup_loss_workspace_floats(_hip.UNSUP_CENSUS, B, ha, wa, 1) == 4 * tiles + _hip.UNSUP_LOSS_PLANES * npix
+    assert hip_lib.qpwc_unsup_loss_fwd_kernel(_hip.UNSUP_CENSUS, B, ha, wa, 1) == b"unsup_loss_fwd_kernel<census>"
+    assert hip_lib.qpwc_unsup_loss_workspace_floats(_hip.UNSUP_CENSUS, 3 * B, ha, wa, 1) == _hip.E_SHAPE   # 2.16 G pixels
+    planned = lo.unsup_planned_bytes(key)
+    assert planned == 4 * (6 + 2 + 2) * npix + npix + 4 * (4 * tiles + 7 * npix)
+    assert planned <= 48 * lo.GIB and 1.10 * planned <= 64 * lo.GIB
+    wins = lo.unsup_windows(key)
+    tags = [x[0] for x in wins]
+    assert len(set(tags)) == len(tags) >= 10 and tags[0] == "first" and tags[-1] == "last"
+    # a window in the rows just behind the pixel under every boundary: all of its elements lie beyond it
+    under = [lo.locate(b, H, W, ch) for ch in (3, 2, 1) for b in lo.crossed(ch * npix)]
+    under += [lo.locate(b % npix, H, W, 1) for b in lo.BOUNDARIES_32]                  # plane b // npix of that pixel
+    assert len(under) == 3 + 2 + 1 + 4
+    for n, y, x in under:
+        assert any(w_[1] == n and w_[2] == y + 1 and w_[4] <= x < w_[5] for w_ in wins), (n, y, x)
+    crops = [lo.unsup_grown(x, lo.UNSUP_MARGIN + 1, H, W) for x in wins]
+    for i, a in enumerate(crops):
+        for c in crops[i + 1:]:
+            assert a[1] != c[1] or a[3] <= c[2] or c[3] <= a[2] or a[5] <= c[4] or c[5] <= a[4], (a, c)
+    # a control exists: some crop's frames lie beyond each modulus the GPU test wraps at
+    for mod_elems in (1 << 29, 1 << 30, 1 << 31):
+        assert any(((c[1] * H + c[2]) * W + c[4]) * 3 >= mod_elems for c in crops)
+    assert 2.0 ** -20 == lo.UNSUP_PARAMS["smooth_eps"] and np.float32(2.0 ** -40) > 0            # eps_s^2 is a normal fp32
+
+
+@pytest.mark.parametrize("kind", ["census", "charbonnier"])
+def test_unsup_window_oracle_is_the_chain_on_a_small_level(kind):
+    """unsup_window_ref against the float64 chain on a whole level that is small enough to have one: 3 x 61 x 67 with a
+    window in the first corner, one inside image 1 and one in the last corner -- count exact, values and gradients within
+    1e-12, the chain's gradient exactly 0 outside the crops, and a crop with other frames moves the value."""
+    from qpwcnet_amd import loss
+    key = (3, 61, 67)
+    B, H, W = key
+    wins = [("first", 0, 0, lo.WIN, 0, lo.WIN), ("inside", 1, 20, 20 + lo.WIN, 25, 25 + lo.WIN),
+            ("last", 2, H - lo.WIN, H, W - lo.WIN, W)]
+    prv, nxt = (torch.full((B, H, W, 3), lo.UNSUP_COLOUR) for _ in range(2))
+    flow, occ = torch.zeros((B, H, W, 2)), torch.ones((B, H, W), dtype=torch.uint8)
+    plants = [lo.unsup_plant(k, x, key) for k, x in enumerate(wins)]
+    lo.unsup_fill(prv, nxt, flow, occ, wins, plants)
+    regs = [p["crop"] for p in plants]
+    crops = [lo.unsup_cut(prv, nxt, flow, occ, r) for r in regs]
+    photo, smooth, count, grads, share = lo.unsup_window_ref(kind, crops, key, torch.float64)
+    p = lo.UNSUP_PARAMS
+    obj = loss.PhotometricLoss(kind, data_format="channels_last", **p)
+    x = flow.double().requires_grad_()
+    total, per, parts = loss.multiscale_unsupervised_torch(obj, torch.cat([prv, nxt], dim=3).double(), [x], [occ])
+    total.backward()
+    assert int(parts["counts"][0]) == count > 100 and 0.9 < share < 1.0
+    assert abs(float(parts["photometric"][0] - photo)) <= 1e-12 * float(photo)
+    assert abs(float(parts["smoothness"][0] - smooth)) <= 1e-12 * float(smooth)
+    top = float(x.grad.abs().max())
+    rest = x.grad.clone()
+    for r, g in zip(regs, grads):
+        n, y0, y1, x0, x1 = r[1:]
+        assert float((x.grad[n:n + 1, y0:y1, x0:x1] - g).abs().max()) <= 1e-12 * top and g.any()
+        rest[n, y0:y1, x0:x1] = 0
+    assert not rest.any()
+    ref32 = lo.unsup_window_ref(kind, crops, key, torch.float32)
+    bounds = lo.unsup_bounds((photo, smooth, count, grads, share), ref32)
+    assert ref32[2] == count and bounds["photo"] <= 1e-4 * float(photo) and bounds["grad"] <= 1e-3 * top
+    alt = crops[:1] + [lo.unsup_cut(prv, nxt, flow, occ, regs[1], frames_at=(1, 0, regs[1][3] - regs[1][2], 0,
+                                                                              regs[1][5] - regs[1][4]))] + crops[2:]
+    assert abs(float(lo.unsup_window_ref(kind, alt, key, torch.float64)[0] - photo)) >= 100 * bounds["photo"]
+
+
+# ---- the input pipelines ---------------------------------------------------------------------------------------------------
+def test_augment_case_crosses_what_it_claims():
+    """3 x 26833 x 26839 source pixels: the pixel index passes 2^29, 2^30 and 2^31 in samples 0, 1 and 2 -- the mask's
+    byte index, the flow's float2 index (bytes 2^32 .. 2^34) and the frames' 6-byte pixel index; the validator's rule
+    admits it; each sample's window reads source rows on both sides of its boundary pixel, under another flip pair, at
+    coordinates that fp32 holds exactly; the plan fits."""
+    key = lo.CASES["augment"]
+    B, H, W = key
+    assert B == 3 and H % 2 and W % 2 and H != W
+    assert lo.crossed(B * H * W) == [P29, P30, P31] and [lo.locate(b, H, W, 1)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    text = open(os.path.join(CSRC, "augment.hip")).read()
+    body = re.search(r"bool augment_shape_ok\(.*?\{(.*?)\n\}", text, re.S).group(1)
+    assert body.count("(int64_t)H * W <= lim") == 1 and "0x7fffffff" in body and H * W <= 0x7fffffff
+    assert lo.AUG_OUT[0] * lo.AUG_OUT[1] <= 0x7fffffff // 6
+    places = lo.augment_placement(key)
+    assert sorted((p["ip"][4], p["ip"][5]) for p in places) == [(0, 1), (1, 0), (1, 1)]
+    for n, p in enumerate(places):
+        m, y, x = p["pixel"]
+        _, r0, r1, c0, c1 = p["src"]
+        rh, rw, oy, ox, ud, lr = p["ip"]
+        assert m == n and (m * H + y) * W + x == lo.BOUNDARIES[n]
+        assert r0 + 8 < y < r1 - 8 and c0 + 8 < x < c1 - 8 and r1 - r0 <= 40 and c1 - c0 <= 40
+        assert (rh, rw) == (2 * H, 2 * W) and 0 <= oy <= rh - lo.AUG_OUT[0] and 0 <= ox <= rw - lo.AUG_OUT[1]
+        ch, cw, coy, cox = p["crop_ip"][:4]
+        assert (ch, cw) == (2 * (r1 - r0), 2 * (c1 - c0)) and 0 <= coy <= ch - lo.AUG_OUT[0] and 0 <= cox <= cw - lo.AUG_OUT[1]
+        # the fp32 source coordinates of the window are exact, and the crop's differ from them by an integer
+        for o, co, size, csize, extent in ((oy, coy, H, r1 - r0, lo.AUG_OUT[0]), (ox, cox, W, c1 - c0, lo.AUG_OUT[1])):
+            i = np.arange(extent)
+            s32 = (np.float32(o + i) + np.float32(0.5)) * (np.float32(size) / np.float32(2 * size)) - np.float32(0.5)
+            c32 = (np.float32(co + i) + np.float32(0.5)) * (np.float32(csize) / np.float32(2 * csize)) - np.float32(0.5)
+            s64 = (o + i + 0.5) * 0.5 - 0.5
+            assert np.array_equal(s32.astype(np.float64), s64) and len(set((s64 - c32).tolist())) == 1
+            assert (s64 - c32)[0] == int((s64 - c32)[0])
+    planned = lo.augment_planned_bytes(key)
+    assert planned == 15 * B * H * W and planned <= 48 * lo.GIB and 1.10 * planned <= 64 * lo.GIB
+
+
+@pytest.mark.parametrize("colour", [True, False], ids=["colour", "plain"])
+def test_augment_crop_oracle_is_the_oracle_on_a_small_image(colour):
+    """augment_window_ref (the restatements on a window's source crop, offsets shifted) against the same restatements on
+    the whole source where that is small: 3 x 301 x 311, the windows across a pixel in the middle of each image."""
+    from test_augment_cpu import ref_augment
+    from test_sparse_augment_cpu import ref_augment_sparse
+    key = (3, 301, 311)
+    B, H, W = key
+    places = lo.augment_placement(key, [(n * H + 140 + 7 * n) * W + 100 + 30 * n for n in range(B)])
+    ims, flo, valid = np.zeros((B, H, W, 6), np.uint8), np.zeros((B, H, W, 2), np.float32), np.zeros((B, H, W), np.uint8)
+    for n, p in enumerate(places):
+        _, r0, r1, c0, c1 = p["src"]
+        for t, crop in zip((ims, flo, valid), lo.augment_source(n, p)):
+            t[n, r0:r1, c0:c1] = crop[0]
+    ip, fp = np.array([p["ip"] for p in places], np.int32), lo.augment_fparams(places)
+    w_ims, w_flo = ref_augment(ims, flo, ip, fp, lo.AUG_OUT, colour=colour)
+    s_ims, s_flo, s_valid = ref_augment_sparse(ims, flo, valid, ip, fp, lo.AUG_OUT, colour=colour)
+    for n, p in enumerate(places):
+        _, r0, r1, c0, c1 = p["src"]
+        cut = lambda t: t[n:n + 1, r0:r1, c0:c1]
+        (r_ims, r_flo), (q_ims, q_flo, q_valid) = lo.augment_window_ref(p, cut(ims), cut(flo), cut(valid), fp[n], colour)
+        assert np.abs(r_ims[0] - w_ims[n]).max() <= 1e-12 and np.abs(r_flo[0] - w_flo[n]).max() <= 1e-12
+        assert np.abs(q_flo[0] - s_flo[n]).max() <= 1e-12 and np.array_equal(q_valid[0], s_valid[n])
+        assert 0.5 < q_valid.mean() < 1.0 and np.abs(r_flo).max() > 8.0 and np.abs(r_ims).max() > 0.25
