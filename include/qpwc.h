@@ -124,7 +124,18 @@ int qpwc_cost_volume_fwd_strided(const void* prv, const void* nxt, void* out,
  * Samples img at (y + flo[...,1], x + flo[...,0]) bilinearly.
  * img/out: (B,H,W,C) or (B,C,H,W) of `dtype`; flo: same layout with 2 channels
  * (x, y), ALWAYS fp32 (coordinates need the precision); flow dims flagged in flo_bcast_mask have extent 1 (e.g. a (1,1,1,2) flow,
- * qpwcnet/app/optical_flow/test_warp.py:32) and flo is dense over the rest. */
+ * qpwcnet/app/optical_flow/test_warp.py:32) and flo is dense over the rest.
+ * NON-FINITE AND HUGE FLOWS (a diverged model; the 1e10 "unknown" of a .flo file) are values like any other: no address
+ * is formed from a flow value before it is clamped into the image.  What the kernels do, and what the CPU restatements
+ * under oracle/ follow (tests/test_nonfinite_flow_cpu.py restates it pixel by pixel):
+ *   mode TFWARP  the corner is int(x + fx), converted toward zero, SATURATING at INT32_MIN / INT32_MAX, NaN -> 0; the
+ *                second corner is corner + 1, except that the second corner of INT32_MAX is INT32_MAX (no wrap); both
+ *                are then clamped to [0, size - 1]; the weights use the clamped corners and the raw sum, so a NaN or
+ *                infinite coordinate gives a NaN output at that pixel, a finite huge one a finite output;
+ *   mode CLAMP   floor and alpha are clamped in floating point with fmaxf / fminf, which return their other operand
+ *                for a NaN: a NaN coordinate samples corner 0 with alpha 0, +Inf the last corner pair with alpha 1,
+ *                -Inf corner 0 with alpha 0; the output is finite whenever img is.
+ * Only the pixel that carries such a flow is affected. */
 int qpwc_warp_fwd(const void* img, const void* flo, void* out,
                   int B, int H, int W, int C, int flo_bcast_mask,
                   int layout, int dtype, int mode, void* stream);
@@ -517,14 +528,20 @@ int qpwc_upsample2x_flow_bwd(const void* grad_out, void* grad_in, int B, int h, 
 
 /* inv_flow = -tf_warp(flow, flow) (occlusion.py:85; app/test/test_invert_flow.py:47): the flow
  * field sampled at its own targets with the tf_warp rules (warp.py:63-153), negated.
- * flow, out: (B,H,W,2) [NHWC] or (B,2,H,W) [NCHW], storage `dtype`, arithmetic fp32. */
+ * flow, out: (B,H,W,2) [NHWC] or (B,2,H,W) [NCHW], storage `dtype`, arithmetic fp32.
+ * Non-finite and huge flows follow mode TFWARP of qpwc_warp_fwd (saturating conversion, NaN -> 0, no wrap of the second
+ * corner, clamp after the conversion): the pixel itself and the pixels whose corners it is come out NaN or finite as
+ * that rule says; no other pixel changes. */
 int qpwc_invert_flow_fwd(const void* flow, void* out, int B, int H, int W, int layout, int dtype,
                          void* stream);
 
 /* estimate_occlusion_map (occlusion.py:27-118): out (B,H,W) fp32, 1 where the pixel leaves the
  * image under `flow` or is the target of no pixel under the inverse flow above
  * (idx3 = clip(int32(p + inv_flow[p])), tensor_scatter_nd_min of zeros into ones), else 0.
- * Two launches (fill, scatter); deterministic. */
+ * Two launches (fill, scatter); deterministic.
+ * The target int32(p + inv_flow[p]) is converted like the corners of qpwc_warp_fwd's mode TFWARP (toward zero,
+ * saturating, NaN -> 0) and then clamped into the image: a pixel whose inverse flow is NaN marks row / column 0, +-Inf or
+ * a huge value the nearest border.  The out-of-bounds test of a NaN sum is false.  The map holds 0 and 1 only. */
 int qpwc_occlusion_fwd(const void* flow, void* out, int B, int H, int W, int layout, int dtype,
                        void* stream);
 

@@ -17,6 +17,7 @@
  * -ffp-contract=off keeps every multiply and add separately rounded, like the
  * reference's unfused TF op graph.
  */
+#include <limits.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -65,6 +66,15 @@ int oracle_cost_volume(const float* prv, const float* nxt, float* out,
 
 static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+/* float -> int as the HIP kernels convert (v_cvt_i32_f32; include/qpwc.h, qpwc_warp_fwd): toward zero, saturating,
+ * NaN -> 0.  A plain (int) cast of a NaN or an out-of-range float is undefined behaviour in C. */
+static inline int sat_trunc(float v) {
+    if (v != v) return 0;
+    if (v >= 2147483648.0f) return INT_MAX;
+    if (v <= -2147483648.0f) return INT_MIN;
+    return (int)v;
+}
+
 /* flow element (b,y,x,ch) with explicit element strides, 0 = broadcast dim */
 static inline float flo_at(const float* flo, const int64_t* fs, int b, int y, int x, int ch) {
     return flo[(size_t)b * fs[0] + (size_t)y * fs[1] + (size_t)x * fs[2] + (size_t)ch * fs[3]];
@@ -104,8 +114,9 @@ int oracle_warp(const float* img, const float* flo, float* out,
                 } else {
                     const float xf = (float)x + fx;              /* warp.py:102 */
                     const float yf = (float)y + fy;
-                    int x0 = (int)xf, y0 = (int)yf;              /* warp.py:115,117 truncation */
-                    int x1 = x0 + 1, y1 = y0 + 1;
+                    int x0 = sat_trunc(xf), y0 = sat_trunc(yf);  /* warp.py:115,117 truncation */
+                    /* the second corner of a corner saturated at INT_MAX is that corner (csrc/common.h) */
+                    int x1 = x0 == INT_MAX ? x0 : x0 + 1, y1 = y0 == INT_MAX ? y0 : y0 + 1;
                     x0 = clampi(x0, 0, W - 1);                   /* warp.py:121-124 */
                     x1 = clampi(x1, 0, W - 1);
                     y0 = clampi(y0, 0, H - 1);

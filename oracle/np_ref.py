@@ -77,6 +77,27 @@ def _from_nhwc(x, data_format):
     return x
 
 
+INT32_MAX = np.int64(2 ** 31 - 1)
+INT32_MIN = np.int64(-2 ** 31)
+
+
+def sat_trunc_i32(v):
+    """float -> int as the HIP kernels convert (v_cvt_i32_f32; include/qpwc.h, qpwc_warp_fwd): toward zero, saturating
+    at the int32 limits, NaN -> 0.  ``astype(np.int32)`` of such values is platform-defined (INT32_MIN on x86).
+    Returns int64 holding int32 values, so that ``+ 1`` cannot wrap."""
+    v = np.asarray(v)
+    ok = np.abs(v) < 2.0 ** 31                                   # False for NaN
+    out = np.where(ok, v, 0).astype(np.int64)                    # in range: truncation
+    out = np.where(v >= 2.0 ** 31, INT32_MAX, out)
+    return np.where(v <= -(2.0 ** 31), INT32_MIN, out)
+
+
+def _second_corner(c0):
+    """``c0 + 1``, except that the second corner of a corner saturated at INT32_MAX is that corner (csrc/common.h,
+    taps_tfwarp): 32-bit arithmetic would wrap it to INT32_MIN."""
+    return np.where(c0 == INT32_MAX, c0, c0 + 1)
+
+
 def _gather_yx(img_nhwc, y, x):
     """``get_pixel_value`` -- qpwcnet/core/warp.py:8-47 (gather_nd, batch_dims=1)."""
     b = np.arange(img_nhwc.shape[0]).reshape(-1, 1, 1)
@@ -105,10 +126,10 @@ def tf_warp(img, flow, data_format=CHANNELS_LAST):
     y = gy + flow_l[..., 1]
     max_y = H - 1
     max_x = W - 1
-    x0 = x.astype(np.int32)                                     # warp.py:115 (truncation)
-    x1 = x0 + 1
-    y0 = y.astype(np.int32)                                     # warp.py:117
-    y1 = y0 + 1
+    x0 = sat_trunc_i32(x)                                       # warp.py:115 (truncation)
+    x1 = _second_corner(x0)
+    y0 = sat_trunc_i32(y)                                       # warp.py:117
+    y1 = _second_corner(y0)
     x0 = np.clip(x0, 0, max_x)                                  # warp.py:121-124
     x1 = np.clip(x1, 0, max_x)
     y0 = np.clip(y0, 0, max_y)
@@ -146,13 +167,15 @@ def interpolate_bilinear(grid, query_points):
         queries = q[..., dim]
         max_floor = np.asarray(size - 2, dtype=dt)
         min_floor = np.asarray(0.0, dtype=dt)
-        floor = np.minimum(np.maximum(min_floor, np.floor(queries)), max_floor)
+        # fmax / fmin, C's fmaxf / fminf: the other operand for a NaN, so a NaN query gives floor 0 and alpha 0 as
+        # in the kernels (csrc/common.h, taps_clamp); np.maximum would carry the NaN into the index
+        floor = np.fmin(np.fmax(min_floor, np.floor(queries)), max_floor)
         int_floor = floor.astype(np.int32)
         floors.append(int_floor)
         ceils.append(int_floor + 1)
         alpha = (queries - floor).astype(grid.dtype)
-        alpha = np.minimum(np.maximum(np.asarray(0.0, grid.dtype), alpha),
-                           np.asarray(1.0, grid.dtype))
+        alpha = np.fmin(np.fmax(np.asarray(0.0, grid.dtype), alpha),
+                        np.asarray(1.0, grid.dtype))
         alphas.append(alpha[..., None])
     flat = grid.reshape(B * H * W, C)
     boff = (np.arange(B) * H * W).reshape(B, 1)
@@ -246,7 +269,7 @@ def estimate_occlusion_map(flow, data_format=CHANNELS_LAST):
     inv_flow = invert_flow(flow, data_format)                   # occlusion.py:85
     dj, di = np.moveaxis(inv_flow, axis, 0)
     i2, j2 = i + di, j + dj
-    idx3 = np.stack([i2, j2], axis=-1).astype(np.int32)         # occlusion.py:88 (truncation)
+    idx3 = sat_trunc_i32(np.stack([i2, j2], axis=-1))           # occlusion.py:88 (truncation)
     idx3 = np.clip(idx3, [0, 0], [h - 1, w - 1])                # occlusion.py:89-92
     b = np.broadcast_to(np.arange(n).reshape(n, 1, 1), (n, h, w))
     map3 = np.ones_like(oob)                                    # occlusion.py:95 scatter_nd_min

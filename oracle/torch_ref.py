@@ -31,11 +31,14 @@ def _interpolate_bilinear(grid, query):
     alphas, floors, ceils = [], [], []
     for dim, size in ((0, H), (1, W)):
         q = query[..., dim]
-        floor = torch.clamp(torch.floor(q), 0.0, float(size - 2))
+        # a NaN query gives floor 0 and alpha 0, as fmaxf(0, NaN) = 0 does in the kernels (csrc/common.h, taps_clamp);
+        # torch.clamp alone would carry the NaN into the index.  Finite queries, and their gradients, are untouched.
+        nan_to_zero = lambda v: torch.where(torch.isnan(v), torch.zeros_like(v), v)
+        floor = torch.clamp(nan_to_zero(torch.floor(q)), 0.0, float(size - 2))
         int_floor = floor.to(torch.int64)
         floors.append(int_floor)
         ceils.append(int_floor + 1)
-        alphas.append(torch.clamp(q - floor, 0.0, 1.0).unsqueeze(-1))
+        alphas.append(torch.clamp(nan_to_zero(q - floor), 0.0, 1.0).unsqueeze(-1))
     flat = grid.reshape(B * H * W, C)
     boff = (torch.arange(B) * H * W).reshape(B, 1)
 
@@ -62,6 +65,18 @@ def warp_v2(img, flo):
     return _interpolate_bilinear(img, query).reshape(B, H, W, C)
 
 
+_INT32_MAX, _INT32_MIN = 2 ** 31 - 1, -2 ** 31
+
+
+def _sat_trunc_i32(v):
+    """float -> int as the HIP kernels convert (include/qpwc.h, qpwc_warp_fwd): toward zero, saturating at the int32
+    limits, NaN -> 0; int64 holding int32 values.  ``.to(torch.int32)`` of such values is undefined."""
+    ok = v.abs() < 2.0 ** 31                                          # False for NaN
+    out = torch.where(ok, v, torch.zeros_like(v)).to(torch.int64)
+    out = torch.where(v >= 2.0 ** 31, torch.full_like(out, _INT32_MAX), out)
+    return torch.where(v <= -(2.0 ** 31), torch.full_like(out, _INT32_MIN), out)
+
+
 def tf_warp(img, flow):
     """``tf_warp`` -- qpwcnet/core/warp.py:63-153."""
     B, H, W, C = img.shape
@@ -69,9 +84,9 @@ def tf_warp(img, flow):
     x = gx.to(flow.dtype).unsqueeze(0) + flow[..., 0]
     y = gy.to(flow.dtype).unsqueeze(0) + flow[..., 1]
     x, y = x.expand(B, H, W), y.expand(B, H, W)
-    x0 = x.to(torch.int32).to(torch.int64)                           # truncation, warp.py:115
-    y0 = y.to(torch.int32).to(torch.int64)
-    x1, y1 = x0 + 1, y0 + 1
+    x0, y0 = _sat_trunc_i32(x), _sat_trunc_i32(y)                    # truncation, warp.py:115
+    # the second corner of a corner saturated at INT32_MAX is that corner (csrc/common.h, taps_tfwarp)
+    x1, y1 = torch.where(x0 == _INT32_MAX, x0, x0 + 1), torch.where(y0 == _INT32_MAX, y0, y0 + 1)
     x0, x1 = x0.clamp(0, W - 1), x1.clamp(0, W - 1)                  # warp.py:121-124
     y0, y1 = y0.clamp(0, H - 1), y1.clamp(0, H - 1)
     b = torch.arange(B).reshape(B, 1, 1)

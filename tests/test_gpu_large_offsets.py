@@ -29,13 +29,13 @@ windows (the area loss takes the kernel's own gt_out, itself held to float64 on 
 copy of the ground truth), so value and grad_pred follow from the windows' crops in float64.  Their magnitudes are
 1e-6 and below, so their bound is relative (LOSS_REL, derived at its definition), not the 1e-4 of the layers.
 
-The masked losses and the flow metrics (the last three entries of CASES) index a uint8 mask by pixel, so a byte offset
+The masked losses and the flow metrics ("masked_loss", "masked_loss_pixel", "flow_quality" of CASES) index a uint8 mask by pixel, so a byte offset
 is an index: their shapes put 2^31 (masked losses, tile path) and 2^30 (the others) pixels into the batch, and the tile
 path's ground truth reaches 2^32 elements (BOUNDARIES_32).  Validity is zero (masked losses) or the prediction is the
 truth (flow metrics) except in planted windows, so the float64 answer needs the windows' crops and the masks' counts
 only; see the comments at their sections.
 
-The label-free losses and the input pipelines (the last two entries of CASES) have a trivial background instead -- one
+The label-free losses and the input pipelines ("unsup_loss", "augment") have a trivial background instead -- one
 colour, zero flow, everything occluded; zero sources with a zero mask -- so that their float64 answers need crops only;
 see the comments at their sections.  On paper, for these two: the casts in the sources are redundant one by one --
 `pix = (b * h + y) * (int64_t)w + x` of unsup_loss_fwd_kernel has an int64_t `b`, and the validator keeps B * h * w
@@ -50,6 +50,13 @@ before the workspace, over whatever lies there; the gradient of every window and
 int64_t p00` to `const int p00` makes sample 2 read the source rows behind its boundary pixel 2^32 pixels lower; the
 control reads them 2^31 lower, finds the zeros that lie there, and every output moves by thousands of bounds.  `int64_t
 pix` to `int pix` in aug_load_pixel wraps `pix * 6` from pixel 357,913,942 on: all three windows lie beyond.
+
+The last three entries of CASES -- the occlusion map and inverse flow, the interpolator's input pipeline, the update
+step -- are held to equality or to their family's float64 oracle on windows and rows of fully random data (the
+occlusion kernels are bit-exact, so their windows need a restatement in the full image's coordinates), and each has the
+control that the data a narrow index would read gives another answer; the comments at their sections say what a 32-bit
+index, a loop without its stride and a truncated unit offset would break, on paper: those mutants write outside their
+tensors and are not run.
 
 Where a family departs from this: grad_img of the warp is a scatter of float atomics, so it is held to (b) only; the
 cost-volume backward is fed a random saved output (it reads it for the LeakyReLU mask only) and gives its two
@@ -95,10 +102,13 @@ Measured on an MI355X (peak of torch.cuda.max_memory_allocated, wall time of the
   flow_quality              22.01 (22.01)        2.1          relative: means 2.7e-7 (bound 1e-5); 1.7e-7 px, 3.5e-13 degrees, count ratios 0.50 ulp
   unsup_loss (census)       46.32 (46.32)        1.5          relative: photometric 4.7e-9, smoothness 1.3e-8 (bound 1e-5); grad_flow 6.4e-9 of a largest 2.4e-3 (bound 2.6e-8)
   augment, dense + sparse   30.18 (30.18)        1.9          frames 4.5e-7, flow 3.8e-6 px, sparse flow 7.6e-6 px (bound 1e-4); masks equal
+  occlusion, inverse flow   26.01 (25.34)        0.4 - 1.3    0 (equality): 33 windows, 3 x 3 one-image launches; 30 controls: the inverse flow differs in 0.86 - 1.00, the map in 0.46 - 0.49 of the pixels behind the boundary
+  triplet                   48.90 (47.76)        0.1 - 0.9       pair 2.3e-7, middle frame 2.0e-7 (bound 1e-4); 16 controls 10151 - 12367 bounds
+  agc_adam step             42.86 (40.85)        2.1 - 4.0    37 rows: p 1.5e-8 (bound 1.56e-7), m 5.3e-8 (1.88e-6), v 4.9e-8 (1.16e-6); p, m, v torch.equal; control 2.6e6 bounds
 unsup_loss: 10 windows, count 1871; the windows' share of the smoothness sum is 0.888 at smooth_eps = 2^-20; the bounds,
 4 x the float32 chain on the same crops, came out at their floor of 1e-5 for both values and at 2.6e-8 (4 x 6.5e-9, of
 a largest gradient of 2.4e-3) for grad_flow.
-The whole module: 20 tests, 3 - 16 s (the seconds are test bodies in different runs).  The peaks above the plan are the boolean of torch.equal on one image (0.67 GiB);
+The whole module: 23 tests, 3 - 16 s (the seconds are test bodies in different runs).  The peaks above the plan are the boolean of torch.equal on one image (0.67 GiB);
 ops.py itself allocates what is planned and nothing else.  The negative controls moved the sums by 1300 - 20500 bounds;
 those of the masked losses moved the loss or grad_pred by 190 - 200000 bounds, those of the flow metrics an image's epe by
 7100 - 100000; those of the label-free loss moved the photometric value by 185 - 10500 bounds, those of the input pipelines
@@ -149,6 +159,11 @@ CASES = {
                                                          # the saved planes 5.04 G, the mask 2^29 bytes and more
     "augment": (3, 26833, 26839),                        # (B, H, W) of the source: 2.161 G pixels of 6 bytes, a float2 and a
                                                          # mask byte each
+    "occlusion": (3, 18917, 18923),                      # (B, H, W) of a flow: 1.0739 G pixels, 2^28 a stride trip: five
+                                                         # trips, the last of 157,349 pixels; 2.148 G flow elements
+    "triplet": (3, 28528, 28534),                        # (B, H, W) of a uint8 frame: 2^29.6 < 0.814 G pixels < 2^30 a sample,
+                                                         # 7.33 GB a frame; the outputs (H / 2, W / 2): 3.66 G and 1.83 G floats
+    "optim": (18683000, 115),                            # (rows, floats a row) of one parameter: 2.1485 G floats, a unit a row
 }
 BOUNDARIES_32 = BOUNDARIES + (1 << 32,)                  # ... and the unsigned index limit, for operands that reach it
 
@@ -2056,5 +2071,573 @@ def test_augment(arena):
     peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
     print("augment: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, controls {:.0f} .. {:.0f} bounds".format(
         peak / GIB, planned / GIB, secs, worst, min(controls), max(controls)))
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- occlusion map and inverse flow: above 2^28 pixels (the stride loops iterate) and past 2^31 flow elements ------
+# csrc/occlusion.hip launches min(ceil(pixels / 256), 2^20) workgroups of 256: one grid-stride trip covers 2^28 pixels.
+# At 3 x 18917 x 18923 every launch makes five trips, the last of 157,349 pixels; the channels-last element index
+# `idx * 2` passes 2^29, 2^30 and 2^31 in images 0, 1 and 2, the channels-first `b * 2 * plane + y * W + x` likewise
+# (2^31 fp16 elements: 2^32 bytes), and the map's pixel index passes 2^29 and 2^30 (2^31 and 2^32 bytes).
+#
+# Both ops are bit-exact against the fp32 numpy restatement (tests/test_gpu_occlusion.py), so every comparison here is
+# equality.  (a) per image against the launch on that image alone, and invert_flow against -tf_warp(flow, flow) of the
+# warp kernel; (b) OCC_WIN x OCC_WIN windows against occ_restatement(), the fp32 chain of oracle.np_ref in the FULL
+# image's coordinates: `(float)y + inv.y` at y near 18000 rounds to 2^-9 where the same window numbered from 0 would
+# not, and the truncated target may differ by a pixel, so a crop handed to np_ref as an image of its own is no oracle;
+# (c) the restatement fed the crop that an element index wrapped at 2^31 elements or 2^32 bytes finds differs from the
+# right answer in every window behind that boundary.
+#
+# What is compared of a window: with |flow| <= F = 6 and weights in [0, 1] the inverse flow of a pixel lies within F,
+# its truncated target within F + 1, and it reads flows within F + 1 of itself: a map pixel depends on flows within
+# 2 F + 2, and pixels 2 F + 3 from a crop edge that is no image edge are compared.  The image's first rows and columns
+# are different: a sample at -1 < x + fx < 0 truncates to corner 0 with the second corner 1 and weights 1 - xf and xf,
+# an extrapolation of up to 3 F an axis and 9 F = 54 pixels over both, so a window that touches the image's top or left
+# edge compares what lies OCC_EDGE_MARGIN = 64 >= 54 + 1 + F + 1 + 1 from its artificial edges.  Past the bottom and
+# right edges both corners clip to the last pixel and the weights cancel.
+#
+# On paper: `int64_t idx` to `int idx` in invert_flow_kernel makes `idx += gridDim.x * blockDim.x` a 32-bit sum; from
+# the fourth trip on it is 2^30 and more, and `idx * 2` as an int wraps at pixel 2^30: image 2 from there on is not
+# written (or written 2^32 elements lower), so (a) fails for image 2 and (b) in the ">2^30 px" window and the corners
+# behind it.  Without the loop's increment a lane runs one trip, pixels from 2^28 on keep what the allocation held: (a)
+# fails for every image, (b) in every window.  A 32-bit `b * 2 * plane` in FlowField::at reads image 2's y plane 2^32
+# elements lower; control (c) shows that other flows there change both results in every such window.
+OCC_F = 6
+OCC_WIN = 160
+OCC_MARGIN = 2 * OCC_F + 3
+OCC_EDGE_MARGIN = 64
+OCC_TRIP = (1 << 20) * 256            # pixels of one grid-stride trip; the CPU companion reads both factors from the source
+
+
+def occ_restatement(crop, origin, full, half=False):
+    """oracle.np_ref.invert_flow and estimate_occlusion_map in fp32 on a crop (h, w, 2) of one image whose first pixel
+    is `origin` = (y, x) of the `full` = (H, W) image: coordinates, clips and the out-of-bounds test are the full
+    image's, gathers that leave the crop read its nearest pixel (what depends on them is not compared: see above).
+    half: the inverse flow as fp16 storage holds it; the map is computed from the unrounded one, as the kernel does.
+    -> (inverse flow (h, w, 2), map (h, w))."""
+    f32 = np.float32
+    crop = np.ascontiguousarray(crop, dtype=f32)
+    h, w, _ = crop.shape
+    (oy, ox), (H, W) = origin, full
+    gy = (oy + np.arange(h)).astype(f32)[:, None]
+    gx = (ox + np.arange(w)).astype(f32)[None, :]
+    x, y = gx + crop[..., 0], gy + crop[..., 1]                       # warp.py:100-111
+    x0, y0 = x.astype(np.int32), y.astype(np.int32)                   # :115-117, |x|, |y| < 2^15: no saturation here
+    x1, y1 = x0 + 1, y0 + 1
+    x0, x1 = np.clip(x0, 0, W - 1), np.clip(x1, 0, W - 1)             # :121-124
+    y0, y1 = np.clip(y0, 0, H - 1), np.clip(y1, 0, H - 1)
+    at = lambda yy, xx: crop[np.clip(yy - oy, 0, h - 1), np.clip(xx - ox, 0, w - 1)]
+    Ia, Ib, Ic, Id = at(y0, x0), at(y1, x0), at(y0, x1), at(y1, x1)   # :127-130
+    x0f, x1f, y0f, y1f = (t.astype(f32) for t in (x0, x1, y0, y1))
+    wa, wb = (x1f - x) * (y1f - y), (x1f - x) * (y - y0f)             # :139-142
+    wc, wd = (x - x0f) * (y1f - y), (x - x0f) * (y - y0f)
+    inv = -(wa[..., None] * Ia + wb[..., None] * Ib + wc[..., None] * Ic + wd[..., None] * Id)   # :151, occlusion.py:85
+    assert inv.dtype == f32
+    i2, j2 = gy + crop[..., 1], gx + crop[..., 0]                     # occlusion.py:60
+    oob = ((i2 < 0) | (i2 >= H) | (j2 < 0) | (j2 >= W)).astype(f32)   # :74
+    ti = np.clip((gy + inv[..., 1]).astype(np.int32), 0, H - 1) - oy  # :86-92
+    tj = np.clip((gx + inv[..., 0]).astype(np.int32), 0, W - 1) - ox
+    inside = (ti >= 0) & (ti < h) & (tj >= 0) & (tj < w)
+    map3 = np.ones((h, w), f32)                                       # :94-95
+    map3[ti[inside], tj[inside]] = 0.0
+    return (inv.astype(np.float16).astype(f32) if half else inv), np.maximum(oob, map3)   # :98
+
+
+def occ_pixels(key):
+    """[(tag, n, y, x)]: the pixels that hold each boundary of the channels-last flow and inverse flow (two elements a
+    pixel), of the map, of the channels-first planes (`b * 2 * plane + y * W + x`, the x plane's index), the first
+    pixel of stride trips 2 and 4, and the four corners of the last image; one entry a pixel."""
+    B, H, W = key
+    plane = H * W
+    out, seen = [], set()
+
+    def add(tag, n, y, x):
+        if (n, y, x) not in seen:
+            seen.add((n, y, x))
+            out.append((tag, n, y, x))
+    for b in crossed(B * plane * 2):
+        add("nhwc>2^%d" % (b.bit_length() - 1), *locate(b, H, W, 2))
+    for b in crossed(B * plane):
+        add("map>2^%d" % (b.bit_length() - 1), *locate(b, H, W, 1))
+    for k in (1, 3):
+        add("trip %d" % (k + 1), *locate(k * OCC_TRIP, H, W, 1))
+    for b in crossed(B * plane * 2):
+        add("nchw>2^%d" % (b.bit_length() - 1), b // plane // 2, b % plane // W, b % W)
+    for tag, y, x in (("top left", 0, 0), ("top right", 0, W - 1), ("bottom left", H - 1, 0), ("bottom right", H - 1, W - 1)):
+        add(tag, B - 1, y, x)
+    return out
+
+
+def occ_windows(key):
+    """[(tag, n, y0, y1, x0, x1, (cy0, cy1, cx0, cx1))]: an OCC_WIN x OCC_WIN window around each pixel of occ_pixels()
+    and the part of it, in window coordinates, that is compared."""
+    B, H, W = key
+    wins = []
+    for tag, n, y, x in occ_pixels(key):
+        (y0, y1), (x0, x1) = _span(y, OCC_WIN, H), _span(x, OCC_WIN, W)
+        m = OCC_EDGE_MARGIN if y0 == 0 or x0 == 0 else OCC_MARGIN
+        cmp_ = (0 if y0 == 0 else m, OCC_WIN - (0 if y1 == H else m), 0 if x0 == 0 else m, OCC_WIN - (0 if x1 == W else m))
+        wins.append((tag, n, y0, y1, x0, x1, cmp_))
+    return wins
+
+
+def occ_element_index(key, win, layout):
+    """(h, w, 2) int64: the element index of every flow value of a window, `idx * 2 + c` (channels-last) or
+    `b * 2 * plane + y * W + x + c * plane` (channels-first), as FlowField::at forms it."""
+    B, H, W = key
+    _, n, y0, y1, x0, x1 = win[:6]
+    yy, xx = np.mgrid[y0:y1, x0:x1].astype(np.int64)
+    if layout == "channels_last":
+        base = ((n * H + yy) * W + xx) * 2
+        return np.stack([base, base + 1], -1)
+    base = n * 2 * H * W + yy * W + xx
+    return np.stack([base, base + H * W], -1)
+
+
+def occ_wrapped(key, win, layout, esize):
+    """What a narrow index would read: [(modulus in elements, mask (h, w, 2) of the window's flow values whose element
+    index reaches it, their indices wrapped)] for 2^31 elements and 2^32 bytes, where the window reaches them."""
+    idx = occ_element_index(key, win, layout)
+    out = []
+    for mod in sorted({1 << 31, (1 << 32) // esize}):
+        mask = idx >= mod
+        if mask.any():
+            out.append((mod, mask, idx[mask] % mod))
+    return out
+
+
+def occlusion_planned_bytes(key):
+    """The fp32 flow, its inverse and the map of the big launches; beside them the inverse flow of one image and the
+    warp kernel's, negated in place."""
+    B, H, W = key
+    return (8 + 8 + 4) * B * H * W + 2 * 8 * H * W
+
+
+def _occ_cut(t, layout, n, y0, x0):
+    """An OCC_WIN x OCC_WIN crop (h, w, 2) of a flow tensor as fp32 on the host (fp16 -> fp32 is exact)."""
+    if layout == "channels_last":
+        return t[n, y0:y0 + OCC_WIN, x0:x0 + OCC_WIN, :].float().cpu().numpy()
+    return t[n, :, y0:y0 + OCC_WIN, x0:x0 + OCC_WIN].permute(1, 2, 0).float().cpu().numpy()
+
+
+def _occ_check(key, flow, inv, occ, layout, what, stats):
+    """Oracles (a), (b) and (c) of one layout and dtype on the big launch's results."""
+    from qpwcnet_amd import warp
+    B, H, W = key
+    half = flow.dtype == torch.float16
+    for n in range(B):
+        one = ops.invert_flow(flow[n:n + 1], layout)
+        assert torch.equal(one, inv[n:n + 1]), "%s: inverse flow of image %d" % (what, n)
+        w_ = warp.tf_warp(flow[n:n + 1], flow[n:n + 1], layout).neg_()
+        assert torch.equal(one, w_), "%s: -tf_warp of image %d" % (what, n)
+        del one, w_
+        one = ops.occlusion_map(flow[n:n + 1], layout)
+        assert torch.equal(one, occ[n:n + 1]), "%s: map of image %d" % (what, n)
+        del one
+    for win in occ_windows(key):
+        tag, n, y0, y1, x0, x1, (c0, c1, d0, d1) = win
+        crop = _occ_cut(flow, layout, n, y0, x0)
+        r_inv, r_map = occ_restatement(crop, (y0, x0), (H, W), half)
+        g_inv = _occ_cut(inv, layout, n, y0, x0)
+        g_map = occ[n, y0:y1, x0:x1].cpu().numpy()
+        a, b = r_inv[c0:c1, d0:d1], g_inv[c0:c1, d0:d1]
+        assert a.dtype == b.dtype == np.float32 and np.array_equal(a, b), (what, tag, "inverse flow", int((a != b).sum()))
+        a, b = r_map[c0:c1, d0:d1], g_map[c0:c1, d0:d1]
+        assert np.array_equal(a, b), (what, tag, "map", int((a != b).sum()))
+        assert a.min() == 0.0 and a.max() == 1.0 and r_inv[c0:c1, d0:d1].any(), (what, tag)      # the window says something
+        stats["windows"] += 1
+        for mod, mask, at in occ_wrapped(key, win, layout, 2 if half else 4):
+            behind = mask.any(-1)[c0:c1, d0:d1]                       # compared pixels with a flow value past the modulus
+            if behind.sum() < 500:
+                continue
+            alt = crop.copy()
+            alt[mask] = flow.view(-1)[torch.from_numpy(at).to(DEV)].float().cpu().numpy()
+            w_inv, w_map = occ_restatement(alt, (y0, x0), (H, W), half)
+            moved = (float((w_inv[c0:c1, d0:d1] != r_inv[c0:c1, d0:d1]).any(-1)[behind].mean()),
+                     float((w_map[c0:c1, d0:d1] != r_map[c0:c1, d0:d1])[behind].mean()))
+            print("{} {}: read at the index mod 2^{}, the inverse flow differs in {:.3f}, the map in {:.3f} of {} pixels".format(
+                what, tag, mod.bit_length() - 1, moved[0], moved[1], int(behind.sum())))
+            assert moved[0] > 0.5 and moved[1] > 0.1, (what, tag, mod, moved)
+            stats["controls"].append(moved)
+
+
+def test_occlusion_and_inverse_flow(arena):
+    """invert_flow_kernel, fill_ones_kernel and occlusion_scatter_kernel at 3 x 18917 x 18923: 1.0739 G pixels (five
+    grid-stride trips, the last partial), 2.148 G flow elements, through ops.invert_flow and ops.occlusion_map; fp32
+    channels_last, fp32 channels_first and fp16 channels_first.  Equality throughout: oracles (a), (b), (c) of the
+    section's comment.  Measured: peak 26.01 GiB (planned 25.34), 0.4 - 1.3 s; 33 windows and 9 one-image launches equal; the 30 controls differ in
+    0.86 - 1.00 (inverse flow) and 0.46 - 0.49 (map) of the compared pixels behind their boundary."""
+    key = CASES["occlusion"]
+    B, H, W = key
+    planned = occlusion_planned_bytes(key)
+    t0 = time.perf_counter()
+    gen = torch.Generator(device=DEV).manual_seed(21)
+    a = arena
+    a["flow"] = flow = _dflow(gen, B, H, W, reach=OCC_F)
+    assert B * H * W > 4 * OCC_TRIP and (B * H * W) % OCC_TRIP and flow.numel() > 1 << 31
+    assert float(flow.abs().max()) == OCC_F
+    stats = {"windows": 0, "controls": []}
+    a["inv"], a["occ"] = ops.invert_flow(flow), ops.occlusion_map(flow)
+    _occ_check(key, flow, a["inv"], a["occ"], "channels_last", "fp32 channels_last", stats)
+    a.pop("inv")
+    occ_last = a.pop("occ")
+    # fp32 channels_first: the same values in planes; the map is the same map
+    a["cf"] = cf = torch.empty((B, 2, H, W), device=DEV)
+    cf.copy_(flow.permute(0, 3, 1, 2))
+    del flow
+    a.pop("flow")
+    a["occ"] = ops.occlusion_map(cf, "channels_first")
+    assert torch.equal(a["occ"], occ_last)
+    del occ_last
+    a["inv"] = ops.invert_flow(cf, "channels_first")
+    _occ_check(key, cf, a["inv"], a["occ"], "channels_first", "fp32 channels_first", stats)
+    a.pop("inv")
+    # fp16 channels_first: the 2^-6 grid within 6 px is exact in fp16, so the map is still the same map
+    a["cf16"] = cf16 = torch.empty((B, 2, H, W), device=DEV, dtype=torch.float16)
+    cf16.copy_(cf)
+    del cf
+    a.pop("cf")
+    assert cf16.numel() > 1 << 31
+    a["inv"], occ16 = ops.invert_flow(cf16, "channels_first"), ops.occlusion_map(cf16, "channels_first")
+    assert a["inv"].dtype == torch.float16 and torch.equal(occ16, a["occ"])
+    del occ16
+    _occ_check(key, cf16, a["inv"], a["occ"], "channels_first", "fp16 channels_first", stats)
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    c = stats["controls"]
+    print("occlusion: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, {} windows equal, {} controls: inverse flow differs in "
+          "{:.3f} .. {:.3f}, map in {:.3f} .. {:.3f} of a window".format(peak / GIB, planned / GIB, secs, stats["windows"], len(c),
+                                                                        min(x[0] for x in c), max(x[0] for x in c),
+                                                                        min(x[1] for x in c), max(x[1] for x in c)))
+    assert stats["windows"] == 3 * len(occ_windows(key)) and len(c) >= 3 * 4
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- the interpolator's input pipeline: 3-byte source pixels, 6- and 3-channel outputs ------------------------------------
+# uint8 frames of 3 x 28528 x 28534: the source pixel index `b * H * W + y * W + x` of triplet_pixel_kernel passes 2^29,
+# 2^30 and 2^31 in samples 0, 1 and 2, aug_load_rgb's `pix * 3` 2^31 and 2^32 bytes.  The output is (H / 2, W / 2): the
+# fp32 source coordinate (i + 0.5) * 2 - 0.5 = 2 i + 0.5 is exact (at another ratio a coordinate near 26000 is good to
+# 2e-3 px, twenty bounds on random uint8 frames), an output pixel reads the 2 x 2 source pixels (2 sy .. 2 sy + 1, 2 sx ..
+# 2 sx + 1) of its pre-flip place (sy, sx), and out_pair (3.66 G floats) passes 2^31, out_mid (1.83 G) 2^30: TileStore's
+# `obase`.  h * w is a multiple of 4: the <vec4> form.  The frames are zero except the sources of the windows.
+#
+# (a) out[n] equals the launch on sample n alone with its parameter row; (b) float64 ref_triplet on the 64 x 64 source
+# crop of TRI_WIN x TRI_WIN output windows across each source boundary (at the output pixel that reads it, where the flips
+# put it), across each element boundary of out_pair and out_mid in both layouts, and on the last pixels of sample 2, the
+# noise from the FULL output's pre-flip pixel index (ref_noise_at), bound BOUND = 1e-4; (c) with the source bytes whose
+# index reaches 2^31 or 2^32 read at the index modulo that, every such window moves by 100 bounds and more.
+#
+# On paper: `int64_t pix` to `int pix` in aug_load_rgb makes `pix * 3` wrap from pixel 715,827,883 on, in sample 0: the
+# windows "src>2^30", "src>2^31" and every output window of samples 1 and 2 read zeros or nothing of theirs, (a) fails for
+# all three samples and (b) there; control (c) is that reading.  `int64_t obase` to `int obase` leaves `(img + base + t) * C`
+# (or `img * C`) a 32-bit product: out_pair from element 2^31 on and out_mid's tail are not written; (a) fails for samples 1
+# and 2 (the one-sample launch has obase 0), (b) in the windows "pair>2^31" of both layouts and "last".
+TRI_WIN = 32
+TRI_FLIPS = ((0, 1), (1, 0), (1, 1))                   # (flip_ud, flip_lr) of samples 0, 1, 2
+
+
+def triplet_output_pixels(key, layout):
+    """[(tag, n, y, x)] in output coordinates: the pixel that reads each boundary pixel of the source (through the
+    sample's flips), the pixel that holds each element boundary of out_pair and out_mid in this layout, the last pixel."""
+    B, H, W = key
+    h, w = H // 2, W // 2
+    out = []
+    for b in crossed(B * H * W):
+        n, Y, X = locate(b, H, W, 1)
+        ud, lr = TRI_FLIPS[n]
+        out.append(("src>2^%d" % (b.bit_length() - 1), n, h - 1 - Y // 2 if ud else Y // 2, w - 1 - X // 2 if lr else X // 2))
+    for name, C in (("pair", 6), ("mid", 3)):
+        for b in crossed(B * h * w * C):
+            if layout == "channels_last":
+                n, y, x = locate(b, h, w, C)
+            else:
+                n, y, x = b // (h * w) // C, b % (h * w) // w, b % w
+            out.append(("%s>2^%d" % (name, b.bit_length() - 1), n, y, x))
+    out.append(("last", B - 1, h - 1, w - 1))
+    return out
+
+
+def triplet_windows(key, layout, pixels=None):
+    """[(tag, n, oy0, ox0, r0, c0)]: TRI_WIN x TRI_WIN output pixels from (oy0, ox0) around each pixel of
+    triplet_output_pixels() (or of `pixels`) and the first of the 2 TRI_WIN x 2 TRI_WIN source pixels (r0, c0) they read."""
+    B, H, W = key
+    h, w = H // 2, W // 2
+    wins = []
+    for tag, n, y, x in triplet_output_pixels(key, layout) if pixels is None else pixels:
+        oy0, ox0 = _span(y, TRI_WIN, h)[0], _span(x, TRI_WIN, w)[0]
+        ud, lr = TRI_FLIPS[n]
+        sy0, sx0 = h - oy0 - TRI_WIN if ud else oy0, w - ox0 - TRI_WIN if lr else ox0        # the pre-flip place
+        wins.append((tag, n, oy0, ox0, 2 * sy0, 2 * sx0))
+    return wins
+
+
+def triplet_counters(key, win):
+    """(TRI_WIN * TRI_WIN,) the noise counters of a window's pre-flip pixels: sy * w + sx of the whole output."""
+    w = key[2] // 2
+    sy, sx = np.mgrid[win[4] // 2:win[4] // 2 + TRI_WIN, win[5] // 2:win[5] // 2 + TRI_WIN]
+    return (sy * w + sx).reshape(-1)
+
+
+def triplet_window_ref(key, win, crops, ip_row, fp_row):
+    """Float64 ref_triplet of a window from the three source crops (1, 2 TRI_WIN, 2 TRI_WIN, 3) -> (pair, mid), the window
+    as the output holds it (flipped), channels last."""
+    from test_triplet_cpu import ref_noise_at, ref_triplet
+    noise = ref_noise_at(ip_row[None, 2:4], triplet_counters(key, win)).reshape(1, TRI_WIN, TRI_WIN, 3)
+    pair, mid = ref_triplet(crops[0], crops[1], crops[2], ip_row[None], fp_row[None], (TRI_WIN, TRI_WIN), noise=noise)
+    return pair[0], mid[0]
+
+
+def triplet_source_bytes(key, win):
+    """(2 TRI_WIN, 2 TRI_WIN, 3) int64: the byte index `pix * 3 + c` of a window's source in a frame."""
+    B, H, W = key
+    _, n, _, _, r0, c0 = win
+    yy, xx = np.mgrid[r0:r0 + 2 * TRI_WIN, c0:c0 + 2 * TRI_WIN].astype(np.int64)
+    return (((n * H + yy) * W + xx) * 3)[..., None] + np.arange(3)
+
+
+def triplet_planned_bytes(key):
+    """Three uint8 frames, out_pair and out_mid of the batch and of one sample."""
+    B, H, W = key
+    return 3 * 3 * B * H * W + 4 * 9 * (B + 1) * (H // 2) * (W // 2)
+
+
+def test_triplet(arena):
+    """triplet_pixel_kernel<vec4> on uint8 frames of 3 x 28528 x 28534 -> 14264 x 14267, both layouts: aug_load_rgb's
+    `pix * 3` past 2^31 and 2^32 bytes, TileStore<.., 6, ..> / <.., 3, ..> at an obase past 2^31 / 2^30 elements.  Oracles
+    (a), (b), (c) of the section's comment.  Measured: peak 48.90 GiB (planned 47.76; the rest is the boolean of torch.equal), 0.1 - 0.9 s; pair 2.3e-7, middle
+    frame 2.0e-7 against the bound of 1e-4; the 16 controls moved their windows by 10151 - 12367 bounds."""
+    from test_augment_cpu import BOUND
+    from test_triplet_cpu import _params
+    key = CASES["triplet"]
+    B, H, W = key
+    h, w = H // 2, W // 2
+    planned = triplet_planned_bytes(key)
+    t0 = time.perf_counter()
+    a = arena
+    frames = [torch.zeros((B, H, W, 3), dtype=torch.uint8, device=DEV) for _ in range(3)]
+    a["frames"] = frames
+    assert B * H * W > 1 << 31 and 1 << 29 < H * W < 1 << 30 and B * h * w * 6 > 1 << 31 and (h * w) % 4 == 0
+    ip_np, fp_np = _params(B, 77)
+    ip_np[:, 0:2] = TRI_FLIPS
+    assert len({tuple(r) for r in fp_np.tolist()}) == B and (fp_np[:, 15] == np.float32(0.02)).all()
+    ip, fp = torch.from_numpy(ip_np).to(DEV), torch.from_numpy(fp_np).to(DEV)
+    wins = {lay: triplet_windows(key, lay) for lay in ("channels_last", "channels_first")}
+    rng = np.random.default_rng(12)
+    for lay in wins:
+        for _, n, _, _, r0, c0 in wins[lay]:
+            for f in frames:
+                f[n, r0:r0 + 2 * TRI_WIN, c0:c0 + 2 * TRI_WIN] = torch.from_numpy(
+                    rng.integers(0, 256, (2 * TRI_WIN, 2 * TRI_WIN, 3), dtype=np.uint8)).to(DEV)
+    worst, controls = {"pair": 0.0, "mid": 0.0}, []
+    for lay in wins:
+        assert ops.augment_triplet_kernel(B, h, w) == "triplet_pixel_kernel<vec4>"
+        a["pair"], a["mid"] = pair, mid = ops.augment_triplet(*frames, ip, fp, (h, w), data_format=lay)
+        assert pair.numel() > 1 << 31 and mid.numel() > 1 << 30
+        for n in range(B):
+            one = ops.augment_triplet(*[f[n:n + 1] for f in frames], ip[n:n + 1], fp[n:n + 1], (h, w), data_format=lay)
+            assert torch.equal(one[0], pair[n:n + 1]) and torch.equal(one[1], mid[n:n + 1]), (lay, n)
+            del one
+        for win in wins[lay]:
+            tag, n, oy0, ox0, r0, c0 = win
+            crops = [f[n:n + 1, r0:r0 + 2 * TRI_WIN, c0:c0 + 2 * TRI_WIN].cpu().numpy() for f in frames]
+            assert all(c.any() for c in crops) and not np.array_equal(crops[0], crops[1])
+            r_pair, r_mid = triplet_window_ref(key, win, crops, ip_np[n], fp_np[n])
+            assert np.abs(r_pair).max() > 0.25 and np.abs(r_mid).max() > 0.25
+            for name, got, ref in (("pair", pair, r_pair), ("mid", mid, r_mid)):
+                g = got[n, oy0:oy0 + TRI_WIN, ox0:ox0 + TRI_WIN] if lay == "channels_last" else \
+                    got[n, :, oy0:oy0 + TRI_WIN, ox0:ox0 + TRI_WIN].permute(1, 2, 0)
+                e = float(np.abs(g.double().cpu().numpy() - ref).max())
+                print("triplet {} {} {}: max|d| = {:.3e}".format(lay, tag, name, e))
+                assert e <= BOUND, (lay, tag, name, e)
+                worst[name] = max(worst[name], e)
+            idx = triplet_source_bytes(key, win)
+            for mod in (1 << 31, 1 << 32):
+                mask = idx >= mod
+                if not mask.any():
+                    continue
+                at = torch.from_numpy(idx[mask] % mod).to(DEV)
+                alt = []
+                for f, c in zip(frames, crops):
+                    c = c.copy()
+                    c[0][mask] = f.view(-1)[at].cpu().numpy()
+                    alt.append(c)
+                w_pair, w_mid = triplet_window_ref(key, win, alt, ip_np[n], fp_np[n])
+                ratio = min(np.abs(w_pair - r_pair).max(), np.abs(w_mid - r_mid).max()) / BOUND
+                print("triplet {} {}: sources read at the byte index mod 2^{} move the window by {:.0f} bounds".format(
+                    lay, tag, mod.bit_length() - 1, ratio))
+                assert ratio >= 100.0, (lay, tag, mod, ratio)
+                controls.append(ratio)
+        del pair, mid, got, g                             # the last two are views of the outputs
+        a.pop("pair"), a.pop("mid")
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("triplet: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s, worst {}, {} controls {:.0f} .. {:.0f} bounds".format(
+        peak / GIB, planned / GIB, secs, worst, len(controls), min(controls), max(controls)))
+    assert len(controls) >= 2 * 6
+    assert planned <= 48 * GIB
+    assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)
+
+
+# ---- the update step on one parameter of more than 2^31 floats --------------------------------------------------------
+# agc_adam_kernel through the C entry point, both tables built by torch on the device: one tensor of 18,683,000 rows of
+# 115 floats (the models' pointwise row: no row but every fourth starts on 16 bytes, so the head / float4 / tail split
+# cycles through its four phases), a unit a row, `un.offset` up to 2,148,544,885.  18.7 M units on 4096 waves: the
+# grid-stride form.
+#
+# (a) p, m and v are torch.equal to a second launch on the same data whose tensor table lists five slices of the arrays,
+# each under 2^29 elements, the units' offsets rebased to their slice: units are independent and the kernel has no
+# atomics, every row has the same addresses in both launches.  Both results of an array do not fit beside the operands:
+# the data is redrawn from its seeds and both launches repeated for each of p, m, v, one array of the first launch
+# kept at a time.  (b) the float64 oracle of tests/test_optim_cpu.py on the rows that straddle elements 2^29, 2^30 and
+# 2^31, the first and the last row and 32 seeded rows, at that module's bounds (tests/test_large_offsets_cpu.py shows
+# that the fp32 torch composition stays within a tenth of them on rows drawn like these).  (c) the float64 answer
+# for the 115 elements that the offset of a row behind 2^31, wrapped there, addresses lies more than 100 bounds away.
+#
+# On paper: `un.offset` cut to 32 bits is negative from row 18,673,771 on: those rows' p, m, v are not updated (or other
+# memory is): (a) fails for all three arrays, (b) on the last row and the seeded rows behind it.
+OPT_SLICE_ROWS = ((1 << 29) - 1) // 115               # whole rows under 2^29 elements
+OPT_SEEDS = {"p": 31, "g": 32, "m": 33, "v": 34}
+
+
+def optim_draw(t, which):
+    """Redraws one array in place from its seed: p ~ N(0, 0.1) as the models' weights, m ~ N(0, 1e-3), v the square of
+    such a number (>= 0), g ~ N(0, 1) before its rows are scaled."""
+    gen = torch.Generator(device=t.device).manual_seed(OPT_SEEDS[which])
+    t.normal_(0.0, {"p": 0.1, "g": 1.0, "m": 1e-3, "v": 1e-3}[which], generator=gen)
+    if which == "v":
+        t.mul_(t)
+
+
+def optim_scale_rows(p, g, cols, clip, eps):
+    """Scales g's rows so that gn / mx is 0.25 (even rows) or 4 (odd rows), mx = max(pn, eps) * clip -> the fp32 ratio
+    of every row afterwards, (rows,)."""
+    pr, gr = p.view(-1, cols), g.view(-1, cols)
+    mx = torch.linalg.vector_norm(pr, dim=1).clamp_(min=eps).mul_(clip)
+    want = torch.full_like(mx, 0.25)
+    want[1::2] = 4.0
+    gr.mul_((want * mx / torch.linalg.vector_norm(gr, dim=1))[:, None])
+    return torch.linalg.vector_norm(gr, dim=1) / mx
+
+
+def optim_tables(base, rows, cols, slice_rows, device):
+    """The tables of both launches, int64 on the device.  base: the addresses of p, g, m, v.
+    -> (tensors (1, 4), units (rows, 3)) of the launch on the whole arrays, (tensors (K, 4), units (rows, 3)) of the
+    launch on K slices of slice_rows rows (the last shorter), offsets counted from the slice's start."""
+    r = torch.arange(rows, dtype=torch.int64, device=device)
+    whole = torch.stack([torch.zeros_like(r), r * cols, torch.full_like(r, cols)], 1).contiguous()
+    sliced = torch.stack([r // slice_rows, (r % slice_rows) * cols, torch.full_like(r, cols)], 1).contiguous()
+    k = -(-rows // slice_rows)
+    starts = torch.arange(k, dtype=torch.int64) * (slice_rows * cols * 4)
+    tens_whole = torch.tensor([list(base)], dtype=torch.int64).to(device)
+    tens_sliced = (torch.tensor(list(base), dtype=torch.int64)[None, :] + starts[:, None]).contiguous().to(device)
+    return (tens_whole, whole), (tens_sliced, sliced)
+
+
+def optim_sample_rows(rows, cols):
+    """The rows held to the oracle: those that straddle elements 2^29, 2^30 and 2^31, the first, the last, 32 seeded."""
+    out = [b // cols for b in crossed(rows * cols)] + [0, rows - 1]
+    rng = np.random.default_rng(41)
+    return out + sorted(int(x) for x in rng.choice(rows, 32, replace=False) if int(x) not in out)
+
+
+def optim_rows_oracle(p, g, m, v):
+    """One update of rows (R, cols) by tests/test_optim_cpu.py's float64 oracle, a unit a row, clipping on, t = 1
+    -> (p, m, v) float64."""
+    from test_optim_cpu import oracle_step, oracle_units
+    name, shape = "rows.pointwise.weight", p.shape + (1, 1)
+    assert oracle_units(name, shape) == [(k * p.shape[1], p.shape[1]) for k in range(p.shape[0])]
+    state = {k: {name: np.asarray(a, np.float64).reshape(shape).copy()} for k, a in (("p", p), ("m", m), ("v", v))}
+    state["t"] = 0
+    oracle_step(state, {name: np.asarray(g).reshape(shape)})
+    return tuple(state[k][name].reshape(p.shape) for k in "pmv")
+
+
+def optim_row_errors(have, want):
+    """(max |p - ref|, max over rows of max |m - ref| / max |ref|, the same for v), as tests/test_optim_cpu.py::errors."""
+    out = []
+    for k in range(3):
+        d = np.abs(np.asarray(have[k], np.float64) - want[k]).max(1)
+        assert np.isfinite(d).all()
+        out.append(float((d if k == 0 else d / np.abs(want[k]).max(1)).max()))
+    return tuple(out)
+
+
+def optim_planned_bytes(key):
+    """p, g, m, v, one array of the first launch kept for the comparison, and the two unit tables."""
+    rows, cols = key
+    return 5 * 4 * rows * cols + 2 * 24 * rows
+
+
+def test_agc_adam_step(arena):
+    """agc_adam_kernel<grid-stride> on one parameter of 18,683,000 rows of 115 floats (2.1485 G): oracles (a), (b), (c)
+    of the section's comment.  Measured: peak 42.86 GiB (planned 40.85), 2.1 - 4.0 s; 37 rows against float64: p 1.5e-8, m
+    5.3e-8, v 4.9e-8 (bounds 1.56e-7, 1.88e-6, 1.16e-6); the control's rows lie 2.6e6 bounds away."""
+    from test_optim_cpu import (AGC_EPS, BETA_1, BETA_2, CLIP, EPSILON, LR, M_BOUND, P_BOUND, V_BOUND, oracle_alpha)
+    key = CASES["optim"]
+    rows, cols = key
+    n = rows * cols
+    planned = optim_planned_bytes(key)
+    t0 = time.perf_counter()
+    L = ops._hip.lib()
+    assert n > (1 << 31) + (1 << 20) and L.qpwc_agc_adam_step_kernel(rows) == b"agc_adam_kernel<grid-stride>"
+    a = arena
+    for k in "pgmv":
+        a[k] = torch.empty(n, device=DEV)
+        optim_draw(a[k], k)
+    p, g, m, v = (a[k] for k in "pgmv")
+    ratio = optim_scale_rows(p, g, cols, CLIP, AGC_EPS)
+    assert float((ratio - 1.0).abs().min()) > 1e-3                                     # no row near the clip threshold
+    assert float(torch.minimum((ratio - 0.25).abs(), (ratio - 4.0).abs()).max()) < 1e-4 and float(v.min()) >= 0.0
+    del ratio
+    sample = optim_sample_rows(rows, cols)
+    at = torch.tensor(sample, device=DEV)
+    before = [t.view(rows, cols)[at].cpu().numpy() for t in (p, g, m, v)]
+    want = optim_rows_oracle(*before)
+    # the control's rows: what the offsets of the first row behind 2^31 and of the last row address when wrapped at 2^31
+    behind = [r for r in (BOUNDARIES[2] // cols + 1, rows - 1)]
+    wrapped = torch.tensor([[r * cols - (1 << 31) + c for c in range(cols)] for r in behind], device=DEV)
+    assert int(wrapped.min()) >= 0
+    alt = optim_rows_oracle(*[t[wrapped].cpu().numpy() for t in (p, g, m, v)])
+    right = optim_rows_oracle(*[t.view(rows, cols)[torch.tensor(behind, device=DEV)].cpu().numpy() for t in (p, g, m, v)])
+    control = float(np.abs(alt[0] - right[0]).max(1).min()) / P_BOUND
+    print("agc_adam: rows read at their offset mod 2^31 move p by {:.0f} bounds".format(control))
+    assert control > 100.0
+    (t_whole, u_whole), (t_sliced, u_sliced) = optim_tables([t.data_ptr() for t in (p, g, m, v)], rows, cols, OPT_SLICE_ROWS, DEV)
+    a["tables"] = (t_whole, u_whole, t_sliced, u_sliced)
+    assert t_sliced.shape == (5, 4) and int(u_sliced[:, 1].max()) + cols <= 1 << 29 and int(u_whole[:, 1].max()) + cols == n
+    alpha = float(np.float32(oracle_alpha(LR, 1)))
+
+    def launch(tens, units):
+        rc = L.qpwc_agc_adam_step(tens.data_ptr(), int(tens.shape[0]), units.data_ptr(), rows, alpha, BETA_1, BETA_2, EPSILON,
+                                  CLIP, AGC_EPS, torch.cuda.current_stream().cuda_stream)
+        ops._hip.check(rc)
+
+    err = None
+    for k, name in enumerate("pmv"):
+        if k:
+            for which in "pmv":
+                optim_draw(a[which], which)
+        launch(t_whole, u_whole)
+        if k == 0:
+            after = [t.view(rows, cols)[at].cpu().numpy() for t in (p, m, v)]
+            err = optim_row_errors(after, want)
+            print("agc_adam: {} rows against float64: p abs {:.3g} (bound {:.3g}), m rel {:.3g} ({:.3g}), v rel {:.3g} ({:.3g})".format(
+                len(sample), err[0], P_BOUND, err[1], M_BOUND, err[2], V_BOUND))
+            assert err[0] <= P_BOUND and err[1] <= M_BOUND and err[2] <= V_BOUND, err
+            assert torch.equal(g.view(rows, cols)[at].cpu(), torch.from_numpy(before[1]))
+        a["kept"] = kept = a[name].clone()
+        for which in "pmv":
+            optim_draw(a[which], which)
+        launch(t_sliced, u_sliced)
+        assert torch.equal(a[name], kept), "%s of the launch on slices" % name
+        del kept
+        a.pop("kept")
+    for t, ref in zip((p, m, v), after):
+        assert np.array_equal(t.view(rows, cols)[at].cpu().numpy(), ref)
+    torch.cuda.synchronize()
+    peak, secs = torch.cuda.max_memory_allocated() - arena["_base"], time.perf_counter() - t0
+    print("agc_adam: peak {:.2f} GiB, planned {:.2f} GiB, {:.2f} s".format(peak / GIB, planned / GIB, secs))
     assert planned <= 48 * GIB
     assert peak <= 1.10 * planned, (peak / GIB, planned / GIB)

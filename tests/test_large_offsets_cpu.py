@@ -8,7 +8,12 @@ losses and the flow metrics, whose masks are indexed by byte, also: the windows 
 and the ground truth's 2^32nd element, a mask read at a wrapped byte offset meets no window, and the windows' flows
 keep the metrics' thresholds at a distance.  For the label-free losses and the input pipelines, whose oracles are crops
 of a trivial background: the shapes cross what they claim, the crops are disjoint, and the crop oracles equal the whole
-float64 restatement on a level and a source small enough to have one.
+float64 restatement on a level and a source small enough to have one.  For the occlusion map, the interpolator's input
+pipeline and the update step: the shapes cross what they claim (and, for the occlusion kernels, make the grid-stride
+loops iterate at least four times with a partial last trip, from the cap and the workgroup size read out of the
+source), the windowed restatements equal oracle.np_ref / ref_triplet where those can run, with the margins the GPU test
+uses, both unit tables address the same elements, and the fp32 torch composition keeps the update step's bounds on
+rows drawn as the GPU test draws them.
 
 The plans are restated from the constants read out of the kernel sources (tests/test_conv_grad_cpu.py::_plan) and
 compared with the library's own host functions, so a changed plan constant that pulls a region back under a boundary
@@ -1252,3 +1257,315 @@ def test_augment_crop_oracle_is_the_oracle_on_a_small_image(colour):
         assert np.abs(r_ims[0] - w_ims[n]).max() <= 1e-12 and np.abs(r_flo[0] - w_flo[n]).max() <= 1e-12
         assert np.abs(q_flo[0] - s_flo[n]).max() <= 1e-12 and np.array_equal(q_valid[0], s_valid[n])
         assert 0.5 < q_valid.mean() < 1.0 and np.abs(r_flo).max() > 8.0 and np.abs(r_ims).max() > 0.25
+
+
+# ---- occlusion map and inverse flow ------------------------------------------------------------------------------------
+def _occlusion_trip():
+    """(workgroup cap, workgroup size) of occlusion.hip: grid_for's `want < CAP ? want : CAP` and the launches' dim3(256)."""
+    text = open(os.path.join(CSRC, "occlusion.hip")).read()
+    body = re.search(r"static unsigned grid_for\(int64_t total\)\s*\{(.*?)\n\}", text, re.S).group(1)
+    assert "(total + 255) / 256" in body, body
+    caps = re.findall(r"\(1 << (\d+)\)", body)
+    assert len(caps) == 2 and caps[0] == caps[1], body
+    assert text.count("dim3(grid), dim3(256)") == text.count("hipLaunchKernelGGL") == 5
+    assert text.count("__launch_bounds__(256)") == 3
+    return 1 << int(caps[0]), 256
+
+
+def test_occlusion_case_crosses_what_it_claims():
+    """3 x 18917 x 18923: `idx * 2` passes 2^29, 2^30 and 2^31 in images 0, 1 and 2, the channels-first plane index too,
+    the map's pixel index 2^29 and 2^30; every launch makes at least four grid-stride trips with a partial last one;
+    check_flow_args admits it; the windows hold what they are named after inside what is compared; the plan fits."""
+    key = lo.CASES["occlusion"]
+    B, H, W = key
+    P = B * H * W
+    assert B == 3 and H % 2 and W % 2 and H != W and P > P30
+    assert lo.crossed(2 * P) == [P29, P30, P31] and [lo.locate(b, H, W, 2)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert lo.crossed(P) == [P29, P30] and [lo.locate(b, H, W, 1)[0] for b in (P29, P30)] == [1, 2]
+    assert [b // (H * W) // 2 for b in lo.BOUNDARIES] == [0, 1, 2] and 2 * P - H * W < P31 < 2 * P   # in the last y plane
+    cap, block = _occlusion_trip()
+    assert cap * block == lo.OCC_TRIP == 1 << 28
+    assert -(-P // lo.OCC_TRIP) >= 4 and 0 < P % lo.OCC_TRIP < lo.OCC_TRIP and P > 3 * lo.OCC_TRIP
+    assert H * W > lo.OCC_TRIP                                         # the launch on one image iterates too
+    # coordinates plus flows on the 2^-6 grid are exact in fp32: 15 + 6 bits
+    assert max(H, W) < 1 << 15 and lo.OCC_F * 64 == 384
+    text = open(os.path.join(CSRC, "capi.hip")).read()
+    body = re.search(r"static int check_flow_args\(.*?\{(.*?)\n\}", text, re.S).group(1)
+    assert "check_common(B, H, W, 2, layout, dtype)" in body
+    assert body.count("(int64_t)B * H * W * 2 >= ((int64_t)1 << 40)") == 1 and body.count("QPWC_E_SHAPE") == 1
+    assert 2 * P < 1 << 40
+    for name in ("qpwc_invert_flow_fwd", "qpwc_occlusion_fwd"):
+        assert re.search(name + r"\(.*?\{\s*const int rc = check_flow_args\(", text, re.S), name
+    planned = lo.occlusion_planned_bytes(key)
+    assert planned == 20 * P + 16 * H * W and planned <= 48 * lo.GIB and 1.10 * planned <= 64 * lo.GIB
+    pixels = lo.occ_pixels(key)
+    assert [p[0] for p in pixels] == ["nhwc>2^29", "nhwc>2^30", "nhwc>2^31", "trip 4", "nchw>2^29", "nchw>2^30", "nchw>2^31",
+                                      "top left", "top right", "bottom left", "bottom right"]
+    # the map's boundaries and trip 2 fall on pixels the channels-last flow already names
+    at = {p[0]: p[1:] for p in pixels}
+    assert at["nhwc>2^29"] == lo.locate(lo.OCC_TRIP, H, W, 1) and at["nhwc>2^30"] == lo.locate(P29, H, W, 1)
+    assert at["nhwc>2^31"] == lo.locate(P30, H, W, 1) and at["trip 4"] == lo.locate(3 * lo.OCC_TRIP, H, W, 1)
+    assert [at[t][0] for t in ("nhwc>2^29", "nhwc>2^30", "nhwc>2^31", "trip 4", "nchw>2^29", "nchw>2^30", "nchw>2^31")] == \
+        [0, 1, 2, 2, 0, 1, 2]
+    wins = lo.occ_windows(key)
+    m = lo.OCC_MARGIN
+    assert m == 2 * lo.OCC_F + 3 and lo.OCC_EDGE_MARGIN >= 9 * lo.OCC_F + 1 + lo.OCC_F + 1 + 1
+    for (tag, n, y, x), win in zip(pixels, wins):
+        _, wn, y0, y1, x0, x1, (c0, c1, d0, d1) = win
+        assert wn == n and (y1 - y0, x1 - x0) == (lo.OCC_WIN, lo.OCC_WIN) and 0 <= y0 and y1 <= H and 0 <= x0 and x1 <= W
+        assert c0 <= y - y0 < c1 and d0 <= x - x0 < d1, tag            # the pixel itself is compared
+        edge = lo.OCC_EDGE_MARGIN if y0 == 0 or x0 == 0 else m
+        assert (c0, d0) == (0 if y0 == 0 else edge, 0 if x0 == 0 else edge), tag
+        assert (lo.OCC_WIN - c1, lo.OCC_WIN - d1) == (0 if y1 == H else edge, 0 if x1 == W else edge), tag
+        assert (c1 - c0) * (d1 - d0) >= 96 * 96
+        if not tag.startswith(("top", "bottom")):
+            assert x0 > 0 and y0 > 0 and c0 < y - y0 - 1 and d0 < x - x0 - 1 and y - y0 + 1 < c1   # both sides of the boundary
+    # the controls: the element indices are the kernel's, and every boundary has windows that reach it
+    for layout, esize, want in (("channels_last", 4, {P30: "nhwc>2^30", P31: "nhwc>2^31"}),
+                                ("channels_first", 4, {P30: "nchw>2^30", P31: "nchw>2^31"}),
+                                ("channels_first", 2, {P31: "nchw>2^31"})):
+        count = {}
+        for (tag, n, y, x), win in zip(pixels, wins):
+            idx = lo.occ_element_index(key, win, layout)
+            assert idx.shape == (lo.OCC_WIN, lo.OCC_WIN, 2) and idx.dtype == np.int64
+            yy, xx = y - win[2], x - win[4]
+            if layout == "channels_last":
+                assert idx[yy, xx, 0] == ((n * H + y) * W + x) * 2 and idx[yy, xx, 1] == idx[yy, xx, 0] + 1
+                if tag.startswith("nhwc"):
+                    assert idx[yy, xx, 0] == 1 << int(tag[-2:])
+            else:
+                assert idx[yy, xx, 0] == n * 2 * H * W + y * W + x and idx[yy, xx, 1] == idx[yy, xx, 0] + H * W
+                if tag.startswith("nchw"):
+                    assert 1 << int(tag[-2:]) in (idx[yy, xx, 0], idx[yy, xx, 1])
+            c0, c1, d0, d1 = win[6]
+            for mod, mask, wrapped in lo.occ_wrapped(key, win, layout, esize):
+                assert mod in (P30, P31) and mod * esize in (1 << 32, 1 << 33) and wrapped.max() < mod
+                assert ((idx[mask] - wrapped) % mod == 0).all() and (idx[mask] - wrapped >= mod).all()
+                if mask.any(-1)[c0:c1, d0:d1].sum() >= 500:
+                    count.setdefault(mod, set()).add(tag)
+        assert sorted(count) == sorted(want), (layout, esize, count)
+        for mod, tag in want.items():                                  # the window across the boundary, and the corners behind it
+            assert tag in count[mod] and {"bottom left", "bottom right"} <= count[mod] and len(count[mod]) >= 4, (layout, mod, count)
+
+
+def _grid_flow(rng, shape, reach):
+    """Flows as the GPU case draws them: multiples of 2^-6 within +-reach, every 5th an integer, every 7th zero."""
+    f = rng.integers(-reach * 64, reach * 64 + 1, size=shape).astype(np.float32) / np.float32(64)
+    flat = f.reshape(-1, 2)
+    flat[::5] = np.round(flat[::5])
+    flat[::7] = 0
+    return f
+
+
+def test_occ_restatement_at_the_origin_is_np_ref_on_the_goldens():
+    """occ_restatement on a whole image at origin (0, 0) against oracle.np_ref, bit for bit, on the goldens' flows (which
+    leave the image and fold), fp32 and with the inverse flow rounded to fp16."""
+    from oracle import np_ref
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import cases
+    for name in sorted(cases.OCC_CASES):
+        fmt = cases.OCC_CASES[name][0]
+        flow = cases.make_flow(name)
+        nhwc = flow if fmt == "channels_last" else np.ascontiguousarray(np.moveaxis(flow, 1, 3))
+        inv, occ = np_ref.invert_flow(nhwc), np_ref.estimate_occlusion_map(nhwc)
+        assert inv.dtype == np.float32
+        for n in range(nhwc.shape[0]):
+            r_inv, r_map = lo.occ_restatement(nhwc[n], (0, 0), nhwc.shape[1:3])
+            assert r_inv.tobytes() == inv[n].tobytes() and np.array_equal(r_map, occ[n]), (name, n)
+            h_inv, h_map = lo.occ_restatement(nhwc[n], (0, 0), nhwc.shape[1:3], half=True)
+            assert np.array_equal(h_inv, inv[n].astype(np.float16).astype(np.float32)) and np.array_equal(h_map, occ[n])
+
+
+@pytest.mark.parametrize("full,origin", [((18200, 200), (18000, 20)), ((200, 18200), (20, 18000)), ((400, 400), (0, 0)),
+                                         ((400, 400), (0, 240)), ((400, 400), (240, 0)), ((400, 400), (240, 240))],
+                         ids=["rows near 18000", "columns near 18000", "top left", "top right", "bottom left", "bottom right"])
+def test_occ_restatement_on_a_crop_is_np_ref_where_it_is_compared(full, origin):
+    """A window of OCC_WIN x OCC_WIN cut from an image small enough for oracle.np_ref, at coordinates near 18000 in one
+    axis (`(float)y + inv.y` rounds to 2^-9 there) and in the four corners: what occ_windows() would compare of it equals
+    np_ref on the whole image, so the margins are enough; the whole window does not (the margins are needed)."""
+    from oracle import np_ref
+    H, W = full
+    oy, ox = origin
+    flow = _grid_flow(np.random.default_rng(5), (1, H, W, 2), lo.OCC_F)
+    inv, occ = np_ref.invert_flow(flow)[0], np_ref.estimate_occlusion_map(flow)[0]
+    y0, y1, x0, x1 = oy, oy + lo.OCC_WIN, ox, ox + lo.OCC_WIN
+    corner = [w for w in lo.occ_windows((1, H, W)) if w[1] == 0 and w[2:6] == (y0, y1, x0, x1)]
+    assert len(corner) == (1 if H == W else 0)
+    c0, c1, d0, d1 = corner[0][6] if corner else (lo.OCC_MARGIN, lo.OCC_WIN - lo.OCC_MARGIN) * 2
+    r_inv, r_map = lo.occ_restatement(flow[0, y0:y1, x0:x1], (y0, x0), full)
+    assert r_inv[c0:c1, d0:d1].tobytes() == np.ascontiguousarray(inv[y0:y1, x0:x1][c0:c1, d0:d1]).tobytes()
+    assert np.array_equal(r_map[c0:c1, d0:d1], occ[y0:y1, x0:x1][c0:c1, d0:d1])
+    assert set(np.unique(r_map[c0:c1, d0:d1])) == {0.0, 1.0}
+    # the reach the margins are derived from: F, and 9 F where the first F rows or columns extrapolate
+    assert np.abs(inv[lo.OCC_F:, lo.OCC_F:]).max() <= lo.OCC_F * (1 + 1e-6) and np.abs(inv).max() <= 9 * lo.OCC_F * (1 + 1e-6)
+    assert not np.array_equal(r_map, occ[y0:y1, x0:x1])
+
+
+# ---- the interpolator's input pipeline ---------------------------------------------------------------------------------
+def test_triplet_case_crosses_what_it_claims():
+    """3 x 28528 x 28534 uint8 frames -> 14264 x 14267: the source pixel index passes 2^29, 2^30 and 2^31 in samples 0, 1
+    and 2, its byte index 2^31 and 2^32; out_pair passes 2^31 elements and out_mid 2^30; the ratio is exactly 2 and the
+    fp32 source coordinates are exact; the shape rule admits it and gives the <vec4> form; every window holds what it is
+    named after and reads source pixels inside its sample; enough windows lie behind the byte boundaries; the plan fits."""
+    key = lo.CASES["triplet"]
+    B, H, W = key
+    h, w = H // 2, W // 2
+    assert B == 3 and H % 2 == 0 and W % 2 == 0 and H != W and 2 ** 29.6 < H * W < 1 << 30
+    assert lo.crossed(B * H * W) == [P29, P30, P31] and [lo.locate(b, H, W, 1)[0] for b in lo.BOUNDARIES] == [0, 1, 2]
+    assert 3 * B * H * W > 1 << 32 and 3 * H * W > 1 << 31                           # bytes of a frame, of a sample
+    assert lo.crossed(B * h * w * 6) == [P29, P30, P31] and lo.crossed(B * h * w * 3) == [P29, P30]
+    assert lo.crossed(h * w * 6) == [P29, P30] and lo.crossed(h * w * 3) == [P29]     # one sample stays under 2^31
+    assert (h * w) % 4 == 0                                                           # tri_vec: the <vec4> form
+    text = open(os.path.join(CSRC, "triplet.hip")).read()
+    assert "((int64_t)h * w) % 4 == 0 && (uintptr_t)out_pair % 16 == 0 && (uintptr_t)out_mid % 16 == 0" in text
+    capi = open(os.path.join(CSRC, "capi.hip")).read()
+    assert "static int triplet_check_shapes(int B, int H, int W, int h, int w) { return augment_check_shapes(B, H, W, h, w); }" in capi
+    body = re.search(r"bool augment_shape_ok\(.*?\{(.*?)\n\}", open(os.path.join(CSRC, "augment.hip")).read(), re.S).group(1)
+    assert "(int64_t)H * W <= lim && (int64_t)h * w <= lim / 6 && (int64_t)B * aug_nblk(h, w) <= lim" in body and "0x7fffffff" in body
+    assert H * W <= 0x7fffffff and h * w <= 0x7fffffff // 6 and B * -(-h * w // 256) <= 0x7fffffff
+    for size, out in ((H, h), (W, w)):
+        i = np.arange(out)
+        s32 = (i.astype(np.float32) + np.float32(0.5)) * (np.float32(size) / np.float32(out)) - np.float32(0.5)
+        assert np.array_equal(s32.astype(np.float64), 2.0 * i + 0.5)                 # lo = 2 i, hi = 2 i + 1, t = 1/2
+    assert h * w <= 0xFFFFFFFF                                                        # the noise counter
+    planned = lo.triplet_planned_bytes(key)
+    assert planned == 18 * B * H * W + 9 * H * W and planned <= 48 * lo.GIB and 1.10 * planned <= 64 * lo.GIB
+    controls = 0
+    for layout in ("channels_last", "channels_first"):
+        pixels, wins = lo.triplet_output_pixels(key, layout), lo.triplet_windows(key, layout)
+        assert [p[0] for p in pixels] == ["src>2^29", "src>2^30", "src>2^31", "pair>2^29", "pair>2^30", "pair>2^31",
+                                          "mid>2^29", "mid>2^30", "last"]
+        assert [p[1] for p in pixels[:3]] == [0, 1, 2] and pixels[-1][1:] == (B - 1, h - 1, w - 1)
+        for (tag, n, y, x), (_, wn, oy0, ox0, r0, c0) in zip(pixels, wins):
+            ud, lr = lo.TRI_FLIPS[n]
+            assert wn == n and 0 <= oy0 <= y < oy0 + lo.TRI_WIN <= h and 0 <= ox0 <= x < ox0 + lo.TRI_WIN <= w
+            assert 0 <= r0 and r0 + 2 * lo.TRI_WIN <= H and 0 <= c0 and c0 + 2 * lo.TRI_WIN <= W and r0 % 2 == 0 and c0 % 2 == 0
+            # the source rows and columns of the output pixel (y, x) lie in the crop
+            sy, sx = h - 1 - y if ud else y, w - 1 - x if lr else x
+            assert r0 <= 2 * sy and 2 * sy + 1 < r0 + 2 * lo.TRI_WIN and c0 <= 2 * sx and 2 * sx + 1 < c0 + 2 * lo.TRI_WIN
+            b = int(tag[-2:]) if tag != "last" else None
+            if tag.startswith("src"):                                                  # ... the boundary source pixel among them
+                m, Y, X = lo.locate(1 << b, H, W, 1)
+                assert m == n and (Y // 2, X // 2) == (sy, sx) and (n * H + Y) * W + X == 1 << b
+                assert 8 < y - oy0 < lo.TRI_WIN - 8 or oy0 in (0, h - lo.TRI_WIN)
+            elif tag != "last":
+                C = 6 if tag.startswith("pair") else 3
+                first = ((n * h + y) * w + x) * C if layout == "channels_last" else (n * C * h + y) * w + x
+                assert (first <= 1 << b < first + C) if layout == "channels_last" else ((1 << b) - first) % (h * w) == 0
+            c = lo.triplet_counters(key, (tag, n, oy0, ox0, r0, c0))
+            assert c.shape == (lo.TRI_WIN ** 2,) and c[0] == (r0 // 2) * w + c0 // 2 and c[-1] == (r0 // 2 + lo.TRI_WIN - 1) * w + c0 // 2 + lo.TRI_WIN - 1
+            idx = lo.triplet_source_bytes(key, (tag, n, oy0, ox0, r0, c0))
+            assert idx[0, 0, 0] == ((n * H + r0) * W + c0) * 3 and idx[1, 2, 1] == ((n * H + r0 + 1) * W + c0 + 2) * 3 + 1
+            controls += sum(bool((idx >= mod).any()) for mod in (1 << 31, 1 << 32))
+        assert {t[1] for t in wins} == {0, 1, 2}
+    assert controls >= 12, controls
+
+
+def test_triplet_window_oracle_is_the_oracle_on_a_small_image():
+    """triplet_window_ref (ref_triplet on a window's source crop with the noise of the whole output's counters) against
+    ref_triplet on the whole, where that is small: 3 x 96 x 104 -> 48 x 52 under the case's flips; and the noise of the
+    window's own counters is another one."""
+    from test_triplet_cpu import _params, ref_noise, ref_noise_at, ref_triplet
+    key = (3, 96, 104)
+    B, H, W = key
+    h, w = H // 2, W // 2
+    rng = np.random.default_rng(3)
+    frames = [rng.integers(0, 256, (B, H, W, 3), dtype=np.uint8) for _ in range(3)]
+    ip, fp = _params(B, 78)
+    ip[:, 0:2] = lo.TRI_FLIPS
+    pair, mid = ref_triplet(*frames, ip, fp, (h, w))
+    wins = lo.triplet_windows(key, "channels_last", [("w%d" % n, n, 20 + 3 * n, 9 + 14 * n) for n in range(B)] + [("last", 2, h - 1, w - 1)])
+    assert [t[2:4] for t in wins] == [(4, 0), (7, 7), (10, 20), (h - lo.TRI_WIN, w - lo.TRI_WIN)]
+    for win in wins:
+        _, n, oy0, ox0, r0, c0 = win
+        crops = [f[n:n + 1, r0:r0 + 2 * lo.TRI_WIN, c0:c0 + 2 * lo.TRI_WIN] for f in frames]
+        r_pair, r_mid = lo.triplet_window_ref(key, win, crops, ip[n], fp[n])
+        assert np.abs(r_pair - pair[n, oy0:oy0 + lo.TRI_WIN, ox0:ox0 + lo.TRI_WIN]).max() <= 1e-12
+        assert np.abs(r_mid - mid[n, oy0:oy0 + lo.TRI_WIN, ox0:ox0 + lo.TRI_WIN]).max() <= 1e-12
+        own = ref_triplet(*crops, ip[n:n + 1], fp[n:n + 1], (lo.TRI_WIN, lo.TRI_WIN))[1][0]
+        assert np.abs(own - r_mid).max() > 100 * 1e-4
+    # ref_noise_at is ref_noise read at its counters, for one row of counters and for one a sample
+    z = ref_noise(ip[:, 2:4], h, w).reshape(B, h * w, 3)
+    at = rng.integers(0, h * w, (B, 40))
+    assert np.array_equal(ref_noise_at(ip[:, 2:4], at[0]), z[:, at[0]])
+    assert np.array_equal(ref_noise_at(ip[:, 2:4], at), np.stack([z[b, at[b]] for b in range(B)]))
+
+
+# ---- the update step --------------------------------------------------------------------------------------------------
+def test_optim_case_crosses_what_it_claims(hip_lib):
+    """18,683,000 rows of 115 floats: the element offsets pass 2^29, 2^30 and 2^31 inside a row each, by more than 2^20;
+    the unit count is admitted and takes the grid-stride form; five slices of whole rows stay under 2^29 elements; the
+    sampled rows hold the boundary rows, the first and the last; the plan fits."""
+    key = lo.CASES["optim"]
+    rows, cols = key
+    n = rows * cols
+    assert cols == 115 and n > P31 + (1 << 20) and lo.crossed(n) == [P29, P30, P31]
+    assert all(b % cols for b in lo.BOUNDARIES)                                       # each boundary lies inside a row
+    assert sorted({(4 * cols * r) % 16 for r in range(8)}) == [0, 4, 8, 12]           # the four phases of a row's start
+    text = open(os.path.join(CSRC, "optim.hip")).read()
+    waves, cap = int(re.search(r"kOptThreads = (\d+)", text).group(1)) // 64, int(re.search(r"kOptMaxBlocks = (\d+)", text).group(1))
+    assert "int64_t agc_adam_max_units() { return 0x7fffffff; }" in text and 1 <= rows <= 0x7fffffff
+    assert rows > 1000 * waves * cap and rows % (waves * cap)                          # thousands of trips a wave, the last uneven
+    assert hip_lib.qpwc_agc_adam_step_kernel(rows) == b"agc_adam_kernel<grid-stride>"
+    assert hip_lib.qpwc_agc_adam_step_kernel(waves * cap) == b"agc_adam_kernel<one unit per wave>"
+    R = lo.OPT_SLICE_ROWS
+    assert R * cols < P29 <= (R + 1) * cols and -(-rows // R) == 5 and 0 < rows - 4 * R < R
+    sample = lo.optim_sample_rows(rows, cols)
+    assert sample[:5] == [P29 // cols, P30 // cols, P31 // cols, 0, rows - 1] and len(set(sample)) == len(sample) >= 35
+    for b, r in zip(lo.BOUNDARIES, sample):
+        assert r * cols < b < (r + 1) * cols
+    assert sum(r * cols >= P31 for r in sample) >= 1 and (P31 // cols + 1) * cols - P31 >= 0
+    planned = lo.optim_planned_bytes(key)
+    assert planned == 20 * n + 48 * rows and planned <= 48 * lo.GIB and 1.10 * planned <= 64 * lo.GIB
+
+
+def test_optim_tables_tile_the_tensor_and_satisfy_the_validator():
+    """optim_tables on a small parameter: both unit tables name every row once, the sliced launch's offsets are counted
+    from its slice and address the same elements, and the tables are what qpwc_agc_adam_step's validator asks for (dense
+    int64: 8-byte aligned, 32 bytes a tensor and 24 a unit, separate allocations)."""
+    rows, cols, R = 1003, 115, 250
+    base = [1 << 20, 1 << 24, 1 << 28, 1 << 32]
+    (tw, uw), (ts, us) = lo.optim_tables(base, rows, cols, R, "cpu")
+    for t in (tw, uw, ts, us):
+        assert t.dtype == torch.int64 and t.is_contiguous() and t.data_ptr() % 8 == 0
+    assert tuple(tw.shape) == (1, 4) and tuple(uw.shape) == tuple(us.shape) == (rows, 3) and tuple(ts.shape) == (5, 4)
+    assert tw[0].tolist() == base and uw[:, 0].eq(0).all() and uw[:, 1].tolist() == [r * cols for r in range(rows)]
+    assert uw[:, 2].eq(cols).all() and us[:, 2].eq(cols).all() and us[:, 0].max() == 4 and us[:, 1].max() == (R - 1) * cols
+    for k in range(4):                                                                 # the same address for every row
+        whole = tw[uw[:, 0], k] + 4 * uw[:, 1]
+        sliced = ts[us[:, 0], k] + 4 * us[:, 1]
+        assert torch.equal(whole, sliced)
+    text = open(os.path.join(CSRC, "capi.hip")).read()
+    assert "{tensors, (size_t)n_tensors * 32, 8, \"tensors\"}, {units, (size_t)n_units * 24, 8, \"units\"}" in text
+
+
+def test_optim_rows_stay_within_the_bounds_in_the_fp32_composition():
+    """optim.step_torch in fp32 on rows drawn and scaled as the GPU case draws them (optim_draw, optim_scale_rows) against
+    the float64 oracle, at t = 1 with clipping on: the bounds of tests/test_optim_cpu.py, 4 x what the composition
+    measured on that module's cases, hold on these rows too, so the GPU case uses them unchanged.
+    Measured here on 4096 rows: p abs 1.5e-08, m rel 7.1e-08, v rel 5.9e-08 (bounds 1.56e-07, 1.88e-06, 1.16e-06)."""
+    from qpwcnet_amd import optim
+    from test_optim_cpu import AGC_EPS, BETA_1, BETA_2, CLIP, EPSILON, LR, M_BOUND, P_BOUND, V_BOUND, oracle_alpha
+    rows, cols = 4096, 115
+    arr = {k: torch.empty(rows * cols) for k in "pgmv"}
+    for k in "pgmv":
+        lo.optim_draw(arr[k], k)
+    ratio = lo.optim_scale_rows(arr["p"], arr["g"], cols, CLIP, AGC_EPS)
+    assert float((ratio - 1.0).abs().min()) > 1e-3 and float(torch.minimum((ratio - 0.25).abs(), (ratio - 4.0).abs()).max()) < 1e-4
+    assert float(arr["v"].min()) >= 0.0 and 0.09 < float(arr["p"].std()) < 0.11
+    before = [arr[k].view(rows, cols).numpy().copy() for k in "pgmv"]
+    want = lo.optim_rows_oracle(*before)
+    # the oracle clipped every odd row by 16 and left the even rows alone
+    g64 = before[1].astype(np.float64)
+    m_plain = before[2] + (g64 - before[2]) * (1.0 - float(np.float32(BETA_1)))
+    assert np.abs(want[1][0::2] - m_plain[0::2]).max() < 1e-15 and np.abs(want[1][1::2] - m_plain[1::2]).max() > 1e-6
+    p = arr["p"].view(rows, cols, 1, 1)
+    optim.step_torch([("rows.pointwise.weight", p)], [arr["g"].view(rows, cols, 1, 1)], [arr["m"].view(rows, cols, 1, 1)],
+                     [arr["v"].view(rows, cols, 1, 1)], float(np.float32(oracle_alpha(LR, 1))), BETA_1, BETA_2, EPSILON, CLIP, AGC_EPS)
+    err = lo.optim_row_errors([arr[k].view(rows, cols).numpy() for k in "pmv"], want)
+    print("step_torch on {} rows: p abs {:.3g} (bound {:.3g}), m rel {:.3g} ({:.3g}), v rel {:.3g} ({:.3g})".format(
+        rows, err[0], P_BOUND, err[1], M_BOUND, err[2], V_BOUND))
+    assert err[0] <= P_BOUND and err[1] <= M_BOUND and err[2] <= V_BOUND, err
+    # the control: other rows' data gives another answer, by far more than a bound
+    other = lo.optim_rows_oracle(*[np.roll(b, 1, axis=0) for b in before])
+    assert float(np.abs(other[0] - want[0]).max(1).min()) / P_BOUND > 100.0

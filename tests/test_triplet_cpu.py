@@ -40,17 +40,24 @@ def ref_philox(counter, key):
     return np.stack(np.broadcast_arrays(*c), axis=-1)
 
 
-def ref_noise(keys, h, w):
-    """(B,h,w,3) float64 standard normals: pixel (y, x) of sample b from counter (y * w + x, 0, 0, 0), key keys[b]."""
+def ref_noise_at(keys, counters):
+    """(B,N,3) float64 standard normals of sample b from the counters (c, 0, 0, 0), c = counters (N,) for every sample or
+    (B,N), under key keys[b]: what a pixel whose pre-flip index in the whole output is c receives."""
     keys = np.asarray(keys).astype(np.int64) & 0xFFFFFFFF
-    counter = np.zeros((1, h * w, 4), np.uint64)
-    counter[0, :, 0] = np.arange(h * w)
+    c0 = np.broadcast_to(np.asarray(counters, np.int64), (len(keys),) + np.shape(counters)[-1:])
+    assert c0.min() >= 0 and c0.max() <= 0xFFFFFFFF
+    counter = np.zeros(c0.shape + (4,), np.uint64)
+    counter[..., 0] = c0
     r = ref_philox(counter, keys.astype(np.uint64)[:, None, :]).astype(np.float64)
     u = np.floor(r / 256.0)                                                     # r >> 8
     u1, u2, v1, v2 = (u[..., 0] + 1) / 2 ** 24, u[..., 1] / 2 ** 24, (u[..., 2] + 1) / 2 ** 24, u[..., 3] / 2 ** 24
     rad, rad2 = np.sqrt(-2.0 * np.log(u1)), np.sqrt(-2.0 * np.log(v1))
-    z = np.stack([rad * np.cos(2 * np.pi * u2), rad * np.sin(2 * np.pi * u2), rad2 * np.cos(2 * np.pi * v2)], axis=-1)
-    return z.reshape(len(keys), h, w, 3)
+    return np.stack([rad * np.cos(2 * np.pi * u2), rad * np.sin(2 * np.pi * u2), rad2 * np.cos(2 * np.pi * v2)], axis=-1)
+
+
+def ref_noise(keys, h, w):
+    """(B,h,w,3) float64 standard normals: pixel (y, x) of sample b from counter (y * w + x, 0, 0, 0), key keys[b]."""
+    return ref_noise_at(keys, np.arange(h * w)).reshape(len(keys), h, w, 3)
 
 
 def ref_resize(x, h, w):
@@ -68,15 +75,18 @@ def ref_resize(x, h, w):
     return top + (bot - top) * ty
 
 
-def ref_triplet(a, b, c, iparams, fparams, dsize, finish=True, noise_before_flips=True):
+def ref_triplet(a, b, c, iparams, fparams, dsize, finish=True, noise_before_flips=True, noise=None):
     """-> (img_pair (B,h,w,6), img1 (B,h,w,3)) float64, channels_last.  noise_before_flips=False is the nearest wrong
-    reading (the noise indexed by the output pixel), for the negative control."""
+    reading (the noise indexed by the output pixel), for the negative control.  noise: the (B,h,w,3) standard normals of
+    the pre-flip pixels, for a window of a larger output whose counters are not its own (ref_noise_at)."""
     h, w = dsize
     fp = np.asarray(fparams, np.float64)
     x = np.stack([a, b, c], axis=0)
     x = x.astype(np.float64) * np.float64(INV255) if x.dtype == np.uint8 else x.astype(np.float64)
     x = ref_resize(x, h, w)                                                     # (3,B,h,w,3)
-    noise = ref_noise(np.asarray(iparams)[:, 2:4], h, w)
+    if noise is None:
+        noise = ref_noise(np.asarray(iparams)[:, 2:4], h, w)
+    assert noise.shape == (x.shape[1], h, w, 3)
     out = np.empty_like(x)
     for n in range(x.shape[1]):
         R, scale, txn, sigma = fp[n, 0:9].reshape(3, 3), fp[n, 9:12], fp[n, 12:15], fp[n, 15]
