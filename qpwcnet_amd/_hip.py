@@ -202,6 +202,18 @@ UNSUP_CENSUS, UNSUP_CHARBONNIER = 0, 1
 UNSUP_LOSS_TILE = (8, 32)               # csrc/unsup_loss.hip: pixels (rows, columns) per workgroup
 UNSUP_LOSS_PLANES = 7                   # floats it saves per pixel for the backward
 
+# The interpolator's SSIM + Charbonnier training loss, declared in include/qpwc_image_loss.h: a table of its own under the
+# same rules, held to its header by tests/test_image_loss_capi_cpu.py.
+IMAGE_LOSS_PROTOTYPES = {
+    "qpwc_image_loss_workspace_floats": (_i64, [_ci, _ci, _pi, _pi, _ci]),
+    "qpwc_image_loss_fwd": (_ci, [_cf, _cf, _cf, _cf, _cf, _pvp, _pvp, _ci, _ci, _pi, _pi, _pi, _ci, _ci, _vp, _vp, _vp,
+                                  _vp, _vp]),
+    "qpwc_image_loss_fwd_kernel": (_str, [_ci, _ci, _pi, _pi, _ci]),
+    "qpwc_image_loss_bwd": (_ci, [_cf, _cf, _cf, _cf, _pvp, _pvp, _vp, _vp, _pvp, _ci, _ci, _pi, _pi, _pi, _ci, _ci, _vp]),
+}
+IMAGE_LOSS_TILE = (16, 32)              # csrc/image_loss.hip: pixels (rows, columns) per workgroup
+IMAGE_LOSS_PLANES = 3                   # floats it saves per SSIM position and channel for the backward
+
 _lib = None
 
 
@@ -235,7 +247,7 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     later = dict(OPTIM_PROTOTYPES, **TRIPLET_PROTOTYPES, **VIS_PROTOTYPES, **QUALITY_PROTOTYPES,
                  **REVIEW_PROTOTYPES, **FLOW_QUALITY_PROTOTYPES, **MASKED_LOSS_PROTOTYPES,
-                 **SPARSE_AUGMENT_PROTOTYPES, **UNSUP_LOSS_PROTOTYPES)
+                 **SPARSE_AUGMENT_PROTOTYPES, **UNSUP_LOSS_PROTOTYPES, **IMAGE_LOSS_PROTOTYPES)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(later.items()):
         if name in later and not hasattr(L, name):
             continue        # QPWC_HIP_LIB naming an older build: the call itself fails, by name (AttributeError)

@@ -1,12 +1,14 @@
 // extern "C" boundary of libqpwc_hip.so (declared in include/qpwc.h).
 // Validates arguments, then enqueues on the caller's stream.  No allocation,
 // no synchronisation, no global state besides a thread-local error string.
+#include <float.h>
 #include <stdarg.h>
 #include <stdio.h>
 
 #include <initializer_list>
 
 #include "../../include/qpwc_flow_quality.h"
+#include "../../include/qpwc_image_loss.h"
 #include "../../include/qpwc_masked_loss.h"
 #include "../../include/qpwc_optim.h"
 #include "../../include/qpwc_quality.h"
@@ -168,6 +170,35 @@ static int unsup_loss_check_range(std::initializer_list<float> positive, std::in
         if (!(v > 0.0f)) return fail(QPWC_E_RANGE, "q, eps and smooth_eps must be > 0, got %g", (double)v);
     for (float v : non_negative)
         if (!(v >= 0.0f)) return fail(QPWC_E_RANGE, "edge and smooth_weight must be >= 0, got %g", (double)v);
+    return QPWC_OK;
+}
+
+// the shape rules of the image loss, shared by qpwc_image_loss_workspace_floats / _fwd / _fwd_kernel / _bwd: the kernels
+// index a level's elements and all levels' tiles in 32 bits
+static int image_loss_check_shapes(int B, int C, const int* h, const int* w, int n_levels) {
+    if (n_levels < 1 || n_levels > 8) return fail(QPWC_E_SHAPE, "n_levels %d outside [1,8]", n_levels);
+    if (C < 1 || C > 4) return fail(QPWC_E_SHAPE, "images take 1..4 channels, got %d", C);
+    if (B <= 0) return fail(QPWC_E_SHAPE, "non-positive extent B=%d", B);
+    for (int i = 0; i < n_levels; ++i) {
+        if (h[i] <= 0 || w[i] <= 0) return fail(QPWC_E_SHAPE, "level %d: non-positive extent %dx%d", i, h[i], w[i]);
+        // factor by factor, so that no product leaves 64 bits: B * C < 2^33 and h * w < 2^62 here
+        if ((int64_t)h[i] * w[i] > INT32_MAX || (int64_t)B * C * ((int64_t)h[i] * w[i]) > INT32_MAX)
+            return fail(QPWC_E_SHAPE, "level %d: B=%d C=%d %dx%d is more than 2^31 - 1 elements", i, B, C, h[i], w[i]);
+    }
+    // every extent is now at most 2^31 - 1 and B * h * w at most 2^31 - 1 per level: the tile counts below fit 64 bits
+    if (image_loss_total_tiles(B, h, w, n_levels) > INT32_MAX)
+        return fail(QPWC_E_SHAPE, "B=%d: more than 2^31 - 1 tiles in all levels", B);
+    return QPWC_OK;
+}
+
+// the parameter ranges of the image loss (a NaN fails every comparison); max_val: NULL in the backward, which has none
+static int image_loss_check_range(float ssim_weight, float q, float eps, const float* max_val, float offset) {
+    if (!(ssim_weight >= 0.0f && ssim_weight <= 1.0f))
+        return fail(QPWC_E_RANGE, "ssim_weight %g outside [0,1]", (double)ssim_weight);
+    if (!(q > 0.0f) || !(eps > 0.0f)) return fail(QPWC_E_RANGE, "q and eps must be > 0, got %g and %g", (double)q, (double)eps);
+    if (max_val && !(*max_val > 0.0f && *max_val <= FLT_MAX))
+        return fail(QPWC_E_RANGE, "max_val must be finite and > 0, got %g", (double)*max_val);
+    if (!(offset >= -FLT_MAX && offset <= FLT_MAX)) return fail(QPWC_E_RANGE, "offset must be finite, got %g", (double)offset);
     return QPWC_OK;
 }
 
@@ -1913,6 +1944,84 @@ int qpwc_unsup_loss_bwd(int kind, float smooth_weight, float smooth_eps, const v
     if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
     return unsup_loss_bwd_launch(kind, smooth_weight, smooth_eps, flow, (const float*)workspace, (const int64_t*)counts,
                                  (const float*)grad_losses, grad_flow, B, h, w, flow_dtype, layout, n_levels,
+                                 (hipStream_t)stream);
+}
+
+int64_t qpwc_image_loss_workspace_floats(int B, int C, const int* h, const int* w, int n_levels) {
+    if (!h || !w) return fail(QPWC_E_NULL, "null pointer argument");
+    const int rc = image_loss_check_shapes(B, C, h, w, n_levels);
+    return rc != QPWC_OK ? rc : image_loss_workspace_floats(B, C, h, w, n_levels);
+}
+
+const char* qpwc_image_loss_fwd_kernel(int B, int C, const int* h, const int* w, int n_levels) {
+    if (!h || !w || image_loss_check_shapes(B, C, h, w, n_levels) != QPWC_OK) return "";
+    return image_loss_fwd_kernel();
+}
+
+int qpwc_image_loss_fwd(float ssim_weight, float q, float eps, float max_val, float offset, const void* const* truth,
+                        const void* const* pred, int B, int C, const int* h, const int* w, const int* pred_dtype,
+                        int layout, int n_levels, void* out_losses, void* out_dssim, void* out_charb, void* workspace,
+                        void* stream) {
+    int rc = check_nonnull({{truth, "truth"}, {pred, "pred"}, {h, "h"}, {w, "w"}, {pred_dtype, "pred_dtype"},
+                            {out_losses, "out_losses"}, {out_dssim, "out_dssim"}, {out_charb, "out_charb"},
+                            {workspace, "workspace"}});
+    if (rc != QPWC_OK) return rc;
+    if ((rc = image_loss_check_shapes(B, C, h, w, n_levels)) != QPWC_OK) return rc;
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if ((rc = image_loss_check_range(ssim_weight, q, eps, &max_val, offset)) != QPWC_OK) return rc;
+    for (int i = 0; i < n_levels; ++i)
+        if (pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported prediction dtype %d", i, pred_dtype[i]);
+    BufCheck bufs[2 * 8 + 4];
+    int k = 0;
+    for (int i = 0; i < n_levels; ++i) {
+        if (!truth[i] || !pred[i]) return fail(QPWC_E_NULL, "null target or prediction at level %d", i);
+        const size_t ne = (size_t)B * C * h[i] * w[i], es = esize(pred_dtype[i]);
+        bufs[k++] = indexed_buf(truth[i], ne * 4, 4, "truth[%d]", i);
+        bufs[k++] = indexed_buf(pred[i], ne * es, es, "pred[%d]", i);
+    }
+    const int n_in = k;
+    bufs[k++] = indexed_buf(out_losses, (size_t)n_levels * 4, 4, "out_losses", 0);
+    bufs[k++] = indexed_buf(out_dssim, (size_t)n_levels * 4, 4, "out_dssim", 0);
+    bufs[k++] = indexed_buf(out_charb, (size_t)n_levels * 4, 4, "out_charb", 0);
+    bufs[k++] = indexed_buf(workspace, (size_t)image_loss_workspace_floats(B, C, h, w, n_levels) * 4, 4, "workspace", 0);
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return image_loss_fwd_launch(ssim_weight, q, eps, max_val, offset, truth, pred, B, C, h, w, pred_dtype, layout,
+                                 n_levels, (float*)out_losses, (float*)out_dssim, (float*)out_charb, (float*)workspace,
+                                 (hipStream_t)stream);
+}
+
+int qpwc_image_loss_bwd(float ssim_weight, float q, float eps, float offset, const void* const* truth,
+                        const void* const* pred, const void* workspace, const void* grad_losses, void* const* grad_pred,
+                        int B, int C, const int* h, const int* w, const int* pred_dtype, int layout, int n_levels,
+                        void* stream) {
+    int rc = check_nonnull({{truth, "truth"}, {pred, "pred"}, {workspace, "workspace"}, {grad_losses, "grad_losses"},
+                            {grad_pred, "grad_pred"}, {h, "h"}, {w, "w"}, {pred_dtype, "pred_dtype"}});
+    if (rc != QPWC_OK) return rc;
+    if ((rc = image_loss_check_shapes(B, C, h, w, n_levels)) != QPWC_OK) return rc;
+    if (layout != QPWC_NHWC && layout != QPWC_NCHW) return fail(QPWC_E_LAYOUT, "Unsupported data format : %d", layout);
+    if ((rc = image_loss_check_range(ssim_weight, q, eps, nullptr, offset)) != QPWC_OK) return rc;
+    for (int i = 0; i < n_levels; ++i)
+        if (pred_dtype[i] != QPWC_F32 && pred_dtype[i] != QPWC_F16)
+            return fail(QPWC_E_DTYPE, "level %d: unsupported prediction dtype %d", i, pred_dtype[i]);
+    BufCheck bufs[2 + 3 * 8];
+    int k = 0;
+    bufs[k++] = indexed_buf(workspace, (size_t)image_loss_workspace_floats(B, C, h, w, n_levels) * 4, 4, "workspace", 0);
+    bufs[k++] = indexed_buf(grad_losses, (size_t)n_levels * 4, 4, "grad_losses", 0);
+    for (int i = 0; i < n_levels; ++i) {
+        if (!truth[i] || !pred[i] || !grad_pred[i]) return fail(QPWC_E_NULL, "null buffer at level %d", i);
+        const size_t ne = (size_t)B * C * h[i] * w[i], es = esize(pred_dtype[i]);
+        bufs[k++] = indexed_buf(truth[i], ne * 4, 4, "truth[%d]", i);
+        bufs[k++] = indexed_buf(pred[i], ne * es, es, "pred[%d]", i);
+    }
+    const int n_in = k;
+    for (int i = 0; i < n_levels; ++i) {
+        const size_t es = esize(pred_dtype[i]);
+        bufs[k++] = indexed_buf(grad_pred[i], (size_t)B * C * h[i] * w[i] * es, es, "grad_pred[%d]", i);
+    }
+    if ((rc = check_bufs(bufs, n_in, k)) != QPWC_OK) return rc;
+    return image_loss_bwd_launch(ssim_weight, q, eps, offset, truth, pred, (const float*)workspace,
+                                 (const float*)grad_losses, grad_pred, B, C, h, w, pred_dtype, layout, n_levels,
                                  (hipStream_t)stream);
 }
 

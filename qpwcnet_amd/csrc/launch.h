@@ -220,6 +220,19 @@ int unsup_loss_bwd_launch(int kind, float smooth_weight, float eps_s, const void
                           const int64_t* counts, const float* grad_losses, void* const* grad_flow, int B, const int* h,
                           const int* w, const int* flow_dtype, int layout, int n, hipStream_t s);
 
+// image_loss.hip (include/qpwc_image_loss.h)
+int64_t image_loss_total_tiles(int B, const int* h, const int* w, int n);
+int64_t image_loss_workspace_floats(int B, int C, const int* h, const int* w, int n);
+const char* image_loss_fwd_kernel();
+int image_loss_fwd_launch(float ssim_weight, float q, float eps, float max_val, float offset, const void* const* truth,
+                          const void* const* pred, int B, int C, const int* h, const int* w, const int* pred_dtype,
+                          int layout, int n, float* out_losses, float* out_dssim, float* out_charb, float* ws,
+                          hipStream_t s);
+int image_loss_bwd_launch(float ssim_weight, float q, float eps, float offset, const void* const* truth,
+                          const void* const* pred, const float* ws, const float* grad_losses, void* const* grad_pred,
+                          int B, int C, const int* h, const int* w, const int* pred_dtype, int layout, int n,
+                          hipStream_t s);
+
 // flow_quality.hip (include/qpwc_flow_quality.h)
 bool flow_quality_shape_ok(int B, int H, int W);
 int64_t flow_quality_workspace_floats(int B, int H, int W);

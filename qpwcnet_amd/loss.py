@@ -14,7 +14,10 @@ as they are.  No CPU path.  Keras' ``sample_weight`` / ``reduction`` are not sup
 truth (below; include/qpwc_masked_loss.h); they do have a torch chain, taken for CPU tensors.
 
 ``PhotometricLoss`` / ``multiscale_unsupervised`` are the label-free losses (census or Charbonnier photometric term plus
-edge-aware smoothness; at the end of this file; include/qpwc_unsup_loss.h), which go beyond the reference as well.
+edge-aware smoothness; include/qpwc_unsup_loss.h), which go beyond the reference as well.
+
+``ImageLoss`` / ``multiscale_image`` are the frame interpolator's SSIM + Charbonnier loss against AutoResizeMseLoss's own
+per-level target (at the end of this file; include/qpwc_image_loss.h), beyond the reference too.
 """
 import torch
 
@@ -516,3 +519,159 @@ def multiscale_unsupervised(obj, pairs, flows, occluded=None):
         _UNSUP_KINDS[obj.kind], [p for p, _ in frames], [n for _, n in frames], flows, occluded, obj.data_format, obj.q,
         obj.eps, obj.smooth_weight, obj.edge, obj.smooth_eps)
     return per_level.sum(), per_level, {"photometric": photo, "smoothness": smooth, "counts": counts}
+
+
+# ---- the interpolator's SSIM + Charbonnier loss (include/qpwc_image_loss.h) ---------------------------------------------
+# MSE on intermediate frames blurs; the model is scored by SSIM (metrics.image_quality).  Per level, against
+# AutoResizeMseLoss's own target: ssim_weight * (1 - SSIM) / 2 + (1 - ssim_weight) * mean ((p - t)^2 + eps^2)^q, SSIM with
+# tf.image.ssim's default window on p + offset and t + offset, unclipped.  The reference has no such loss.  HIP tensors
+# take qpwc_image_loss_fwd / _bwd; CPU tensors take the torch chain below.  Non-finite images are out of scope.
+
+class ImageLoss:
+    """The structural loss of one or more image levels: ``ssim_weight`` times the structural dissimilarity
+    (1 - mean SSIM) / 2 plus (1 - ``ssim_weight``) times the Charbonnier term mean ((y_pred - target)^2 + eps^2)^q.
+    SSIM is ``metrics.image_quality``'s (filter_size 11, sigma 1.5, k1 0.01, k2 0.03) on the images plus ``offset``
+    (0.5 takes [-0.5, 0.5] to [0, 1]) with dynamic range ``max_val``, without clipping; a level below 11 x 11 has no
+    SSIM position: its dssim is 0.  ssim_weight = 0.85 is the conventional value (Godard et al.), a hyperparameter
+    nobody has tuned here.  The per-level target is AutoResizeMseLoss's: y_true resized bilinearly to the level.
+    ``loss(y_true, y_pred)`` is one level; ``multiscale_image`` takes the network's list.  Layout from
+    ``image_data_format()`` at construction unless given."""
+
+    def __init__(self, ssim_weight=0.85, q=0.5, eps=1e-3, max_val=1.0, offset=0.5, data_format=None, name=None):
+        ssim_weight, q, eps, max_val, offset = (float(v) for v in (ssim_weight, q, eps, max_val, offset))
+        if not 0.0 <= ssim_weight <= 1.0:
+            raise ValueError("ssim_weight must be in [0, 1], got {}".format(ssim_weight))
+        if not (q > 0.0 and eps > 0.0):
+            raise ValueError("q and eps must be > 0, got {} and {}".format(q, eps))
+        if not (max_val > 0.0 and max_val < float("inf") and abs(offset) < float("inf")):
+            raise ValueError("max_val must be finite and > 0 and offset finite, got {} and {}".format(max_val, offset))
+        self.ssim_weight, self.q, self.eps, self.max_val, self.offset = ssim_weight, q, eps, max_val, offset
+        self.data_format = image_data_format() if data_format is None else data_format
+        self.axis = get_axis(self.data_format)
+        self.name = name
+
+    def __call__(self, y_true, y_pred):
+        return multiscale_image(self, y_true, [y_pred])[1].reshape(())
+
+    def call(self, y_true, y_pred):
+        return self(y_true, y_pred)
+
+    def get_config(self):
+        return {"name": self.name, "ssim_weight": self.ssim_weight, "q": self.q, "eps": self.eps, "max_val": self.max_val,
+                "offset": self.offset, "data_format": self.data_format}
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+def _image_args(obj, y_true, y_preds):
+    """-> (y_preds, level shapes) after the checks both paths share."""
+    if not isinstance(obj, ImageLoss):
+        raise TypeError("multiscale_image takes an ImageLoss, got {}".format(type(obj).__name__))
+    if not isinstance(y_true, torch.Tensor):
+        raise TypeError("y_true must be a torch.Tensor")
+    if y_true.requires_grad and torch.is_grad_enabled():
+        raise ValueError("y_true requires grad: the losses are differentiable in y_pred only, a gradient for y_true "
+                         "would be dropped (detach it)")
+    if y_true.dim() != 4 or not 1 <= y_true.shape[obj.axis] <= 4:
+        raise ValueError("y_true must be a batched image of 1..4 channels on axis {} ({}), got shape {}".format(
+            obj.axis, obj.data_format, tuple(y_true.shape)))
+    y_preds = list(y_preds)
+    if not 1 <= len(y_preds) <= 8:
+        raise ValueError("the losses take 1..8 prediction levels, got {}".format(len(y_preds)))
+    shapes = []
+    for i, p in enumerate(y_preds):
+        if not isinstance(p, torch.Tensor):
+            raise TypeError("y_preds[{}] must be a torch.Tensor".format(i))
+        if p.device != y_true.device:
+            raise ValueError("y_preds[{}] is on {}, y_true on {}".format(i, p.device, y_true.device))
+        if p.dim() != 4 or p.shape[0] != y_true.shape[0] or p.shape[obj.axis] != y_true.shape[obj.axis]:
+            raise ValueError("y_preds[{}] must be a batched image ({}) of batch {} and {} channels, got shape {}".format(
+                i, obj.data_format, y_true.shape[0], y_true.shape[obj.axis], tuple(p.shape)))
+        h, w = (p.shape[1], p.shape[2]) if obj.axis == 3 else (p.shape[2], p.shape[3])
+        if h < 1 or w < 1:
+            raise ValueError("y_preds[{}] is empty: shape {}".format(i, tuple(p.shape)))
+        shapes.append((int(h), int(w)))
+    return y_preds, shapes
+
+
+def resized_ground_truth_torch(y_true, shapes, data_format):
+    """``ops.resized_ground_truth`` composed from torch operators, on any device and in y_true's dtype: the four
+    bilinear corners of tf.image.resize (half-pixel centres, no antialias) with the kernel's fp32 weights along each
+    axis in every dtype, combined as the kernel combines them."""
+    x = y_true.detach()
+    x = x if get_axis(data_format) == 3 else x.permute(0, 2, 3, 1)
+    H, W = x.shape[1:3]
+    out = []
+    for h, w in shapes:
+        y0, y1, ly0, ly1 = (t.to(x.device) for t in _axis_weights(int(h), H))
+        x0, x1, lx0, lx1 = (t.to(x.device) for t in _axis_weights(int(w), W))
+        ly0, ly1 = ly0.to(x.dtype).view(1, -1, 1, 1), ly1.to(x.dtype).view(1, -1, 1, 1)
+        lx0, lx1 = lx0.to(x.dtype).view(1, 1, -1, 1), lx1.to(x.dtype).view(1, 1, -1, 1)
+        top, bot = x[:, y0], x[:, y1]
+        g = ly0 * (lx0 * top[:, :, x0] + lx1 * top[:, :, x1]) + ly1 * (lx0 * bot[:, :, x0] + lx1 * bot[:, :, x1])
+        out.append(g if get_axis(data_format) == 3 else g.permute(0, 3, 1, 2).contiguous())
+    return out
+
+
+def _image_level_torch(obj, t, p):
+    """(dssim, charbonnier) of one level: target t and prediction p, (B,C,h,w) in one dtype."""
+    import torch.nn.functional as F
+    C, h, w = t.shape[1:]
+    d = p - t
+    charb = ((d * d + obj.eps ** 2) ** obj.q).mean()
+    if h < metrics.SSIM_FILTER["filter_size"] or w < metrics.SSIM_FILTER["filter_size"]:
+        return p.sum() * 0, charb
+    g = metrics.ssim_window().to(device=t.device, dtype=t.dtype)
+    rows, cols = g.view(1, 1, 1, -1).repeat(C, 1, 1, 1), g.view(1, 1, -1, 1).repeat(C, 1, 1, 1)
+    conv = lambda x: F.conv2d(F.conv2d(x.contiguous(), rows, groups=C), cols, groups=C)
+    c1 = float(torch.tensor((metrics.SSIM_FILTER["k1"] * obj.max_val) ** 2, dtype=torch.float64).float())
+    c2 = float(torch.tensor((metrics.SSIM_FILTER["k2"] * obj.max_val) ** 2, dtype=torch.float64).float())
+    vt, vp = t + obj.offset, p + obj.offset
+    mt, mp = conv(vt), conv(vp)
+    num0, den0 = 2.0 * mt * mp, mt * mt + mp * mp
+    num1, den1 = 2.0 * conv(vt * vp), conv(vt * vt + vp * vp)
+    s = (num0 + c1) / (den0 + c1) * ((num1 - num0 + c2) / (den1 - den0 + c2))
+    return (1.0 - s.mean()) / 2.0, charb
+
+
+def multiscale_image_torch(obj, y_true, y_preds):
+    """``multiscale_image`` composed from torch operators (``F.conv2d(groups=C)`` along the rows and then the columns
+    with ``metrics.ssim_window()``), on any device, in y_true's dtype (float64 inputs give the float64 reference) and
+    differentiable in y_preds through torch autograd: the path CPU tensors take and the baseline the kernels are timed
+    against."""
+    y_preds, shapes = _image_args(obj, y_true, y_preds)
+    dssim, charb = [], []
+    for t, p in zip(resized_ground_truth_torch(y_true, shapes, obj.data_format), y_preds):
+        if obj.axis == 3:
+            t, p = t.permute(0, 3, 1, 2), p.permute(0, 3, 1, 2)
+        s, c = _image_level_torch(obj, t, p.to(t.dtype))
+        dssim.append(s)
+        charb.append(c)
+    dssim, charb = torch.stack(dssim), torch.stack(charb)
+    per_level = obj.ssim_weight * dssim + (1.0 - obj.ssim_weight) * charb
+    return per_level.sum(), per_level, {"dssim": dssim.detach(), "charbonnier": charb.detach()}
+
+
+def multiscale_image(obj, y_true, y_preds):
+    """The SSIM + Charbonnier loss of 1..8 predicted images against one full-resolution image -> (total, per_level,
+    parts): per_level [L] (what autograd differentiates, in y_preds only), total = per_level.sum(), parts = {'dssim'
+    [L], 'charbonnier' [L]}, fp32 on the inputs' device with nothing read back.  ``obj``: an ImageLoss; ``y_true``:
+    float32 (B,H,W,C) / (B,C,H,W) by obj.data_format, 1..4 channels, never differentiated; ``y_preds``: what
+    InterpolatorModel returns, each fp32 or fp16 at its own (h, w); the gradient comes back in each one's dtype and
+    layout.  Per level the target is AutoResizeMseLoss's (ops.resized_ground_truth, one launch for all levels), so the
+    loss swaps in for ``multiscale(AutoResizeMseLoss(), ...)`` without changing what a level is compared against.  HIP
+    tensors: the targets, then one forward launch for all levels plus a fold, and one backward launch, no host
+    synchronisation; CPU tensors: ``multiscale_image_torch``."""
+    y_preds, shapes = _image_args(obj, y_true, y_preds)
+    if not y_true.is_cuda:
+        return multiscale_image_torch(obj, y_true, y_preds)
+    if y_true.dtype != torch.float32:
+        raise ValueError("y_true must be float32, got {}".format(y_true.dtype))
+    if ops._wants_grad(*y_preds):
+        ops._refuse_capture("the image loss")       # before the targets' launch
+    truths = ops.resized_ground_truth(y_true, shapes, obj.data_format)
+    per_level, dssim, charb = ops.image_loss(truths, y_preds, obj.data_format, obj.ssim_weight, obj.q, obj.eps,
+                                             obj.max_val, obj.offset)
+    return per_level.sum(), per_level, {"dssim": dssim, "charbonnier": charb}

@@ -2033,6 +2033,146 @@ def unsup_loss(kind, prvs, nxts, flows, occluded=None, data_format=CHANNELS_LAST
     return unsup_loss_fwd(kind, prvs, nxts, flows, occluded, data_format, q, eps, smooth_weight, edge, smooth_eps)[:4]
 
 
+def resized_ground_truth(y_true, shapes, data_format=CHANNELS_LAST):
+    """AutoResizeMseLoss's per-level target (qpwcnet/train/loss.py:177-197): y_true resized to every (h, w) of shapes as
+    tf.image.resize does it (bilinear, half-pixel centres, no antialias), any channel count, no flow scale -> list of
+    dense fp32 tensors in data_format; up to 8 levels per pass over y_true (qpwc_loss_fwd with gt_out only)."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    out = []
+    for k in range(0, len(shapes), 8):
+        out += [t.contiguous() for t in loss_fwd(_hip.LOSS_AUTORESIZE_MSE, y_true, None, data_format, want_gt=True,
+                                                 shapes=shapes[k:k + 8])[2]]
+    return out
+
+
+def image_loss_kernel(B, C, shapes):
+    """The forward kernel ``qpwc_image_loss_fwd`` takes for these levels ('image_loss_fwd_kernel'; host only).  '' for
+    arguments the entry point refuses."""
+    n = len(shapes)
+    ha, wa = (ctypes.c_int * n)(*[int(h) for h, _ in shapes]), (ctypes.c_int * n)(*[int(w) for _, w in shapes])
+    name = _hip.lib().qpwc_image_loss_fwd_kernel(int(B), int(C), ha, wa, n)
+    return name.decode() if name else ""
+
+
+class _ImageLossOperands:
+    """What both image loss entry points make of their operands: per level the fp32 target and the prediction (fp32 or
+    fp16), dense in `data_format` and of one shape, all levels of one batch and channel count; B, C, the level shapes and
+    the ctypes arrays."""
+
+    def __init__(self, truths, preds, data_format):
+        get_axis(data_format)
+        truths, preds = list(truths), list(preds)
+        self.n = n = len(preds)
+        if not 1 <= n <= 8:
+            raise ValueError("the losses take 1..8 prediction levels, got {}".format(n))
+        if len(truths) != n:
+            raise ValueError("{} predictions against {} targets".format(n, len(truths)))
+        self.nhwc = nhwc = data_format == CHANNELS_LAST
+        self.layout = _hip.NHWC if nhwc else _hip.NCHW
+        self.truths, self.preds, self.hs, self.ws_ = [], [], [], []
+        for i, (t, p) in enumerate(zip(truths, preds)):
+            for name, x in (("truth", t), ("pred", p)):
+                _check_tensor("{}[{}]".format(name, i), x)
+                if x.device != preds[0].device:
+                    raise ValueError("{}[{}] is on {}, pred[0] on {}".format(name, i, x.device, preds[0].device))
+            B, h, w, C = p.shape if nhwc else (p.shape[0], p.shape[2], p.shape[3], p.shape[1])
+            if not 1 <= C <= 4 or (i and (B, C) != (self.B, self.C)):
+                raise ValueError("pred[{}] must be an image of 1..4 channels ({}) of one batch size and channel count, "
+                                 "got {}".format(i, data_format, tuple(p.shape)))
+            self.B, self.C = int(B), int(C)
+            if t.dtype != torch.float32 or t.shape != p.shape:
+                raise ValueError("truth[{}] must be float32 {}, got {} {}".format(i, tuple(p.shape), t.dtype,
+                                                                                  tuple(t.shape)))
+            if _wants_grad(t):
+                raise ValueError("truth[{}] requires grad: the losses are differentiable in y_pred only, a gradient for "
+                                 "y_true would be dropped (detach it)".format(i))
+            self.truths.append(t.contiguous())
+            self.preds.append(p.contiguous())
+            self.hs.append(int(h))
+            self.ws_.append(int(w))
+        self.dev = self.preds[0].device
+        self.ha, self.wa = (ctypes.c_int * n)(*self.hs), (ctypes.c_int * n)(*self.ws_)
+        self.pdt = (ctypes.c_int * n)(*[_DTYPES[p.dtype] for p in self.preds])
+
+    def ptrs(self, ts):
+        return (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in ts])
+
+
+def image_loss_fwd(truths, preds, data_format=CHANNELS_LAST, ssim_weight=0.85, q=0.5, eps=1e-3, max_val=1.0, offset=0.5):
+    """The SSIM + Charbonnier loss of 1..8 levels (qpwc_image_loss_fwd, include/qpwc_image_loss.h) -> (losses, dssim,
+    charbonnier: fp32 [L], saved), all on the device.  truths[l]: the level's fp32 target, preds[l]: fp32 or fp16, both
+    dense in data_format and of one shape.  saved: what image_loss_bwd takes (the operands and the workspace the forward
+    filled).  One launch plus the fold, the workspace from torch's allocator on the current stream; enqueues and
+    returns: no host synchronisation."""
+    o = _ImageLossOperands(truths, preds, data_format)
+    n, dev = o.n, o.dev
+    L = _hip.lib()
+    nws = L.qpwc_image_loss_workspace_floats(o.B, o.C, o.ha, o.wa, n)
+    _hip.check(min(int(nws), 0))
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+        losses, dssim, charb = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))   # no shared base
+        with _timed("image_loss", (o.B, o.hs[0], o.ws_[0], o.C, n)):
+            rc = L.qpwc_image_loss_fwd(float(ssim_weight), float(q), float(eps), float(max_val), float(offset),
+                                       o.ptrs(o.truths), o.ptrs(o.preds), o.B, o.C, o.ha, o.wa, o.pdt, o.layout, n,
+                                       losses.data_ptr(), dssim.data_ptr(), charb.data_ptr(), ws.data_ptr(),
+                                       _stream(ws))
+    _hip.check(rc)
+    return losses, dssim, charb, (o, ws)
+
+
+def image_loss_bwd(saved, grad_losses, ssim_weight=0.85, q=0.5, eps=1e-3, offset=0.5):
+    """d losses / d preds times grad_losses [L] (on the device) in each prediction's dtype and layout, all levels in one
+    launch (qpwc_image_loss_bwd); saved from image_loss_fwd with the same parameters."""
+    o, ws = saved
+    g = grad_losses.to(torch.float32).contiguous()
+    if g.numel() != o.n or g.device != o.dev:
+        raise ValueError("grad_losses must be a device vector of {} elements".format(o.n))
+    with torch.cuda.device(o.dev):
+        grads = [torch.empty_like(p) for p in o.preds]
+        with _timed("image_loss_bwd", (o.n,)):
+            rc = _hip.lib().qpwc_image_loss_bwd(float(ssim_weight), float(q), float(eps), float(offset),
+                                                o.ptrs(o.truths), o.ptrs(o.preds), ws.data_ptr(), g.data_ptr(),
+                                                o.ptrs(grads), o.B, o.C, o.ha, o.wa, o.pdt, o.layout, o.n, _stream(g))
+    _hip.check(rc)
+    return grads
+
+
+class _ImageLossFn(torch.autograd.Function):
+    """image_loss_fwd() with qpwc_image_loss_bwd as its gradient: the forward saves s's three partial derivatives per
+    position, the backward runs the transposed window pass over them; the targets are constants."""
+
+    @staticmethod
+    def forward(ctx, cfg, truths, *preds):
+        data_format, ssim_weight, q, eps, max_val, offset = cfg
+        losses, dssim, charb, saved = image_loss_fwd(truths, preds, data_format, ssim_weight, q, eps, max_val, offset)
+        ctx.cfg, ctx.saved, ctx.n = cfg, saved, len(preds)
+        ctx.mark_non_differentiable(dssim, charb)
+        ctx.set_materialize_grads(False)
+        return losses, dssim, charb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_losses, *_others):
+        _refuse_capture("the image loss backward")
+        if grad_losses is None:
+            return (None,) * (2 + ctx.n)
+        _, ssim_weight, q, eps, _, offset = ctx.cfg
+        grads = image_loss_bwd(ctx.saved, grad_losses, ssim_weight, q, eps, offset)
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+def image_loss(truths, preds, data_format=CHANNELS_LAST, ssim_weight=0.85, q=0.5, eps=1e-3, max_val=1.0, offset=0.5):
+    """(losses, dssim, charbonnier: fp32 [L]) of image_loss_fwd(); the losses are differentiable in the predictions when
+    grad is enabled and one of them requires it (the parts are reported, not differentiated)."""
+    preds = list(preds)
+    if _wants_grad(*preds):
+        _refuse_capture("the image loss")
+        cfg = (data_format, float(ssim_weight), float(q), float(eps), float(max_val), float(offset))
+        return _ImageLossFn.apply(cfg, list(truths), *preds)
+    return image_loss_fwd(truths, preds, data_format, ssim_weight, q, eps, max_val, offset)[:3]
+
+
 def _dw_sources(sources):
     """-> (kept tensors, ctypes pointer/channel/stride arrays, B, H, W, C) for 1..3 sources."""
     import ctypes
